@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: frames/s of the streamed encode + classify path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -24,6 +24,15 @@ Passes over the same K steps:
      `_cls.h5` + `_outputs.csv` written by rank 0's writer threads; wall time from the first clip to the last file.
 `gates` = the correctness gates of section 8(d) evaluated in this very process against the fixtures made from the
 reference (tests/golden): CLS relative error on the golden frames, head label mismatches on golden rows.
+
+A plain run times pass 1 only (pass 2 instead with --no-host-path): set-up, W warm-up steps, --preroll-seconds of untimed
+HBM-resident work, the untimed pre-roll, the K timed steps, the outputs (--dump-outputs) and the line; nothing in it but the
+K timed steps grows with K.  Pass 2 as `hbm_resident`, passes 3-4, the `value_r3_definition` pass, `gates`, `label_exact`,
+`roofline` and `cpu_baseline` come with --full only (the --no-* options switch them off one by one there).
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the timed pass returned - the fp16 CLS rows (as float32) and the
+head's probabilities - as DIR/cls.npy and DIR/probs.npy, with DIR/row_index.npy (float64) naming the frames they belong to;
+above 60 MiB in all, a fixed seeded sample of rows.  The inputs depend on the arguments only (seeded weights and clip).
 
 Prints ONE JSON line on rank 0 (see README/DESIGN.md for the fields).
 """
@@ -283,6 +292,39 @@ def files_pass(args, enc, head, rank: int, world: int, device) -> dict:
     return out
 
 
+DUMP_BYTES = 60 << 20      # --dump-outputs budget (all files together)
+
+
+def sample_rows(rows):
+    """The rows --dump-outputs writes, copied out at once (device results are views that the next pass overwrites).
+    ``rows``: [(cls16, probs)] per rank, in rank order - host arrays or device tensors.  All of them when they fit in
+    DUMP_BYTES, else a fixed seeded sample of positions in the concatenation; only the kept rows are converted.
+    Returns (cls float32, probs float32, row positions float64)."""
+    counts = [int(c.shape[0]) for c, _ in rows]
+    n, width = sum(counts), int(rows[0][0].shape[1]) + int(rows[0][1].shape[1])
+    keep = min(n, DUMP_BYTES // (4 * width + 8))
+    idx = np.arange(n) if keep == n else np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+
+    def take(a, loc):
+        if isinstance(a, torch.Tensor):
+            return a[torch.from_numpy(loc).to(a.device)].float().cpu().numpy()
+        return np.asarray(a)[loc].astype(np.float32)
+    cls, probs, start = [], [], 0
+    for (c, p), m in zip(rows, counts):
+        loc = idx[(idx >= start) & (idx < start + m)] - start
+        cls.append(take(c, loc))
+        probs.append(take(p, loc))
+        start += m
+    return np.concatenate(cls), np.concatenate(probs), idx.astype(np.float64)
+
+
+def dump_outputs(out_dir: str, sample) -> None:
+    """--dump-outputs: sample_rows()'s result as DIR/cls.npy, DIR/probs.npy (float32) and DIR/row_index.npy (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in zip(("cls", "probs", "row_index"), sample):
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def _null_line(args, n_gpus: int, ranks_seen, error: str) -> str:
     return json.dumps({"metric": METRIC, "value": None, "unit": "frames/s", "n_gpus": n_gpus, "ranks_seen": ranks_seen,
                        "steps": args.steps, "warmup": args.warmup, "ms_per_step": None, "higher_is_better": True, "scaling": "weak",
@@ -358,6 +400,11 @@ def main() -> None:
                     help="untimed steady-state work right before each timed pass, besides the W warm-up steps: a short run "
                          "(the driver's --steps 20 is 58 ms) otherwise starts from an idle device - clocks down, power "
                          "management settling - and reads several % under a 157-step run of the same binary")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement and check (hbm_resident, value_r3_definition, roofline, files_path, "
+                         "gates, label_exact, cpu_baseline); a plain run times the headline pass only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed pass's outputs (CLS rows, probabilities) as DIR/*.npy after the timed steps")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:     # no launcher around us: be the launcher (before any GPU call)
@@ -510,10 +557,15 @@ def main() -> None:
         finally:
             done()
 
+    # what the last timed pass returned on rank 0, for --dump-outputs: [(cls16, probs)] per rank, in rank order
+    last_out: list = []
+
     def gather(cls16, probs):
         if world > 1:
-            cdist.gather_rows([cls16], dst=0)
-            cdist.gather_rows([probs], dst=0)
+            g16 = cdist.gather_rows([cls16], dst=0)
+            gpr = cdist.gather_rows([probs], dst=0)
+            return [(t[0], u[0]) for t, u in zip(g16, gpr)] if rank == 0 else []
+        return [(cls16, probs)]
 
     # warm-up (also builds the RCCL communicator and the rope table outside the timed region)
     t_w = time.perf_counter()
@@ -540,9 +592,10 @@ def main() -> None:
         torch.cuda.synchronize(device)
         t0 = time.perf_counter()
         c16, pr = run(K)
-        gather(c16, pr)
+        rows = gather(c16, pr)
         torch.cuda.synchronize(device)
         cdist.barrier()
+        last_out[:] = rows
         return cdist.max_over_ranks(time.perf_counter() - t0, device)
 
     def run_host_gathered(steps: int):
@@ -559,6 +612,7 @@ def main() -> None:
                 gpr = cdist.gather_rows([torch.empty((0, BEHAVIORS), dtype=torch.float32, device=device)], dst=0)
                 hosted = [(t[0].cpu(), u[0].cpu()) for t, u in zip(g16[1:], gpr[1:])]       # rank 0 now holds every row
                 assert all(t.shape[0] == steps * B for t, _ in hosted)
+                last_out[:] = [(c16h, prh)] + hosted
                 return c16h, prh
             c16, pr = stream.finish()
             cdist.gather_rows([c16], dst=0)
@@ -576,10 +630,26 @@ def main() -> None:
         c16h, prh = run_host_gathered(K)
         torch.cuda.synchronize(device)
         cdist.barrier()
+        if world == 1:
+            last_out[:] = [(c16h, prh)]
         return cdist.max_over_ranks(time.perf_counter() - t0, device), c16h, prh
 
-    # pass 2 of the docstring first (it also serves as extra warm-up): frames resident in HBM, results left there
-    dt = timed()
+    # pass 2 of the docstring first (it also serves as extra warm-up): frames resident in HBM, results left there.  A plain run
+    # times it only when it is the headline (--no-host-path).  Otherwise the same HBM-resident work runs untimed for
+    # --preroll-seconds of wall time, whatever K is, in place of the device time pass 2 used to spend before the host pass
+    dt, dump = None, None
+    if args.full or clip_host is None:
+        dt = timed()
+        if args.dump_outputs and clip_host is None:
+            dump = sample_rows(last_out)
+    else:
+        warm_steps, t_end = 0, time.perf_counter() + args.preroll_seconds
+        while time.perf_counter() < t_end:
+            run(min(cap_steps, 32))
+            torch.cuda.synchronize(device)
+            warm_steps += min(cap_steps, 32)
+        print(f"[bench] warm-up: {warm_steps} HBM-resident steps in {args.preroll_seconds:.1f} s; pre-roll: {preroll_iters} x "
+              f"{preroll_steps} steps", file=sys.stderr, flush=True)
     # pass 1: the timed region proper (EXACTLY K steps, nothing instrumented): pinned host memory -> host memory -> value
     dt_host, host_equal, dt_r3 = None, None, None
     if clip_host is not None:
@@ -591,9 +661,10 @@ def main() -> None:
                 torch.empty((K * B, BEHAVIORS), dtype=torch.float32, pin_memory=True)]
         del warm
         dt_host, c16h, prh = timed_host()
+        dump = sample_rows(last_out) if args.dump_outputs else None
         # the SAME pass as rounds 1-3 defined `value`: RGB bytes over PCIe (green picked on the device), no untimed
         # pre-roll before the clock - so that a reader can separate kernel gains from changes of the metric's definition
-        if world == 1 and args.host_input == "green":
+        if args.full and world == 1 and args.host_input == "green":
             args.host_input = "rgb"
             try:
                 run_host_gathered(max(Wm, 1))
@@ -604,18 +675,19 @@ def main() -> None:
                 dt_r3 = time.perf_counter() - t0
             finally:
                 args.host_input = "green"
-        c16d, prd = run(K)                        # the two passes must agree bit for bit
-        torch.cuda.synchronize(device)
-        if rank == 0:
-            host_equal = bool(np.array_equal(c16d.cpu().numpy().view(np.uint16), c16h.view(np.uint16)) and
-                              np.array_equal(prd.cpu().numpy(), prh))
+        if args.full:
+            c16d, prd = run(K)                    # the two passes must agree bit for bit
+            torch.cuda.synchronize(device)
+            if rank == 0:
+                host_equal = bool(np.array_equal(c16d.cpu().numpy().view(np.uint16), c16h.view(np.uint16)) and
+                                  np.array_equal(prd.cpu().numpy(), prh))
     # pass 2: the same K steps again with every kernel launch bracketed by HIP events on the launch
     # stream -> per-kernel durations for the roofline (the events cost a few % of throughput, which
     # is why they are kept out of pass 1; both wall times are reported)
     # That pass runs one batch at a time (one compute lane): with two batches in flight a kernel's event
     # interval also contains the other lane's kernels, so it would not be that kernel's duration.
     prof, dt_events = {}, None
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         torch.cuda.synchronize(device)
         enc.set_lanes(1)
         preroll(run)                              # (outside the profile: its launches must not be counted into K steps' shares)
@@ -629,7 +701,7 @@ def main() -> None:
     # has run that yet, so it gets a watchdog: if it has not come back in time, the line below is still printed (with the
     # failure stated) and the ranks exit, instead of hanging the run that produced every other number in it.
     files = None
-    if args.files > 0:
+    if args.full and args.files > 0:
         import threading
         box: dict = {}
 
@@ -660,7 +732,7 @@ def main() -> None:
         finished.set()
         return
     frames_total = K * B * world
-    hbm_value = frames_total / dt
+    hbm_value = frames_total / dt if dt is not None else None
     value = frames_total / dt_host if dt_host is not None else hbm_value
     dt_value = dt_host if dt_host is not None else dt
     flops_frame = cfg.flops_per_frame(args.hw, args.hw) + hcfg.flops_per_frame_naive()
@@ -677,7 +749,7 @@ def main() -> None:
                               "cbas_fused_push_u8_host (H2D of the RGB bytes on the copy stream, green picked on the device)") +
                              " -> encoder -> head -> fp16 CLS rows + fp32 probabilities in host memory"
                              + (" of rank 0 (RCCL gather inside the timed region)" if world > 1 else "") +
-                             ": SURVEY section 8(d)'s metric definition, PCIe inclusive (HBM-resident figure: hbm_resident)")
+                             ": SURVEY section 8(d)'s metric definition, PCIe inclusive" + (" (HBM-resident figure: hbm_resident)" if args.full else ""))
                             if dt_host is not None else
                             "uint8 RGB frames resident in HBM before the clock starts; results left in HBM (--no-host-path)",
                    "batch": B, "batches_in_flight": args.lanes, "frames_per_gpu": K * B, "frame": [args.hw, args.hw], "parallelism": f"clip-per-gpu x{world}",
@@ -693,7 +765,7 @@ def main() -> None:
                    "head_gflop_per_frame": round(hcfg.flops_per_frame_naive() / 1e9, 4)},
         "end_to_end_tflops": round(value * flops_frame / 1e12, 2),
     }
-    if dt_host is not None:
+    if args.full and dt_host is not None:
         out["hbm_resident"] = {
             "value": round(hbm_value, 2), "unit": "frames/s", "ms_per_step": round(dt / K * 1e3, 4),
             "what": "the same K steps with the uint8 frames already in HBM when the clock starts and the CLS rows / "
@@ -706,7 +778,7 @@ def main() -> None:
                                               "the device), W warm-up steps and NO untimed pre-roll before the K timed steps"}
     if files is not None:
         out["files_path"] = files
-    if not args.no_gates and not hung:
+    if args.full and not args.no_gates and not hung:
         out["gates"] = gates(enc, head, args.model, args.hw, args.precision)
         # `value` is the 16-bit configuration BASELINE.json names; whether ITS labels are the reference's is stated here, next
         # to it, so that nobody reads the fp16 figure as meeting the label half of the contract (label_exact does)
@@ -714,7 +786,7 @@ def main() -> None:
     # Secondary leg, N = 1 only: the SAME model, head and clip through precision 4 - fp32 storage / attention / LayerNorm with
     # the GEMM products as three-term fp16 splits - the mode whose argmax labels are the reference's.  `value`
     # above stays the default fp16-operand mode's, as BASELINE.json's config asks; this says what label identity costs.
-    if (world == 1 and args.precision == 0 and not args.no_label_exact and not args.no_gates and not hung
+    if (args.full and world == 1 and args.precision == 0 and not args.no_label_exact and not args.no_gates and not hung
             and (args.model, args.hw) == ("vitb16", 224)):
         enc4 = None
         try:
@@ -793,13 +865,15 @@ def main() -> None:
                                                      "resident; taken in its own runs, not in this one")
             except Exception:  # noqa: BLE001
                 pass
-    if world == 1 and not args.no_cpu_baseline and not hung:
+    if args.full and world == 1 and not args.no_cpu_baseline and not hung:
         out["cpu_baseline"] = cpu_baseline(args.model, args.hw, args.cpu_frames, 8)
         if (args.model, args.hw) == ("vitb16", 224):
             # BASELINE.md section 4 / configs[0]: the reference's own CPU-runnable case (ViT-S/16, 64 frames, batch 8) beside it
             out["cpu_baseline"]["cfg1_vits16"] = cpu_baseline("vits16", 224, 64, 8)
     if hung:
         out["error"] = "files_path pass hung (watchdog fired): gates and cpu_baseline skipped, exit code 3"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dump)
     finished.set()
     emit(json.dumps(out))
     if hung:

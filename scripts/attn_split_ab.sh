@@ -7,7 +7,7 @@ set -e
 OUT=$GRAFT_REPO_ROOT/gpurun_out/attn_ab
 mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
-B="--precision 4 --no-label-exact --no-cpu-baseline --no-gates --files 0"
+B="--full --precision 4 --no-label-exact --no-cpu-baseline --no-gates --files 0"
 for round in 1 2; do
   for form in 0 1; do
     CBAS_ATTN_SPLIT_FORM=$form python bench.py $B > $OUT/bench_form${form}_r${round}.json 2>> $OUT/bench.err
@@ -15,7 +15,7 @@ for round in 1 2; do
   done
 done
 cd /tmp && export TMPDIR=/tmp
-Q="--no-cpu-baseline --no-host-path --no-gates --files 0 --preroll-seconds 0 --no-label-exact --lanes 1 --precision 4 --steps 60 --warmup 3"
+Q="--full --no-cpu-baseline --no-host-path --no-gates --files 0 --preroll-seconds 0 --no-label-exact --lanes 1 --precision 4 --steps 60 --warmup 3"
 for form in 0 1; do
   export CBAS_ATTN_SPLIT_FORM=$form
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_form$form -- python3 $GRAFT_REPO_ROOT/bench.py $Q > $OUT/prof_form$form.json 2>> $OUT/prof.err

@@ -11,7 +11,7 @@ for round in $(seq 1 ${ROUNDS:-2}); do
   for gm in ${GMS:-0 2 3 4 6}; do
     V=${GM_VAR:-CBAS_GEMM_GM}                       # GM_VAR=CBAS_GEMM_GM_WIDE: only the shapes with N >= 2048 (precision 4)
     if [ $gm = 0 ]; then unset $V; else export $V=$gm; fi
-    python bench.py --precision $P --no-label-exact --no-cpu-baseline --no-host-path --files 0 --steps 40 --warmup 3 > $OUT/bench_p${P}_gm${gm}_r$round.json 2>> $OUT/bench.err
+    python bench.py --full --precision $P --no-label-exact --no-cpu-baseline --no-host-path --files 0 --steps 40 --warmup 3 > $OUT/bench_p${P}_gm${gm}_r$round.json 2>> $OUT/bench.err
     python3 -c "
 import json; d=json.load(open('$OUT/bench_p${P}_gm${gm}_r$round.json')); k=d['roofline']['by_kernel']; g=d.get('gates') or {}
 print(json.dumps({'precision': $P, 'group_m': $gm, 'round': $round, 'value': d['value'], 'gemm_us': {n: k[n]['avg_us'] for n in k if 'gemm' in n}, 'cls_rel_err_max': g.get('cls_rel_err_max')}))" | tee -a $OUT/summary.jsonl

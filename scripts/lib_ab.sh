@@ -7,7 +7,7 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/lib_ab_$TAG
 mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
 cp cbas_amd/libcbas_mi355x.so /tmp/cbas_new.so
-B="--no-label-exact --no-cpu-baseline --files 0"
+B="--full --no-label-exact --no-cpu-baseline --files 0"
 for round in 1 2; do
   for which in old new; do
     if [ $which = old ]; then cp $OLD cbas_amd/libcbas_mi355x.so; else cp /tmp/cbas_new.so cbas_amd/libcbas_mi355x.so; fi
