@@ -118,6 +118,8 @@ DEBUG_SIGNATURES = {
     "cbas_head_debug_expand_module": (c_int, [c_void_p, C.c_char_p, C.c_char_p]),
     "cbas_head_debug_expand_repeat": (c_int, [c_void_p, c_int, c_int]),
     "cbas_head_debug_expand_stats": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int]),
+    "cbas_debug_gemm_run": (c_int, [c_void_p]),
+    "cbas_debug_attention_run": (c_int, [c_void_p]),
     "cbas_debug_build": (c_int, []),
 }
 

@@ -10,6 +10,7 @@
 
 #include "api_common.h"
 #include "kernels.h"
+#include "vit32_epilogue.h"
 
 #if !CBAS_BUILD_DEBUG
 #error "api_debug.hip belongs to the debug build only (-DCBAS_BUILD_DEBUG=1)"
@@ -432,5 +433,198 @@ extern "C" int cbas_debug_gemm_f8(int M, int N, int K, int tile, const float* A_
     if (W8_host) HIP_TRY(hipMemcpy(W8_host, W8, (int64_t)N * K, hipMemcpyDeviceToHost));
     if (Wsc_host) HIP_TRY(hipMemcpy(Wsc_host, Wsc, (int64_t)N * K / 32, hipMemcpyDeviceToHost));
     hipFree(A); hipFree(W); hipFree(x); hipFree(bias); hipFree(lam); hipFree(A8); hipFree(W8); hipFree(Asc); hipFree(Wsc);
+    return CBAS_OK;
+}
+
+// ---- tests: one GEMM / attention launch on host operands (include/cbas_mi355x_debug.h) -----------------------------------
+namespace {
+// q | k | v rows [rows][3D] fp32 (q already x 1/8) -> the head-split operands of precision 4, as the q|k|v epilogue writes
+// them (store_head_split4 with the ATT_* scales; q's 1/8 is already in the value); q_rows: a [rows][D] q image (sec0 = 0 only)
+__global__ void pack_head_split_kernel(const float* __restrict__ src, float* __restrict__ dst, int64_t rows, int width, int D) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;     // one thread = 4 consecutive columns
+    const int per_row = width / 4;
+    if (i >= rows * per_row) return;
+    const int64_t r = i / per_row;
+    const int c = (int)(i - r * per_row) * 4;
+    const int sec = c / D, hc = c - sec * D;
+    const float sc = sec == 0 ? ATT_QS : (sec == 1 ? ATT_KS : ATT_VS);
+    store_head_split4(dst + r * width + sec * D + (hc & ~63), hc & 63, *reinterpret_cast<const f32x4*>(src + r * width + c), sc);
+}
+
+struct DevBufs {                       // frees what it holds on every return path
+    std::vector<void*> p;
+    template <typename T> hipError_t alloc(T** out, size_t bytes) {
+        *out = nullptr;
+        const hipError_t e = hipMalloc(reinterpret_cast<void**>(out), bytes ? bytes : 4);
+        if (e == hipSuccess) p.push_back(*out);
+        return e;
+    }
+    ~DevBufs() { for (void* q : p) (void)hipFree(q); }
+};
+}  // namespace
+
+extern "C" int cbas_debug_gemm_run(const cbas_debug_gemm_args* a) {
+    if (!a || a->struct_bytes != (int64_t)sizeof(cbas_debug_gemm_args))
+        return cbas_fail(CBAS_EINVAL, "cbas_debug_gemm_args: struct_bytes %lld, library expects %lld", a ? (long long)a->struct_bytes : -1ll,
+                         (long long)sizeof(cbas_debug_gemm_args));
+    const int arith = a->arith, epi = a->epi;
+    if (arith != 0 && arith != 1 && arith != 3 && arith != 4) return cbas_fail(CBAS_EINVAL, "arith %d", arith);
+    if (epi < EPI_PATCH || epi > EPI_GELU) return cbas_fail(CBAS_EINVAL, "epi %d", epi);
+    if (a->M <= 0 || a->M_alloc < a->M || a->K <= 0 || a->lda < a->K || a->ldo < a->N || a->N <= 0 || !a->A || !a->W || !a->bias || !a->out)
+        return cbas_fail(CBAS_EINVAL, "bad GEMM test shape / pointers");
+    if ((epi == EPI_RESID && !a->lambda) || (arith == 4 && a->lda % 32))
+        return cbas_fail(CBAS_EINVAL, "EPI_RESID needs lambda; split operands need lda %% 32 == 0");
+    const bool patch = epi == EPI_PATCH, rope = epi == EPI_QKV && a->rope_cos && a->rope_sin;
+    if (patch && (a->P <= 0 || a->M % a->P || (int64_t)(a->M / a->P) * a->T > a->out_rows || a->T < a->n_prefix + a->P))
+        return cbas_fail(CBAS_EINVAL, "EPI_PATCH: M must be frames x P and out_rows >= frames x T");
+    if (!patch && a->out_rows < a->M) return cbas_fail(CBAS_EINVAL, "out_rows < M");
+    if (epi == EPI_QKV && (a->T <= 0 || a->n_prefix < 0)) return cbas_fail(CBAS_EINVAL, "EPI_QKV needs T and n_prefix");
+    if (rope && (a->rope_nh <= 0 || a->rope_nw <= 0 || a->P != a->rope_nh * a->rope_nw || a->T > a->n_prefix + a->P))
+        return cbas_fail(CBAS_EINVAL, "RoPE: P = nh x nw and T <= n_prefix + P");
+    const bool out16 = (arith == 0 || arith == 1) && (epi == EPI_QKV || epi == EPI_GELU);
+    const size_t osz = (size_t)a->out_rows * a->ldo * (out16 ? 2 : 4);
+    const size_t na = (size_t)a->M_alloc * a->lda, nw = (size_t)a->N * a->K;
+    DevBufs B;
+    float *A32, *W32, *bias, *lam = nullptr, *pos = nullptr, *rc = nullptr, *rs = nullptr, *fac = nullptr;
+    void* out;
+    HIP_TRY(B.alloc(&A32, na * 4));
+    HIP_TRY(B.alloc(&W32, nw * 4));
+    HIP_TRY(B.alloc(&bias, (size_t)a->N * 4));
+    HIP_TRY(B.alloc(&out, osz));
+    HIP_TRY(hipMemcpy(A32, a->A, na * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(W32, a->W, nw * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(bias, a->bias, (size_t)a->N * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(out, a->out, osz, hipMemcpyHostToDevice));
+    if (a->lambda) { HIP_TRY(B.alloc(&lam, (size_t)a->N * 4)); HIP_TRY(hipMemcpy(lam, a->lambda, (size_t)a->N * 4, hipMemcpyHostToDevice)); }
+    if (patch && a->pos) {
+        HIP_TRY(B.alloc(&pos, (size_t)a->P * a->N * 4));
+        HIP_TRY(hipMemcpy(pos, a->pos, (size_t)a->P * a->N * 4, hipMemcpyHostToDevice));
+    }
+    const int nh = a->rope_nh, nwd = a->rope_nw;
+    if (rope) {
+        const size_t nt = (size_t)a->P * 64;
+        HIP_TRY(B.alloc(&rc, nt * 4));
+        HIP_TRY(B.alloc(&rs, nt * 4));
+        HIP_TRY(hipMemcpy(rc, a->rope_cos, nt * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(rs, a->rope_sin, nt * 4, hipMemcpyHostToDevice));
+        if (a->rope_lds) {             // the by-axis copy, built from the tables as ensure_rope builds it (api_enc.hip)
+            std::vector<float> f((size_t)(nh + nwd) * 32);
+            for (int iy = 0; iy < nh; ++iy)
+                for (int d = 0; d < 16; ++d) {
+                    f[(size_t)iy * 32 + d] = a->rope_cos[(size_t)(iy * nwd) * 64 + d];
+                    f[(size_t)iy * 32 + 16 + d] = a->rope_sin[(size_t)(iy * nwd) * 64 + d];
+                }
+            for (int ix = 0; ix < nwd; ++ix)
+                for (int d = 0; d < 16; ++d) {
+                    f[(size_t)(nh + ix) * 32 + d] = a->rope_cos[(size_t)ix * 64 + 16 + d];
+                    f[(size_t)(nh + ix) * 32 + 16 + d] = a->rope_sin[(size_t)ix * 64 + 16 + d];
+                }
+            HIP_TRY(B.alloc(&fac, f.size() * 4));
+            HIP_TRY(hipMemcpy(fac, f.data(), f.size() * 4, hipMemcpyHostToDevice));
+        }
+    }
+    const unsigned magic = rope ? (unsigned)((1ull << 32) / (unsigned)nwd) + 1u : 0u;
+    int rcode = 0;
+    if (arith == 0 || arith == 1) {
+        f16 *A16, *Wh, *Wl = nullptr;
+        HIP_TRY(B.alloc(&A16, na * 2));
+        HIP_TRY(B.alloc(&Wh, nw * 2));
+        if (arith == 1) HIP_TRY(B.alloc(&Wl, nw * 2));
+        LAUNCH_TRY(launch_convert_f16(A32, A16, nullptr, (int64_t)na, 0));
+        LAUNCH_TRY(launch_convert_f16(W32, Wh, Wl, (int64_t)nw, 0));
+        GemmParams p{};
+        p.tile = a->tile; p.group_m = a->group_m; p.A = A16; p.lda = a->lda; p.W = Wh; p.W_lo = Wl;
+        p.M = a->M; p.M_pad = a->M_alloc; p.N = a->N; p.K = a->K; p.bias = bias; p.lambda = lam; p.ldo = a->ldo;
+        if (out16) p.out_f16 = (f16*)out; else p.out_f32 = (float*)out;
+        p.patches_per_frame = a->P; p.tokens_per_frame = a->T; p.n_prefix = a->n_prefix; p.in_scale = a->in_scale; p.pos = pos;
+        p.rope_cos = rc; p.rope_sin = rs; p.rope_fac = fac; p.rope_nh = nh; p.rope_nw = nwd; p.rope_magic = magic;
+        p.D = a->D; p.sec0 = a->sec0;
+        rcode = launch_gemm((GemmEpilogue)epi, p, 0);
+    } else {
+        const bool split = arith == 4;
+        const float *Ag = A32, *Wg = W32;
+        if (split) {
+            float *As, *Ws;
+            HIP_TRY(B.alloc(&As, na * 4));
+            HIP_TRY(B.alloc(&Ws, nw * 4));
+            LAUNCH_TRY(launch_pack_split_weight(A32, As, a->M_alloc, a->lda, a->a_scale, 0));
+            LAUNCH_TRY(launch_pack_split_weight(W32, Ws, a->N, a->K, a->w_scale, 0));
+            Ag = As; Wg = Ws;
+        }
+        Gemm32VitParams p{};
+        p.A = Ag; p.lda = a->lda; p.W = Wg; p.M = a->M; p.N = a->N; p.K = a->K; p.bias = bias; p.lambda = lam;
+        p.out = (float*)out; p.ldo = a->ldo;
+        p.patches_per_frame = a->P; p.tokens_per_frame = a->T; p.n_prefix = a->n_prefix; p.pos = pos;
+        p.rope_cos = rc; p.rope_sin = rs; p.rope_fac = fac; p.rope_nh = nh; p.rope_nw = nwd; p.rope_magic = magic;
+        p.D = a->D; p.sec0 = a->sec0;
+        p.split = split; p.a_scale = split ? a->a_scale : 1.f; p.w_scale = split ? a->w_scale : 1.f; p.out_scale = a->out_scale;
+        if (split) {
+            vit32_split_set_forms(a->tile < 0 ? 0 : a->forms);
+            gemm_split_pp_set_tile(a->tile > 0 ? a->tile : 0, nullptr);
+        }
+        rcode = launch_gemm_f32_vit((GemmEpilogue)epi, p, 0);
+        if (split) { gemm_split_pp_set_tile(0, nullptr); vit32_split_set_forms(-1); }
+    }
+    if (rcode) return cbas_fail(CBAS_EINVAL, "GEMM launch failed (arith %d, epi %d, tile %d: rc=%d)", arith, epi, a->tile, rcode);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(a->out, out, osz, hipMemcpyDeviceToHost));
+    return CBAS_OK;
+}
+
+extern "C" int cbas_debug_attention_run(const cbas_debug_attention_args* a) {
+    if (!a || a->struct_bytes != (int64_t)sizeof(cbas_debug_attention_args))
+        return cbas_fail(CBAS_EINVAL, "cbas_debug_attention_args: struct_bytes %lld, library expects %lld", a ? (long long)a->struct_bytes : -1ll,
+                         (long long)sizeof(cbas_debug_attention_args));
+    const int arith = a->arith, n = a->n, T = a->T, D = a->D;
+    if (arith != 0 && arith != 3 && arith != 4) return cbas_fail(CBAS_EINVAL, "arith %d", arith);
+    const int64_t rows = (int64_t)n * T, orows_min = a->q_cls ? n : rows;
+    if (n <= 0 || T <= 0 || D != a->n_heads * 64 || a->rows_alloc < rows || a->out_rows < orows_min || !a->qkv || !a->out)
+        return cbas_fail(CBAS_EINVAL, "bad attention test shape / pointers");
+    // the device image is padded past the caller's rows (zeros): whatever a kernel may stage beyond the last frame lies inside it
+    const int64_t dev_rows = round_up(a->rows_alloc, 256) + 256;
+    const size_t nq = (size_t)a->rows_alloc * 3 * D, ndev = (size_t)dev_rows * 3 * D, ncls = (size_t)n * D;
+    const size_t osz = (size_t)a->out_rows * D * (arith == 0 ? 2 : 4);
+    DevBufs B;
+    float *q32, *c32 = nullptr;
+    void* out;
+    HIP_TRY(B.alloc(&q32, ndev * 4));
+    HIP_TRY(hipMemset(q32, 0, ndev * 4));
+    HIP_TRY(hipMemcpy(q32, a->qkv, nq * 4, hipMemcpyHostToDevice));
+    if (a->q_cls) {
+        HIP_TRY(B.alloc(&c32, (size_t)round_up(n, 256) * D * 4));
+        HIP_TRY(hipMemset(c32, 0, (size_t)round_up(n, 256) * D * 4));
+        HIP_TRY(hipMemcpy(c32, a->q_cls, ncls * 4, hipMemcpyHostToDevice));
+    }
+    HIP_TRY(B.alloc(&out, osz));
+    HIP_TRY(hipMemcpy(out, a->out, osz, hipMemcpyHostToDevice));
+    int rc = 0;
+    if (arith == 0) {
+        f16 *q16, *c16 = nullptr;
+        HIP_TRY(B.alloc(&q16, ndev * 2));
+        LAUNCH_TRY(launch_convert_f16(q32, q16, nullptr, (int64_t)ndev, 0));
+        if (c32) {
+            HIP_TRY(B.alloc(&c16, (size_t)round_up(n, 256) * D * 2));
+            LAUNCH_TRY(launch_convert_f16(c32, c16, nullptr, (int64_t)round_up(n, 256) * D, 0));
+        }
+        rc = launch_attention(q16, c16, out, nullptr, 0, n, T, D, a->n_heads, 0);
+    } else if (arith == 3) {
+        rc = launch_attention_f32(q32, c32, (float*)out, n, T, D, a->n_heads, 0.f, 0);
+    } else {
+        float *qs, *cs = nullptr;
+        HIP_TRY(B.alloc(&qs, ndev * 4));
+        const int64_t t4 = dev_rows * (3 * D / 4);
+        hipLaunchKernelGGL(pack_head_split_kernel, dim3((unsigned)((t4 + 255) / 256)), dim3(256), 0, 0, q32, qs, dev_rows, 3 * D, D);
+        if (c32) {
+            const int64_t crow = round_up(n, 256);
+            HIP_TRY(B.alloc(&cs, (size_t)crow * D * 4));
+            const int64_t c4 = crow * (D / 4);
+            hipLaunchKernelGGL(pack_head_split_kernel, dim3((unsigned)((c4 + 255) / 256)), dim3(256), 0, 0, c32, cs, crow, D, D);
+        }
+        HIP_TRY(hipGetLastError());
+        rc = launch_attention_f32(qs, cs, (float*)out, n, T, D, a->n_heads, 16.f, 0);    // the encoder's context scale (api_enc.hip)
+    }
+    if (rc) return cbas_fail(CBAS_EINVAL, "attention launch failed (arith %d, T %d: rc=%d)", arith, T, rc);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(a->out, out, osz, hipMemcpyDeviceToHost));
     return CBAS_OK;
 }

@@ -78,6 +78,51 @@ int cbas_debug_overlap(int mode, int iters, float* ms_out);
 int cbas_debug_gemm_f8(int M, int N, int K, int tile, const float* A_host, const float* W_host, float* out_host,
                        uint8_t* A8_host, uint32_t* Asc_host, uint8_t* W8_host, uint32_t* Wsc_host);
 
+/* Tests: ONE library GEMM launch on host operands (tests/test_gpu_kernel_reference.py compares it with a float64 reference).
+ * The harness converts / splits the fp32 host operands on the device with the library's own routines (launch_convert_f16,
+ * launch_pack_split_weight), uploads the initial output buffer (the residual stream for EPI_RESID / EPI_PATCH, canaries
+ * elsewhere), launches, and copies the WHOLE output buffer back: rows >= M and columns >= N are the caller's canaries.
+ *   arith  0: fp16 A and W (launch_gemm)   1: fp16 A, W as hi + lo (launch_gemm)   3: fp32 (launch_gemm_f32_vit)
+ *          4: split operands (launch_gemm_f32_vit: ping-pong / skinny / 128 x 128 forms)
+ *   epi    EPI_PATCH 0, EPI_QKV 1, EPI_RESID 2, EPI_GELU 3
+ *   tile   arith 0 / 1: a GemmTile id (0 = the library's pick); arith 4: 0 = the planner, 128 / 160 / 192 / 256 = a ping-pong
+ *          tile height, -1 = the 128 x 128 kernels (every form off)
+ *   forms  arith 4, tile >= 0: vit32_split_set_forms bits (-1: the environment's); restored to -1 on return
+ * out holds out_rows x ldo elements in the output's native width: fp32 (EPI_PATCH / EPI_RESID, every arith 3 epilogue),
+ * fp16 (EPI_QKV / EPI_GELU of arith 0 / 1), or the raw split image at fp32 size (EPI_QKV / EPI_GELU of arith 4: the head-split
+ * layout of the attention operands, resp. the GEMM operand layout scaled by out_scale); the test decodes it. */
+typedef struct cbas_debug_gemm_args {
+    int64_t struct_bytes;        /* sizeof(cbas_debug_gemm_args): a mismatch is rejected */
+    int arith, epi, tile, forms, group_m;
+    int M, M_alloc, N, K, lda, ldo, D, sec0;
+    int T, n_prefix, P, rope_nh, rope_nw, rope_lds;   /* rope_lds: hand the kernels the by-axis table (LDS copy) too */
+    int out_rows;                /* rows of the output buffer (>= M; EPI_PATCH: frames x T) */
+    float in_scale, a_scale, w_scale, out_scale;
+    const float* A;              /* [M_alloc][lda] */
+    const float* W;              /* [N][K] */
+    const float* bias;           /* [N] */
+    const float* lambda;         /* [N] (EPI_RESID), or NULL */
+    const float* pos;            /* [P][N] (EPI_PATCH), or NULL */
+    const float* rope_cos;       /* [P][64] (EPI_QKV), or NULL: no RoPE */
+    const float* rope_sin;
+    void* out;                   /* in / out: [out_rows][ldo] */
+} cbas_debug_gemm_args;
+int cbas_debug_gemm_run(const cbas_debug_gemm_args* a);
+
+/* Tests: ONE attention launch on a host q|k|v image [rows_alloc][3D] (q already x 1/8 and RoPE'd; rows_alloc >= n T, the
+ * rows past n T are uploaded as given).  arith 0: fp16 operands (launch_attention); 3: fp32 (launch_attention_f32); 4: the
+ * head-split operands of precision 4 (packed with store_head_split4 and the ATT_* scales), context in the split operand
+ * layout x 16 as the encoder uses it.  q_cls [n][D] or NULL: the CLS-only form.  out: [out_rows][D] (fp16 / fp32 / split
+ * image), uploaded first and copied back whole: rows >= n T (n) are the caller's canaries. */
+typedef struct cbas_debug_attention_args {
+    int64_t struct_bytes;
+    int arith, n, T, D, n_heads, rows_alloc, out_rows;
+    const float* qkv;
+    const float* q_cls;
+    void* out;
+} cbas_debug_attention_args;
+int cbas_debug_attention_run(const cbas_debug_attention_args* a);
+
 /* Root-cause probe (round 5): run a kernel from a separately built code object IN PLACE of the library's head_expand_kernel
  * on this handle (same grid, block, dynamic LDS and arguments: scripts/probes/expand_r4/expand_r4.hip has the signature).
  * hsaco_path = NULL restores the library's kernel.  scripts/expand_rootcause.py builds instruction-level variants of the

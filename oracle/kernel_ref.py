@@ -1,0 +1,278 @@
+"""ORACLE (test infrastructure, not product code): float64 references of single GEMM and attention launches, the
+exact precision-3 accumulator, and element-wise error bounds derived from where each kernel rounds.
+
+Used by tests/test_gpu_kernel_reference.py (the kernels through cbas_debug_gemm_run / cbas_debug_attention_run) and
+tests/test_kernel_reference_bounds.py (the references and bounds themselves, on the CPU).
+
+Units: u32 = 2^-24 (fp32 unit roundoff), u16 = 2^-11 (fp16).  A bound is a float64 array shaped like the output; a kernel
+output y passes when |y - ref| <= bound everywhere (non-finite y never passes).  Every bound is a sum of the terms its
+docstring names; no term is fitted to measured errors.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+from oracle.vit_oracle import _rotate_half, gelu_erf, rope_cos_sin  # noqa: F401  (re-exported for the tests)
+
+try:
+    from scipy.special import erf as _erf64
+except Exception:  # pragma: no cover
+    _erf64 = np.vectorize(math.erf, otypes=[np.float64])
+
+U32 = 2.0 ** -24
+U16 = 2.0 ** -11
+F16_SUB = 2.0 ** -25          # half of fp16's subnormal step: the absolute rounding error below 2^-14
+EPI_PATCH, EPI_QKV, EPI_RESID, EPI_GELU = 0, 1, 2, 3
+ATT_QS, ATT_KS, ATT_VS, ATT_CTX = 16.0, 4.0, 4.0, 16.0      # vit32_epilogue.h / api_enc.hip split scales
+GELU_SLOPE = 1.13             # max |d gelu / dx| (at x ~ 1.5: 1.1289)
+
+
+# ---- operand roundings ------------------------------------------------------------------------------------------------
+def f16(x) -> np.ndarray:
+    """fp32 -> fp16 (round to nearest even, as the device's conversion), returned as float64."""
+    return np.asarray(x, np.float32).astype(np.float16).astype(np.float64)
+
+
+def split_halves(x, scale: float):
+    """precision 4's split of an fp32 value (vit32_epilogue.h store_split4): s = x * scale (power of two, exact),
+    hi = fp16(s), lo = fp16(s - hi) (the fp32 subtraction is exact by Sterbenz).  float64 hi, lo (scaled units)."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        s = np.asarray(x, np.float32) * np.float32(scale)
+        hi = s.astype(np.float16)
+        lo = (s - hi.astype(np.float32)).astype(np.float16)
+    return hi.astype(np.float64), lo.astype(np.float64)
+
+
+def split_value(x, scale: float) -> np.ndarray:
+    hi, lo = split_halves(x, scale)
+    return (hi + lo) / scale
+
+
+def decode_split_operand(raw: np.ndarray, ncols: int, scale: float) -> np.ndarray:
+    """The GEMM-operand split image (store_split4: per 32-column K-tile 128 bytes = [hi 32 x fp16 | lo 32 x fp16], value
+    k = 16 h + 4 g + e at position 8 g + 4 h + e) of rows [R][ld] float32 -> float64 [R][ncols] = (hi + lo) / scale."""
+    R = raw.shape[0]
+    h = np.ascontiguousarray(raw[:, :ncols]).view(np.float16).reshape(R, ncols // 32, 2, 32).astype(np.float64)
+    k = np.arange(32)
+    pos = 8 * ((k % 16) // 4) + 4 * (k // 16) + k % 4
+    return ((h[:, :, 0, pos] + h[:, :, 1, pos]) / scale).reshape(R, ncols)
+
+
+def decode_head_split(raw: np.ndarray, ncols: int, scales) -> np.ndarray:
+    """The attention-operand split image (store_head_split4: per 64-column head 256 bytes = [hi 64 | lo 64] fp16 in d
+    order) -> float64 (hi + lo) / scale; `scales` gives the scale per D-wide section (q | k | v) of the columns."""
+    R = raw.shape[0]
+    h = np.ascontiguousarray(raw[:, :ncols]).view(np.float16).reshape(R, ncols // 64, 2, 64).astype(np.float64)
+    v = (h[:, :, 0] + h[:, :, 1]).reshape(R, ncols)
+    sc = np.repeat(np.asarray(scales, np.float64), ncols // len(scales))
+    return v / sc
+
+
+# ---- exact fp32 accumulation ------------------------------------------------------------------------------------------
+def f32_mfma_k_order(K: int) -> np.ndarray:
+    """k order of the precision-3 GEMM (vit_f32.hip gemm_f32_vit_kernel): per 32-wide K-tile, kk = 0, 1 and e = 0..3 issue
+    one v_mfma_f32_16x16x4_f32 each, whose four products are k = 16 kk + 4 g + e for lane groups g = 0..3 (the 16-byte
+    chunk kk * 4 + g of the row).  The MFMA is a bitwise fmaf chain over its k index g (MI355X_MICROARCH.md, matrix cores)."""
+    kt, kk, e, g = np.meshgrid(np.arange(K // 32), np.arange(2), np.arange(4), np.arange(4), indexing="ij")
+    return (kt * 32 + kk * 16 + g * 4 + e).reshape(-1)
+
+
+def round_f32_with_residual(s: np.ndarray, err: np.ndarray) -> np.ndarray:
+    """Correctly rounded fp32 of the exact value s + err, where s = fl64(s + err) (a TwoSum pair).  fp32(s) is right
+    unless s sits exactly on an fp32 midpoint (representable in float64): then the sign of err decides."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        r = s.astype(np.float32)
+        r64 = r.astype(np.float64)
+        other = np.nextafter(r, np.where(s > r64, np.float32(np.inf), np.float32(-np.inf)).astype(np.float32))
+        tie = np.isfinite(s) & (s != r64) & (s - r64 == other.astype(np.float64) - s)
+        # at a tie r is the even neighbour; the exact value lies on the side err points to
+        pick = np.where(err > 0, np.maximum(r, other), np.minimum(r, other))
+        r = np.where(tie & (err != 0), pick, r)
+    return r
+
+
+def fmaf_chain(A: np.ndarray, W: np.ndarray, order=None) -> np.ndarray:
+    """C[m][n] = fmaf(a_k, w_k, C) over k in `order` (default 0..K-1), starting from +0, every step rounded once to fp32:
+    the product a_k w_k is exact in float64 (24 + 24 bits), the sum is a TwoSum pair, rounded with
+    round_f32_with_residual.  A [M][K], W [N][K] fp32; returns fp32 [M][N]."""
+    A = np.asarray(A, np.float32).astype(np.float64)
+    W = np.asarray(W, np.float32).astype(np.float64)
+    ks = range(A.shape[1]) if order is None else order
+    acc = np.zeros((A.shape[0], W.shape[0]), np.float32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for k in ks:
+            p = A[:, k:k + 1] * W[None, :, k]
+            a = acc.astype(np.float64)
+            s = a + p
+            bb = s - a
+            err = (a - (s - bb)) + (p - bb)
+            acc = round_f32_with_residual(s, np.where(np.isfinite(err), err, 0.0))
+    return acc
+
+
+# ---- GEMM references --------------------------------------------------------------------------------------------------
+def gemm_acc(arith: int, A, W, a_scale: float = 1.0, w_scale: float = 1.0):
+    """float64 accumulator reference and its bound.  Returns (acc, E, S) with S = sum_k |a_k w_k| of the operands used.
+      arith 0 / 1: products of the fp16-rounded operands (fp16 A; W fp16, or W hi + lo for arith 1, whose residual
+                   2^-11 |w| rounding of lo adds 2^-22 |a w| per product); E = K u32 S (fp32 accumulation, products exact).
+      arith 3:     exact products of the fp32 operands; E = K u32 S.
+      arith 4:     exact products of the fp32 operands; each split product (a_hi w_hi + a_hi w_lo + a_lo w_hi) is off by
+                   the two representation residues and the dropped a_lo w_lo: 3 * 2^-22 |a w|; a low half below fp16's
+                   normal range rounds absolutely: 2^-25 / scale per operand, times the other operand; E adds K u32 S."""
+    A32 = np.asarray(A, np.float32)
+    W32 = np.asarray(W, np.float32)
+    K = A32.shape[1]
+    if arith in (0, 1):
+        a = f16(A32)
+        if arith == 1:
+            hi, lo = f16(W32), f16(np.asarray(W32, np.float32) - np.asarray(W32, np.float32).astype(np.float16).astype(np.float32))
+            w = hi + lo
+        else:
+            w = f16(W32)
+        acc = a @ w.T
+        S = np.abs(a) @ np.abs(w).T
+        E = K * U32 * S + (2.0 ** -22 * S if arith == 1 else 0.0)
+        return acc, E, S
+    a = A32.astype(np.float64)
+    w = W32.astype(np.float64)
+    acc = a @ w.T
+    S = np.abs(a) @ np.abs(w).T
+    E = K * U32 * S
+    if arith == 4:
+        sub = (np.ones_like(a) / a_scale) @ np.abs(w).T + np.abs(a) @ (np.ones_like(w) / w_scale).T
+        E = E + 3 * 2.0 ** -22 * S + 2 * F16_SUB * sub
+    return acc, E, S
+
+
+def out_rounding(ref: np.ndarray, kind: str) -> np.ndarray:
+    """Rounding of the stored output: 'f16' 2^-11 |ref| + 2^-25 (subnormal step), 'f32' 2^-24 |ref| (+ fp32's tiny
+    subnormal step), 'split' (hi + lo to 22 bits: 2^-22 |ref|, and 2^-25 / scale absolute - the caller adds the latter)."""
+    r = np.abs(ref)
+    if kind == "f16":
+        return U16 * r + F16_SUB
+    if kind == "split":
+        return 2.0 ** -22 * r
+    return U32 * r + 2.0 ** -149
+
+
+def gemm_epilogue_ref(epi: int, acc, E, S, *, bias, lam=None, x0=None, pos=None, in_scale=1.0, frames_P=None, T=None,
+                      n_prefix=0, cos=None, sin=None, D=None, sec0=0):
+    """float64 epilogue on the reference accumulator, and the propagated bound (before the output's own rounding).
+      PATCH  y = acc in_scale + b (+ pos[p]) scattered to row frame T + n_prefix + p; E' = in_scale E + 2 u32 (|acc in_scale| + |b| + |pos|)
+      RESID  y = x + (acc + b) lam;   E' = |lam| (E + u32 |acc + b|) + 2 u32 (|(acc + b) lam| + |y|)
+      QKV    v = acc + b; RoPE on patch rows of q, k: v c + rotate_half(v) s; q x 1/8;
+             E' = |c| Ev + |s| Ev[partner] + 3 u32 (|v c| + |v_p s|), Ev = E + u32 |v|  (x 1/8 exact)
+      GELU   y = gelu(acc + b) (float64 erf); E' = 1.13 (E + u32 |v|) + the caller's implementation term
+    Returns (ref rows as stored: [rows][N], bound, valid-row index for PATCH or None)."""
+    b = np.asarray(bias, np.float64)[None, :]
+    M, N = acc.shape
+    if epi == EPI_PATCH:
+        v = acc * in_scale + b
+        pe = np.zeros_like(v)
+        if pos is not None:
+            pe = np.asarray(pos, np.float64)[np.arange(M) % frames_P]
+        y = v + pe
+        Ey = in_scale * E + 2 * U32 * (np.abs(acc * in_scale) + np.abs(b) + np.abs(pe) + np.abs(y))
+        frame, p = np.arange(M) // frames_P, np.arange(M) % frames_P
+        return y, Ey, frame * T + n_prefix + p
+    if epi == EPI_RESID:
+        lamv = np.asarray(lam, np.float64)[None, :]
+        v = acc + b
+        y = np.asarray(x0, np.float64) + v * lamv
+        Ey = np.abs(lamv) * (E + U32 * np.abs(v)) + 2 * U32 * (np.abs(v * lamv) + np.abs(y))
+        return y, Ey, None
+    if epi == EPI_GELU:
+        v = acc + b
+        y = 0.5 * v * (1.0 + _erf64(v / math.sqrt(2.0)))
+        return y, GELU_SLOPE * (E + U32 * np.abs(v)), None
+    # EPI_QKV
+    v = acc + b
+    Ev = E + U32 * np.abs(v)
+    y = v.copy()
+    Ey = Ev.copy()
+    t = np.arange(M) % T
+    rows = np.nonzero(t >= n_prefix)[0]
+    if cos is not None and len(rows):
+        c = np.asarray(cos, np.float64)[t[rows] - n_prefix]
+        s = np.asarray(sin, np.float64)[t[rows] - n_prefix]
+        for h0 in range(0, N, 64):
+            sec = h0 // D + sec0
+            if sec >= 2:
+                continue
+            vh = v[rows, h0:h0 + 64]
+            rot = _rotate_half(vh)
+            y[rows, h0:h0 + 64] = vh * c + rot * s
+            eh = Ev[rows, h0:h0 + 64]
+            ep = np.concatenate([eh[:, 32:], eh[:, :32]], axis=1)
+            Ey[rows, h0:h0 + 64] = np.abs(c) * eh + np.abs(s) * ep + 3 * U32 * (np.abs(vh * c) + np.abs(rot * s))
+    qcols = np.array([(c // D + sec0) == 0 for c in range(N)])
+    y[:, qcols] *= 0.125
+    Ey[:, qcols] *= 0.125
+    return y, Ey, None
+
+
+# ---- attention --------------------------------------------------------------------------------------------------------
+def attention_operands(arith: int, qkv: np.ndarray, D: int):
+    """The q, k, v values a kernel multiplies: fp16-rounded (arith 0), fp32 (3), split with the ATT_* scales (4)."""
+    q, k, v = qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:3 * D]
+    if arith == 0:
+        return f16(q), f16(k), f16(v)
+    if arith == 4:
+        return split_value(q, ATT_QS), split_value(k, ATT_KS), split_value(v, ATT_VS)
+    return (np.asarray(q, np.float32).astype(np.float64), np.asarray(k, np.float32).astype(np.float64),
+            np.asarray(v, np.float32).astype(np.float64))
+
+
+def attention_ref(arith: int, qkv: np.ndarray, n: int, T: int, D: int, q_cls=None):
+    """softmax(q k^T) v per (frame, head) in float64 on the operands the kernel multiplies (q already carries 1/8), and
+    the bound.  With P = softmax row, V = sum_j P_j |v_j| (per output element), Sq = max_j sum_d |q_d k_jd| (per query):
+      scores: fp32 accumulation of 64 exact products, 64 u32 Sq (arith 4: + 3 * 2^-22 Sq for the split products), plus the
+              exp argument's rounding (u32 |s - m| log2e) - a score error ds moves P_j by at most a factor e^(2 ds);
+      probabilities: arith 0 rounds the unnormalised p to fp16 (u16 relative, 2^-25 absolute below 2^-14: T 2^-25 max|v| / l,
+              l >= 1); arith 4 splits them x 1024 (2^-22 relative, 2^-25 / 1024 absolute); arith 3 keeps fp32 (exp: 2 u32);
+      P.V: fp32 accumulation, T u32 V;   1 / l: the row sum rounded like P (same eta) times |O|;
+      output: fp16 (arith 0), fp32 (3), split x 16 (4: 2^-22 |O| + 2^-25 / 16).
+    Returns (O [rows][D], bound)."""
+    hd = 64
+    H = D // hd
+    q, k, v = attention_operands(arith, qkv[: n * T], D)
+    if q_cls is not None:
+        q = attention_operands(arith, np.concatenate([q_cls, q_cls, q_cls], axis=1), D)[0]
+        nq = 1
+    else:
+        nq = T
+    qh = q.reshape(n, nq, H, hd).transpose(0, 2, 1, 3)
+    kh = k.reshape(n, T, H, hd).transpose(0, 2, 1, 3)
+    vh = v.reshape(n, T, H, hd).transpose(0, 2, 1, 3)
+    s = qh @ kh.transpose(0, 1, 3, 2)                          # [n][H][nq][T]
+    m = s.max(axis=-1, keepdims=True)
+    e = np.exp(s - m)
+    lsum = e.sum(axis=-1, keepdims=True)
+    P = e / lsum
+    O = P @ vh
+    Vabs = P @ np.abs(vh)
+    Sq = (np.abs(qh) @ np.abs(kh).transpose(0, 1, 3, 2)).max(axis=-1, keepdims=True)
+    smax = np.abs(s - m).max(axis=-1, keepdims=True)
+    ds = 64 * U32 * Sq + U32 * 1.45 * smax + (3 * 2.0 ** -22 * Sq if arith == 4 else 0.0)
+    eta = {0: U16, 3: 2 * U32, 4: 2.0 ** -22}[arith]
+    absP = {0: F16_SUB, 3: 0.0, 4: F16_SUB / 1024}[arith]
+    vmax = np.abs(vh).max(axis=-2, keepdims=True)
+    bound = ((eta + 2.5 * ds + T * U32 + 2 * U32) * Vabs + (eta + 2.5 * ds + T * U32) * np.abs(O)
+             + T * absP * (vmax + np.abs(O)) / lsum)
+    if arith == 0:
+        bound = bound + U16 * np.abs(O) + F16_SUB
+    elif arith == 4:
+        bound = bound + 2.0 ** -22 * np.abs(O) + F16_SUB / ATT_CTX + 2.0 ** -22 * Vabs
+    else:
+        bound = bound + U32 * np.abs(O)
+    to_rows = lambda x: x.transpose(0, 2, 1, 3).reshape(n * nq, D)   # noqa: E731
+    return to_rows(O), to_rows(bound)
+
+
+def ratio(y, ref, bound) -> float:
+    """max |y - ref| / bound (inf where y is not finite)."""
+    y = np.asarray(y, np.float64)
+    d = np.where(np.isfinite(y), np.abs(y - ref), np.inf)
+    return float((d / bound).max()) if d.size else 0.0

@@ -29,3 +29,27 @@ def test_tile_variants_are_bit_identical(shape):
     assert ref != 0
     for t in TILES + ([8, 9] if m <= 64 else []):            # 64x128 and the skinny ring kernel for the CLS-row GEMMs
         assert run(t) == ref, (shape, t)
+
+
+@pytest.mark.parametrize("epi", ["resid", "qkv"])
+@pytest.mark.parametrize("shape", [(1000, 768, 256), (12865, 768, 768), (300, 2304, 768)], ids=lambda s: "x".join(map(str, s)))
+def test_tile_variants_are_bit_identical_on_residual_and_qkv_epilogues(epi, shape):
+    """The same through cbas_debug_gemm_run with non-zero bias, lambda, residual x and real RoPE tables (the bench above
+    only runs the GELU epilogue on a zero bias): every tile form's bytes equal the 128x128 kernel's."""
+    import numpy as np
+    from oracle import kernel_ref as R
+    from test_gpu_kernel_reference import gemm_run, make_gemm, out_buffer
+
+    m, n, k = shape
+    e = R.EPI_RESID if epi == "resid" else R.EPI_QKV
+    d = make_gemm(np.random.default_rng(m + n), e, m, n, k, frames_P=(14, 14))
+
+    def run(tile, rope_lds=0):
+        return gemm_run(0, e, d["A"], d["W"], d["bias"], M=m, out=out_buffer(0, e, d), tile=tile, lam=d.get("lam"),
+                        cos=d.get("cos"), sin=d.get("sin"), D=d.get("D", 0), T=d.get("T", 0), n_prefix=d.get("n_prefix", 0),
+                        P=d.get("P", 0), nh=d.get("nh", 0), nw=d.get("nw", 0), rope_lds=rope_lds)
+
+    ref = run(1)
+    for t in TILES:
+        for lds in ((0, 1) if e == R.EPI_QKV and t >= 13 else (0,)):
+            assert np.array_equal(run(t, lds).view(np.uint8), ref.view(np.uint8)), (shape, epi, t, lds)
