@@ -26,7 +26,9 @@ class EncConfig(C.Structure):
                 ("num_heads", c_int32), ("num_register_tokens", c_int32), ("patch_size", c_int32),
                 ("layer_norm_eps", c_float), ("rope_theta", c_float), ("max_batch", c_int32),
                 ("max_height", c_int32), ("max_width", c_int32), ("precision", c_int32),
-                ("use_rope", c_int32), ("pos_embed_grid", c_int32)]
+                ("use_rope", c_int32), ("pos_embed_grid", c_int32),
+                # ABI 11: 0 = ViT (the fields above); 1 = DINOv3 ConvNeXt (stage_widths / stage_depths)
+                ("family", c_int32), ("stage_widths", c_int32 * 4), ("stage_depths", c_int32 * 4)]
 
 
 class HeadConfigC(C.Structure):
@@ -124,7 +126,7 @@ DEBUG_SIGNATURES = {
 }
 
 ENC_SLOTS = 3
-EXPECTED_ABI = 10         # CBAS_ABI_VERSION of include/cbas_mi355x.h these ctypes structures mirror
+EXPECTED_ABI = 11         # CBAS_ABI_VERSION of include/cbas_mi355x.h these ctypes structures mirror
 PROF_CATS = ["patch_gemm", "layernorm", "qkv_gemm", "attention", "oproj_gemm", "up_gemm", "down_gemm", "other"]
 
 

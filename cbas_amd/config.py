@@ -1,4 +1,4 @@
-"""Configuration records for the encoder (DINOv3 ViT) and the classifier head.
+"""Configuration records for the encoders (DINOv3 ViT, DINOv2-with-registers, DINOv3 ConvNeXt) and the classifier head.
 
 The field names follow the HF ``config.json`` of a DINOv3 ViT checkpoint
 (``transformers/models/dinov3_vit/configuration_dinov3_vit.py:74-101``) so that a
@@ -11,6 +11,7 @@ from __future__ import annotations
 import json
 import os
 from dataclasses import dataclass, asdict
+from typing import Tuple
 
 
 @dataclass(frozen=True)
@@ -126,6 +127,101 @@ DINOV2_REG_TINY = ViTConfig(hidden_size=128, intermediate_size=512, num_hidden_l
 
 NAMED_VIT = {"vits16": VIT_S16, "vitb16": VIT_B16, "vitl16": VIT_L16, "tiny": VIT_TINY,
              "dinov2regb14": DINOV2_REG_B14, "dinov2regtiny": DINOV2_REG_TINY}
+
+
+@dataclass(frozen=True)
+class ConvNextConfig:
+    """HF ``DINOv3ConvNextConfig`` (transformers models/dinov3_convnext/configuration_dinov3_convnext.py): the four-stage
+    DINOv3 ConvNeXt whose ``DINOv3ConvNextModel`` puts LayerNorm(global mean pool of the last stage) at row 0 of
+    ``last_hidden_state`` - the row the reference keeps (backend/cbas.py:677).  Defaults are ConvNeXt-T."""
+    hidden_sizes: Tuple[int, ...] = (96, 192, 384, 768)
+    depths: Tuple[int, ...] = (3, 3, 9, 3)
+    layer_norm_eps: float = 1e-6
+    layer_scale_init_value: float = 1e-6
+    drop_path_rate: float = 0.0
+    hidden_act: str = "gelu"
+    num_channels: int = 3
+    image_size: int = 224
+    model_type: str = "dinov3_convnext"
+
+    @property
+    def hidden_size(self) -> int:
+        """Width of the row the encoder emits (the last stage's)."""
+        return int(self.hidden_sizes[-1])
+
+    def stage_grids(self, height: int, width: int):
+        """(h, w) of the four stages: the 4x4 / stride-4 stem, then three 2x2 / stride-2 downsamples (floor, as PyTorch)."""
+        h, w, out = height // 4, width // 4, []
+        for i in range(4):
+            if i:
+                h, w = h // 2, w // 2
+            out.append((h, w))
+        return out
+
+    def flops_per_frame(self, height: int, width: int) -> float:
+        """Algorithmic FLOPs (MAC = 2): stem + downsamples + sum of depth * HW * (49 C + 8 C^2)."""
+        mac, prev = 0, self.num_channels
+        for i, ((h, w), C, d) in enumerate(zip(self.stage_grids(height, width), self.hidden_sizes, self.depths)):
+            mac += h * w * C * prev * (16 if i == 0 else 4)
+            mac += d * h * w * (49 * C + 8 * C * C)
+            prev = C
+        return 2.0 * mac
+
+    def validate(self) -> None:
+        if self.model_type != "dinov3_convnext":
+            raise NotImplementedError(f"model_type={self.model_type!r} is not a DINOv3 ConvNeXt")
+        if len(self.hidden_sizes) != 4 or len(self.depths) != 4:
+            raise NotImplementedError("a DINOv3 ConvNeXt with 4 stages is expected")
+        if any(c <= 0 or c % 32 or c > 1536 for c in self.hidden_sizes):
+            raise NotImplementedError(f"hidden_sizes={tuple(self.hidden_sizes)}: every width must be a multiple of 32 (<= 1536)")
+        if any(d < 1 or d > 64 for d in self.depths):
+            raise NotImplementedError(f"depths={tuple(self.depths)} outside [1, 64]")
+        if self.hidden_act != "gelu":
+            raise NotImplementedError(f"hidden_act={self.hidden_act!r}; only exact-erf 'gelu' is implemented")
+        if self.num_channels != 3:
+            raise NotImplementedError("num_channels must be 3 (the reference replicates the green plane 3 times)")
+
+    def to_json(self) -> str:
+        d = asdict(self)
+        d.update(hidden_sizes=list(self.hidden_sizes), depths=list(self.depths), num_stages=4)
+        return json.dumps(d, indent=2)
+
+    @classmethod
+    def from_json_file(cls, path: str) -> "ConvNextConfig":
+        with open(path, "r") as f:
+            raw = json.load(f)
+        mt = raw.get("model_type")
+        if mt != "dinov3_convnext":
+            raise NotImplementedError(f"model_type={mt!r} is not a DINOv3 ConvNeXt")
+        known = {k: raw[k] for k in cls.__dataclass_fields__ if k in raw}
+        for key in ("hidden_sizes", "depths"):
+            if key in known:
+                known[key] = tuple(int(v) for v in known[key])
+        if isinstance(known.get("image_size"), (list, tuple)):
+            known["image_size"] = int(known["image_size"][0])
+        return cls(**known)
+
+
+CONVNEXT_T = ConvNextConfig()
+CONVNEXT_S = ConvNextConfig(depths=(3, 3, 27, 3))
+# Tiny config for fast kernel parity (not a published architecture)
+CONVNEXT_TINY = ConvNextConfig(hidden_sizes=(32, 64, 128, 256), depths=(1, 1, 2, 1), image_size=64)
+
+NAMED_CONVNEXT = {"convnext_t": CONVNEXT_T, "convnext_s": CONVNEXT_S, "convnext_tiny": CONVNEXT_TINY}
+
+
+def encoder_config_from_json(path: str):
+    """The encoder config of a checkpoint's ``config.json``, by its ``model_type``: ``ConvNextConfig`` for
+    ``dinov3_convnext``, else ``ViTConfig`` (which refuses the families that are not built)."""
+    with open(path, "r") as f:
+        mt = json.load(f).get("model_type", "dinov3_vit")
+    if mt == "dinov3_convnext":
+        return ConvNextConfig.from_json_file(path)
+    return ViTConfig.from_json_file(path)
+
+
+def is_convnext(cfg) -> bool:
+    return isinstance(cfg, ConvNextConfig)
 
 
 @dataclass(frozen=True)

@@ -129,6 +129,22 @@ struct cbas_enc {
     // on lane 0's own stream, so that mixing the two forms on one handle never races on the workspace
     hipEvent_t lane0_async_done = nullptr, sync_done = nullptr;
     bool lane0_async_used = false, sync_used = false;
+    // DINOv3 ConvNeXt (cfg.family == 1): weights, repacked at create into one device arena (precision 4: the GEMM weights
+    // once more in the split format, at the same offsets in w32); the workspace is x (residual stream, row stride Cp),
+    // h16 (every GEMM's A operand) and u16 (GELU(pointwise_conv1)), all fp32
+    struct CnxBlock { const float *dw_t, *dw_b, *ln_w, *ln_b, *pw1_w, *pw1_b, *pw2_w, *pw2_b, *gamma; float sc1 = 1.f, sc2 = 1.f; };
+    struct CnxStage {
+        int C = 0, Cp = 0;                                         // width, width rounded up to the GEMM's 128-column tile
+        const float *ds_ln_w = nullptr, *ds_ln_b = nullptr, *ds_w = nullptr, *ds_b = nullptr;   // stage 0: the stem
+        float sc_ds = 1.f;
+        std::vector<CnxBlock> blocks;
+    };
+    CnxStage cnx[4];
+    const float *cnx_norm_w = nullptr, *cnx_norm_b = nullptr;
+    float* cnx_arena = nullptr;
+    int64_t cnx_x_cap = 0, cnx_a_cap = 0, cnx_u_cap = 0;      // floats per lane
+    int cnx_tap = -1;                  // debug build: the point the last tapped ConvNeXt pass stopped at
+    int cnx_tap_rows = 0;
     // optional per-kernel-category timing (HIP events on the launch stream)
     bool prof_on = false;
     struct ProfRec { hipEvent_t a, b; int cat; double flops; };
@@ -138,7 +154,19 @@ struct cbas_enc {
 
 namespace {
 
+int64_t cnx_weights_count(const cbas_enc_config& c) {
+    int64_t n = 0, prev = 0;
+    for (int i = 0; i < 4; ++i) {
+        const int64_t C = c.stage_widths[i];
+        n += i == 0 ? C * 3 * 16 + C + 2 * C : 2 * prev + C * prev * 4 + C;
+        n += (int64_t)c.stage_depths[i] * (49 * C + C + 2 * C + (4 * C * C + 4 * C) + (4 * C * C + C) + C);
+        prev = C;
+    }
+    return n + 2 * prev;
+}
+
 int64_t weights_count(const cbas_enc_config& c) {
+    if (c.family == 1) return cnx_weights_count(c);
     const int64_t D = c.hidden_size, F = c.intermediate_size, R = c.num_register_tokens, p = c.patch_size;
     const int64_t G = c.pos_embed_grid;
     int64_t n = D + R * D + (G > 0 ? (1 + G * G) * D : 0) + D * 3 * p * p + D;
@@ -298,9 +326,32 @@ void set_rope(const cbas_enc* h, GemmParams& p) {
     p.rope_magic = (unsigned)((1ull << 32) / (unsigned)h->rope_nw) + 1u;
 }
 
+// ConvNeXt: floats of x, of the GEMM operand buffer and of the GELU buffer that n frames of height x width need
+void cnx_sizes(const cbas_enc* h, int64_t n, int height, int width, int64_t* x, int64_t* a, int64_t* u) {
+    int64_t hh = height / 4, ww = width / 4;
+    *x = 0; *a = n * hh * ww * 32; *u = 0;
+    for (int i = 0; i < 4; ++i) {
+        const cbas_enc::CnxStage& S = h->cnx[i];
+        if (i > 0) { hh /= 2; ww /= 2; *a = std::max(*a, n * hh * ww * 4 * h->cnx[i - 1].C); }
+        const int64_t rows = n * hh * ww;
+        *x = std::max(*x, rows * S.Cp);
+        *a = std::max(*a, rows * S.C);
+        *u = std::max(*u, rows * 4 * S.C);
+    }
+}
+
 int check_frame(cbas_enc* h, int n, int height, int width) {
     if (!h) return cbas_fail(CBAS_EINVAL, "null encoder handle");
     if (n <= 0 || n > h->cfg.max_batch) return cbas_fail(CBAS_EINVAL, "n=%d outside (0, max_batch=%d]", n, h->cfg.max_batch);
+    if (h->cfg.family == 1) {
+        if (height < 32 || width < 32) return cbas_fail(CBAS_EINVAL, "frame %dx%d: a ConvNeXt needs at least 32x32", height, width);
+        int64_t x, a, u;
+        cnx_sizes(h, n, height, width, &x, &a, &u);
+        if (x > h->cnx_x_cap || a > h->cnx_a_cap || u > h->cnx_u_cap)
+            return cbas_fail(CBAS_EINVAL, "%d frames of %dx%d exceed the workspace (max_batch=%d, %dx%d)", n, height, width,
+                             h->cfg.max_batch, h->cfg.max_height, h->cfg.max_width);
+        return CBAS_OK;
+    }
     const int ps = h->cfg.patch_size;
     if (height < ps || width < ps) return cbas_fail(CBAS_EINVAL, "frame %dx%d smaller than one patch", height, width);
     const int64_t P = (int64_t)(height / ps) * (width / ps);
@@ -633,9 +684,74 @@ int run_blocks(cbas_enc* h, int n, int height, int width, int patch_k, float in_
     return CBAS_OK;
 }
 
+// DINOv3 ConvNeXt ([cx] = transformers models/dinov3_convnext/modeling_dinov3_convnext.py, DINOv3ConvNextModel.forward), after
+// the stem's im2col has been written to h16: the whole network on the fp32 GEMMs of the ViT (precision 4: split operands) and
+// the kernels of convnext_f32.hip.  stop >= 0 (debug taps): 0 ends after the stem's LayerNorm, 1 + i after stage i.
+int run_cnx(cbas_enc* h, int n, int height, int width, float* cls_f32, f16* cls_f16, hipStream_t st, int stop) {
+    const int split = h->cfg.precision == 4;
+    const float eps = h->cfg.layer_norm_eps;
+    float* const A32 = reinterpret_cast<float*>(h->h16);
+    float* const u32 = reinterpret_cast<float*>(h->u16);
+    auto gemm = [&](const float* A, int64_t lda, const float* W, int M, int N, int K, const float* bias,
+                    float* out, int64_t ldo, float a_scale, float w_scale) {
+        Gemm32VitParams g{};
+        g.A = A; g.lda = lda; g.W = W; g.M = M; g.N = N; g.K = K; g.bias = bias; g.out = out; g.ldo = ldo;
+        g.patches_per_frame = M; g.tokens_per_frame = M; g.n_prefix = 0;      // EPI_PATCH: output row m = A row m
+        g.split = split; g.a_scale = a_scale; g.w_scale = w_scale;
+        return g;
+    };
+    int hh = height / 4, ww = width / 4;
+    int M = n * hh * ww;
+    const cbas_enc::CnxStage& S0 = h->cnx[0];
+    {
+        Gemm32VitParams g = gemm(A32, 32, S0.ds_w, M, S0.Cp, 32, S0.ds_b, h->x, S0.Cp, 1.f, S0.sc_ds);
+        { PROF(CBAS_PROF_PATCH, 2.0 * M * S0.C * 48); LAUNCH_TRY(launch_gemm_f32_vit(EPI_PATCH, g, st)); }
+        { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_cnx_ln_rows(h->x, S0.Cp, S0.ds_ln_w, S0.ds_ln_b, M, S0.C, eps, st)); }
+    }
+    h->cnx_tap_rows = M;
+    if (stop == 0) return CBAS_OK;
+    for (int i = 0; i < 4; ++i) {
+        const cbas_enc::CnxStage& S = h->cnx[i];
+        const int C = S.C;
+        if (i > 0) {
+            const cbas_enc::CnxStage& P = h->cnx[i - 1];
+            { PROF(CBAS_PROF_LAYERNORM, 0.0);
+              LAUNCH_TRY(launch_cnx_downsample(h->x, P.Cp, n, hh, ww, S.ds_ln_w, S.ds_ln_b, P.C, eps, A32, split, st)); }
+            hh /= 2; ww /= 2;
+            M = n * hh * ww;
+            Gemm32VitParams g = gemm(A32, 4 * P.C, S.ds_w, M, S.Cp, 4 * P.C, S.ds_b, h->x, S.Cp, 1.f, S.sc_ds);
+            { PROF(CBAS_PROF_PATCH, 2.0 * M * C * 4.0 * P.C); LAUNCH_TRY(launch_gemm_f32_vit(EPI_PATCH, g, st)); }
+        }
+        for (const cbas_enc::CnxBlock& b : S.blocks) {
+            { PROF(CBAS_PROF_LAYERNORM, 0.0);
+              LAUNCH_TRY(launch_cnx_dwconv_ln(h->x, S.Cp, n, hh, ww, b.dw_t, b.dw_b, b.ln_w, b.ln_b, C, eps, A32, split, st)); }
+            Gemm32VitParams u = gemm(A32, C, b.pw1_w, M, 4 * C, C, b.pw1_b, u32, 4 * C, 1.f, b.sc1);
+            u.out_scale = 4.f;                                        // the GELU output as pointwise_conv2's split A operand
+            { PROF(CBAS_PROF_UP, 2.0 * M * 4.0 * C * C); LAUNCH_TRY(launch_gemm_f32_vit(EPI_GELU, u, st)); }
+            Gemm32VitParams d = gemm(u32, 4 * C, b.pw2_w, M, S.Cp, 4 * C, b.pw2_b, h->x, S.Cp, 4.f, b.sc2);
+            d.lambda = b.gamma;                                       // x += (pointwise_conv2 + b) * gamma
+            { PROF(CBAS_PROF_DOWN, 2.0 * M * 4.0 * C * C); LAUNCH_TRY(launch_gemm_f32_vit(EPI_RESID, d, st)); }
+        }
+        h->cnx_tap_rows = M;
+        if (stop == 1 + i) return CBAS_OK;
+    }
+    if (cls_f32 || cls_f16) {
+        PROF(CBAS_PROF_LAYERNORM, 0.0);
+        LAUNCH_TRY(launch_cnx_pool_ln(h->x, h->cnx[3].Cp, n, hh * ww, h->cnx_norm_w, h->cnx_norm_b, h->cnx[3].C, eps, cls_f32,
+                                      cls_f16, h->nonfinite_dev, st));
+    }
+    return CBAS_OK;
+}
+
 int forward_u8_one(cbas_enc* h, const uint8_t* frames_dev, int n, int height, int width, int64_t frame_stride,
                    int64_t row_stride, int64_t pixel_stride, float* cls_f32, f16* cls_f16, hipStream_t st,
                    int stop_layer, int stop_stage) {
+    if (h->cfg.family == 1) {
+        LAUNCH_TRY(launch_cnx_stem_im2col_u8(frames_dev, n, height, width, frame_stride, row_stride, pixel_stride,
+                                             reinterpret_cast<float*>(h->h16), h->cfg.precision == 4, st));
+        h->cnx_tap = stop_layer;
+        return run_cnx(h, n, height, width, cls_f32, cls_f16, st, stop_layer);
+    }
     const int ps = h->cfg.patch_size;
     const int T = (height / ps) * (width / ps) + h->NP;
     if (h->cfg.precision >= 3)
@@ -701,7 +817,7 @@ extern "C" void cbas_enc_destroy(cbas_enc* h) {
     for (auto& t : h->pos_tables) { if (t.cos) (void)hipFree(t.cos); if (t.sin) (void)hipFree(t.sin); if (t.fac) (void)hipFree(t.fac); if (t.pos) (void)hipFree(t.pos); }
     void* bufs[] = {h->blob, h->w16, h->w16_lo, h->qkv_bias_all, h->prefix_dev,
                     h->A_patch, h->h16, h->qkv16, h->u16, h->x, h->cls16, h->w8, h->w8_sc, h->sc_h, h->sc_u,
-                    h->w16_fold, h->fold_vec, h->x16, h->lnst, h->w32};
+                    h->w16_fold, h->fold_vec, h->x16, h->lnst, h->w32, h->cnx_arena};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (h->compute) (void)hipStreamDestroy(h->compute);
@@ -710,11 +826,220 @@ extern "C" void cbas_enc_destroy(cbas_enc* h) {
     delete h;
 }
 
+namespace {
+
+// host-streaming slots (both families)
+int create_slots(cbas_enc* h) {
+#define SLOT_TRY(expr)                                                                                              \
+    do {                                                                                                           \
+        hipError_t _e = (expr);                                                                                    \
+        if (_e != hipSuccess)                                                                                      \
+            return cbas_fail(_e == hipErrorOutOfMemory ? CBAS_ENOMEM : CBAS_EHIP, "%s failed: %s (%s:%d)", #expr,  \
+                             hipGetErrorString(_e), __FILE__, __LINE__);                                           \
+    } while (0)
+    const cbas_enc_config& c = h->cfg;
+    h->slot_bytes = (int64_t)c.max_batch * c.max_height * c.max_width * 4;
+    for (Slot& s : h->slots) {
+        SLOT_TRY(hipHostMalloc(&s.in_host, h->slot_bytes, hipHostMallocDefault));
+        SLOT_TRY(hipHostMalloc(&s.out16_host, (int64_t)c.max_batch * h->D * 2, hipHostMallocDefault));
+        SLOT_TRY(hipHostMalloc(&s.out32_host, (int64_t)c.max_batch * h->D * 4, hipHostMallocDefault));
+        SLOT_TRY(hipMalloc(&s.in_dev, h->slot_bytes));
+        SLOT_TRY(hipMalloc(&s.out16_dev, (int64_t)c.max_batch * h->D * 2));
+        SLOT_TRY(hipMalloc(&s.out32_dev, (int64_t)c.max_batch * h->D * 4));
+        SLOT_TRY(hipEventCreateWithFlags(&s.ev_copied, hipEventDisableTiming));
+        SLOT_TRY(hipEventCreateWithFlags(&s.ev_done, hipEventDisableTiming));
+        SLOT_TRY(hipEventCreateWithFlags(&s.ev_in, hipEventDisableTiming));
+    }
+    return CBAS_OK;
+#undef SLOT_TRY
+}
+
+int cnx_check_config(const cbas_enc_config& c) {
+    if (c.precision != 3 && c.precision != 4)
+        return cbas_fail(CBAS_EINVAL, "precision=%d: ConvNeXt encoders run in precision 3 (fp32) or 4 (fp32 storage, split-fp16 "
+                                      "GEMM products) only", c.precision);
+    for (int i = 0; i < 4; ++i) {
+        if (c.stage_widths[i] <= 0 || c.stage_widths[i] % 32 || c.stage_widths[i] > 1536)
+            return cbas_fail(CBAS_EINVAL, "ConvNeXt stage_widths[%d]=%d must be a positive multiple of 32 up to 1536", i,
+                             c.stage_widths[i]);
+        if (c.stage_depths[i] < 1 || c.stage_depths[i] > 64)
+            return cbas_fail(CBAS_EINVAL, "ConvNeXt stage_depths[%d]=%d outside [1, 64]", i, c.stage_depths[i]);
+    }
+    if (c.hidden_size != c.stage_widths[3])
+        return cbas_fail(CBAS_EINVAL, "hidden_size=%d must be the last stage's width %d (the row width)", c.hidden_size,
+                         c.stage_widths[3]);
+    if (!(c.layer_norm_eps > 0.f)) return cbas_fail(CBAS_EINVAL, "layer_norm_eps must be positive");
+    if (c.max_batch <= 0 || c.max_height < 32 || c.max_width < 32)
+        return cbas_fail(CBAS_EINVAL, "bad batch/frame-size field (a ConvNeXt needs frames of at least 32x32)");
+    return CBAS_OK;
+}
+
+// ConvNeXt weights and workspaces.  The blob (include/cbas_mi355x.h) is read on the host and repacked into one arena:
+//   stem weight [Cp0][32]: the 3 identical input channels summed in double and rounded once (launch_pack_patch_weight_f32's
+//   rule), k = 4 i + j; downsample weights [Cp][4 C_prev] with k = (2 kh + kw) C_prev + c (the operand order of
+//   launch_cnx_downsample); depthwise taps [49][C]; pointwise_conv2, its bias, gamma and the stem / downsample biases padded to
+//   Cp rows with zeros (padding columns of the residual stream stay 0).  Rows past C of a GEMM weight are zero.
+int cnx_build(cbas_enc* h, const float* wh) {
+    const cbas_enc_config& c = h->cfg;
+    const bool split = c.precision == 4;
+    std::vector<float> ar;
+    struct Gw { int64_t off, N, K; float* sc; };
+    std::vector<Gw> gw;                                     // GEMM weights (split-packed in precision 4)
+    std::vector<std::pair<const float**, int64_t>> fix;     // pointers into the arena, set after the upload
+    auto take = [&](int64_t n) { const int64_t o = (int64_t)ar.size(); ar.resize(ar.size() + n, 0.f); return o; };
+    auto pow2_scale = [](float maxabs) {                    // as cbas_enc_create's
+        if (!(maxabs > 0.f) || !std::isfinite(maxabs)) return 1.0f;
+        int e = 0;
+        (void)frexpf(maxabs, &e);
+        e = std::min(20, std::max(-20, 1 - e));
+        return ldexpf(1.0f, e);
+    };
+    auto gemm_w = [&](int64_t off, int64_t N, int64_t K, float* sc, const float** ptr) {
+        float m = 0.f;
+        for (int64_t i = 0; i < N * K; ++i) m = std::max(m, fabsf(ar[off + i]));
+        *sc = split ? pow2_scale(m) : 1.f;
+        gw.push_back({off, N, K, sc});
+        fix.push_back({ptr, off});
+    };
+    auto vec = [&](const float* src, int64_t n, int64_t n_pad, const float** ptr) {
+        const int64_t o = take(n_pad);
+        std::copy(src, src + n, ar.begin() + o);
+        fix.push_back({ptr, o});
+    };
+    const float* p = wh;
+    int prev = 0, prevp = 0;
+    for (int i = 0; i < 4; ++i) {
+        cbas_enc::CnxStage& S = h->cnx[i];
+        const int C = c.stage_widths[i], Cp = (int)round_up(C, 128);
+        S.C = C; S.Cp = Cp;
+        if (i == 0) {
+            const int64_t o = take((int64_t)Cp * 32);
+            for (int co = 0; co < C; ++co)
+                for (int k = 0; k < 16; ++k) {
+                    const float* b = p + (int64_t)co * 48 + k;
+                    ar[o + (int64_t)co * 32 + k] = (float)(((double)b[0] + (double)b[16]) + (double)b[32]);
+                }
+            p += (int64_t)C * 48;
+            gemm_w(o, Cp, 32, &S.sc_ds, &S.ds_w);
+            vec(p, C, Cp, &S.ds_b); p += C;
+            vec(p, C, C, &S.ds_ln_w); p += C;
+            vec(p, C, C, &S.ds_ln_b); p += C;
+        } else {
+            vec(p, prev, prev, &S.ds_ln_w); p += prev;
+            vec(p, prev, prev, &S.ds_ln_b); p += prev;
+            const int64_t K = 4 * (int64_t)prev, o = take((int64_t)Cp * K);
+            for (int co = 0; co < C; ++co)                 // HF (C, C_prev, 2, 2) -> [co][(2 kh + kw) C_prev + ci]
+                for (int ci = 0; ci < prev; ++ci)
+                    for (int q = 0; q < 4; ++q) ar[o + co * K + (int64_t)q * prev + ci] = p[((int64_t)co * prev + ci) * 4 + q];
+            p += (int64_t)C * K;
+            gemm_w(o, Cp, K, &S.sc_ds, &S.ds_w);
+            vec(p, C, Cp, &S.ds_b); p += C;
+        }
+        S.blocks.resize(c.stage_depths[i]);
+        for (cbas_enc::CnxBlock& b : S.blocks) {
+            const int64_t o = take(49 * (int64_t)C);
+            for (int ch = 0; ch < C; ++ch)
+                for (int t = 0; t < 49; ++t) ar[o + (int64_t)t * C + ch] = p[(int64_t)ch * 49 + t];
+            fix.push_back({&b.dw_t, o});
+            p += 49 * (int64_t)C;
+            vec(p, C, C, &b.dw_b); p += C;
+            vec(p, C, C, &b.ln_w); p += C;
+            vec(p, C, C, &b.ln_b); p += C;
+            const int64_t o1 = take(4 * (int64_t)C * C);
+            std::copy(p, p + 4 * (int64_t)C * C, ar.begin() + o1);
+            p += 4 * (int64_t)C * C;
+            gemm_w(o1, 4 * C, C, &b.sc1, &b.pw1_w);
+            vec(p, 4 * C, 4 * C, &b.pw1_b); p += 4 * C;
+            const int64_t o2 = take((int64_t)Cp * 4 * C);
+            std::copy(p, p + 4 * (int64_t)C * C, ar.begin() + o2);
+            p += 4 * (int64_t)C * C;
+            gemm_w(o2, Cp, 4 * C, &b.sc2, &b.pw2_w);
+            vec(p, C, Cp, &b.pw2_b); p += C;
+            vec(p, C, Cp, &b.gamma); p += C;
+        }
+        prev = C; prevp = Cp;
+    }
+    (void)prevp;
+    vec(p, prev, prev, &h->cnx_norm_w); p += prev;
+    vec(p, prev, prev, &h->cnx_norm_b); p += prev;
+    if (p - wh != cnx_weights_count(c)) return cbas_fail(CBAS_EHIP, "ConvNeXt weight repack consumed %lld floats",
+                                                         (long long)(p - wh));
+    hipStream_t st = h->compute;
+    HIP_TRY(hipMalloc(&h->cnx_arena, ar.size() * sizeof(float)));
+    HIP_TRY(hipMemcpy(h->cnx_arena, ar.data(), ar.size() * sizeof(float), hipMemcpyHostToDevice));
+    for (auto& f : fix) *f.first = h->cnx_arena + f.second;
+    if (split) {
+        // the GEMM weights once more in the split format, at the same offsets
+        HIP_TRY(hipMalloc(&h->w32, ar.size() * sizeof(float)));
+        for (const Gw& g : gw) {
+            if (launch_pack_split_weight(h->cnx_arena + g.off, h->w32 + g.off, g.N, (int)g.K, *g.sc, st))
+                return cbas_fail(CBAS_EHIP, "split packing of a ConvNeXt weight failed");
+            for (auto& f : fix)
+                if (f.second == g.off) *f.first = h->w32 + g.off;
+        }
+    }
+    // workspaces: lane 0 on the handle's compute stream, lane 1 on its own
+    cnx_sizes(h, c.max_batch, c.max_height, c.max_width, &h->cnx_x_cap, &h->cnx_a_cap, &h->cnx_u_cap);
+    const char* e = getenv("CBAS_LANES");
+    h->n_lanes = (e && atoi(e) == 1) ? 1 : 2;
+    for (int l = 0; l < h->n_lanes; ++l) {
+        cbas_enc::Lane& L = h->lanes[l];
+        HIP_TRY(hipMalloc(&L.x, h->cnx_x_cap * sizeof(float)));
+        HIP_TRY(hipMalloc(&L.h16, h->cnx_a_cap * sizeof(float)));
+        HIP_TRY(hipMalloc(&L.u16, h->cnx_u_cap * sizeof(float)));
+        HIP_TRY(hipMemsetAsync(L.x, 0, h->cnx_x_cap * sizeof(float), st));      // the padding columns stay 0 from here on
+        HIP_TRY(hipMemsetAsync(L.h16, 0, h->cnx_a_cap * sizeof(float), st));
+        HIP_TRY(hipMemsetAsync(L.u16, 0, h->cnx_u_cap * sizeof(float), st));
+        if (l == 0) L.stream = h->compute;
+        else HIP_TRY(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
+    }
+    use_lane(h, 0);
+    HIP_TRY(hipEventCreateWithFlags(&h->lane0_async_done, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&h->sync_done, hipEventDisableTiming));
+    HIP_TRY(hipMalloc(&h->nonfinite_dev, sizeof(unsigned)));
+    HIP_TRY(hipMemsetAsync(h->nonfinite_dev, 0, sizeof(unsigned), st));
+    int rc = create_slots(h);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    return CBAS_OK;
+}
+
+}  // namespace
+
 extern "C" int cbas_enc_create(const cbas_enc_config* cfg, const float* weights_host, int64_t n_weights,
                                int device_id, cbas_enc** out) {
     if (!cfg || !weights_host || !out) return cbas_fail(CBAS_EINVAL, "null argument");
     *out = nullptr;
     const cbas_enc_config& c = *cfg;
+    if (c.family == 1) {
+        int rc = cnx_check_config(c);
+        if (rc) return rc;
+        if (n_weights != weights_count(c))
+            return cbas_fail(CBAS_EINVAL, "weights blob has %lld floats, config needs %lld", (long long)n_weights,
+                             (long long)weights_count(c));
+        HIP_TRY(hipSetDevice(device_id));
+        cbas_enc* h = new (std::nothrow) cbas_enc();
+        if (!h) return cbas_fail(CBAS_ENOMEM, "out of host memory");
+        h->cfg = c; h->device = device_id;
+        h->D = c.hidden_size;
+        rc = CBAS_OK;
+        if (hipStreamCreateWithFlags(&h->compute, hipStreamNonBlocking) != hipSuccess ||
+            hipStreamCreateWithFlags(&h->copy, hipStreamNonBlocking) != hipSuccess ||
+            hipStreamCreateWithFlags(&h->aux, hipStreamNonBlocking) != hipSuccess)
+            rc = cbas_fail(CBAS_EHIP, "stream creation failed");
+        if (!rc) rc = cnx_build(h, weights_host);
+        if (rc) {
+            const int code = rc;
+            char msg[sizeof(g_cbas_err)];
+            memcpy(msg, g_cbas_err, sizeof(msg));
+            cbas_enc_destroy(h);
+            memcpy(g_cbas_err, msg, sizeof(msg));
+            return code;
+        }
+        *out = h;
+        return CBAS_OK;
+    }
+    if (c.family != 0) return cbas_fail(CBAS_EINVAL, "family=%d: 0 (ViT) or 1 (DINOv3 ConvNeXt)", c.family);
     if (c.hidden_size <= 0 || c.hidden_size % 128 || c.num_heads * 64 != c.hidden_size)
         return cbas_fail(CBAS_EINVAL, "hidden_size=%d must be a multiple of 128 with head_dim 64 (num_heads=%d)",
                          c.hidden_size, c.num_heads);
@@ -1031,17 +1356,10 @@ extern "C" int cbas_enc_create(const cbas_enc_config* cfg, const float* weights_
     }
 
     // host-streaming slots
-    h->slot_bytes = (int64_t)c.max_batch * c.max_height * c.max_width * 4;
-    for (Slot& s : h->slots) {
-        CREATE_TRY(hipHostMalloc(&s.in_host, h->slot_bytes, hipHostMallocDefault));
-        CREATE_TRY(hipHostMalloc(&s.out16_host, (int64_t)c.max_batch * D * 2, hipHostMallocDefault));
-        CREATE_TRY(hipHostMalloc(&s.out32_host, (int64_t)c.max_batch * D * 4, hipHostMallocDefault));
-        CREATE_TRY(hipMalloc(&s.in_dev, h->slot_bytes));
-        CREATE_TRY(hipMalloc(&s.out16_dev, (int64_t)c.max_batch * D * 2));
-        CREATE_TRY(hipMalloc(&s.out32_dev, (int64_t)c.max_batch * D * 4));
-        CREATE_TRY(hipEventCreateWithFlags(&s.ev_copied, hipEventDisableTiming));
-        CREATE_TRY(hipEventCreateWithFlags(&s.ev_done, hipEventDisableTiming));
-        CREATE_TRY(hipEventCreateWithFlags(&s.ev_in, hipEventDisableTiming));
+    rc = create_slots(h);
+    if (rc) {
+        cbas_enc_destroy(h);
+        return rc;
     }
     CREATE_TRY(hipStreamSynchronize(st));
 #undef CREATE_TRY
@@ -1092,9 +1410,15 @@ extern "C" int cbas_enc_forward_f32(cbas_enc* h, const float* x_dev, int n, int 
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
     const int ps = h->cfg.patch_size;
-    const int T = (height / ps) * (width / ps) + h->NP;
+    const int T = ps > 0 ? (height / ps) * (width / ps) + h->NP : 0;
     rc = sync_enter(h, st);
     if (rc) return rc;
+    if (h->cfg.family == 1) {
+        LAUNCH_TRY(launch_cnx_stem_im2col_f32(x_dev, n, height, width, reinterpret_cast<float*>(h->h16), h->cfg.precision == 4, st));
+        rc = run_cnx(h, n, height, width, cls_f32_dev, (f16*)cls_f16_dev, st, -1);
+        if (rc) return rc;
+        return sync_leave(h, st);
+    }
     if (h->cfg.precision >= 3)
         LAUNCH_TRY(launch_im2col_f32_f32(x_dev, n, height, width, reinterpret_cast<float*>(h->A_patch), h->x, h->prefix, h->NP, h->D, T, ps,
                                          h->cfg.precision == 4, st));
@@ -1121,6 +1445,19 @@ extern "C" int cbas_enc_debug_read(cbas_enc* h, int which, void* host_out, int64
     if (!h || !host_out) return cbas_fail(CBAS_EINVAL, "null argument");
     const void* src = nullptr;
     int64_t cap = 0;
+    if (h->cfg.family == 1) {
+        // the tensor the last tapped pass stopped at: rows of C floats out of the residual stream's Cp-float rows
+        if (which < 4 || which > 8) return cbas_fail(CBAS_EINVAL, "ConvNeXt taps are which = 4 (stem) .. 8 (stage 3); got %d", which);
+        if (h->cnx_tap != which - 4) return cbas_fail(CBAS_ESTATE, "the last tapped pass stopped at %d, not %d", h->cnx_tap, which - 4);
+        const cbas_enc::CnxStage& S = h->cnx[which == 4 ? 0 : which - 5];
+        const int64_t need = (int64_t)h->cnx_tap_rows * S.C * 4;
+        if (n_bytes != need) return cbas_fail(CBAS_EINVAL, "tap %d holds %lld bytes, asked for %lld", which, (long long)need, (long long)n_bytes);
+        HIP_TRY(hipSetDevice(h->device));
+        HIP_TRY(hipStreamSynchronize(h->compute));
+        HIP_TRY(hipMemcpy2D(host_out, (size_t)S.C * 4, h->x, (size_t)S.Cp * 4, (size_t)S.C * 4, (size_t)h->cnx_tap_rows,
+                            hipMemcpyDeviceToHost));
+        return CBAS_OK;
+    }
     switch (which) {
         case 0: src = h->x; cap = h->rows_cap * h->D * 4; break;
         // precision 3 keeps these as fp32 (4 bytes per element)

@@ -197,6 +197,27 @@ int launch_attention_f32(const float* qkv, const float* q_cls, float* out, int n
                          float split_scale, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------
+// DINOv3 ConvNeXt (precision 3 / 4, convnext_f32.hip): channels-last fp32 rows (frame, y, x), row stride ld >= C, C % 32 == 0.
+// split != 0 (precision 4): the GEMM operand A is written in the split hi | lo format of vit32_epilogue.h, scale 1.
+// ---------------------------------------------------------------------------------------------
+// stem: the 4 x 4 / stride-4 patch of output pixel m at A[m][4 i + j] (k < 16), A[m][16..31] = 0
+int launch_cnx_stem_im2col_u8(const uint8_t* frames, int n, int height, int width, int64_t frame_stride, int64_t row_stride,
+                              int64_t pixel_stride, float* A, int split, hipStream_t stream);
+int launch_cnx_stem_im2col_f32(const float* frames, int n, int height, int width, float* A, int split, hipStream_t stream);
+// LayerNorm over the first C columns of M rows, in place
+int launch_cnx_ln_rows(float* x, int64_t ld, const float* gamma, const float* beta, int64_t M, int C, float eps, hipStream_t stream);
+// 2 x 2 / stride-2 downsample operand: A[m][(2 kh + kw) C + c] = LayerNorm(x[pixel (2 oy + kh, 2 ox + kw)])[c]
+int launch_cnx_downsample(const float* x, int64_t ldx, int n, int hi, int wi, const float* gamma, const float* beta, int C, float eps,
+                          float* A, int split, hipStream_t stream);
+// A[m][c] = LayerNorm(depthwise 7 x 7 (x) + bias)[c]; wt = the taps tap-major [49][C]
+int launch_cnx_dwconv_ln(const float* x, int64_t ld, int n, int hh, int ww, const float* wt, const float* bias, const float* gamma,
+                         const float* beta, int C, float eps, float* A, int split, hipStream_t stream);
+// row 0 of DINOv3ConvNextModel: LayerNorm(mean over the hw pixels of each frame) -> cls_f32 / cls_f16 [n][C]; `nonfinite` as
+// launch_final_norm_cls
+int launch_cnx_pool_ln(const float* x, int64_t ld, int n, int hw, const float* gamma, const float* beta, int C, float eps,
+                       float* cls_f32, f16* cls_f16, unsigned* nonfinite, hipStream_t stream);
+
+// ---------------------------------------------------------------------------------------------
 // classifier head (all fp32)
 // ---------------------------------------------------------------------------------------------
 struct Gemm32Params {

@@ -20,12 +20,16 @@ import numpy as np
 import torch
 
 from . import _lib
-from .config import ViTConfig, find_checkpoint_dir
-from .weights import load_encoder_checkpoint
+from .config import ViTConfig, find_checkpoint_dir, is_convnext
+from .weights import load_encoder_checkpoint, convnext_param_shapes
 
 
 def pack_encoder_weights(cfg: ViTConfig, w: Dict[str, np.ndarray]) -> np.ndarray:
     """Flatten an HF state dict into the blob order documented in include/cbas_mi355x.h."""
+    if is_convnext(cfg):
+        # the ConvNeXt blob is the state dict in convnext_param_shapes' order, every tensor as stored
+        return np.ascontiguousarray(np.concatenate([np.asarray(w[k], np.float32).reshape(-1)
+                                                    for k in convnext_param_shapes(cfg)]))
     from .weights import canonical_encoder_weights
     w = dict(canonical_encoder_weights(cfg, w))    # DINOv2-with-registers keys -> the DINOv3 names used below
     D = cfg.hidden_size
@@ -102,16 +106,26 @@ class DinoEncoder:
 
     def _init(self, cfg: ViTConfig, weights, device, max_batch, max_frame, precision):
         cfg.validate()
+        convnext = is_convnext(cfg)
+        if convnext and int(precision) not in (3, 4):
+            raise ValueError(f"precision {int(precision)}: DINOv3 ConvNeXt encoders run in precision 3 (fp32) or 4 (the default: "
+                             "fp32 with split-fp16 GEMM products) only")
         self.config = cfg
         self.device = torch.device(device)
         self._dev = _device_index(self.device)
         self.max_batch = int(max_batch)
         self.max_frame = (int(max_frame[0]), int(max_frame[1]))
         self._lib = _lib.load()
-        self._cfg_c = _lib.EncConfig(cfg.hidden_size, cfg.intermediate_size, cfg.num_hidden_layers,
-                                     cfg.num_attention_heads, cfg.num_register_tokens, cfg.patch_size,
-                                     cfg.layer_norm_eps, cfg.rope_theta, self.max_batch, self.max_frame[0],
-                                     self.max_frame[1], int(precision), int(cfg.use_rope), int(cfg.pos_embed_grid))
+        if convnext:
+            self._cfg_c = _lib.EncConfig(hidden_size=cfg.hidden_size, layer_norm_eps=cfg.layer_norm_eps, max_batch=self.max_batch,
+                                         max_height=self.max_frame[0], max_width=self.max_frame[1], precision=int(precision),
+                                         family=1, stage_widths=(C.c_int32 * 4)(*cfg.hidden_sizes),
+                                         stage_depths=(C.c_int32 * 4)(*cfg.depths))
+        else:
+            self._cfg_c = _lib.EncConfig(cfg.hidden_size, cfg.intermediate_size, cfg.num_hidden_layers,
+                                         cfg.num_attention_heads, cfg.num_register_tokens, cfg.patch_size,
+                                         cfg.layer_norm_eps, cfg.rope_theta, self.max_batch, self.max_frame[0],
+                                         self.max_frame[1], int(precision), int(cfg.use_rope), int(cfg.pos_embed_grid))
         blob = pack_encoder_weights(cfg, weights)
         need = self._lib.cbas_enc_weights_count(C.byref(self._cfg_c))
         if need != blob.shape[0]:
@@ -178,10 +192,8 @@ class DinoEncoder:
             twin.config, twin.device, twin._dev = self.config, self.device, self._dev
             twin.max_batch, twin.max_frame = self.max_batch, self.max_frame
             twin._lib, twin._blob = self._lib, self._blob
-            c = self._cfg_c
-            twin._cfg_c = _lib.EncConfig(c.hidden_size, c.intermediate_size, c.num_layers, c.num_heads, c.num_register_tokens,
-                                         c.patch_size, c.layer_norm_eps, c.rope_theta, c.max_batch, c.max_height, c.max_width,
-                                         3, c.use_rope, c.pos_embed_grid)
+            twin._cfg_c = _lib.EncConfig.from_buffer_copy(self._cfg_c)       # every field, the family's included
+            twin._cfg_c.precision = 3
             twin._h = None
             twin.model_identifier = getattr(self, "model_identifier", "<in-memory>")
             twin._create()
@@ -351,6 +363,12 @@ class DinoEncoder:
         torch.cuda.synchronize(self.device)
         _lib.check(self._lib.cbas_enc_debug_forward_u8(self._h, frames.data_ptr() + off, n, H, W, *strides,
                                                        stop_layer, stop_stage), "cbas_enc_debug_forward_u8")
+        if is_convnext(self.config):
+            # stop_layer 0: the stem after its LayerNorm, 1 + i: stage i; which = 4 + stop_layer (cbas_mi355x_debug.h)
+            (h, w), Cw = self.config.stage_grids(H, W)[max(0, stop_layer - 1)], self.config.hidden_sizes[max(0, stop_layer - 1)]
+            out = np.empty((n * h * w, Cw), np.float32)
+            _lib.check(self._lib.cbas_enc_debug_read(self._h, which, out.ctypes.data, out.nbytes), "cbas_enc_debug_read")
+            return out
         T = self.config.num_tokens(H, W)
         D, F = self.config.hidden_size, self.config.intermediate_size
         if self.precision == 4 and which in (1, 3):

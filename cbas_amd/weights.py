@@ -17,7 +17,7 @@ from typing import Dict, Tuple
 
 import numpy as np
 
-from .config import ViTConfig, HeadConfig
+from .config import ViTConfig, HeadConfig, ConvNextConfig, encoder_config_from_json, is_convnext
 
 _M64 = np.uint64(0xFFFFFFFFFFFFFFFF)
 
@@ -115,7 +115,69 @@ def canonical_encoder_weights(cfg: ViTConfig, w: Dict[str, np.ndarray]) -> Dict[
     return out
 
 
+def convnext_param_shapes(cfg: ConvNextConfig) -> Dict[str, Tuple[int, ...]]:
+    """HF ``DINOv3ConvNextModel.state_dict()`` names and shapes, in the blob order of include/cbas_mi355x.h."""
+    s: Dict[str, Tuple[int, ...]] = {}
+    prev = cfg.num_channels
+    for i, (C, depth) in enumerate(zip(cfg.hidden_sizes, cfg.depths)):
+        p = f"model.stages.{i}."
+        if i == 0:
+            s[p + "downsample_layers.0.weight"] = (C, prev, 4, 4)
+            s[p + "downsample_layers.0.bias"] = (C,)
+            s[p + "downsample_layers.1.weight"] = (C,)
+            s[p + "downsample_layers.1.bias"] = (C,)
+        else:
+            s[p + "downsample_layers.0.weight"] = (prev,)
+            s[p + "downsample_layers.0.bias"] = (prev,)
+            s[p + "downsample_layers.1.weight"] = (C, prev, 2, 2)
+            s[p + "downsample_layers.1.bias"] = (C,)
+        for j in range(depth):
+            q = f"{p}layers.{j}."
+            s[q + "depthwise_conv.weight"] = (C, 1, 7, 7)
+            s[q + "depthwise_conv.bias"] = (C,)
+            s[q + "layer_norm.weight"] = (C,)
+            s[q + "layer_norm.bias"] = (C,)
+            s[q + "pointwise_conv1.weight"] = (4 * C, C)
+            s[q + "pointwise_conv1.bias"] = (4 * C,)
+            s[q + "pointwise_conv2.weight"] = (C, 4 * C)
+            s[q + "pointwise_conv2.bias"] = (C,)
+            s[q + "gamma"] = (C,)
+        prev = C
+    s["layer_norm.weight"] = (prev,)
+    s["layer_norm.bias"] = (prev,)
+    return s
+
+
+def synth_convnext_weights(cfg: ConvNextConfig, seed: int = 1234) -> Dict[str, np.ndarray]:
+    """Seeded random ConvNeXt weights on the same counter-based generator.  LayerNorm gains / offsets, biases and the layer
+    scale ``gamma`` are randomised too: at its 1e-6 init every block would be an identity and a wrong block invisible."""
+    out: Dict[str, np.ndarray] = {}
+    for name, shape in convnext_param_shapes(cfg).items():
+        leaf = name.split(".")[-1]
+        is_norm = len(shape) == 1 and ("layer_norm" in name or ("downsample_layers" in name and
+                                                                  name.split(".")[-2] == ("1" if ".stages.0." in name else "0")))
+        if leaf == "gamma":
+            w = synth_uniform(seed, name, shape, 0.2, 1.0)
+        elif is_norm and leaf == "weight":
+            w = synth_uniform(seed, name, shape, 0.7, 1.3)
+        elif is_norm and leaf == "bias":
+            w = synth_uniform(seed, name, shape, -0.2, 0.2)
+        elif leaf == "bias":
+            w = synth_uniform(seed, name, shape, -0.1, 0.1)
+        elif "depthwise_conv" in name:
+            w = synth_normal(seed, name, shape, 0.1)
+        elif ".stages.0.downsample_layers.0." in name:
+            w = synth_normal(seed, name, shape, 0.2)
+        else:
+            fan_in = int(np.prod(shape[1:]))
+            w = synth_normal(seed, name, shape, 1.0 / np.sqrt(fan_in))
+        out[name] = w
+    return out
+
+
 def encoder_param_shapes(cfg: ViTConfig) -> Dict[str, Tuple[int, ...]]:
+    if is_convnext(cfg):
+        return convnext_param_shapes(cfg)
     if cfg.model_type == "dinov2_with_registers":
         return _dinov2_param_shapes(cfg)
     D, F, R, p, C = cfg.hidden_size, cfg.intermediate_size, cfg.num_register_tokens, cfg.patch_size, cfg.num_channels
@@ -258,7 +320,7 @@ def _load_safetensors_f32(path: str) -> Dict[str, np.ndarray]:
 
 def load_encoder_checkpoint(ckpt_dir: str) -> Tuple[ViTConfig, Dict[str, np.ndarray]]:
     """Read ``config.json`` + ``model.safetensors`` written by ``save_pretrained`` / the HF hub."""
-    cfg = ViTConfig.from_json_file(os.path.join(ckpt_dir, "config.json"))
+    cfg = encoder_config_from_json(os.path.join(ckpt_dir, "config.json"))
     st_path = os.path.join(ckpt_dir, "model.safetensors")
     index = os.path.join(ckpt_dir, "model.safetensors.index.json")
     if os.path.exists(st_path):

@@ -52,7 +52,7 @@ extern "C" {
 #define CBAS_ESTATE       -4   /* call sequence error (e.g. wait on an idle slot) */
 #define CBAS_ERANGE       -5   /* a frame's CLS row came out NaN / infinite: an activation left the arithmetic mode's range */
 
-#define CBAS_ABI_VERSION   10
+#define CBAS_ABI_VERSION   11
 
 typedef struct cbas_enc  cbas_enc;
 typedef struct cbas_head cbas_head;
@@ -103,6 +103,15 @@ typedef struct cbas_enc_config {
     int32_t use_rope;             /* 1: DINOv3 (RoPE on patch rows, no additive position embedding)     */
     int32_t pos_embed_grid;       /* G > 0: DINOv2-with-registers, learned (1+G*G, D) position embedding,
                                      bicubic-antialias interpolated to each frame's patch grid; else 0 */
+    /* ABI 11: the encoder family.  All-zero trailing fields keep the ViT behaviour of ABI 10. */
+    int32_t family;               /* 0: ViT (the fields above); 1: DINOv3 ConvNeXt (transformers models/dinov3_convnext,
+                                     DINOv3ConvNextModel: row 0 = LayerNorm(global mean pool of the last stage)).  ConvNeXt uses
+                                     stage_widths / stage_depths, layer_norm_eps, max_batch, max_height, max_width and
+                                     precision (3 or 4 only); hidden_size must equal stage_widths[3] (the row width), the
+                                     other ViT fields are ignored.  Every width must be a multiple of 32, hidden_act exact-erf
+                                     GELU (the caller checks the config; this struct has no activation field). */
+    int32_t stage_widths[4];      /* ConvNeXt hidden_sizes: 96 192 384 768 (tiny / small)                          */
+    int32_t stage_depths[4];      /* ConvNeXt depths: 3 3 9 3 (tiny), 3 3 27 3 (small)                               */
 } cbas_enc_config;
 
 /* Number of float32 elements cbas_enc_create expects in `weights`, in this order:
@@ -111,12 +120,25 @@ typedef struct cbas_enc_config {
  *   then per layer: norm1.w[D] norm1.b[D] q.w[D*D] q.b[D] k.w[D*D] k.b[D] (zeros for DINOv3) v.w[D*D] v.b[D] o.w[D*D] o.b[D]
  *                   ls1[D] norm2.w[D] norm2.b[D] up.w[F*D] up.b[F] down.w[D*F] down.b[D] ls2[D],
  *   then norm.w[D] norm.b[D].
- * Linear weights are (out_features, in_features) row-major, exactly the HF state_dict tensors. */
+ * Linear weights are (out_features, in_features) row-major, exactly the HF state_dict tensors.
+ * family = 1 (ConvNeXt), with C_i = stage_widths[i] and the HF DINOv3ConvNextModel state-dict tensors as stored:
+ *   stem: downsample_layers.0.weight[C0*3*4*4] .bias[C0], stem LayerNorm downsample_layers.1.weight[C0] .bias[C0],
+ *   per stage i > 0: LayerNorm downsample_layers.0.weight[C_{i-1}] .bias[C_{i-1}], conv downsample_layers.1.weight[C_i*C_{i-1}*2*2]
+ *                    .bias[C_i],
+ *   per block of stage i (stage_depths[i] of them): depthwise_conv.weight[C*49] .bias[C], layer_norm.weight[C] .bias[C],
+ *                    pointwise_conv1.weight[4C*C] .bias[4C], pointwise_conv2.weight[C*4C] .bias[C], gamma[C],
+ *   then the final layer_norm.weight[C3] .bias[C3]. */
 int64_t cbas_enc_weights_count(const cbas_enc_config* cfg);
 
 int cbas_enc_create(const cbas_enc_config* cfg, const float* weights_host, int64_t n_weights,
                     int device_id, cbas_enc** out);
 void cbas_enc_destroy(cbas_enc* h);
+
+/* ConvNeXt handles take every forward / submit / wait / fused-session entry point below unchanged; frames must be at least
+ * 32 x 32 (the stem and the three downsamples divide by 32; odd sizes drop the last row / column at each step, as PyTorch's
+ * strided convolutions do).  cbas_enc_set_prune_last_layer is accepted and has no effect; cbas_enc_profile_read reports the
+ * stem and downsample GEMMs as CBAS_PROF_PATCH, the LayerNorm / depthwise / pooling kernels as CBAS_PROF_LAYERNORM,
+ * pointwise_conv1 as CBAS_PROF_UP and pointwise_conv2 as CBAS_PROF_DOWN. */
 
 /* DinoEncoder.forward on a device tensor: x (n,1,H,W) float32 in [0,1] (gray; replicated to 3
  * identical channels by the reference, folded into the patch weights here).  Writes CLS rows:

@@ -22,7 +22,9 @@ int cbas_debug_build(void);
 /* Bring-up/debug: run the forward pass only up to (layer, stage) and copy an internal buffer to
  * the host.  stage: 0 embeddings (x), then per layer 1 LN1(h16) 2 QKV(qkv16) 3 attention(h16)
  * 4 o_proj residual (x) 5 LN2 (h16) 6 up_proj+GELU (u16) 7 down_proj residual (x).
- * which: 0 x f32 (rows,D)  1 h16 (rows,D)  2 qkv16 (rows,3D)  3 u16 (rows,F); rows = n*T. */
+ * which: 0 x f32 (rows,D)  1 h16 (rows,D)  2 qkv16 (rows,3D)  3 u16 (rows,F); rows = n*T.
+ * ConvNeXt handles (family 1): stop_layer 0 stops after the stem and its LayerNorm, stop_layer 1 + i after stage i (stop_stage
+ * is ignored); which = 4 + stop_layer then reads that tensor as f32 (n*h*w, C) rows (frame, y, x), C = the stage's width. */
 int cbas_enc_debug_forward_u8(cbas_enc* h, const uint8_t* frames_dev, int n, int height, int width,
                               int64_t frame_stride, int64_t row_stride, int64_t pixel_stride,
                               int stop_layer, int stop_stage);
