@@ -50,6 +50,7 @@ struct cbas_head_trainer {
     float *terms, *sums, *dfinal, *dlstm, *dlin, *part_pool, *part_exp, *cs_tmp, *dhA, *dhB, *dgin, *hprev, *dxl, *daug, *dproj,
         *XT, *dprojT, *augT, *dZT, *dginT, *xinT, *hprevT, *latentT, *dlogT, *Rc, *RcT, *cov, *Gm, *sq, *dlat_cov, *wlin0T, *wihT,
         *skbuf;                                                          // split-K partial tiles
+    float* xg = nullptr;             // [max_batch][T][I] windows gathered by cbas_head_train_step_rows (the step's operand)
     std::vector<void*> allocs;
 };
 
@@ -250,6 +251,7 @@ extern "C" int cbas_head_train_create(const cbas_head_config* cfg, const cbas_tr
         if (8 * h * (L0 > H2 ? L0 : H2) > mx) mx = 8 * h * (L0 > H2 ? L0 : H2);
         TRY_HIP(dalloc(&t->skbuf, 16 * mx));
     }
+    TRY_HIP(dalloc(&t->xg, R * I));      // filled below like every other buffer: ordered before the handle is handed out
     // dalloc zero-fills with hipMemset on the NULL stream, which may return before the fill has run, and the training step is
     // queued on the caller's stream - in CBAS a torch stream, NON-BLOCKING, hence not ordered after the null stream: beside a
     // busy encoder the fills of G / M / V landed after the first steps had written them (r5: 114 of 125 forty-step runs
@@ -384,6 +386,35 @@ extern "C" int cbas_head_train_step(cbas_head_trainer* t, const float* x_dev, co
         loss_host[0] = loss_host[1] + loss_host[2];
     }
     return CBAS_OK;
+}
+
+extern "C" int cbas_rows_gather_windows(const uint16_t* rows_f16_dev, int64_t n_rows, int32_t dim, const int64_t* first_row_dev,
+                                        int32_t n_windows, int32_t seq_len, float* x_out_dev, void* stream) {
+    if (!rows_f16_dev || !first_row_dev || !x_out_dev) return cbas_fail(CBAS_EINVAL, "rows_f16_dev / first_row_dev / x_out_dev NULL");
+    if (n_rows < 0) return cbas_fail(CBAS_EINVAL, "n_rows=%lld is negative", (long long)n_rows);
+    if (dim < 1 || seq_len < 1 || seq_len > ROWS_GATHER_MAX_SEQ || (int64_t)dim * seq_len > ROWS_GATHER_MAX_WINDOW)
+        return cbas_fail(CBAS_EINVAL, "dim=%d, seq_len=%d: both at least 1, seq_len <= %d and dim * seq_len <= %lld", dim, seq_len,
+                         ROWS_GATHER_MAX_SEQ, (long long)ROWS_GATHER_MAX_WINDOW);
+    if (n_windows < 1) return cbas_fail(CBAS_EINVAL, "n_windows=%d must be at least 1", n_windows);
+    LAUNCH_TRY(launch_rows_gather(rows_f16_dev, n_rows, dim, first_row_dev, n_windows, seq_len, x_out_dev, (hipStream_t)stream));
+    return CBAS_OK;
+}
+
+extern "C" int cbas_head_train_step_rows(cbas_head_trainer* t, const uint16_t* rows_f16_dev, int64_t n_rows, int32_t dim,
+                                         const int64_t* first_row_dev, const int32_t* labels_dev, int32_t n_windows,
+                                         int32_t seq_len, int32_t update, float* loss_host, void* stream) {
+    if (!t) return cbas_fail(CBAS_EINVAL, "null trainer handle");
+    if (!rows_f16_dev || !first_row_dev || !labels_dev) return cbas_fail(CBAS_EINVAL, "rows_f16_dev / first_row_dev / labels_dev NULL");
+    if (dim != t->I || seq_len != t->T)
+        return cbas_fail(CBAS_EINVAL, "rows of width %d in windows of %d: the trainer was created for in_features=%d, seq_len=%d", dim,
+                         seq_len, t->I, t->T);
+    if (n_windows < 1 || n_windows > t->Bcap) return cbas_fail(CBAS_EINVAL, "n_windows=%d outside [1, max_batch=%lld]", n_windows, (long long)t->Bcap);
+    HIP_TRY(hipSetDevice(t->device));
+    // t->xg holds max_batch windows and was filled before cbas_head_train_create returned; the gather and the step that
+    // reads it are queued on the same stream
+    const int rc = cbas_rows_gather_windows(rows_f16_dev, n_rows, dim, first_row_dev, n_windows, seq_len, t->xg, stream);
+    if (rc != CBAS_OK) return rc;
+    return cbas_head_train_step(t, t->xg, labels_dev, n_windows, update, loss_host, stream);
 }
 
 extern "C" int cbas_head_train_read(cbas_head_trainer* t, int32_t what, float* blob_host, int64_t n) {

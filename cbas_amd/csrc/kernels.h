@@ -316,3 +316,10 @@ int launch_colsum(const float* src, int64_t rows, int cols, int64_t ld, float sc
 int launch_add_vec(const float* a, const float* b, float* out, int n, hipStream_t st);      // b == nullptr: copy
 int launch_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float wd, int64_t wd_lo, int64_t wd_hi,
                      float wd_special, int step, hipStream_t st);
+
+// rows_gather.hip: x_out[w][t][:] = float(rows_f16[first_row[w] + t][:]); rows outside [0, n_rows) read as zeros.
+// Returns -1 for a null pointer, a non-positive size or a window beyond the limits below.
+constexpr int ROWS_GATHER_MAX_SEQ = 1 << 16;
+constexpr int64_t ROWS_GATHER_MAX_WINDOW = (int64_t)1 << 23;      // seq_len * dim elements (grid.y stays under 65 536 blocks)
+int launch_rows_gather(const uint16_t* rows_f16, int64_t n_rows, int dim, const int64_t* first_row, int n_windows, int seq_len,
+                       float* x_out, hipStream_t st);

@@ -82,3 +82,37 @@ def train_windows(seed: int, n: int, dim: int, n_classes: int, seq_len: int = 31
     y = rng.integers(0, n_classes, n).astype(np.int64)
     proto = synth_normal(seed, "train_proto", (n_classes, dim), 0.5).astype(np.float32)
     return (x + proto[y][:, None, :]).astype(np.float32), y
+
+
+def cls_project(root: str, sizes, dim: int, n_classes: int, seed: int, block: int = 24, skip_classes=()):
+    """A synthetic project of ``_cls.h5`` files under ``root`` (written with ``h5io.ClsWriter``): file i is
+    ``clip{i}_cls.h5`` with ``sizes[i]`` half-precision rows of a CLS-like walk, offset per frame by the prototype of that
+    frame's class.  Classes change every ``block`` frames in an order drawn from ``seed`` (never one of ``skip_classes``), so
+    the classes are unbalanced.  Returns ``(paths, [int64 labels per frame, one array per file])``."""
+    import os
+    from . import h5io
+    classes = np.array([c for c in range(n_classes) if c not in set(skip_classes)], np.int64)
+    proto = synth_normal(seed, "project_proto", (n_classes, dim), 0.5).astype(np.float32)
+    paths, labels = [], []
+    for i, n in enumerate(sizes):
+        n = int(n)
+        draws = _hash_stream(seed, f"project_labels_{i}", n // block + 1)
+        # squaring the draw skews the choice towards the first classes
+        pick = ((draws % np.uint64(1000)).astype(np.float64) / 1000.0) ** 2
+        lab = np.repeat(classes[(pick * len(classes)).astype(np.int64)], block)[:n]
+        rows = (cls_walk(seed + 1 + i, n, dim).astype(np.float32) + proto[lab]).astype(np.float16)
+        path = os.path.join(root, f"clip{i}_cls.h5")
+        with h5io.ClsWriter(path, dim) as w:
+            w.append(rows)
+        paths.append(path)
+        labels.append(lab)
+    return paths, labels
+
+
+def label_runs(labels: np.ndarray):
+    """``[(start, end, class)]`` (end inclusive) of the runs of equal labels of one file: instances as CBAS stores them."""
+    labels = np.asarray(labels)
+    cuts = np.flatnonzero(np.diff(labels)) + 1
+    starts = np.concatenate([[0], cuts])
+    ends = np.concatenate([cuts, [len(labels)]]) - 1
+    return [(int(a), int(b), int(labels[a])) for a, b in zip(starts, ends)]

@@ -52,6 +52,8 @@ extern "C" {
 #define CBAS_ESTATE       -4   /* call sequence error (e.g. wait on an idle slot) */
 #define CBAS_ERANGE       -5   /* a frame's CLS row came out NaN / infinite: an activation left the arithmetic mode's range */
 
+/* Still 11 with cbas_rows_gather_windows / cbas_head_train_step_rows: they are additions.  No structure and no existing
+ * signature changed, so a caller built against the earlier version 11 header runs unchanged. */
 #define CBAS_ABI_VERSION   11
 
 typedef struct cbas_enc  cbas_enc;
@@ -368,6 +370,23 @@ void cbas_head_train_destroy(cbas_head_trainer* t);
  * only (no Adam step; the step counter and the dropout stream do not advance). */
 int cbas_head_train_step(cbas_head_trainer* t, const float* x_dev, const int32_t* labels_dev, int32_t n_windows,
                          int32_t update, float* loss_host, void* stream);
+
+/* Training and scoring from a store of CLS rows that stays in device memory.  The reference builds every window on the
+ * host: one HDF5 slice of seq_len rows around the centre frame, `.float()`, stacked into the batch and copied to the device
+ * (LazyStandardDataset / LazyBalancedDataset.__getitem__, backend/cbas.py:194-228, feeding the loop of cbas.py:1326-1348).
+ * Here the half-precision rows of all `_cls.h5` files lie in one device array and a window is named by its first row:
+ *   x_out[w][t][:] = float(rows[first_row[w] + t][:])        w < n_windows, t < seq_len      (f16 -> f32 is exact)
+ * rows_f16_dev (n_rows, dim) IEEE half, first_row_dev (n_windows) int64, x_out_dev (n_windows, seq_len, dim) float32: all
+ * device pointers, on the device `stream` belongs to.  A row outside [0, n_rows) is never read and comes out as zeros.
+ * CBAS_EINVAL: a NULL pointer, n_rows < 0, dim / seq_len / n_windows < 1, seq_len > 65536, dim * seq_len > 2^23. */
+int cbas_rows_gather_windows(const uint16_t* rows_f16_dev, int64_t n_rows, int32_t dim, const int64_t* first_row_dev,
+                             int32_t n_windows, int32_t seq_len, float* x_out_dev, void* stream);
+/* cbas_head_train_step on windows gathered from such a store: exactly cbas_rows_gather_windows into a buffer the trainer
+ * has owned since cbas_head_train_create (max_batch windows), then cbas_head_train_step on it, both on `stream`.
+ * CBAS_EINVAL also when dim != in_features, seq_len != the trainer's seq_len or n_windows > max_batch. */
+int cbas_head_train_step_rows(cbas_head_trainer* t, const uint16_t* rows_f16_dev, int64_t n_rows, int32_t dim,
+                              const int64_t* first_row_dev, const int32_t* labels_dev, int32_t n_windows, int32_t seq_len,
+                              int32_t update, float* loss_host, void* stream);
 
 /* Copy the current parameters (what = 0) or the gradients of the last step (what = 1) to the host, in the
  * blob order of cbas_head_create (n = cbas_head_weights_count).  Synchronises the device. */
