@@ -2,6 +2,7 @@
 // See include/cbas_mi355x.h for the contract and the reference lines each entry point replaces.
 #include <math.h>
 #include <string.h>
+#include <mutex>
 #include <new>
 #include <vector>
 
@@ -10,6 +11,7 @@
 
 namespace {
 constexpr int64_t WCHUNK = 4096;     // most windows per pass (bounds the workspace at ~1 GB for T = 31, h = 64)
+constexpr int64_t SCORE_CHUNK = 512;  // windows gathered per pass of cbas_head_score_rows (49 MB of fp32 windows at T = 31, I = 768)
 }
 
 struct cbas_head {
@@ -30,6 +32,10 @@ struct cbas_head {
     int64_t win_cap = 0;             // windows per pass the per-window buffers hold
     int64_t proj_rows_cap = 0;       // rows of `proj` (explicit windows: w*T; sliding: w + T)
     int64_t rows32_cap = 0;          // rows of `rows32` (sliding mode with half-precision input only)
+    // cbas_head_score_rows: allocated by its first call
+    float* score_x = nullptr;        // [SCORE_CHUNK][T][I] gathered windows
+    float* score_logits = nullptr;   // [SCORE_CHUNK][C] logits of a pass when the caller keeps none
+    unsigned* score_flags = nullptr; // HEAD_SCORE_FLAG_* of the call in flight (a 16-byte block)
 #if CBAS_BUILD_DEBUG
     hipModule_t expand_module = nullptr;     // cbas_head_debug_expand_module: a probe kernel run in place of head_expand_kernel
     hipFunction_t expand_fn = nullptr;
@@ -220,7 +226,8 @@ extern "C" void cbas_head_destroy(cbas_head* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
-    void* bufs[] = {h->wbuf, h->rows32, h->proj, h->aug, h->xl, h->gin, h->hout, h->lin_logits, h->hfull};
+    void* bufs[] = {h->wbuf, h->rows32, h->proj, h->aug, h->xl, h->gin, h->hout, h->lin_logits, h->hfull,
+                    h->score_x, h->score_logits, h->score_flags};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
 #if CBAS_BUILD_DEBUG
@@ -364,6 +371,89 @@ extern "C" int cbas_head_forward_windows(cbas_head* h, const float* x_dev, int64
                        latent_dev ? latent_dev + w0 * 2 * d.h : nullptr, st);
         if (rc) return rc;
     }
+    return CBAS_OK;
+}
+
+extern "C" int cbas_head_score_rows(cbas_head* h, const uint16_t* rows_f16_dev, int64_t n_rows, int32_t dim,
+                                    const int64_t* first_row_dev, const int32_t* labels_dev, int64_t n_windows,
+                                    float* logits_out_dev, int32_t* pred_out_dev, int64_t* confusion_dev, void* stream) {
+    if (!h) return cbas_fail(CBAS_EINVAL, "null head handle");
+    if (!rows_f16_dev || !first_row_dev) return cbas_fail(CBAS_EINVAL, "rows_f16_dev / first_row_dev NULL");
+    const HeadDims& d = h->d;
+    if (dim != d.I) return cbas_fail(CBAS_EINVAL, "rows of width %d: the head was created for in_features=%d", dim, d.I);
+    if (n_rows < 0 || n_windows < 1 || n_windows > 0x7fffffff)
+        return cbas_fail(CBAS_EINVAL, "n_rows=%lld, n_windows=%lld: n_rows >= 0 and 1 <= n_windows < 2^31", (long long)n_rows,
+                         (long long)n_windows);
+    if (confusion_dev && !labels_dev) return cbas_fail(CBAS_EINVAL, "confusion_dev without labels_dev");
+    if (!logits_out_dev && !pred_out_dev && !confusion_dev) return cbas_fail(CBAS_EINVAL, "no output requested");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (!h->score_x) HIP_TRY(hipMalloc(&h->score_x, (size_t)SCORE_CHUNK * d.T * d.I * sizeof(float)));
+    if (!h->score_logits) HIP_TRY(hipMalloc(&h->score_logits, (size_t)SCORE_CHUNK * d.C * sizeof(float)));
+    if (!h->score_flags) HIP_TRY(hipMalloc(&h->score_flags, 16));
+    HIP_TRY(hipMemsetAsync(h->score_flags, 0, 16, st));
+    for (int64_t w0 = 0; w0 < n_windows; w0 += SCORE_CHUNK) {
+        const int64_t nw = n_windows - w0 < SCORE_CHUNK ? n_windows - w0 : SCORE_CHUNK;
+        int rc = cbas_rows_gather_windows(rows_f16_dev, n_rows, dim, first_row_dev + w0, (int32_t)nw, d.T, h->score_x, stream);
+        if (rc) return rc;
+        float* lg = logits_out_dev ? logits_out_dev + w0 * d.C : h->score_logits;
+        rc = cbas_head_forward_windows(h, h->score_x, nw, lg, nullptr, stream);
+        if (rc) return rc;
+        LAUNCH_TRY(launch_head_score(lg, labels_dev ? labels_dev + w0 : nullptr, nw, d.C, pred_out_dev ? pred_out_dev + w0 : nullptr,
+                                     reinterpret_cast<unsigned long long*>(confusion_dev), h->score_flags, st));
+    }
+    unsigned flags = 0;
+    HIP_TRY(hipMemcpyAsync(&flags, h->score_flags, sizeof(flags), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (flags & HEAD_SCORE_FLAG_LABEL) return cbas_fail(CBAS_EINVAL, "a label lies outside [0, %d)", d.C);
+    if (flags & HEAD_SCORE_FLAG_NAN) return cbas_fail(CBAS_ERANGE, "a window's logits hold a NaN: it has no label");
+    return CBAS_OK;
+}
+
+namespace {
+// cbas_logits_nll has no handle to keep its scratch in: one block per device for the life of the process (1 KB of partials
+// and the ticket word).  Launches that share it are ordered on the device: a launch on another stream than the last one
+// first waits for the last one's event.
+struct NllScratch {
+    unsigned long long* partials = nullptr;
+    unsigned* ticket = nullptr;
+    hipEvent_t done = nullptr;
+    hipStream_t last = nullptr;
+    bool used = false;
+};
+constexpr int NLL_MAX_DEVICES = 64;
+NllScratch g_nll[NLL_MAX_DEVICES];
+std::mutex g_nll_mutex;
+}  // namespace
+
+extern "C" int cbas_logits_nll(const float* logits_dev, const int32_t* labels_dev, int64_t n, int32_t n_classes, float temp,
+                               float* out2_dev, void* stream) {
+    if (!logits_dev || !labels_dev || !out2_dev) return cbas_fail(CBAS_EINVAL, "logits_dev / labels_dev / out2_dev NULL");
+    if (n < 1 || n_classes < 1 || n_classes > HEAD_SCORE_MAX_CLASSES)
+        return cbas_fail(CBAS_EINVAL, "n=%lld, n_classes=%d: n >= 1 and 1 <= n_classes <= %d", (long long)n, n_classes,
+                         HEAD_SCORE_MAX_CLASSES);
+    if (!(temp > 0.f)) return cbas_fail(CBAS_EINVAL, "temp=%g must be positive", (double)temp);
+    hipPointerAttribute_t attr;
+    HIP_TRY(hipPointerGetAttributes(&attr, out2_dev));
+    const int dev = attr.device;
+    if (dev < 0 || dev >= NLL_MAX_DEVICES) return cbas_fail(CBAS_EINVAL, "out2_dev lies on device %d", dev);
+    HIP_TRY(hipSetDevice(dev));
+    hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lock(g_nll_mutex);
+    NllScratch& s = g_nll[dev];
+    if (!s.partials) {
+        // the ticket's 16-byte block begins the allocation, the partials follow it
+        void* p = nullptr;
+        HIP_TRY(hipMalloc(&p, 16 + (size_t)LOGITS_NLL_MAX_BLOCKS * sizeof(unsigned long long)));
+        s.ticket = reinterpret_cast<unsigned*>(p);
+        s.partials = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(p) + 16);
+        HIP_TRY(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+    }
+    if (s.used && s.last != st) HIP_TRY(hipStreamWaitEvent(st, s.done, 0));
+    LAUNCH_TRY(launch_logits_nll(logits_dev, labels_dev, n, n_classes, temp, s.partials, s.ticket, out2_dev, st));
+    HIP_TRY(hipEventRecord(s.done, st));
+    s.last = st;
+    s.used = true;
     return CBAS_OK;
 }
 

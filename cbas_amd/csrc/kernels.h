@@ -323,3 +323,17 @@ constexpr int ROWS_GATHER_MAX_SEQ = 1 << 16;
 constexpr int64_t ROWS_GATHER_MAX_WINDOW = (int64_t)1 << 23;      // seq_len * dim elements (grid.y stays under 65 536 blocks)
 int launch_rows_gather(const uint16_t* rows_f16, int64_t n_rows, int dim, const int64_t* first_row, int n_windows, int seq_len,
                        float* x_out, hipStream_t st);
+
+// head_score_kernels.hip: the per-batch host work of the reference's scoring and calibration loops, on the device.
+// launch_head_score: pred[w] = first index of the row maximum of logits (n, C) (-1 for a row with a NaN), confusion[y][pred] += 1
+// (64-bit integer atomics; labels / confusion may both be null, pred may be null); *flags |= the bits below.
+constexpr int HEAD_SCORE_MAX_CLASSES = 64;
+constexpr unsigned HEAD_SCORE_FLAG_NAN = 1u;        // a logit row holds a NaN
+constexpr unsigned HEAD_SCORE_FLAG_LABEL = 2u;      // a label outside [0, C)
+int launch_head_score(const float* logits, const int* labels, int64_t n, int C, int* pred, unsigned long long* confusion,
+                      unsigned* flags, hipStream_t st);
+// launch_logits_nll: out2 = {mean cross-entropy of logits / temp, its derivative with respect to temp}, summed in a fixed
+// order.  partials: LOGITS_NLL_MAX_BLOCKS 8-byte words; ticket: the first word of a 16-byte block that the launcher zeroes.
+constexpr int LOGITS_NLL_MAX_BLOCKS = 128;
+int launch_logits_nll(const float* logits, const int* labels, int64_t n, int C, float temp, unsigned long long* partials,
+                      unsigned* ticket, float* out2, hipStream_t st);

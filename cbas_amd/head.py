@@ -57,6 +57,30 @@ def _to_numpy(v) -> np.ndarray:
     return np.asarray(v, dtype=np.float32)
 
 
+class LSTMFacts:
+    """What ``model.lstm`` answers for the head: the shape of the stacked bidirectional LSTM, read-only.  The reference's
+    bundle writer reads ``hidden_size`` and ``num_layers`` from it (backend/workthreads.py:876-877); no other attribute of
+    ``torch.nn.LSTM`` is promised - the weights live in the head's state dict."""
+
+    __slots__ = ("_facts",)
+
+    def __init__(self, input_size: int, hidden_size: int, num_layers: int):
+        object.__setattr__(self, "_facts", {"input_size": int(input_size), "hidden_size": int(hidden_size),
+                                            "num_layers": int(num_layers), "bidirectional": True})
+
+    def __getattr__(self, name):
+        try:
+            return object.__getattribute__(self, "_facts")[name]
+        except KeyError:
+            raise AttributeError(f"the MI355X head's lstm has only {sorted(self._facts)}; no attribute {name!r}") from None
+
+    def __setattr__(self, name, value):
+        raise AttributeError("the MI355X head's lstm attributes are read-only")
+
+    def __repr__(self):
+        return "LSTMFacts(" + ", ".join(f"{k}={v}" for k, v in self._facts.items()) + ")"
+
+
 class ClassifierLSTMDeltas:
     def __init__(self, in_features, out_features, seq_len=31, bottleneck_dim=128, dropout_p=0.15,
                  use_acceleration=True, ema_alpha=0.3, center_window_size=5, lstm_hidden_size=64, lstm_layers=1):
@@ -67,6 +91,9 @@ class ClassifierLSTMDeltas:
         self.config.validate()
         self.in_features, self.out_features = in_features, out_features
         self.seq_len, self.sw, self.hsl = seq_len, center_window_size, seq_len // 2
+        # what the reference's bundle writer reads for model_meta.json (workthreads.py:875-877)
+        self.use_acceleration = bool(use_acceleration)
+        self.lstm = LSTMFacts(self.config.lin0_dim, lstm_hidden_size, lstm_layers)
         self.device: Optional[torch.device] = None
         self._weights: Optional[Dict[str, np.ndarray]] = None
         self._h = None
@@ -169,6 +196,38 @@ class ClassifierLSTMDeltas:
         _lib.check(self._lib.cbas_head_forward_windows(self._h, x.data_ptr(), B, logits.data_ptr(),
                                                        latent.data_ptr(), stream), "cbas_head_forward_windows")
         return logits, latent
+
+    # -- a split's windows out of a resident store: logits, argmax and confusion matrix on the device --------
+    def score_rows(self, rows: torch.Tensor, first_row: torch.Tensor, labels: Optional[torch.Tensor] = None,
+                   want_logits: bool = False, want_pred: bool = False):
+        """``cbas_head_score_rows`` over the windows ``rows[first_row[w] : first_row[w] + seq_len]`` of a float16 store on
+        this device.  Returns ``(logits (n, C) float32 or None, pred (n,) int32 or None, confusion (C, C) int64 or None)``,
+        all on the device; ``confusion[true][predicted]`` is returned when ``labels`` are given.  The first of equal maxima
+        is the prediction, as ``torch.argmax``.  A window whose logits hold a NaN, or a label outside ``[0, C)``, raises."""
+        self._ensure()
+        if rows.dim() != 2 or rows.dtype != torch.float16 or not rows.is_cuda or not rows.is_contiguous() \
+                or rows.shape[1] != self.in_features:
+            raise ValueError(f"rows must be a contiguous float16 (N, {self.in_features}) tensor on {self.device}, got "
+                             f"{rows.dtype} {tuple(rows.shape)} on {rows.device}")
+        n = int(first_row.shape[0])
+        if first_row.dim() != 1 or n < 1 or (labels is not None and tuple(labels.shape) != (n,)):
+            raise ValueError(f"first_row {tuple(first_row.shape)} must be (n >= 1,) and labels, when given, (n,)")
+        f = first_row.to(rows.device, torch.int64).contiguous()
+        y = labels.to(rows.device, torch.int32).contiguous() if labels is not None else None
+        C_ = self.out_features
+        logits = torch.empty((n, C_), dtype=torch.float32, device=rows.device) if want_logits else None
+        pred = torch.empty((n,), dtype=torch.int32, device=rows.device) if want_pred else None
+        confusion = torch.zeros((C_, C_), dtype=torch.int64, device=rows.device) if y is not None else None
+        if logits is None and pred is None and confusion is None:
+            raise ValueError("score_rows: nothing asked for (labels, want_logits or want_pred)")
+        with torch.cuda.device(rows.device):
+            stream = torch.cuda.current_stream(rows.device).cuda_stream
+            _lib.check(self._lib.cbas_head_score_rows(
+                self._h, rows.data_ptr(), int(rows.shape[0]), int(rows.shape[1]), f.data_ptr(),
+                y.data_ptr() if y is not None else None, n, logits.data_ptr() if logits is not None else None,
+                pred.data_ptr() if pred is not None else None, confusion.data_ptr() if confusion is not None else None,
+                stream), "cbas_head_score_rows")
+        return logits, pred, confusion
 
     # -- whole-clip sliding-window inference --------------------------------------------------------
     def infer_clip(self, cls_rows: torch.Tensor, temperature: float = 1.0, want_logits: bool = False):

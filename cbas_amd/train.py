@@ -16,14 +16,21 @@ first-row indices that ``cbas_head_train_step_rows`` / ``cbas_rows_gather_window
 ``CBAS_TRAIN_RESIDENT=0`` or rows that do not fit (free device memory minus 2 GiB, ``CBAS_TRAIN_RESIDENT_MAX_GB``) keep
 the host loader; the ``log`` line "training data: ..." says which path runs and why.
 
+The tail of a training job runs from the same rows: ``evaluate_on_split`` (backend/cbas.py:1222-1251) scores a split with one
+``cbas_head_score_rows`` call and copies back the confusion matrix, ``fit_temperature`` (backend/workthreads.py:103-137) keeps
+the logits on the device and evaluates the L-BFGS closure with ``cbas_logits_nll``; inside ``keep_rows()`` they and
+``train_lstm_model`` share one store.
+
 Dropout keep-masks come from a counter-based hash (seed, step, layer, element) instead of torch's
 global RNG, so a run is reproducible from its seed; the masks have the reference's rates (0.1 after
 the three bottleneck GELUs, 0.15 after lin0's GELU).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
+import threading
 from typing import Dict, List, Mapping, Optional, Sequence
 
 import numpy as np
@@ -289,6 +296,7 @@ class ResidentRows:
     def __init__(self, plan: "_ds.StorePlan", device):
         self.device = torch.device(device)
         self.files = dict(plan.files)
+        self.dim = int(plan.dim)
         self.rows = torch.zeros((plan.total_rows, plan.dim), dtype=torch.float16, device=self.device)
         for path, (base, n) in plan.files.items():
             try:
@@ -338,13 +346,12 @@ def _thousands(n: int) -> str:
     return f"{n:,}".replace(",", " ")
 
 
-def plan_training_data(train_set, test_set, seq_len: int, in_features: int, device):
-    """Decide between rows resident in device memory and the host loader.  Returns ``(plan or None, one line that says
-    which and why)``; raises ValueError for files whose row width is not ``in_features``."""
+def _plan_sets(sets, names, seq_len: int, in_features: int):
+    """``(StorePlan, None)`` for manifest datasets whose half-precision rows can lie in one store, else ``(None, the
+    "training data: host loader (...)" line that says why not)``."""
     if os.environ.get("CBAS_TRAIN_RESIDENT", "1").strip() == "0":
         return None, "training data: host loader (CBAS_TRAIN_RESIDENT=0)"
-    sets = [train_set] + ([test_set] if test_set is not None and len(test_set) > 0 else [])
-    for name, ds in zip(("training", "test"), sets):
+    for name, ds in zip(names, sets):
         if _ds.manifest_kind(ds) is None:
             return None, f"training data: host loader (the {name} set is not a manifest dataset)"
         if int(ds.seq_len) != int(seq_len):
@@ -354,12 +361,118 @@ def plan_training_data(train_set, test_set, seq_len: int, in_features: int, devi
         return None, f"training data: host loader ({plan.not_half[0]} does not hold half-precision rows)"
     if plan.total_rows == 0:
         return None, "training data: host loader (no readable _cls.h5 file in the manifests)"
+    return plan, None
+
+
+def _fit_line(plan, device):
+    """The memory rule: ``(True, "training data: resident in HBM (...)")`` or ``(False, "... host loader (...)")``."""
     allowed = _resident_budget(device)
     if plan.nbytes > allowed:
-        return None, (f"training data: host loader ({_thousands(plan.total_rows)} rows need {plan.nbytes / 1e6:.0f} MB, "
-                      f"{max(allowed, 0.0) / 1e6:.0f} MB may be used)")
-    return plan, (f"training data: resident in HBM ({len(plan.files)} files, {_thousands(plan.total_rows)} rows, "
+        return False, (f"training data: host loader ({_thousands(plan.total_rows)} rows need {plan.nbytes / 1e6:.0f} MB, "
+                       f"{max(allowed, 0.0) / 1e6:.0f} MB may be used)")
+    return True, (f"training data: resident in HBM ({len(plan.files)} files, {_thousands(plan.total_rows)} rows, "
                   f"{plan.nbytes / 1e6:.0f} MB)")
+
+
+def plan_training_data(train_set, test_set, seq_len: int, in_features: int, device):
+    """Decide between rows resident in device memory and the host loader.  Returns ``(plan or None, one line that says
+    which and why)``; raises ValueError for files whose row width is not ``in_features``."""
+    sets = [train_set] + ([test_set] if test_set is not None and len(test_set) > 0 else [])
+    plan, why_not = _plan_sets(sets, ("training", "test"), seq_len, in_features)
+    if plan is None:
+        return None, why_not
+    fits, line = _fit_line(plan, device)
+    return (plan if fits else None), line
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# keep_rows(): one store for a whole training job
+# ---------------------------------------------------------------------------------------------------------------
+class _RowCache:
+    """The last ``ResidentRows`` built inside a ``keep_rows()`` scope, with the size and mtime each of its files had."""
+
+    def __init__(self):
+        self.store = None
+        self.stamps: Dict[str, tuple] = {}
+
+    def drop(self):
+        self.store = None
+        self.stamps = {}
+
+
+_row_cache: Optional[_RowCache] = None
+_row_cache_lock = threading.RLock()
+
+
+def _file_stamp(path: str):
+    try:
+        st = os.stat(path)
+        return (int(st.st_size), int(st.st_mtime_ns))
+    except OSError:
+        return None
+
+
+@contextlib.contextmanager
+def keep_rows():
+    """Scope in which the resident rows outlive the call that read them: ``train_lstm_model``, ``evaluate_on_split`` and
+    ``fit_temperature`` keep the last store they built and reuse it when the next plan needs only files it holds, each
+    with the size and mtime it had when it was read.  Any other plan builds a new store, which replaces the kept one.  The
+    store is released when the OUTERMOST scope ends, also by an exception; outside a scope nothing is kept."""
+    global _row_cache
+    with _row_cache_lock:
+        outermost = _row_cache is None
+        if outermost:
+            _row_cache = _RowCache()
+        cache = _row_cache
+    try:
+        yield cache
+    finally:
+        if outermost:
+            with _row_cache_lock:
+                cache.drop()
+                _row_cache = None
+
+
+def _kept_store(plan, device):
+    """The kept store when it can serve ``plan`` on ``device``, else None."""
+    cache = _row_cache
+    if cache is None or cache.store is None:
+        return None
+    store = cache.store
+    if torch.device(store.device) != torch.device(device) or store.dim != plan.dim:
+        return None
+    for path, (_base, n) in plan.files.items():
+        held = store.files.get(path)
+        if held is None or held[1] != n or cache.stamps.get(path) is None or cache.stamps[path] != _file_stamp(path):
+            return None
+    return store
+
+
+def open_store(sets, names, seq_len: int, in_features: int, device, log=print):
+    """The resident store for the manifest datasets ``sets`` or None for the host loader; ``log`` gets the one line that
+    says which.  Inside ``keep_rows()`` a kept store that holds the files is reused ("training data: kept rows ...": no
+    file is read, no memory is taken) and a new one is kept."""
+    plan, why_not = _plan_sets(sets, names, seq_len, in_features)
+    if plan is None:
+        log(why_not)
+        return None
+    with _row_cache_lock:
+        store = _kept_store(plan, device)
+        if store is not None:
+            log(f"training data: kept rows reused ({len(plan.files)} of the {len(store.files)} files in device memory, "
+                f"{_thousands(plan.total_rows)} rows)")
+            return store
+        if _row_cache is not None:
+            _row_cache.drop()                           # its memory counts as free for the store that replaces it
+        fits, line = _fit_line(plan, device)
+        log(line)
+        if not fits:
+            return None
+        stamps = {path: _file_stamp(path) for path in plan.files}       # before the read: a later write changes them
+        store = ResidentRows(plan, device)
+        if _row_cache is not None:
+            _row_cache.store, _row_cache.stamps = store, stamps
+        return store
 
 
 def _predict_resident(model: ClassifierLSTMDeltas, loader, store: ResidentRows, seq_len: int, xbuf: torch.Tensor, cancel_event=None):
@@ -393,14 +506,13 @@ def train_lstm_model(train_set, test_set, seq_len: int, behaviors: list, cancel_
         raise RuntimeError("cbas_amd.train.train_lstm_model runs on a GPU device only")
     gen = torch.Generator()
     gen.manual_seed(int(seed))
-    plan, line = plan_training_data(train_set, test_set, seq_len, in_features, device)
-    log(line)
-    store = xbuf = None
+    has_test = test_set is not None and len(test_set) > 0
+    store = open_store([train_set] + ([test_set] if has_test else []), ("training", "test"), seq_len, in_features, device, log)
+    xbuf = None
     collate = collate_fn
-    if plan is not None:
+    if store is not None:
         # the same loaders over an index-only view: the sampler's randperm, the loader's per-iterator seed draw and the
         # balanced counter are consumed exactly as on the host path, so the batches are the same, draw for draw
-        store = ResidentRows(plan, device)
         train_set = _IndexView(train_set, seq_len, store.files)
         test_set = _IndexView(test_set, seq_len, store.files) if test_set is not None and len(test_set) > 0 else None
         xbuf = torch.empty((batch_size, seq_len, in_features), dtype=torch.float32, device=device)
@@ -499,3 +611,247 @@ def train_lstm_model(train_set, test_set, seq_len: int, behaviors: list, cancel_
         final_model.load_state_dict(best_state)
         return final_model.to(device).eval(), epoch_reports, best_epoch
     return None, None, -1
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the tail of a training job: the held-out split and the calibration temperature (backend/workthreads.py:671-677, 838-852)
+# ---------------------------------------------------------------------------------------------------------------
+def _resident_for(model, dataset, name: str, device):
+    """The store to score ``dataset`` from with ``model``, or None for the host loader."""
+    if not isinstance(model, ClassifierLSTMDeltas) or device.type != "cuda" or _ds.manifest_kind(dataset) is None:
+        return None
+    if len(dataset) == 0:
+        return None
+    return open_store([dataset], (name,), model.seq_len, model.in_features, device, print)
+
+
+def evaluate_on_split(model, dataset, behaviors, device=None):
+    """backend/cbas.py:1222-1251: ``{"report": sklearn's classification_report dict, "cm": confusion matrix}`` of ``model`` on
+    ``dataset``, ``{"report": {}, "cm": np.array([])}`` when nothing could be scored.  A manifest dataset is scored from rows
+    resident in device memory (``cbas_head_score_rows``: one call for the split, the confusion matrix is all that comes back);
+    anything else, or ``CBAS_TRAIN_RESIDENT=0``, takes the reference's loop over a host ``DataLoader``.  The report is a
+    function of the confusion matrix alone, so both paths return equal reports."""
+    from sklearn.metrics import classification_report, confusion_matrix
+
+    if device is None:
+        device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
+    device = torch.device(device)
+    labels_range = range(len(behaviors))
+    store = _resident_for(model, dataset, "test", device)
+    model.to(device).eval()
+    if store is not None:
+        loader = torch.utils.data.DataLoader(_IndexView(dataset, model.seq_len, store.files), batch_size=512, shuffle=False,
+                                             num_workers=0, collate_fn=_collate_index)
+        batches = [(f, l) for f, l in loader if f.numel()]
+        if not batches:
+            return {"report": {}, "cm": np.array([])}
+        first, labels = torch.cat([f for f, _ in batches]), torch.cat([l for _, l in batches])
+        store.check(first.numpy(), model.seq_len)
+        _, _, confusion = model.score_rows(store.rows, first, labels)
+        cm = confusion.cpu().numpy().astype(np.int64)
+        true_idx, pred_idx = np.nonzero(cm)
+        y_true, y_pred = np.repeat(true_idx, cm[true_idx, pred_idx]), np.repeat(pred_idx, cm[true_idx, pred_idx])
+    else:
+        loader = torch.utils.data.DataLoader(dataset, batch_size=512, shuffle=False, num_workers=0, collate_fn=collate_fn)
+        y_true, y_pred = [], []
+        with torch.no_grad():
+            for x, y in loader:
+                valid = (y != -1)
+                if not valid.any():
+                    continue
+                logits, _ = model(x[valid].to(device))
+                y_true.extend(y[valid].cpu().numpy())
+                y_pred.extend(logits.argmax(1).cpu().numpy())
+        if not y_true:
+            return {"report": {}, "cm": np.array([])}
+        cm = confusion_matrix(y_true, y_pred, labels=labels_range)
+    rep = classification_report(y_true, y_pred, target_names=behaviors, output_dict=True, zero_division=0, labels=labels_range)
+    return {"report": rep, "cm": cm}
+
+
+def lbfgs_scalar(closure, x0, lr: float = 1.0, max_iter: int = 20, max_eval: Optional[int] = None, tolerance_grad: float = 1e-7,
+                 tolerance_change: float = 1e-9, history_size: int = 100):
+    """One ``torch.optim.LBFGS([x], lr, max_iter, ...).step(closure)`` without line search, for ONE float32 parameter,
+    statement for statement: the same evaluations in the same order, the same stopping tests, every quantity that is a
+    float32 tensor there a float32 here (a one-element dot product is a product).  ``closure(x)`` returns
+    ``(loss, d loss / d x)`` at the float32 ``x``.  Returns ``(x, iterations, closure calls)``."""
+    f32 = np.float32
+    if max_eval is None:
+        max_eval = max_iter * 5 // 4                      # torch's default
+    tol_grad, tol_change = f32(tolerance_grad), f32(tolerance_change)
+
+    def evaluate(x):
+        loss, grad = closure(x)
+        return float(f32(loss)), f32(grad)
+
+    x = f32(x0)
+    loss, g = evaluate(x)
+    evals, n_iter = 1, 0
+    if abs(g) <= tol_grad:
+        return x, n_iter, evals
+    old_dirs, old_stps, ro = [], [], []
+    d = t = prev_g = None
+    h_diag = f32(1.0)
+    with np.errstate(all="ignore"):
+        while n_iter < max_iter:
+            n_iter += 1
+            # the direction: -H g by the two-loop recursion over the (y, s) pairs kept so far
+            if n_iter == 1:
+                d = -g
+            else:
+                y = f32(g - prev_g)
+                s = f32(d * t)
+                ys = f32(y * s)
+                if ys > f32(1e-10):
+                    if len(old_dirs) == history_size:
+                        old_dirs.pop(0), old_stps.pop(0), ro.pop(0)
+                    old_dirs.append(y), old_stps.append(s), ro.append(f32(f32(1.0) / ys))
+                    h_diag = f32(ys / f32(y * y))
+                k = len(old_dirs)
+                al = [None] * k
+                q = f32(-g)
+                for i in range(k - 1, -1, -1):
+                    al[i] = f32(f32(old_stps[i] * q) * ro[i])
+                    q = f32(q + f32(old_dirs[i] * f32(-al[i])))
+                d = f32(q * h_diag)
+                for i in range(k):
+                    be_i = f32(f32(old_dirs[i] * d) * ro[i])
+                    d = f32(d + f32(old_stps[i] * f32(al[i] - be_i)))
+            prev_g, prev_loss = g, loss
+            # the step length: lr, scaled down by the gradient's size in the first iteration
+            if n_iter == 1:
+                inv = f32(f32(1.0) / abs(g))
+                t = f32(inv * f32(lr)) if inv < 1.0 else f32(lr)
+            else:
+                t = f32(lr)
+            if f32(g * d) > -tol_change:                  # the directional derivative is below the tolerance
+                break
+            x = f32(x + f32(d * t))
+            evaluated = 0
+            if n_iter != max_iter:
+                loss, g = evaluate(x)
+                evaluated = 1
+            evals += evaluated
+            if n_iter == max_iter or evals >= max_eval:
+                break
+            if abs(g) <= tol_grad:
+                break
+            if abs(f32(d * t)) <= tol_change:
+                break
+            if abs(loss - prev_loss) < tolerance_change:
+                break
+    return x, n_iter, evals
+
+
+def calibration_temperature(T) -> np.float32:
+    """``clamp(softplus(T) + 1e-3, max=10)`` of workthreads.py:130 and :136, in float32 with torch's own softplus."""
+    t = torch.as_tensor(np.float32(T))
+    return np.float32(torch.clamp(torch.nn.functional.softplus(t) + 1e-3, max=10.0).item())
+
+
+def calibration_chain(T) -> np.float32:
+    """d calibration_temperature / d T as autograd forms it: softplus' derivative ``z / (z + 1)``, ``z = exp(T)`` (1 beyond
+    torch's threshold of 20), and the clamp, which passes the gradient on where its input is <= 10."""
+    t = torch.as_tensor(np.float32(T))
+    if float(torch.nn.functional.softplus(t) + 1e-3) > 10.0:
+        return np.float32(0.0)
+    if float(t) > 20.0:
+        return np.float32(1.0)
+    z = torch.exp(t)
+    return np.float32((z / (z + 1.0)).item())
+
+
+FIT_TEMPERATURE_LBFGS = dict(lr=0.01, max_iter=50)        # workthreads.py:111; everything else torch's default
+FIT_TEMPERATURE_START = 1.0                               # workthreads.py:110
+
+
+def fit_temperature_from(mean_nll_and_slope):
+    """The fit of workthreads.py:110-137 given ``mean_nll_and_slope(temp) -> (mean cross-entropy of logits / temp, its
+    derivative with respect to temp)``.  Returns ``(temperature as a Python float, iterations, closure calls)``."""
+    def closure(T):
+        loss, slope = mean_nll_and_slope(calibration_temperature(T))
+        return loss, np.float32(np.float32(slope) * calibration_chain(T))
+
+    T, n_iter, evals = lbfgs_scalar(closure, FIT_TEMPERATURE_START, **FIT_TEMPERATURE_LBFGS)
+    return float(calibration_temperature(T)), n_iter, evals
+
+
+def device_nll(logits: torch.Tensor, labels: torch.Tensor):
+    """``temp -> (loss, d loss / d temp)`` over logits (n, C) float32 and labels (n,) that stay on the device: one
+    ``cbas_logits_nll`` launch and one 8-byte copy per call."""
+    if logits.dim() != 2 or not logits.is_cuda or logits.shape[0] < 1:
+        raise ValueError(f"logits must be a (n >= 1, C) tensor on a GPU, got {tuple(logits.shape)} on {logits.device}")
+    logits = logits.detach().to(torch.float32).contiguous()
+    y = labels.to(logits.device, torch.int32).contiguous()
+    n, n_classes = int(logits.shape[0]), int(logits.shape[1])
+    if tuple(y.shape) != (n,):
+        raise ValueError(f"labels has shape {tuple(y.shape)}, expected ({n},)")
+    lo, hi = int(y.min()), int(y.max())
+    if lo < 0 or hi >= n_classes:
+        raise ValueError(f"labels span [{lo}, {hi}], the logits have {n_classes} classes")
+    lib = _lib.load()
+    out2 = torch.empty(2, dtype=torch.float32, device=logits.device)
+
+    def mean_nll_and_slope(temp):
+        with torch.cuda.device(logits.device):
+            stream = torch.cuda.current_stream(logits.device).cuda_stream
+            _lib.check(lib.cbas_logits_nll(logits.data_ptr(), y.data_ptr(), n, n_classes, float(temp), out2.data_ptr(), stream),
+                       "cbas_logits_nll")
+        v = out2.cpu().numpy()
+        return np.float32(v[0]), np.float32(v[1])
+
+    return mean_nll_and_slope
+
+
+def _loader_index_batches(loader):
+    """The index batches a DataLoader would draw, in its order (its batch sampler, or its sampler one by one)."""
+    if getattr(loader, "batch_sampler", None) is not None:
+        return iter(loader.batch_sampler)
+    return ([i] for i in loader.sampler)
+
+
+def fit_temperature(model, val_loader, device):
+    """backend/workthreads.py:103-137: the calibration temperature ``infer_file`` divides the logits by, as a Python float
+    (1.0 for an empty loader).  The logits stay on the device: a manifest dataset behind ``val_loader`` is scored from
+    resident rows in the loader's order, anything else by iterating the loader as the reference does.  The loss and its
+    derivative come from ``cbas_logits_nll`` (summed in a fixed order), the optimiser is ``lbfgs_scalar``.  A window the
+    store cannot serve is a ValueError that names its file (the reference fails on its label -1 inside the loss)."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"cbas_amd.train.fit_temperature runs on a GPU device only (got {device}); there is no CPU path")
+    model.to(device)
+    model.eval()
+    dataset = getattr(val_loader, "dataset", None)
+    store = _resident_for(model, dataset, "validation", device)
+    if store is not None:
+        seq_len = model.seq_len
+        first_of, label_of = _ds.manifest_windows(dataset.manifest, seq_len, store.files)
+        first, labels = [], []
+        for batch in _loader_index_batches(val_loader):
+            for idx in batch:
+                m = _ds.resolve_index(dataset, idx)
+                if first_of[m] < 0:
+                    path, centre = dataset.manifest[m][0], dataset.manifest[m][1]
+                    raise ValueError(f"fit_temperature: the window of frame {centre} of {path} cannot be read (its file is "
+                                     f"unreadable or the window reaches outside it); calibrating on the rest would not be "
+                                     f"what the reference computes")
+                first.append(int(first_of[m]))
+                labels.append(int(label_of[m]))
+        if not first:
+            return 1.0
+        first = np.asarray(first, np.int64)
+        store.check(first, seq_len)
+        logits, _, _ = model.score_rows(store.rows, torch.from_numpy(first), want_logits=True)
+        labels = torch.from_numpy(np.asarray(labels, np.int64))
+    else:
+        all_logits, all_labels = [], []
+        with torch.no_grad():
+            for d, l in val_loader:
+                logits, _ = model(d.to(device))
+                all_logits.append(logits)
+                all_labels.append(l)
+        if not all_logits:
+            return 1.0
+        logits, labels = torch.cat(all_logits).detach(), torch.cat(all_labels)
+    temperature, _, _ = fit_temperature_from(device_nll(logits, labels))
+    return temperature

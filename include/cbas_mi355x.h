@@ -52,8 +52,9 @@ extern "C" {
 #define CBAS_ESTATE       -4   /* call sequence error (e.g. wait on an idle slot) */
 #define CBAS_ERANGE       -5   /* a frame's CLS row came out NaN / infinite: an activation left the arithmetic mode's range */
 
-/* Still 11 with cbas_rows_gather_windows / cbas_head_train_step_rows: they are additions.  No structure and no existing
- * signature changed, so a caller built against the earlier version 11 header runs unchanged. */
+/* Still 11 with cbas_rows_gather_windows / cbas_head_train_step_rows and with cbas_head_score_rows / cbas_logits_nll: they
+ * are additions.  No structure and no existing signature changed, so a caller built against the earlier version 11 header
+ * runs unchanged. */
 #define CBAS_ABI_VERSION   11
 
 typedef struct cbas_enc  cbas_enc;
@@ -387,6 +388,38 @@ int cbas_rows_gather_windows(const uint16_t* rows_f16_dev, int64_t n_rows, int32
 int cbas_head_train_step_rows(cbas_head_trainer* t, const uint16_t* rows_f16_dev, int64_t n_rows, int32_t dim,
                               const int64_t* first_row_dev, const int32_t* labels_dev, int32_t n_windows, int32_t seq_len,
                               int32_t update, float* loss_host, void* stream);
+
+/* The tail of a training job on the device: scoring a split and fitting the calibration temperature from such a store.
+ *
+ * cbas_head_score_rows replaces the loop of evaluate_on_split (backend/cbas.py:1235-1242) and the logit collection of
+ * fit_temperature (backend/workthreads.py:115-120): per batch of 512 a host-built window tensor, its copy to the device,
+ * model(x), `logits.argmax(1).cpu()`; then sklearn's confusion_matrix over the host lists (cbas.py:1250).  Here the
+ * n_windows windows named by first_row_dev (int64, as for cbas_rows_gather_windows) are gathered and run through the head
+ * 512 at a time, and per window w:
+ *   logits_out_dev[w][:]  = the head's logits (float32, n_windows x C), bit-identical to cbas_rows_gather_windows +
+ *                           cbas_head_forward_windows on any split of the windows into batches;        may be NULL
+ *   pred_out_dev[w]       = index of the FIRST maximum of the logits, as torch.argmax (int32);          may be NULL
+ *   confusion_dev[labels_dev[w]][pred] += 1   (int64, C x C, row = true label; ADDED to what the caller put there, with
+ *                           integer atomics, so the matrix does not depend on the order of execution);  may be NULL
+ * labels_dev (int32, n_windows) is needed with confusion_dev only.  All pointers are device pointers on the head's device.
+ * The call synchronises `stream` once before it returns, to report: CBAS_ERANGE when a window's logits hold a NaN (such a
+ * window gets prediction -1 and no count), CBAS_EINVAL for a label outside [0, C) (no count), a NULL rows / first_row,
+ * dim != in_features, n_windows < 1 or no output requested. */
+int cbas_head_score_rows(cbas_head* h, const uint16_t* rows_f16_dev, int64_t n_rows, int32_t dim,
+                         const int64_t* first_row_dev, const int32_t* labels_dev, int64_t n_windows,
+                         float* logits_out_dev, int32_t* pred_out_dev, int64_t* confusion_dev, void* stream);
+/* The closure of fit_temperature (backend/workthreads.py:127-133, `criterion(all_logits / temp, all_labels)` and its
+ * backward pass), one launch per evaluation:
+ *   out2_dev[0] = mean over the n rows of -log_softmax(logits[r] / temp)[labels[r]]      (float32 row terms, as torch's)
+ *   out2_dev[1] = d out2_dev[0] / d temp = mean of (logits[r][label] - sum_j softmax(logits[r] / temp)[j] * logits[r][j]) / temp^2
+ * logits_dev (n, n_classes) float32, labels_dev (n) int32, out2_dev two floats: device pointers on one device; nothing is
+ * copied or synchronised.  The rows are summed in a fixed order without floating-point atomics (per thread in ascending row
+ * order, a tree per workgroup, a tree over the workgroups' partial sums in the workgroup that finishes last; the grid depends
+ * on n alone), so equal inputs give equal bits on every launch.  The chain rule from temp to the fitted parameter
+ * (softplus, clamp) is the caller's.  A label outside [0, n_classes) makes both results NaN.
+ * CBAS_EINVAL: a NULL pointer, n < 1, n_classes outside [1, 64], temp <= 0 or NaN. */
+int cbas_logits_nll(const float* logits_dev, const int32_t* labels_dev, int64_t n, int32_t n_classes, float temp,
+                    float* out2_dev, void* stream);
 
 /* Copy the current parameters (what = 0) or the gradients of the last step (what = 1) to the host, in the
  * blob order of cbas_head_create (n = cbas_head_weights_count).  Synchronises the device. */
