@@ -75,6 +75,7 @@ SIGNATURES = {
     "cbas_fused_rows_ready": (c_int64, [c_void_p, c_int32]),
     "cbas_enc_set_lanes": (c_int, [c_void_p, c_int]),
     "cbas_enc_set_prune_last_layer": (c_int, [c_void_p, c_int]),
+    "cbas_enc_set_pos_interp": (c_int, [c_void_p, c_int]),
     "cbas_enc_profile": (c_int, [c_void_p, c_int]),
     "cbas_enc_profile_read": (c_int, [c_void_p, C.POINTER(C.c_double), C.POINTER(c_int64), C.POINTER(C.c_double),
                                       c_int]),
@@ -129,9 +130,12 @@ DEBUG_SIGNATURES = {
     "cbas_debug_gemm_run": (c_int, [c_void_p]),
     "cbas_debug_attention_run": (c_int, [c_void_p]),
     "cbas_debug_build": (c_int, []),
+    "cbas_debug_pos_interp_matrix": (c_int, [c_int, c_int, c_int, c_void_p]),
+    "cbas_debug_pos_table": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
 }
 
 ENC_SLOTS = 3
+POS_INTERP_BICUBIC_AA, POS_INTERP_BICUBIC = 0, 1      # CBAS_POS_INTERP_* of include/cbas_mi355x.h
 EXPECTED_ABI = 11         # CBAS_ABI_VERSION of include/cbas_mi355x.h these ctypes structures mirror
 PROF_CATS = ["patch_gemm", "layernorm", "qkv_gemm", "attention", "oproj_gemm", "up_gemm", "down_gemm", "other"]
 

@@ -1,4 +1,4 @@
-"""Configuration records for the encoders (DINOv3 ViT, DINOv2-with-registers, DINOv3 ConvNeXt) and the classifier head.
+"""Configuration records for the encoders (DINOv3 ViT, DINOv2 with and without registers, DINOv3 ConvNeXt) and the classifier head.
 
 The field names follow the HF ``config.json`` of a DINOv3 ViT checkpoint
 (``transformers/models/dinov3_vit/configuration_dinov3_vit.py:74-101``) so that a
@@ -10,8 +10,12 @@ from __future__ import annotations
 
 import json
 import os
-from dataclasses import dataclass, asdict
+from dataclasses import dataclass, asdict, replace
 from typing import Tuple
+
+
+# the two HF DINOv2 model types: same blocks, same state-dict keys (minus the register tokens of the plain one)
+DINOV2_FAMILIES = ("dinov2_with_registers", "dinov2")
 
 
 @dataclass(frozen=True)
@@ -36,7 +40,8 @@ class ViTConfig:
     # encoder family: "dinov3_vit" (RoPE, no additive position embedding) or "dinov2_with_registers"
     # (learned position embedding on a pos_embed_grid x pos_embed_grid lattice, bicubically
     # interpolated to the frame's patch grid; no RoPE; key bias) - CBAS's default project encoder
-    # (reference backend/cbas.py:1030-1033)
+    # (reference backend/cbas.py:1030-1033) - or "dinov2" (the same without register tokens, and with the
+    # position embedding interpolated WITHOUT antialiasing: HF modeling_dinov2.py:86-91)
     model_type: str = "dinov3_vit"
     use_rope: bool = True
     pos_embed_grid: int = 0
@@ -72,8 +77,10 @@ class ViTConfig:
             raise NotImplementedError("head_dim must be 64 (all DINOv3 ViT-S/B/L checkpoints)")
         if self.patch_size not in (14, 16):
             raise NotImplementedError("patch_size must be 14 (DINOv2) or 16 (DINOv3)")
-        if self.model_type not in ("dinov3_vit", "dinov2_with_registers"):
+        if self.model_type not in ("dinov3_vit",) + DINOV2_FAMILIES:
             raise NotImplementedError(f"model_type={self.model_type!r} is not built")
+        if self.model_type == "dinov2" and self.num_register_tokens != 0:
+            raise NotImplementedError("model_type='dinov2' has no register tokens (that is 'dinov2_with_registers')")
         if self.use_rope == (self.pos_embed_grid > 0):
             raise NotImplementedError("exactly one of RoPE / learned position embedding is expected")
         if not (self.query_bias and self.value_bias and self.proj_bias and self.mlp_bias):
@@ -81,7 +88,7 @@ class ViTConfig:
 
     def to_json(self) -> str:
         d = asdict(self)
-        if self.model_type == "dinov2_with_registers":      # write the fields HF's config class reads back
+        if self.model_type in DINOV2_FAMILIES:               # write the fields HF's config class reads back
             d.update(mlp_ratio=self.intermediate_size // self.hidden_size, qkv_bias=self.query_bias,
                      use_swiglu_ffn=self.use_gated_mlp)
         return json.dumps(d, indent=2)
@@ -91,20 +98,21 @@ class ViTConfig:
         with open(path, "r") as f:
             raw = json.load(f)
         mt = raw.get("model_type", "dinov3_vit")
-        if mt not in ("dinov3_vit", "dinov2_with_registers"):
-            raise NotImplementedError(f"model_type={mt!r}: only DINOv3 ViT and DINOv2-with-registers encoders are built")
+        if mt not in ("dinov3_vit",) + DINOV2_FAMILIES:
+            raise NotImplementedError(f"model_type={mt!r}: only DINOv3 ViT and DINOv2 (with or without registers) encoders are built")
         known = {k: raw[k] for k in cls.__dataclass_fields__ if k in raw}
         for key in ("patch_size", "image_size"):
             if isinstance(known.get(key), (list, tuple)):
                 known[key] = int(known[key][0])
-        if mt == "dinov2_with_registers":
-            # HF Dinov2WithRegistersConfig (configuration_dinov2_with_registers.py): mlp_ratio, qkv_bias, use_swiglu_ffn
+        if mt in DINOV2_FAMILIES:
+            # HF Dinov2WithRegistersConfig (configuration_dinov2_with_registers.py) and Dinov2Config (configuration_dinov2.py):
+            # mlp_ratio, qkv_bias, use_swiglu_ffn; plain DINOv2 has no register tokens
             hs = int(raw.get("hidden_size", 768))
             qkv_bias = bool(raw.get("qkv_bias", True))
             known.update(intermediate_size=hs * int(raw.get("mlp_ratio", 4)), query_bias=qkv_bias, key_bias=qkv_bias,
                          value_bias=qkv_bias, use_gated_mlp=bool(raw.get("use_swiglu_ffn", False)), use_rope=False,
                          layer_norm_eps=float(raw.get("layer_norm_eps", 1e-6)),
-                         num_register_tokens=int(raw.get("num_register_tokens", 4)),
+                         num_register_tokens=int(raw.get("num_register_tokens", 4)) if mt == "dinov2_with_registers" else 0,
                          patch_size=int(known.get("patch_size", 16)), image_size=int(known.get("image_size", 224)))
             known["pos_embed_grid"] = known["image_size"] // known["patch_size"]
         return cls(**known)
@@ -124,9 +132,13 @@ DINOV2_REG_B14 = ViTConfig(hidden_size=768, intermediate_size=3072, num_hidden_l
 DINOV2_REG_TINY = ViTConfig(hidden_size=128, intermediate_size=512, num_hidden_layers=2, num_attention_heads=2,
                             patch_size=14, image_size=70, layer_norm_eps=1e-6, key_bias=True,
                             model_type="dinov2_with_registers", use_rope=False, pos_embed_grid=5)
+# Plain DINOv2 ("facebook/dinov2-base", the third encoder the reference's cbas_config.yaml.example names): the R = 0 twins
+DINOV2_B14 = replace(DINOV2_REG_B14, model_type="dinov2", num_register_tokens=0)
+DINOV2_TINY = replace(DINOV2_REG_TINY, model_type="dinov2", num_register_tokens=0)
 
 NAMED_VIT = {"vits16": VIT_S16, "vitb16": VIT_B16, "vitl16": VIT_L16, "tiny": VIT_TINY,
-             "dinov2regb14": DINOV2_REG_B14, "dinov2regtiny": DINOV2_REG_TINY}
+             "dinov2regb14": DINOV2_REG_B14, "dinov2regtiny": DINOV2_REG_TINY,
+             "dinov2b14": DINOV2_B14, "dinov2tiny": DINOV2_TINY}
 
 
 @dataclass(frozen=True)

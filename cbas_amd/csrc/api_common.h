@@ -13,6 +13,10 @@
 
 extern thread_local char g_cbas_err[512];
 
+// api_enc.hip: the host-side builder of the DINOv2 position tables (mode: CBAS_POS_INTERP_*), shared with the debug entries
+void cbas_build_pos_table(int mode, const float* src, int G, int D, int nh, int nw, float* out);
+void cbas_pos_interp_matrix(int mode, int in_size, int out_size, float* W);
+
 static inline int cbas_fail(int code, const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);

@@ -18,6 +18,20 @@
 
 extern "C" int cbas_debug_build(void) { return 1; }
 
+static int pos_interp_mode_ok(int mode) { return mode == CBAS_POS_INTERP_BICUBIC_AA || mode == CBAS_POS_INTERP_BICUBIC; }
+
+extern "C" int cbas_debug_pos_interp_matrix(int mode, int in_size, int out_size, float* W) {
+    if (!pos_interp_mode_ok(mode) || in_size < 1 || out_size < 1 || !W) return cbas_fail(CBAS_EINVAL, "cbas_debug_pos_interp_matrix: bad argument");
+    cbas_pos_interp_matrix(mode, in_size, out_size, W);
+    return CBAS_OK;
+}
+
+extern "C" int cbas_debug_pos_table(int mode, const float* src, int G, int D, int nh, int nw, float* out) {
+    if (!pos_interp_mode_ok(mode) || G < 1 || D < 1 || nh < 1 || nw < 1 || !src || !out) return cbas_fail(CBAS_EINVAL, "cbas_debug_pos_table: bad argument");
+    cbas_build_pos_table(mode, src, G, D, nh, nw, out);
+    return CBAS_OK;
+}
+
 // ---- bring-up: stand-alone GEMM timing / bit-exactness harness ---------------------------------
 namespace {
 __global__ void fill_random_f16(f16* p, int64_t n, uint32_t seed, float scale) {

@@ -83,6 +83,7 @@ struct cbas_enc {
     float* prefix_dev = nullptr;        // (1+R, D): cls (+ its position embedding for DINOv2) | registers
     float* pos_tab = nullptr;           // DINOv2: (Pmax, D) position embedding interpolated to the current grid
     std::vector<float> pos_host;        // DINOv2: raw (1+G*G, D) table
+    int pos_interp = CBAS_POS_INTERP_BICUBIC_AA;   // how it is resampled to a frame's grid (cbas_enc_set_pos_interp)
     // RoPE (DINOv3) / interpolated position-embedding (DINOv2) tables, one set per patch grid seen so far.  A new
     // grid gets FRESH device buffers filled by a blocking copy, so no stream has to be drained when a queue mixes
     // resolutions; rope_cos / rope_sin / pos_tab point at the set of the batch being queued (kernel arguments are
@@ -231,7 +232,79 @@ int acquire_pos_table(cbas_enc* h, int nh, int nw, cbas_enc::PosTable** out) {
     return 1;                                  // caller fills it
 }
 
-// DINOv2: position embedding of the patch tokens for an nh x nw grid ([v2] interpolate_pos_encoding :93-145)
+// ATen's cubic convolution coefficients, a = -0.75, in float like ATen (UpSample.h cubic_convolution1 / cubic_convolution2,
+// get_cubic_upsample_coefficients).  The outer polynomial and the source index below are written with fmaf: ATen's x86 builds
+// contract them, and the outer taps (a few 1e-4 after cancellation) then agree with torch's to 1.2e-7 instead of 7e-7.
+static inline float cubic_conv1(float x, float A) { return ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f; }
+static inline float cubic_conv2(float x, float A) { return fmaf(fmaf(fmaf(A, x, -5.f * A), x, 8.f * A), x, -4.f * A); }
+
+// (out, in) weights of F.interpolate(size=, mode="bicubic", align_corners=False) - NO antialiasing - along one axis: ATen's
+// upsample_bicubic2d (UpSampleKernel.cpp HelperInterpCubic::compute_indices_weights).  The scale comes from the sizes
+// (HF passes size=), the source index (dst + 0.5) * in / out - 0.5 is not clamped, its four taps floor - 1 ... floor + 2 are
+// clamped to [0, in - 1]; taps that clamp onto one index add up in the matrix.
+static std::vector<float> bicubic_matrix(int in_size, int out_size) {
+    std::vector<float> W((size_t)out_size * in_size, 0.f);
+    const float scale = (float)in_size / (float)out_size, A = -0.75f;
+    for (int i = 0; i < out_size; ++i) {
+        const float real = fmaf(scale, (float)i + 0.5f, -0.5f);
+        int idx = (int)floorf(real); if (idx > in_size - 1) idx = in_size - 1;
+        float t = real - (float)idx; t = t < 0.f ? 0.f : (t > 1.f ? 1.f : t);
+        const float co[4] = {cubic_conv2(t + 1.f, A), cubic_conv1(t, A), cubic_conv1(1.f - t, A), cubic_conv2((1.f - t) + 1.f, A)};
+        for (int k = 0; k < 4; ++k) {
+            int j = idx - 1 + k; j = j < 0 ? 0 : (j > in_size - 1 ? in_size - 1 : j);
+            W[(size_t)i * in_size + j] += co[k];
+        }
+    }
+    return W;
+}
+
+}  // namespace
+
+// DINOv2: the (nh*nw, D) position embedding of the patch tokens from the stored (G*G, D) one.  mode picks the filter:
+// CBAS_POS_INTERP_BICUBIC_AA [v2] interpolate_pos_encoding :93-145 (with registers), CBAS_POS_INTERP_BICUBIC HF
+// modeling_dinov2.py:57-95 (plain DINOv2).  Both skip the resampling at the stored grid (the stored table, bit for bit).
+void cbas_build_pos_table(int mode, const float* src, int G, int D, int nh, int nw, float* out) {
+    const size_t n_out = (size_t)nh * nw * D;
+    if (nh == G && nw == G) {
+        memcpy(out, src, n_out * 4);
+        return;
+    }
+    const bool aa = mode == CBAS_POS_INTERP_BICUBIC_AA;
+    const std::vector<float> Wh = aa ? aa_bicubic_matrix(G, nh) : bicubic_matrix(G, nh);
+    const std::vector<float> Ww = aa ? aa_bicubic_matrix(G, nw) : bicubic_matrix(G, nw);
+    std::vector<float> tmp((size_t)G * nw * D, 0.f);     // width pass, then height pass (separable)
+    for (int i = 0; i < G; ++i)
+        for (int x = 0; x < nw; ++x) {
+            float* tp = &tmp[((size_t)i * nw + x) * D];
+            for (int j = 0; j < G; ++j) {
+                const float w = Ww[(size_t)x * G + j];
+                if (w == 0.f) continue;
+                const float* sp = src + ((size_t)i * G + j) * D;
+                for (int d = 0; d < D; ++d) tp[d] += w * sp[d];
+            }
+        }
+    std::fill(out, out + n_out, 0.f);
+    for (int y = 0; y < nh; ++y)
+        for (int i = 0; i < G; ++i) {
+            const float w = Wh[(size_t)y * G + i];
+            if (w == 0.f) continue;
+            for (int x = 0; x < nw; ++x) {
+                float* o = &out[((size_t)y * nw + x) * D];
+                const float* tp = &tmp[((size_t)i * nw + x) * D];
+                for (int d = 0; d < D; ++d) o[d] += w * tp[d];
+            }
+        }
+}
+
+// one axis' (out_size, in_size) weight matrix of either filter (the debug build's cbas_debug_pos_interp_matrix)
+void cbas_pos_interp_matrix(int mode, int in_size, int out_size, float* W) {
+    const std::vector<float> m = mode == CBAS_POS_INTERP_BICUBIC_AA ? aa_bicubic_matrix(in_size, out_size) : bicubic_matrix(in_size, out_size);
+    memcpy(W, m.data(), m.size() * 4);
+}
+
+namespace {
+
+// DINOv2: position embedding of the patch tokens for an nh x nw grid
 int ensure_pos_embed(cbas_enc* h, int nh, int nw) {
     cbas_enc::PosTable* t = nullptr;
     const int rc = acquire_pos_table(h, nh, nw, &t);
@@ -239,35 +312,8 @@ int ensure_pos_embed(cbas_enc* h, int nh, int nw) {
     h->pos_tab = t->pos;
     if (rc == 0) return CBAS_OK;
     const int P = nh * nw, G = h->cfg.pos_embed_grid, D = h->D;
-    const float* src = h->pos_host.data() + D;               // skip the cls position
     std::vector<float> out((size_t)P * D);
-    if (nh == G && nw == G) {
-        memcpy(out.data(), src, out.size() * 4);
-    } else {
-        const std::vector<float> Wh = aa_bicubic_matrix(G, nh), Ww = aa_bicubic_matrix(G, nw);
-        std::vector<float> tmp((size_t)G * nw * D, 0.f);     // width pass, then height pass (separable)
-        for (int i = 0; i < G; ++i)
-            for (int x = 0; x < nw; ++x) {
-                float* tp = &tmp[((size_t)i * nw + x) * D];
-                for (int j = 0; j < G; ++j) {
-                    const float w = Ww[(size_t)x * G + j];
-                    if (w == 0.f) continue;
-                    const float* sp = src + ((size_t)i * G + j) * D;
-                    for (int d = 0; d < D; ++d) tp[d] += w * sp[d];
-                }
-            }
-        std::fill(out.begin(), out.end(), 0.f);
-        for (int y = 0; y < nh; ++y)
-            for (int i = 0; i < G; ++i) {
-                const float w = Wh[(size_t)y * G + i];
-                if (w == 0.f) continue;
-                for (int x = 0; x < nw; ++x) {
-                    float* o = &out[((size_t)y * nw + x) * D];
-                    const float* tp = &tmp[((size_t)i * nw + x) * D];
-                    for (int d = 0; d < D; ++d) o[d] += w * tp[d];
-                }
-            }
-    }
+    cbas_build_pos_table(h->pos_interp, h->pos_host.data() + D /* skip the cls position */, G, D, nh, nw, out.data());
     HIP_TRY(hipMemcpy(t->pos, out.data(), out.size() * 4, hipMemcpyHostToDevice));   // blocking; nothing reads t yet
     t->nh = nh; t->nw = nw;
     return CBAS_OK;
@@ -1624,6 +1670,19 @@ extern "C" int cbas_enc_set_lanes(cbas_enc* h, int n_lanes) {
         if (s.busy) return cbas_fail(CBAS_ESTATE, "cbas_enc_set_lanes with a batch in flight");
     h->n_lanes = n_lanes;
     h->submit_count = 0;
+    return CBAS_OK;
+}
+
+extern "C" int cbas_enc_set_pos_interp(cbas_enc* h, int mode) {
+    if (!h) return cbas_fail(CBAS_EINVAL, "null handle");
+    if (h->cfg.family != 0 || h->cfg.pos_embed_grid <= 0)
+        return cbas_fail(CBAS_EINVAL, "cbas_enc_set_pos_interp: the handle has no learned position embedding");
+    if (mode != CBAS_POS_INTERP_BICUBIC_AA && mode != CBAS_POS_INTERP_BICUBIC)
+        return cbas_fail(CBAS_EINVAL, "cbas_enc_set_pos_interp: mode=%d: 0 (bicubic, antialiased) or 1 (bicubic)", mode);
+    if (mode != h->pos_interp && !h->pos_tables.empty())
+        return cbas_fail(CBAS_EINVAL, "cbas_enc_set_pos_interp: call it before the first batch (tables of %d grid(s) are built)",
+                         (int)h->pos_tables.size());
+    h->pos_interp = mode;
     return CBAS_OK;
 }
 

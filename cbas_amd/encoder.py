@@ -33,7 +33,9 @@ def pack_encoder_weights(cfg: ViTConfig, w: Dict[str, np.ndarray]) -> np.ndarray
     from .weights import canonical_encoder_weights
     w = dict(canonical_encoder_weights(cfg, w))    # DINOv2-with-registers keys -> the DINOv3 names used below
     D = cfg.hidden_size
-    parts = [w["embeddings.cls_token"].reshape(-1), w["embeddings.register_tokens"].reshape(-1)]
+    parts = [w["embeddings.cls_token"].reshape(-1)]
+    if cfg.num_register_tokens > 0:                # plain DINOv2 (R = 0) has no such tensor: an empty register block
+        parts.append(w["embeddings.register_tokens"].reshape(-1))
     if cfg.pos_embed_grid > 0:
         parts.append(w["embeddings.position_embeddings"].reshape(-1))
     parts += [w["embeddings.patch_embeddings.weight"].reshape(-1), w["embeddings.patch_embeddings.bias"].reshape(-1)]
@@ -68,7 +70,7 @@ DEFAULT_PRECISION = 4
 
 
 class DinoEncoder:
-    """MI355X DINOv3 ViT encoder behind the reference's ``DinoEncoder`` interface."""
+    """MI355X encoder (DINOv3 ViT / ConvNeXt, DINOv2 with or without registers) behind the reference's ``DinoEncoder`` interface."""
 
     def __init__(self, model_identifier: str, device="cuda", max_batch: int = 128,
                  max_frame: Tuple[int, int] = (256, 256), precision: Optional[int] = None):
@@ -139,6 +141,10 @@ class DinoEncoder:
         _lib.check(self._lib.cbas_enc_create(C.byref(self._cfg_c), self._blob.ctypes.data, self._blob.shape[0], self._dev,
                                              C.byref(h)), "cbas_enc_create")
         self._h = h
+        if getattr(self.config, "model_type", None) == "dinov2":
+            # plain DINOv2 resamples its position table without antialiasing (HF modeling_dinov2.py:86-91).  Set on EVERY handle
+            # built from this config - the rebuild for larger frames and the precision-3 range-fallback twin come through here
+            _lib.check(self._lib.cbas_enc_set_pos_interp(h, _lib.POS_INTERP_BICUBIC), "cbas_enc_set_pos_interp")
 
     def _fit_frame(self, H: int, W: int) -> None:
         """The reference takes any frame size; the workspace here is sized at create.  Frames larger than

@@ -17,7 +17,7 @@ from typing import Dict, Tuple
 
 import numpy as np
 
-from .config import ViTConfig, HeadConfig, ConvNextConfig, encoder_config_from_json, is_convnext
+from .config import ViTConfig, HeadConfig, ConvNextConfig, DINOV2_FAMILIES, encoder_config_from_json, is_convnext
 
 _M64 = np.uint64(0xFFFFFFFFFFFFFFFF)
 
@@ -65,7 +65,8 @@ def synth_uniform(seed: int, name: str, shape: Tuple[int, ...], lo: float, hi: f
 # ----------------------------------------------------------------------------------------------
 
 def _dinov2_param_shapes(cfg: ViTConfig) -> Dict[str, Tuple[int, ...]]:
-    """HF ``Dinov2WithRegistersModel`` state-dict keys (modeling_dinov2_with_registers.py:75-92, 203-320, 362-381, 455-470)."""
+    """HF ``Dinov2WithRegistersModel`` state-dict keys (modeling_dinov2_with_registers.py:75-92, 203-320, 362-381, 455-470);
+    ``Dinov2Model`` (modeling_dinov2.py:43-55) has the same ones without ``embeddings.register_tokens``."""
     D, F, R, p, C, G = (cfg.hidden_size, cfg.intermediate_size, cfg.num_register_tokens, cfg.patch_size,
                         cfg.num_channels, cfg.pos_embed_grid)
     s: Dict[str, Tuple[int, ...]] = {
@@ -89,6 +90,8 @@ def _dinov2_param_shapes(cfg: ViTConfig) -> Dict[str, Tuple[int, ...]]:
                         ("mlp.fc1.weight", (F, D)), ("mlp.fc1.bias", (F,)), ("mlp.fc2.weight", (D, F)),
                         ("mlp.fc2.bias", (D,)), ("layer_scale2.lambda1", (D,))):
             s[pre + nm] = shp
+    if cfg.model_type == "dinov2":
+        del s["embeddings.register_tokens"]
     return s
 
 
@@ -100,9 +103,9 @@ _V2_TO_CANON = (("embeddings.patch_embeddings.projection.", "embeddings.patch_em
 
 
 def canonical_encoder_weights(cfg: ViTConfig, w: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
-    """Rename a DINOv2-with-registers state dict to the DINOv3 key names the packer and the oracle use
+    """Rename a DINOv2 state dict (with or without registers) to the DINOv3 key names the packer and the oracle use
     (same tensors, same shapes); a DINOv3 state dict is returned unchanged."""
-    if cfg.model_type != "dinov2_with_registers":
+    if cfg.model_type not in DINOV2_FAMILIES:
         return w
     out = {}
     for k, v in w.items():
@@ -178,7 +181,7 @@ def synth_convnext_weights(cfg: ConvNextConfig, seed: int = 1234) -> Dict[str, n
 def encoder_param_shapes(cfg: ViTConfig) -> Dict[str, Tuple[int, ...]]:
     if is_convnext(cfg):
         return convnext_param_shapes(cfg)
-    if cfg.model_type == "dinov2_with_registers":
+    if cfg.model_type in DINOV2_FAMILIES:
         return _dinov2_param_shapes(cfg)
     D, F, R, p, C = cfg.hidden_size, cfg.intermediate_size, cfg.num_register_tokens, cfg.patch_size, cfg.num_channels
     s: Dict[str, Tuple[int, ...]] = {

@@ -52,8 +52,8 @@ extern "C" {
 #define CBAS_ESTATE       -4   /* call sequence error (e.g. wait on an idle slot) */
 #define CBAS_ERANGE       -5   /* a frame's CLS row came out NaN / infinite: an activation left the arithmetic mode's range */
 
-/* Still 11 with cbas_rows_gather_windows / cbas_head_train_step_rows and with cbas_head_score_rows / cbas_logits_nll: they
- * are additions.  No structure and no existing signature changed, so a caller built against the earlier version 11 header
+/* Still 11 with cbas_rows_gather_windows / cbas_head_train_step_rows, with cbas_head_score_rows / cbas_logits_nll and with
+ * cbas_enc_set_pos_interp: they are additions.  No structure and no existing signature changed, so a caller built against the earlier version 11 header
  * runs unchanged. */
 #define CBAS_ABI_VERSION   11
 
@@ -104,8 +104,9 @@ typedef struct cbas_enc_config {
                                         and |GELU output| < 16 376 (far above what ViT checkpoints with "massive activation"
                                         channels produce: tests/test_gpu_fp32.py); precision 3 has no such bound. */
     int32_t use_rope;             /* 1: DINOv3 (RoPE on patch rows, no additive position embedding)     */
-    int32_t pos_embed_grid;       /* G > 0: DINOv2-with-registers, learned (1+G*G, D) position embedding,
-                                     bicubic-antialias interpolated to each frame's patch grid; else 0 */
+    int32_t pos_embed_grid;       /* G > 0: DINOv2 (with registers, or plain with num_register_tokens = 0), learned (1+G*G, D)
+                                     position embedding, bicubic-antialias interpolated to each frame's patch grid unless
+                                     cbas_enc_set_pos_interp says otherwise; else 0 */
     /* ABI 11: the encoder family.  All-zero trailing fields keep the ViT behaviour of ABI 10. */
     int32_t family;               /* 0: ViT (the fields above); 1: DINOv3 ConvNeXt (transformers models/dinov3_convnext,
                                      DINOv3ConvNextModel: row 0 = LayerNorm(global mean pool of the last stage)).  ConvNeXt uses
@@ -212,6 +213,24 @@ int cbas_enc_set_lanes(cbas_enc* h, int n_lanes);
  * attention, o_proj, LayerNorm 2 and the MLP for the n CLS rows only (rows are independent: the CLS output is
  * bit-identical).  enable = 0 restores the full last layer (used by the tests that prove the identity). */
 int cbas_enc_set_prune_last_layer(cbas_enc* h, int enable);
+/* How a handle with a learned position embedding (pos_embed_grid = G > 0) resamples its G x G table to a frame's nh x nw patch
+ * grid.  The two HF DINOv2 families differ in exactly this:
+ *   CBAS_POS_INTERP_BICUBIC_AA (the default of a new handle): Dinov2WithRegistersEmbeddings.interpolate_pos_encoding
+ *       (transformers models/dinov2_with_registers/modeling_dinov2_with_registers.py:93-145) calls F.interpolate(mode="bicubic",
+ *       align_corners=False, antialias=True): Keys kernel a = -0.5, support widened by the scale when downsampling, weights
+ *       normalised per output.
+ *   CBAS_POS_INTERP_BICUBIC: Dinov2Embeddings.interpolate_pos_encoding of plain DINOv2 ("facebook/dinov2-base"; transformers
+ *       models/dinov2/modeling_dinov2.py:57-95, the call at :86-91) passes size=(nh, nw), mode="bicubic", align_corners=False and
+ *       NO antialias: ATen's upsample_bicubic2d - source index (dst + 0.5) * G / n - 0.5 (scale from the sizes, not clamped), the
+ *       four taps floor - 1 ... floor + 2 clamped to [0, G - 1], cubic convolution coefficients with a = -0.75.  At CBAS's 256 x 256
+ *       video (18 x 18 from 37 x 37) the two tables differ in the first digit.
+ * Both use the stored table as it is, bit for bit, when nh = nw = G (modeling_dinov2.py:71-72).  The tables are built on the
+ * first batch of each grid, so call this between cbas_enc_create and the first forward / submit (a plain-DINOv2 handle is
+ * cbas_enc_create with num_register_tokens = 0 followed by this); changing the mode once a table exists is CBAS_EINVAL.
+ * Everything after the table - its cache per resolution, the patch GEMM epilogue that adds it - is the same for both. */
+#define CBAS_POS_INTERP_BICUBIC_AA 0
+#define CBAS_POS_INTERP_BICUBIC    1
+int cbas_enc_set_pos_interp(cbas_enc* h, int mode);
 
 /* Bring-up, test and measurement-harness entry points (stage taps, implementation switches, stand-alone GEMM
  * harnesses, the MFMA neighbour) are NOT part of this boundary: include/cbas_mi355x_debug.h, built only into

@@ -139,6 +139,13 @@ int cbas_head_debug_expand_module(cbas_head* h, const char* hsaco_path, const ch
 int cbas_head_debug_expand_repeat(cbas_head* h, int mode, int repeat);
 int cbas_head_debug_expand_stats(cbas_head* h, uint64_t* counts4, float* rows_out, int max_rows, int reset);
 
+/* Tests, host only (no device is touched): the position-table builder of cbas_enc_set_pos_interp.
+ *   cbas_debug_pos_interp_matrix: W (out_size x in_size, row-major) = one axis' weights of `mode`'s filter.
+ *   cbas_debug_pos_table: out (nh * nw, D) = the stored patch-position table src (G * G, D) resampled to nh x nw the way a
+ *       handle in `mode` builds it (separable: width pass, then height pass; the stored table itself when nh = nw = G). */
+int cbas_debug_pos_interp_matrix(int mode, int in_size, int out_size, float* W);
+int cbas_debug_pos_table(int mode, const float* src, int G, int D, int nh, int nw, float* out);
+
 #ifdef __cplusplus
 }
 #endif
