@@ -76,6 +76,7 @@ SIGNATURES = {
     "cbas_enc_set_lanes": (c_int, [c_void_p, c_int]),
     "cbas_enc_set_prune_last_layer": (c_int, [c_void_p, c_int]),
     "cbas_enc_set_pos_interp": (c_int, [c_void_p, c_int]),
+    "cbas_enc_set_fp8_plan": (c_int, [c_void_p, c_int]),
     "cbas_enc_profile": (c_int, [c_void_p, c_int]),
     "cbas_enc_profile_read": (c_int, [c_void_p, C.POINTER(C.c_double), C.POINTER(c_int64), C.POINTER(C.c_double),
                                       c_int]),
@@ -120,6 +121,8 @@ DEBUG_SIGNATURES = {
                                       C.POINTER(C.c_ulonglong)]),
     "cbas_debug_gemm_f8": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p]),
+    "cbas_debug_gemm_gelu_forms": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cbas_debug_mfma_neighbor": (c_int, [c_int, c_void_p]),
     "cbas_debug_gemm_split_bench": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, C.POINTER(c_float)]),
     "cbas_head_debug_read": (c_int, [c_void_p, c_int, c_void_p, c_int64]),

@@ -305,3 +305,46 @@ def find_checkpoint_dir(model_identifier: str) -> str:
     raise FileNotFoundError(
         f"encoder checkpoint {model_identifier!r} is neither a local directory nor present in the "
         f"Hugging Face cache ({snap}); this build never downloads")
+
+
+# ---- MX-fp8 plans (precision 2): which projection GEMMs of a layer take MX-fp8 operands -------------------------------------
+# bits of include/cbas_mi355x.h CBAS_FP8_PLAN_*; the activations follow their consumers (cbas_enc_set_fp8_plan)
+FP8_PLAN_BITS = {"qkv": 1, "proj": 2, "up": 4, "down": 8}
+FP8_PLANS = {"all": 15, "mlp": 12, "mlp_qkv": 13, "up": 4, "down": 8}
+FP8_PLAN_DEFAULT = FP8_PLANS["all"]             # every release's precision 2
+
+
+def parse_fp8_plan(plan) -> int:
+    """A plan name (FP8_PLANS), a '+'-joined list of GEMM names ('qkv+up') or a mask 0..15 (int or decimal string) -> the mask.
+    None is the default plan.  Anything else is a ValueError naming what is accepted."""
+    if plan is None:
+        return FP8_PLAN_DEFAULT
+    if isinstance(plan, bool):
+        raise ValueError(f"fp8 plan {plan!r}: a name ({', '.join(FP8_PLANS)}), GEMM names joined by '+' or a mask 0..15")
+    if isinstance(plan, int):
+        mask = plan
+    else:
+        text = str(plan).strip().lower()
+        if text in FP8_PLANS:
+            return FP8_PLANS[text]
+        if text.isdigit():
+            mask = int(text)
+        elif text and all(t in FP8_PLAN_BITS for t in text.split("+")):
+            mask = 0
+            for t in text.split("+"):
+                mask |= FP8_PLAN_BITS[t]
+        else:
+            raise ValueError(f"fp8 plan {plan!r}: a name ({', '.join(FP8_PLANS)}), GEMM names ({', '.join(FP8_PLAN_BITS)}) joined "
+                             "by '+' or a mask 0..15")
+    if not 0 <= mask <= 15:
+        raise ValueError(f"fp8 plan mask {mask}: 0..15 (1 qkv, 2 proj, 4 up, 8 down)")
+    return mask
+
+
+def fp8_plan_name(mask: int) -> str:
+    """The name a plan is written under (file stamps, study records): its FP8_PLANS name, else 'p<mask>'."""
+    mask = parse_fp8_plan(mask)
+    for name, m in FP8_PLANS.items():
+        if m == mask:
+            return name
+    return f"p{mask}"

@@ -477,6 +477,74 @@ struct DevBufs {                       // frees what it holds on every return pa
 };
 }  // namespace
 
+// The up projection in the four forms the fp8 plans use: {fp16, MX-fp8} operands x {fp16, MX-fp8} result (see the header).
+extern "C" int cbas_debug_gemm_gelu_forms(int M, int N, int K, int tile, int a_fp8, int out_fp8, const float* A_host,
+                                          const float* W_host, const float* bias_host, uint16_t* out16_host, uint8_t* out8_host,
+                                          uint32_t* outsc_host, uint8_t* A8_host, uint32_t* Asc_host, uint8_t* W8_host,
+                                          uint32_t* Wsc_host) {
+    if (M <= 0 || N <= 0 || K <= 0 || N % 256 || K % 256 || !A_host || !W_host || !bias_host || (out_fp8 ? !out8_host || !outsc_host : !out16_host))
+        return cbas_fail(CBAS_EINVAL, "bad GELU GEMM test shape / pointers");
+    const int64_t M_pad = round_up(M, 256);
+    DevBufs bufs;
+    float *A = nullptr, *W = nullptr, *bias = nullptr;
+    HIP_TRY(bufs.alloc(&A, M_pad * (int64_t)K * 4));
+    HIP_TRY(bufs.alloc(&W, (int64_t)N * K * 4));
+    HIP_TRY(bufs.alloc(&bias, (int64_t)N * 4));
+    HIP_TRY(hipMemset(A, 0, M_pad * (int64_t)K * 4));
+    HIP_TRY(hipMemcpy(A, A_host, (int64_t)M * K * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(W, W_host, (int64_t)N * K * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(bias, bias_host, (int64_t)N * 4, hipMemcpyHostToDevice));
+    GemmParams p{};
+    p.tile = tile; p.M = M; p.M_pad = (int)M_pad; p.N = N; p.K = K; p.lda = K; p.bias = bias; p.ldo = N;
+    uint8_t *A8 = nullptr, *W8 = nullptr;
+    uint32_t *Asc = nullptr, *Wsc = nullptr;
+    if (a_fp8) {
+        HIP_TRY(bufs.alloc(&A8, M_pad * (int64_t)K));
+        HIP_TRY(bufs.alloc(&W8, (int64_t)N * K));
+        HIP_TRY(bufs.alloc(&Asc, M_pad * (int64_t)K / 32));
+        HIP_TRY(bufs.alloc(&Wsc, (int64_t)N * K / 32));
+        LAUNCH_TRY(launch_pack_fp8_weight(A, A8, Asc, (int)M_pad, K, (int)M_pad, 0, 0));
+        LAUNCH_TRY(launch_pack_fp8_weight(W, W8, Wsc, N, K, N, 0, 0));
+        p.A8 = A8; p.W8 = W8; p.A_sc = Asc; p.W_sc = Wsc; p.sc_lda = (int)M_pad;
+    } else {
+        f16 *A16 = nullptr, *W16 = nullptr;
+        HIP_TRY(bufs.alloc(&A16, M_pad * (int64_t)K * 2));
+        HIP_TRY(bufs.alloc(&W16, (int64_t)N * K * 2));
+        LAUNCH_TRY(launch_convert_f16(A, A16, nullptr, M_pad * (int64_t)K, 0));
+        LAUNCH_TRY(launch_convert_f16(W, W16, nullptr, (int64_t)N * K, 0));
+        p.A = A16; p.W = W16;
+    }
+    f16* o16 = nullptr;
+    uint8_t* o8 = nullptr;
+    uint32_t* osc = nullptr;
+    if (out_fp8) {
+        HIP_TRY(bufs.alloc(&o8, (int64_t)M * N));
+        HIP_TRY(bufs.alloc(&osc, (int64_t)(N / 128) * M_pad * 4));
+        HIP_TRY(hipMemset(osc, 0, (int64_t)(N / 128) * M_pad * 4));
+        p.out_f8 = o8; p.out_sc = osc; p.sc_ldo = (int)M_pad;
+    } else {
+        HIP_TRY(bufs.alloc(&o16, (int64_t)M * N * 2));
+        p.out_f16 = o16;
+    }
+    const GemmEpilogue epi = out_fp8 ? EPI_GELU_F8 : EPI_GELU;
+    const int rc = tile ? launch_gemm_8ph(epi, p, tile, 0) : launch_gemm(epi, p, 0);
+    if (rc) return cbas_fail(CBAS_EINVAL, "GELU GEMM launch failed (a_fp8=%d out_fp8=%d tile=%d rc=%d)", a_fp8, out_fp8, tile, rc);
+    HIP_TRY(hipDeviceSynchronize());
+    if (out_fp8) {
+        HIP_TRY(hipMemcpy(out8_host, o8, (int64_t)M * N, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(outsc_host, osc, (int64_t)(N / 128) * M_pad * 4, hipMemcpyDeviceToHost));
+    } else {
+        HIP_TRY(hipMemcpy(out16_host, o16, (int64_t)M * N * 2, hipMemcpyDeviceToHost));
+    }
+    if (a_fp8) {
+        if (A8_host) HIP_TRY(hipMemcpy(A8_host, A8, (int64_t)M * K, hipMemcpyDeviceToHost));
+        if (Asc_host) HIP_TRY(hipMemcpy(Asc_host, Asc, M_pad * (int64_t)K / 32, hipMemcpyDeviceToHost));
+        if (W8_host) HIP_TRY(hipMemcpy(W8_host, W8, (int64_t)N * K, hipMemcpyDeviceToHost));
+        if (Wsc_host) HIP_TRY(hipMemcpy(Wsc_host, Wsc, (int64_t)N * K / 32, hipMemcpyDeviceToHost));
+    }
+    return CBAS_OK;
+}
+
 extern "C" int cbas_debug_gemm_run(const cbas_debug_gemm_args* a) {
     if (!a || a->struct_bytes != (int64_t)sizeof(cbas_debug_gemm_args))
         return cbas_fail(CBAS_EINVAL, "cbas_debug_gemm_args: struct_bytes %lld, library expects %lld", a ? (long long)a->struct_bytes : -1ll,

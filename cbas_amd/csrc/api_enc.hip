@@ -84,6 +84,11 @@ struct cbas_enc {
     float* pos_tab = nullptr;           // DINOv2: (Pmax, D) position embedding interpolated to the current grid
     std::vector<float> pos_host;        // DINOv2: raw (1+G*G, D) table
     int pos_interp = CBAS_POS_INTERP_BICUBIC_AA;   // how it is resampled to a frame's grid (cbas_enc_set_pos_interp)
+    // precision 2: which GEMMs of a layer take MX-fp8 operands (CBAS_FP8_PLAN_* bits; cbas_enc_set_fp8_plan).  A GEMM outside the
+    // plan runs as precision 0 runs it, on the fp16 weights every precision-2 handle holds anyway (the CLS tail of the pruned
+    // last layer uses them), in the same workspace: an fp8 activation is half the bytes of the fp16 one it replaces.
+    int fp8_plan = CBAS_FP8_PLAN_ALL;
+    bool vit_forward_seen = false;      // a ViT forward was queued: the plan is fixed from here on
     // RoPE (DINOv3) / interpolated position-embedding (DINOv2) tables, one set per patch grid seen so far.  A new
     // grid gets FRESH device buffers filled by a blocking copy, so no stream has to be drained when a queue mixes
     // resolutions; rope_cos / rope_sin / pos_tab point at the set of the batch being queued (kernel arguments are
@@ -436,7 +441,8 @@ int run_last_layer_cls(cbas_enc* h, const LayerW& w, int n, int T, hipStream_t s
     f16* cc = qc + cap * D;                 // [n][D] attention context of the CLS rows
     f16* hc = cc + cap * D;                 // [n][D] LayerNorm 2 of the CLS rows
     f16* uc = hc + cap * D;                 // [n][F] GELU(up_proj)
-    const bool split = h->cfg.precision == 1, f8 = h->cfg.precision == 2;
+    // precision 2: the k | v projection of all rows follows the plan's q|k|v bit; the CLS tail is fp16 in every plan
+    const bool split = h->cfg.precision == 1, f8 = h->cfg.precision == 2 && (h->fp8_plan & CBAS_FP8_PLAN_QKV);
     const int sc_ld = (int)h->rows_cap;
     GemmParams kv{};                        // k | v sections of the fused QKV weight, all rows
     if (f8) {
@@ -625,6 +631,12 @@ int run_blocks(cbas_enc* h, int n, int height, int width, int patch_k, float in_
     // done for n rows instead of n*T (rows are independent: bit-identical CLS).  Debug taps run it in full.
     const bool prune = h->prune_last && stop_layer < 0 && (cls_f32 || cls_f16);
     const bool split = h->cfg.precision == 1, f8 = h->cfg.precision == 2;
+    // precision 2: the GEMMs with MX-fp8 operands (cbas_enc_set_fp8_plan).  An activation is stored in the format of the GEMM
+    // that consumes it: LayerNorm 1 -> q|k|v, attention context -> o_proj, LayerNorm 2 -> up, GELU output -> down.
+    const int plan = f8 ? h->fp8_plan : 0;
+    const bool f8_qkv = plan & CBAS_FP8_PLAN_QKV, f8_proj = plan & CBAS_FP8_PLAN_PROJ, f8_up = plan & CBAS_FP8_PLAN_UP,
+               f8_down = plan & CBAS_FP8_PLAN_DOWN;
+    h->vit_forward_seen = true;
     // LayerNorm fold.  LN(x) W^T + b = rstd (x (gamma o W)^T - mean colsum(gamma o W)) + (beta W^T + b): the two GEMMs that
     // consume a LayerNorm output ([tf]:404-445: q|k|v after norm1, up_proj after norm2) run on the raw fp16 residual stream
     // with gamma folded into their weights and apply mean / rstd in their epilogues; the two GEMMs that produce the residual
@@ -680,12 +692,12 @@ int run_blocks(cbas_enc* h, int n, int height, int width, int patch_k, float in_
             { PROF(CBAS_PROF_DOWN, 2.0 * M * (double)F * D); LAUNCH_TRY(launch_gemm(more ? EPI_RESID_LN : EPI_RESID, d, st)); }
             continue;
         }
-        if (f8) { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f8(h->x, D, w.ln1_w, w.ln1_b, h8, h->sc_h, sc_ld, M, D, h->cfg.layer_norm_eps, st)); }
+        if (f8_qkv) { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f8(h->x, D, w.ln1_w, w.ln1_b, h8, h->sc_h, sc_ld, M, D, h->cfg.layer_norm_eps, st)); }
         else { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f16(h->x, D, w.ln1_w, w.ln1_b, h->h16, M, D, h->cfg.layer_norm_eps, st)); }
         if (stop(1)) return CBAS_OK;
 
         GemmParams q{};
-        if (f8) { q.A8 = h8; q.A_sc = h->sc_h; q.sc_lda = sc_ld; q.W8 = w.wqkv8; q.W_sc = w.sqkv; }
+        if (f8_qkv) { q.A8 = h8; q.A_sc = h->sc_h; q.sc_lda = sc_ld; q.W8 = w.wqkv8; q.W_sc = w.sqkv; }
         else { q.A = h->h16; q.W = w.wqkv; q.W_lo = split ? w.wqkv_lo : nullptr; }
         q.M = M; q.M_pad = M_pad; q.N = 3 * D; q.K = D; q.bias = w.qkv_b; q.out_f16 = h->qkv16; q.ldo = 3 * D;
         q.tokens_per_frame = T; q.n_prefix = h->NP; q.D = D;
@@ -694,31 +706,31 @@ int run_blocks(cbas_enc* h, int n, int height, int width, int patch_k, float in_
         if (stop(2)) return CBAS_OK;
 
         { PROF(CBAS_PROF_ATTENTION, 4.0 * n * (double)T * T * D);
-          LAUNCH_TRY(launch_attention(h->qkv16, nullptr, h->h16, f8 ? h->sc_h : nullptr, sc_ld, n, T, D, h->NH, st)); }
+          LAUNCH_TRY(launch_attention(h->qkv16, nullptr, h->h16, f8_proj ? h->sc_h : nullptr, sc_ld, n, T, D, h->NH, st)); }
         if (stop(3)) return CBAS_OK;
 
         GemmParams o{};
-        if (f8) { o.A8 = h8; o.A_sc = h->sc_h; o.sc_lda = sc_ld; o.W8 = w.wo8; o.W_sc = w.so; }
+        if (f8_proj) { o.A8 = h8; o.A_sc = h->sc_h; o.sc_lda = sc_ld; o.W8 = w.wo8; o.W_sc = w.so; }
         else { o.A = h->h16; o.W = w.wo; o.W_lo = split ? w.wo_lo : nullptr; }
         o.M = M; o.M_pad = M_pad; o.N = D; o.K = D; o.bias = w.o_b; o.lambda = w.ls1; o.out_f32 = h->x; o.ldo = D;
         { PROF(CBAS_PROF_OPROJ, 2.0 * M * (double)D * D); LAUNCH_TRY(launch_gemm(EPI_RESID, o, st)); }
         if (stop(4)) return CBAS_OK;
 
-        if (f8) { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f8(h->x, D, w.ln2_w, w.ln2_b, h8, h->sc_h, sc_ld, M, D, h->cfg.layer_norm_eps, st)); }
+        if (f8_up) { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f8(h->x, D, w.ln2_w, w.ln2_b, h8, h->sc_h, sc_ld, M, D, h->cfg.layer_norm_eps, st)); }
         else { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f16(h->x, D, w.ln2_w, w.ln2_b, h->h16, M, D, h->cfg.layer_norm_eps, st)); }
         if (stop(5)) return CBAS_OK;
 
-        GemmParams u{};
-        if (f8) {
-            u.A8 = h8; u.A_sc = h->sc_h; u.sc_lda = sc_ld; u.W8 = w.wup8; u.W_sc = w.sup;
-            u.out_f8 = u8; u.out_sc = h->sc_u; u.sc_ldo = sc_ld;
-        } else { u.A = h->h16; u.W = w.wup; u.W_lo = split ? w.wup_lo : nullptr; u.out_f16 = h->u16; }
+        GemmParams u{};                     // operands by the plan's `up` bit, result in the format `down` consumes
+        if (f8_up) { u.A8 = h8; u.A_sc = h->sc_h; u.sc_lda = sc_ld; u.W8 = w.wup8; u.W_sc = w.sup; }
+        else { u.A = h->h16; u.W = w.wup; u.W_lo = split ? w.wup_lo : nullptr; }
+        if (f8_down) { u.out_f8 = u8; u.out_sc = h->sc_u; u.sc_ldo = sc_ld; }
+        else u.out_f16 = h->u16;
         u.M = M; u.M_pad = M_pad; u.N = F; u.K = D; u.bias = w.up_b; u.ldo = F;
-        { PROF(CBAS_PROF_UP, 2.0 * M * (double)F * D); LAUNCH_TRY(launch_gemm(f8 ? EPI_GELU_F8 : EPI_GELU, u, st)); }
+        { PROF(CBAS_PROF_UP, 2.0 * M * (double)F * D); LAUNCH_TRY(launch_gemm(f8_down ? EPI_GELU_F8 : EPI_GELU, u, st)); }
         if (stop(6)) return CBAS_OK;
 
         GemmParams d{};
-        if (f8) { d.A8 = u8; d.A_sc = h->sc_u; d.sc_lda = sc_ld; d.W8 = w.wdown8; d.W_sc = w.sdown; }
+        if (f8_down) { d.A8 = u8; d.A_sc = h->sc_u; d.sc_lda = sc_ld; d.W8 = w.wdown8; d.W_sc = w.sdown; }
         else { d.A = h->u16; d.W = w.wdown; d.W_lo = split ? w.wdown_lo : nullptr; }
         d.M = M; d.M_pad = M_pad; d.N = D; d.K = F; d.bias = w.down_b; d.lambda = w.ls2; d.out_f32 = h->x; d.ldo = D;
         { PROF(CBAS_PROF_DOWN, 2.0 * M * (double)F * D); LAUNCH_TRY(launch_gemm(EPI_RESID, d, st)); }
@@ -1683,6 +1695,22 @@ extern "C" int cbas_enc_set_pos_interp(cbas_enc* h, int mode) {
         return cbas_fail(CBAS_EINVAL, "cbas_enc_set_pos_interp: call it before the first batch (tables of %d grid(s) are built)",
                          (int)h->pos_tables.size());
     h->pos_interp = mode;
+    return CBAS_OK;
+}
+
+extern "C" int cbas_enc_set_fp8_plan(cbas_enc* h, int plan) {
+    if (!h) return cbas_fail(CBAS_EINVAL, "null handle");
+    if (h->cfg.family != 0 || h->cfg.precision != 2)
+        return cbas_fail(CBAS_EINVAL, "cbas_enc_set_fp8_plan: only a precision-2 (MX-fp8) ViT handle has a plan (this one: %s, precision %d)",
+                         h->cfg.family == 0 ? "ViT" : "ConvNeXt", h->cfg.precision);
+    if (plan < 0 || plan > CBAS_FP8_PLAN_ALL)
+        return cbas_fail(CBAS_EINVAL, "cbas_enc_set_fp8_plan: plan=%d: a mask of 1 (qkv), 2 (proj), 4 (up), 8 (down)", plan);
+    if (h->vit_forward_seen)
+        return cbas_fail(CBAS_EINVAL, "cbas_enc_set_fp8_plan: call it before the handle's first forward / submit (rows of one handle "
+                                      "come from one plan)");
+    // nothing to allocate or repack: the handle holds the fp16 weights of every GEMM beside the MX-fp8 ones, and both lanes'
+    // workspaces fit either format of every activation (the plan is read per launch sequence, whichever lane runs it)
+    h->fp8_plan = plan;
     return CBAS_OK;
 }
 

@@ -240,6 +240,11 @@ __device__ __forceinline__ void gemm_epilogue_tile(const GemmParams& p, int row_
                 for (int j = 0; j < 4; ++j) {
                     const f32x4 w = acc[i][j] + bv[j];
                     v[j] = gelu_fast4(w);
+                    if (EPIX == EPI_GELU_F8_H) {
+                        // fp16 operands (fp8 plans with `down` but not `up`): quantise what EPI_GELU would have stored, bit for bit
+                        const f16x4 hv = {(f16)v[j][0], (f16)v[j][1], (f16)v[j][2], (f16)v[j][3]};
+                        v[j] = f32x4{(float)hv[0], (float)hv[1], (float)hv[2], (float)hv[3]};
+                    }
                 }
                 int sb[2];
 #pragma unroll

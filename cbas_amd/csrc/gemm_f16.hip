@@ -240,7 +240,14 @@ int launch_gemm(GemmEpilogue epi, const GemmParams& p_in, hipStream_t stream) {
         if (p.tile >= GEMM_TILE_PP_256x256 && p.tile <= GEMM_TILE_PP_AUTO) return launch_gemm_8ph(epi, p, p.tile, stream);   // bring-up
         return launch_gemm_8ph(epi, p, t256 >= 120 ? GEMM_TILE_PP_AUTO : GEMM_TILE_PP_128x256, stream);
     }
-    if (epi == EPI_GELU_F8) return -1;
+    if (epi == EPI_GELU_F8) {
+        // fp16 operands with an MX-fp8 result (fp8 plans): the epilogue exists in the ping-pong kernel only, so every problem
+        // size runs there, small ones on its 128-row tile (a row must not depend on how many rows shared its batch)
+        if (p.W_lo || p.N % 256 || p.K % 128) return -1;
+        const long t256 = (long)((p.M + 255) / 256) * (p.N / 256);
+        if (p.tile >= GEMM_TILE_PP_256x256 && p.tile <= GEMM_TILE_PP_AUTO) return launch_gemm_8ph(epi, p, p.tile, stream);   // bring-up
+        return launch_gemm_8ph(epi, p, t256 >= 120 ? GEMM_TILE_PP_AUTO : GEMM_TILE_PP_128x256, stream);
+    }
     const int tile = pick_tile(p);
     int rc = dispatch_gemm(epi, p, tile, stream);
     if (rc == -3) return -1;

@@ -29,6 +29,9 @@
 // hands out workgroups in block order, so the small tiles fill the last, partial round of the big
 // ones (612 big tiles on 256 CUs are 3 rounds; 504 big + 204 half-size tiles finish in about 2.65).
 //
+// Operand form and epilogue are independent template arguments: the fp8 plans (cbas_enc_set_fp8_plan) add MX-fp8 operands with
+// the fp16 GELU epilogue and fp16 operands with the MX-fp8 GELU epilogue to the combinations precision 0 / 2 use.
+//
 // MX-fp8 form (F8 = true, precision 2): operands are e4m3 bytes with one E8M0 scale per 32 k-elements.  A K-tile is
 // 128 k-elements = the same 128-byte LDS rows, swizzle, staging schedule and fragment reads as the fp16 form; the two
 // 16-byte fragment reads of a lane (chunks q and 4+q of a row, q = lane >> 4) are exactly the 32 bytes
@@ -722,12 +725,15 @@ int launch_gemm_8ph(GemmEpilogue epi, const GemmParams& p_in, int tile, hipStrea
         switch (epi) {
             case EPI_QKV:     return launch_8ph_epi<EPI_QKV, true>(p, tile, stream);
             case EPI_RESID:   return launch_8ph_epi<EPI_RESID, true>(p, tile, stream);
-            case EPI_GELU_F8: return launch_8ph_epi<EPI_GELU_F8, true>(p, tile, stream);
+            case EPI_GELU:    return p.out_f16 ? launch_8ph_epi<EPI_GELU, true>(p, tile, stream) : -1;       // plan `up` alone: fp16 out
+            case EPI_GELU_F8: return p.out_f8 && p.out_sc ? launch_8ph_epi<EPI_GELU_F8, true>(p, tile, stream) : -1;
             default: return -1;
         }
     }
     if (p.K % (2 * BK)) return -1;
     switch (epi) {
+        // plan `down` alone: fp16 operands, MX-fp8 out (N in whole scale tiles of 128 columns: N % 256 above)
+        case EPI_GELU_F8: return p.out_f8 && p.out_sc ? launch_8ph_epi<EPI_GELU_F8_H, false>(p, tile, stream) : -1;
         case EPI_PATCH: return launch_8ph_epi<EPI_PATCH, false>(p, tile, stream);
         case EPI_QKV:   return launch_8ph_epi<EPI_QKV, false>(p, tile, stream);
         case EPI_RESID: return launch_8ph_epi<EPI_RESID, false>(p, tile, stream);

@@ -16,8 +16,13 @@ enum GemmEpilogue {
     EPI_QKV_LN = 5,   // EPI_QKV on raw fp16 x with W = fp16(gamma o W): rstd * (acc - mean * colsum) + bias', then as EPI_QKV
     EPI_GELU_LN = 6,  // EPI_GELU likewise
     EPI_RESID_LN = 7, // EPI_RESID that also writes fp16 x and the per-row statistics the next EPI_*_LN needs
+    // fp8 plans (gemm_f16_8ph.hip only): what EPI_GELU_F8 becomes on fp16 operands - the GELU value is rounded to fp16 first, so
+    // the bytes and scales are the quantisation of exactly what EPI_GELU would have stored (callers pass EPI_GELU_F8)
+    EPI_GELU_F8_H = 8,
 };
-constexpr int epi_base(int epi) { return epi == EPI_QKV_LN ? EPI_QKV : epi == EPI_GELU_LN ? EPI_GELU : epi == EPI_RESID_LN ? EPI_RESID : epi; }
+constexpr int epi_base(int epi) {
+    return epi == EPI_QKV_LN ? EPI_QKV : epi == EPI_GELU_LN ? EPI_GELU : epi == EPI_RESID_LN ? EPI_RESID : epi == EPI_GELU_F8_H ? EPI_GELU_F8 : epi;
+}
 
 enum GemmTile { GEMM_TILE_AUTO = 0, GEMM_TILE_128x128 = 1, GEMM_TILE_256x128 = 2, GEMM_TILE_128x256 = 3,
                 GEMM_TILE_256x256 = 4,
@@ -38,7 +43,8 @@ struct GemmParams {
     const f16* W_lo;     // [N][K]  residual W - fp16(W) as fp16, or nullptr
     // MX-fp8 operands (precision 2; gemm_f16_8ph.hip only): e4m3 bytes, K contiguous, plus E8M0 block scales, one
     // byte per 32 k-elements, stored K-tile-major as dwords: sc[(k / 128) * ld + row] byte (k % 128) / 32.
-    // A8 != nullptr selects the fp8 kernel (A / W above are then unused).
+    // A8 != nullptr selects the fp8 kernel (A / W above are then unused).  The output format follows the epilogue, not the
+    // operands (fp8 plans): EPI_GELU on fp8 operands writes fp16, EPI_GELU_F8 on fp16 operands writes out_f8 / out_sc.
     const uint8_t* A8;   // [M_pad][lda]
     const uint8_t* W8;   // [N][K]
     const uint32_t* A_sc;   // [K/128][sc_lda]
@@ -46,7 +52,7 @@ struct GemmParams {
     int sc_lda;
     int sc_ldw;          // 0: N (W_sc may point into a wider array, e.g. the k|v columns of the fused q|k|v scales)
     uint8_t* out_f8;     // EPI_GELU_F8: [M][ldo] bytes
-    uint32_t* out_sc;    // EPI_GELU_F8: [N/128][sc_ldo]
+    uint32_t* out_sc;    // EPI_GELU_F8: [N/128][sc_ldo] (A_sc layout of the consumer)
     int sc_ldo;
     int M;               // valid rows (stores are skipped for rows >= M)
     int M_pad;           // rows allocated in A (loads of rows >= M_pad are clamped)

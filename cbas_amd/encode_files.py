@@ -43,6 +43,14 @@ def find_videos(root: str, stamp: str) -> List[str]:
     return sorted(out)
 
 
+def run_stamp(encoder_id: str, precision: int, fp8_plan=None) -> str:
+    """The encoder stamp of a run's files and of the bundles it accepts: what pipeline.file_attrs writes.  MX-fp8 rows carry
+    '#mx-fp8', and the plan's name when it is not the default one ('#mx-fp8-mlp'): a head trained on another plan's rows -
+    or on fp16 rows - is refused by the comparison in bundle.load_model_bundle."""
+    from . import pipeline as P
+    return encoder_id + ("#" + P.fp8_tag(fp8_plan) if int(precision) == 2 else "")
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("videos", nargs="*")
@@ -69,6 +77,10 @@ def main(argv=None) -> int:
                     help="allow --precision 2: rows are ~6e-2 from the fp32 reference, NOT interchangeable with fp16 rows; "
                          "the files are stamped '<encoder>#mx-fp8' + attr encoder_precision so that CBAS and this tool "
                          "treat them as made by a different encoder")
+    ap.add_argument("--fp8-plan", default=None,
+                    help="with --precision 2: which GEMMs take MX-fp8 operands - all (default), mlp, mlp_qkv, up, down, GEMM names "
+                         "joined by '+' or a mask 0..15 (1 qkv, 2 proj, 4 up, 8 down); default: CBAS_FP8_PLAN from the "
+                         "environment.  The files are stamped with the plan ('#mx-fp8-mlp')")
     args = ap.parse_args(argv)
     if args.precision is None:
         from .encoder import DEFAULT_PRECISION
@@ -76,6 +88,16 @@ def main(argv=None) -> int:
     if args.precision == 2 and not args.experimental_fp8:
         ap.error("--precision 2 writes MX-fp8 rows that heads trained on fp16 embeddings must not consume; "
                  "pass --experimental-fp8 to write them (stamped as such)")
+
+    from .config import parse_fp8_plan
+    fp8_plan = None
+    if args.precision == 2:
+        try:
+            fp8_plan = parse_fp8_plan(args.fp8_plan if args.fp8_plan is not None else os.environ.get("CBAS_FP8_PLAN") or None)
+        except ValueError as e:
+            ap.error(str(e))
+    elif args.fp8_plan is not None:
+        ap.error("--fp8-plan needs --precision 2")
 
     from . import dist as cdist, pipeline as P
     from .bundle import load_model_bundle
@@ -85,7 +107,7 @@ def main(argv=None) -> int:
     torch.cuda.set_device(local)
     device = torch.device("cuda", local)
     videos = list(args.videos)
-    stamp = args.encoder + ("#" + P.FP8_TAG if args.precision == 2 else "")      # what pipeline.file_attrs writes
+    stamp = run_stamp(args.encoder, args.precision, fp8_plan)
     if args.dir:
         videos += find_videos(args.dir, stamp)
     if not videos:
@@ -94,10 +116,10 @@ def main(argv=None) -> int:
         return 0
     P.set_project_stamp(args.encoder)                       # what gui_state.proj.encoder_model_identifier is to encode_file
     enc = DinoEncoder(args.encoder, device=device, max_batch=args.max_batch, max_frame=tuple(args.max_frame),
-                      precision=args.precision)
+                      precision=args.precision, fp8_plan=fp8_plan)
     head = meta = None
     if args.model_bundle:
-        # an MX-fp8 run only accepts a head whose bundle says it was trained on MX-fp8 rows (same '#mx-fp8' stamp)
+        # an MX-fp8 run only accepts a head whose bundle says it was trained on MX-fp8 rows of the same plan (same stamp)
         head, meta = load_model_bundle(args.model_bundle, device=device, project_encoder=stamp,
                                        in_features=enc.config.hidden_size)
         if head is None:

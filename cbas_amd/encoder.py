@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .config import ViTConfig, find_checkpoint_dir, is_convnext
+from .config import ViTConfig, find_checkpoint_dir, is_convnext, parse_fp8_plan, fp8_plan_name, FP8_PLAN_DEFAULT
 from .weights import load_encoder_checkpoint, convnext_param_shapes
 
 
@@ -73,7 +73,7 @@ class DinoEncoder:
     """MI355X encoder (DINOv3 ViT / ConvNeXt, DINOv2 with or without registers) behind the reference's ``DinoEncoder`` interface."""
 
     def __init__(self, model_identifier: str, device="cuda", max_batch: int = 128,
-                 max_frame: Tuple[int, int] = (256, 256), precision: Optional[int] = None):
+                 max_frame: Tuple[int, int] = (256, 256), precision: Optional[int] = None, fp8_plan=None):
         # max_batch: frames per encoder launch sequence.  A frame's row does not depend on its batch (bit-exact:
         # tests/test_gpu_parity.py::test_vitb_full_batch_invariance), so this is scheduling only: 128 runs the file path
         # ~3 % faster than 64 (fewer partly-filled tile rounds per frame; 256 adds nothing) for ~1 GB more workspace.
@@ -91,24 +91,35 @@ class DinoEncoder:
             if precision == 2:
                 raise ValueError("CBAS_PRECISION=2 (MX-fp8) is not selectable through the environment: its rows are not "
                                  "interchangeable with the other modes' (pass precision=2 explicitly)")
-        self._init(cfg, weights, device, max_batch, max_frame, precision)
+        if fp8_plan is None and int(precision) == 2:
+            # precision 2 is only ever asked for explicitly; WHICH of its GEMMs are MX-fp8 may come from the environment
+            # (name or mask: config.parse_fp8_plan) - the files are stamped with the plan either way (pipeline.file_attrs)
+            fp8_plan = os.environ.get("CBAS_FP8_PLAN") or None
+        self._init(cfg, weights, device, max_batch, max_frame, precision, **({} if fp8_plan is None else {"fp8_plan": fp8_plan}))
         self.model_identifier = model_identifier
         mode = {0: "fp16 operands - the reference's own GPU behaviour under autocast (fast mode)", 1: "fp16 activations, hi + lo split weights",
                 2: "MX-fp8 operands", 3: "fp32 end to end (label-exact)",
                 4: "fp32 with split-fp16 GEMM products (label-exact; CBAS_PRECISION=0 selects the fast mode)"}.get(int(precision), "?")
+        if int(precision) == 2 and self.fp8_plan != FP8_PLAN_DEFAULT:
+            mode += f", plan {fp8_plan_name(self.fp8_plan)!r} (mask {self.fp8_plan}: the other GEMMs run on fp16 operands)"
         print(f"cbas_amd: MI355X encoder on {getattr(self, 'device', device)}, precision {int(precision)}: {mode}")
 
     @classmethod
     def from_weights(cls, cfg: ViTConfig, weights: Dict[str, np.ndarray], device="cuda", max_batch: int = 64,
-                     max_frame: Tuple[int, int] = (256, 256), precision: int = 0) -> "DinoEncoder":
+                     max_frame: Tuple[int, int] = (256, 256), precision: int = 0, fp8_plan=None) -> "DinoEncoder":
+        """``fp8_plan`` (precision 2 only): which GEMMs take MX-fp8 operands - "all" (the default), "mlp", "mlp_qkv", "up",
+        "down", GEMM names joined by '+', or a mask (config.parse_fp8_plan)."""
         self = cls.__new__(cls)
-        self._init(cfg, weights, device, max_batch, max_frame, precision)
+        self._init(cfg, weights, device, max_batch, max_frame, precision, fp8_plan)
         self.model_identifier = "<in-memory>"
         return self
 
-    def _init(self, cfg: ViTConfig, weights, device, max_batch, max_frame, precision):
+    def _init(self, cfg: ViTConfig, weights, device, max_batch, max_frame, precision, fp8_plan=None):
         cfg.validate()
         convnext = is_convnext(cfg)
+        if fp8_plan is not None and int(precision) != 2:
+            raise ValueError(f"fp8_plan={fp8_plan!r} needs precision=2 (MX-fp8); precision {int(precision)} has no fp8 GEMMs")
+        self._fp8_plan = parse_fp8_plan(fp8_plan)
         if convnext and int(precision) not in (3, 4):
             raise ValueError(f"precision {int(precision)}: DINOv3 ConvNeXt encoders run in precision 3 (fp32) or 4 (the default: "
                              "fp32 with split-fp16 GEMM products) only")
@@ -145,6 +156,9 @@ class DinoEncoder:
             # plain DINOv2 resamples its position table without antialiasing (HF modeling_dinov2.py:86-91).  Set on EVERY handle
             # built from this config - the rebuild for larger frames and the precision-3 range-fallback twin come through here
             _lib.check(self._lib.cbas_enc_set_pos_interp(h, _lib.POS_INTERP_BICUBIC), "cbas_enc_set_pos_interp")
+        if self.precision == 2 and self._fp8_plan != FP8_PLAN_DEFAULT:
+            # like the position filter: on every handle of this encoder, the one rebuilt for larger frames included
+            _lib.check(self._lib.cbas_enc_set_fp8_plan(h, self._fp8_plan), "cbas_enc_set_fp8_plan")
 
     def _fit_frame(self, H: int, W: int) -> None:
         """The reference takes any frame size; the workspace here is sized at create.  Frames larger than
@@ -168,6 +182,12 @@ class DinoEncoder:
         3 fp32 end to end - the reference's CPU arithmetic, 4 the same with the GEMM products as three-term fp16 splits (as
         exact, three times as fast: the DEFAULT of an encoder built the reference's way) (include/cbas_mi355x.h)."""
         return int(self._cfg_c.precision)
+
+    @property
+    def fp8_plan(self) -> int:
+        """Precision 2: the mask of GEMMs that take MX-fp8 operands (1 qkv, 2 proj, 4 up, 8 down; 15 = "all", the default);
+        0 in every other precision.  ``config.fp8_plan_name`` gives its name."""
+        return int(getattr(self, "_fp8_plan", 0)) if self.precision == 2 else 0
 
     # -- nn.Module-like surface used by the reference ------------------------------------------
     def eval(self):
@@ -200,6 +220,7 @@ class DinoEncoder:
             twin._lib, twin._blob = self._lib, self._blob
             twin._cfg_c = _lib.EncConfig.from_buffer_copy(self._cfg_c)       # every field, the family's included
             twin._cfg_c.precision = 3
+            twin._fp8_plan = self._fp8_plan      # carried, not applied: the fp32 twin has no fp8 GEMM (its fp8_plan reads 0)
             twin._h = None
             twin.model_identifier = getattr(self, "model_identifier", "<in-memory>")
             twin._create()

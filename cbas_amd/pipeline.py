@@ -215,19 +215,29 @@ def _current_stamp() -> Optional[str]:
 FP8_TAG = "mx-fp8"
 
 
+def fp8_tag(fp8_plan=None) -> str:
+    """What marks rows of the MX-fp8 mode: 'mx-fp8' for the default plan (all four GEMMs; what every earlier file carries),
+    'mx-fp8-<plan>' for any other - rows of different plans are different encoders' rows."""
+    from .config import FP8_PLAN_DEFAULT, fp8_plan_name, parse_fp8_plan
+    mask = parse_fp8_plan(fp8_plan)
+    return FP8_TAG if mask == FP8_PLAN_DEFAULT else f"{FP8_TAG}-{fp8_plan_name(mask)}"
+
+
 def file_attrs(encoder=None) -> dict:
     """Root attributes of a ``_cls.h5`` (backend/cbas.py:414-416): the project's encoder stamp + schema version when a
     project is set.  Rows made in the MX-fp8 throughput mode (precision 2) are NOT interchangeable with fp16 rows (CLS
     error ~6e-2 against the 1e-3 contract), so such files say so: an ``encoder_precision`` attribute, and a stamp with a
     ``#mx-fp8`` suffix - the reference's project loader (startup_page.py:100-117) and its model loader
-    (workthreads.py:390-399) then treat them as made by a different encoder instead of consuming them silently."""
+    (workthreads.py:390-399) then treat them as made by a different encoder instead of consuming them silently.  A plan other
+    than the default one (``encoder.fp8_plan``) is named in both: ``#mx-fp8-mlp``."""
     fp8 = int(getattr(encoder, "precision", 0) or 0) == 2
+    tag = fp8_tag(getattr(encoder, "fp8_plan", None)) if fp8 else ""
     attrs = {}
     stamp = _current_stamp()
     if stamp:
-        attrs = {"encoder_model_identifier": stamp + ("#" + FP8_TAG if fp8 else ""), "schema_version": SCHEMA_VERSION}
+        attrs = {"encoder_model_identifier": stamp + ("#" + tag if fp8 else ""), "schema_version": SCHEMA_VERSION}
     if fp8:
-        attrs["encoder_precision"] = FP8_TAG
+        attrs["encoder_precision"] = tag
     return attrs
 
 

@@ -52,8 +52,8 @@ extern "C" {
 #define CBAS_ESTATE       -4   /* call sequence error (e.g. wait on an idle slot) */
 #define CBAS_ERANGE       -5   /* a frame's CLS row came out NaN / infinite: an activation left the arithmetic mode's range */
 
-/* Still 11 with cbas_rows_gather_windows / cbas_head_train_step_rows, with cbas_head_score_rows / cbas_logits_nll and with
- * cbas_enc_set_pos_interp: they are additions.  No structure and no existing signature changed, so a caller built against the earlier version 11 header
+/* Still 11 with cbas_rows_gather_windows / cbas_head_train_step_rows, with cbas_head_score_rows / cbas_logits_nll, with
+ * cbas_enc_set_pos_interp and with cbas_enc_set_fp8_plan: they are additions.  No structure and no existing signature changed, so a caller built against the earlier version 11 header
  * runs unchanged. */
 #define CBAS_ABI_VERSION   11
 
@@ -231,6 +231,21 @@ int cbas_enc_set_prune_last_layer(cbas_enc* h, int enable);
 #define CBAS_POS_INTERP_BICUBIC_AA 0
 #define CBAS_POS_INTERP_BICUBIC    1
 int cbas_enc_set_pos_interp(cbas_enc* h, int mode);
+/* Which projection GEMMs of a precision-2 (MX-fp8) ViT handle take MX-fp8 operands: a mask of CBAS_FP8_PLAN_* bits.  A new
+ * handle has CBAS_FP8_PLAN_ALL - every earlier release's precision 2, bit for bit.  A GEMM outside the plan runs exactly as
+ * precision 0 runs it (fp16 operands, fp32 accumulation), and every activation is stored in the format of the GEMM that
+ * consumes it: LayerNorm 1 follows QKV, the attention context PROJ, LayerNorm 2 UP, the GELU output DOWN.  The pruned last
+ * layer follows the same plan for its k | v projection; its CLS tail is fp16 in every plan.  Plan 0 is precision 0's rows.
+ * Rows of different plans are different encoders' rows (as precision 2's are against precision 0's): train a head on the rows
+ * of the plan it will be fed.  Costs no device memory: a precision-2 handle holds the fp16 weights beside the MX-fp8 ones.
+ * Valid between cbas_enc_create and the handle's first forward / submit, on a precision-2 ViT handle; anything else - another
+ * precision, a ConvNeXt handle, a mask outside 0..15, a handle that has run - is CBAS_EINVAL.  Applies to both compute lanes. */
+#define CBAS_FP8_PLAN_QKV   1      /* q|k|v projection */
+#define CBAS_FP8_PLAN_PROJ  2      /* o_proj */
+#define CBAS_FP8_PLAN_UP    4      /* mlp.up_proj */
+#define CBAS_FP8_PLAN_DOWN  8      /* mlp.down_proj */
+#define CBAS_FP8_PLAN_ALL   15
+int cbas_enc_set_fp8_plan(cbas_enc* h, int plan);
 
 /* Bring-up, test and measurement-harness entry points (stage taps, implementation switches, stand-alone GEMM
  * harnesses, the MFMA neighbour) are NOT part of this boundary: include/cbas_mi355x_debug.h, built only into

@@ -80,6 +80,14 @@ int cbas_debug_overlap(int mode, int iters, float* ms_out);
 int cbas_debug_gemm_f8(int M, int N, int K, int tile, const float* A_host, const float* W_host, float* out_host,
                        uint8_t* A8_host, uint32_t* Asc_host, uint8_t* W8_host, uint32_t* Wsc_host);
 
+/* Tests: the up projection's GEMM (GELU epilogue, bias) in each of the four operand / result forms of the fp8 plans.
+ * a_fp8: operands quantised as cbas_debug_gemm_f8 does (and returned the same way), else rounded to fp16.  out_fp8: the result
+ * is MX-fp8 - out8_host [M][N] e4m3 bytes + outsc_host [N/128][round_up(M,256)] dwords, the layout the down projection reads
+ * its A operand in - else out16_host [M][N] fp16 bits.  Pointers of the form not asked for may be NULL.  tile as above. */
+int cbas_debug_gemm_gelu_forms(int M, int N, int K, int tile, int a_fp8, int out_fp8, const float* A_host, const float* W_host,
+                               const float* bias_host, uint16_t* out16_host, uint8_t* out8_host, uint32_t* outsc_host,
+                               uint8_t* A8_host, uint32_t* Asc_host, uint8_t* W8_host, uint32_t* Wsc_host);
+
 /* Tests: ONE library GEMM launch on host operands (tests/test_gpu_kernel_reference.py compares it with a float64 reference).
  * The harness converts / splits the fp32 host operands on the device with the library's own routines (launch_convert_f16,
  * launch_pack_split_weight), uploads the initial output buffer (the residual stream for EPI_RESID / EPI_PATCH, canaries

@@ -89,14 +89,20 @@ def windows_of(rows16: torch.Tensor, seq_len: int) -> torch.Tensor:
 
 def study(model="vitb16", hw=224, n_classes=6, epochs=30, train_clips=6, train_len=1200, test_clips=3, test_len=1024,
           plans=(2,), lr=1e-3, seed=0, verbose=True):
+    """plans: encoder modes to compare with fp16 - a precision (2 = MX-fp8 in all four GEMMs, recorded under "2") or the
+    name of an fp8 plan of precision 2 ("mlp", "mlp_qkv", ...: config.FP8_PLANS, recorded under that name)."""
     cfg = C.NAMED_VIT[model]
     enc_w = W.synth_encoder_weights(cfg, 1234)
     seq_len = 31
     hcfg = C.HeadConfig(in_features=cfg.hidden_size, out_features=n_classes, seq_len=seq_len)
     log = print if verbose else (lambda *a, **k: None)
 
+    def tag_of(p):
+        return f"fp8 plan {p!r}" if isinstance(p, str) else f"precision {p}"
+
     def encode(prec, clips):
-        enc = DinoEncoder.from_weights(cfg, enc_w, "cuda", max_batch=64, max_frame=(hw, hw), precision=prec)
+        kw = {"precision": 2, "fp8_plan": prec} if isinstance(prec, str) else {"precision": prec}
+        enc = DinoEncoder.from_weights(cfg, enc_w, "cuda", max_batch=64, max_frame=(hw, hw), **kw)
         out = [enc.encode_u8(fr, want_f32=False)[0].clone() for fr, _ in clips]
         torch.cuda.synchronize()
         enc.close()
@@ -165,16 +171,16 @@ def study(model="vitb16", hw=224, n_classes=6, epochs=30, train_clips=6, train_l
                "flips_at_margin_over_0.2": int((flips & (margin > 0.2)).sum())}
         # the mode's own contract: its rows are a DIFFERENT encoder's rows (files are stamped '#mx-fp8', a bundle trained on
         # fp16 rows is refused) - a head trained on this mode's rows, evaluated on this mode's held-out rows
-        own = train_head(rows_train_p[p], f"precision {p} rows")
+        own = train_head(rows_train_p[p], f"{tag_of(p)} rows")
         po = np.concatenate([own.infer_clip(r, 1.0).cpu().numpy() for r in rows_test[p]])
         again = np.concatenate([own.infer_clip(r, 1.0).cpu().numpy() for r in encode(p, test)])
         own.close()
         rec["own_head_accuracy"] = float((po.argmax(1) == truth).mean())
         rec["own_head_bit_reproducible"] = bool(np.array_equal(po, again))
         out["plans"][str(p)] = rec
-        log(f"precision {p}: a head trained on THIS mode's rows scores {rec['own_head_accuracy']:.4f} on its held-out rows "
+        log(f"{tag_of(p)}: a head trained on THIS mode's rows scores {rec['own_head_accuracy']:.4f} on its held-out rows "
             f"(fp16 pipeline: {out['fp16_accuracy']:.4f}); encode + classify twice bit-identical: {rec['own_head_bit_reproducible']}")
-        log(f"precision {p}: CLS rel err max {cls_rel:.3e}; accuracy {rec['accuracy']:.4f}; agreement with fp16 {rec['agreement']:.4f} "
+        log(f"{tag_of(p)}: CLS rel err max {cls_rel:.3e}; accuracy {rec['accuracy']:.4f}; agreement with fp16 {rec['agreement']:.4f} "
             f"({rec['flips']} flips, largest fp16 margin at a flip {rec['flip_margin_max']:.3f}); |dp| median {rec['dp_median']:.2e} "
             f"p99 {rec['dp_p99']:.2e} max {rec['dp_max']:.2e}; flips outside the near-tie band: {rec['flips_outside_near_tie_band']}")
     head.close()
@@ -187,10 +193,10 @@ if __name__ == "__main__":
     ap.add_argument("--hw", type=int, default=224)
     ap.add_argument("--epochs", type=int, default=30)
     ap.add_argument("--classes", type=int, default=6)
-    ap.add_argument("--plans", default="2")
+    ap.add_argument("--plans", default="2", help="comma-separated: precisions (2) and / or fp8 plan names (mlp,mlp_qkv,up,down)")
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
-    res = study(a.model, a.hw, a.classes, a.epochs, plans=tuple(int(x) for x in a.plans.split(",")), lr=a.lr)
+    res = study(a.model, a.hw, a.classes, a.epochs, plans=tuple(int(x) if x.isdigit() else x for x in a.plans.split(",")), lr=a.lr)
     if a.json:
         json.dump(res, open(a.json, "w"), indent=1)
