@@ -61,6 +61,9 @@ SIGNATURES = {
     "cbas_enc_check_finite": (c_int, [c_void_p]),
     "cbas_enc_copy_stream": (c_void_p, [c_void_p]),
     "cbas_enc_get_config": (c_int, [c_void_p, C.POINTER(EncConfig)]),
+    "cbas_enc_weights_count_mlp": (c_int64, [C.POINTER(EncConfig), c_int32]),
+    "cbas_enc_create_mlp": (c_int, [C.POINTER(EncConfig), c_int32, c_void_p, c_int64, c_int, C.POINTER(c_void_p)]),
+    "cbas_enc_get_mlp": (c_int, [c_void_p, C.POINTER(c_int32)]),
     "cbas_head_get_config": (c_int, [c_void_p, C.POINTER(HeadConfigC)]),
     "cbas_fused_create": (c_int, [c_void_p, c_void_p, c_int64, c_float, c_int64, C.POINTER(c_void_p)]),
     "cbas_fused_destroy": (None, [c_void_p]),
@@ -123,6 +126,8 @@ DEBUG_SIGNATURES = {
                                    c_void_p]),
     "cbas_debug_gemm_gelu_forms": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cbas_debug_gemm_swiglu": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_float, c_float, c_float, c_void_p]),
     "cbas_debug_mfma_neighbor": (c_int, [c_int, c_void_p]),
     "cbas_debug_gemm_split_bench": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, C.POINTER(c_float)]),
     "cbas_head_debug_read": (c_int, [c_void_p, c_int, c_void_p, c_int64]),
@@ -139,6 +144,7 @@ DEBUG_SIGNATURES = {
 
 ENC_SLOTS = 3
 POS_INTERP_BICUBIC_AA, POS_INTERP_BICUBIC = 0, 1      # CBAS_POS_INTERP_* of include/cbas_mi355x.h
+MLP_GELU, MLP_SWIGLU = 0, 1                           # CBAS_MLP_* of include/cbas_mi355x.h
 EXPECTED_ABI = 11         # CBAS_ABI_VERSION of include/cbas_mi355x.h these ctypes structures mirror
 PROF_CATS = ["patch_gemm", "layernorm", "qkv_gemm", "attention", "oproj_gemm", "up_gemm", "down_gemm", "other"]
 

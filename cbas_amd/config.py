@@ -65,13 +65,21 @@ class ViTConfig:
         D, F, L = self.hidden_size, self.intermediate_size, self.num_hidden_layers
         P, T = self.num_patches(height, width), self.num_tokens(height, width)
         patch = P * self.num_channels * self.patch_size ** 2 * D
-        per_layer = 4 * T * D * D + 2 * T * D * F + 2 * T * T * D
+        mlp = (3 if self.use_gated_mlp else 2) * T * D * F       # gated: gate_proj, up_proj and down_proj
+        per_layer = 4 * T * D * D + mlp + 2 * T * T * D
         return 2.0 * (patch + L * per_layer)
 
     def validate(self) -> None:
         if self.use_gated_mlp:
-            raise NotImplementedError("gated (SwiGLU) MLP variants (S+/H+) are not on the hot path")
-        if self.hidden_act != "gelu":
+            # DINOv3ViTGatedMLP ([tf] modeling_dinov3_vit.py:360-373): down_proj(silu(gate_proj(x)) * up_proj(x)) - ViT-S+ / H+
+            if self.model_type in DINOV2_FAMILIES:
+                raise NotImplementedError("DINOv2 SwiGLU checkpoints (use_swiglu_ffn) are not built: HF's Dinov2SwiGLUFFN keeps gate "
+                                          "and up in one weights_in tensor (another weight layout) and its hidden width "
+                                          "(int(4 D * 2 / 3) rounded up to 8) is not a multiple of 128 at any supported width")
+            if self.hidden_act != "silu":
+                raise NotImplementedError(f"gated MLP with hidden_act={self.hidden_act!r}; the gated (SwiGLU) MLP of DINOv3 "
+                                          "ViT-S+ / H+ is built with 'silu' only")
+        elif self.hidden_act != "gelu":
             raise NotImplementedError(f"hidden_act={self.hidden_act!r}; only exact-erf 'gelu' is implemented")
         if self.head_dim != 64:
             raise NotImplementedError("head_dim must be 64 (all DINOv3 ViT-S/B/L checkpoints)")
@@ -121,6 +129,16 @@ class ViTConfig:
 VIT_S16 = ViTConfig(hidden_size=384, intermediate_size=1536, num_hidden_layers=12, num_attention_heads=6)
 VIT_B16 = ViTConfig(hidden_size=768, intermediate_size=3072, num_hidden_layers=12, num_attention_heads=12)
 VIT_L16 = ViTConfig(hidden_size=1024, intermediate_size=4096, num_hidden_layers=24, num_attention_heads=16)
+# The gated-MLP family (use_gated_mlp, hidden_act "silu"; shapes from the public model cards of
+# facebook/dinov3-vits16plus-pretrain-lvd1689m and facebook/dinov3-vith16plus-pretrain-lvd1689m)
+VIT_S16PLUS = ViTConfig(hidden_size=384, intermediate_size=1536, num_hidden_layers=12, num_attention_heads=6,
+                        use_gated_mlp=True, hidden_act="silu")
+VIT_H16PLUS = ViTConfig(hidden_size=1280, intermediate_size=5120, num_hidden_layers=32, num_attention_heads=20,
+                        use_gated_mlp=True, hidden_act="silu")
+# Tiny gated config (not a published architecture): F = 384 makes the fused gate | up GEMM N = 768 - three 256-column tiles -
+# and gives the down projection K = 384
+VIT_TINY_GATED = ViTConfig(hidden_size=128, intermediate_size=384, num_hidden_layers=2, num_attention_heads=2,
+                           image_size=64, use_gated_mlp=True, hidden_act="silu")
 # Tiny config for fast oracle/kernel parity (not a published architecture).
 VIT_TINY = ViTConfig(hidden_size=128, intermediate_size=512, num_hidden_layers=2, num_attention_heads=2,
                      image_size=64)
@@ -137,6 +155,7 @@ DINOV2_B14 = replace(DINOV2_REG_B14, model_type="dinov2", num_register_tokens=0)
 DINOV2_TINY = replace(DINOV2_REG_TINY, model_type="dinov2", num_register_tokens=0)
 
 NAMED_VIT = {"vits16": VIT_S16, "vitb16": VIT_B16, "vitl16": VIT_L16, "tiny": VIT_TINY,
+             "vits16plus": VIT_S16PLUS, "vith16plus": VIT_H16PLUS, "tiny_gated": VIT_TINY_GATED,
              "dinov2regb14": DINOV2_REG_B14, "dinov2regtiny": DINOV2_REG_TINY,
              "dinov2b14": DINOV2_B14, "dinov2tiny": DINOV2_TINY}
 

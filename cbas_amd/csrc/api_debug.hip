@@ -234,6 +234,9 @@ extern "C" int cbas_debug_gemm_bench(int M, int N, int K, int tile, int iters, f
     // tile >= 100: residual epilogue (o_proj/down_proj style, fp32 in/out) with tile id = tile - 100;
     // tile >= 200: q|k|v epilogue (RoPE tables of 196 patches, 201 tokens per frame, D = N / 3) with tile id = tile - 200
     // + 500: MX-fp8 operands (random e4m3 bytes, unit scales; the GELU form then writes fp8 + scales): timing only
+    // 3000 + tile id: the gated MLP's gate | up epilogue (EPI_SWIGLU: N = 2 F interleaved columns, F columns stored): timing only
+    const bool swiglu = tile >= 3000;
+    if (swiglu) tile -= 3000;
     const bool ln = tile >= 2000;            // 2000 + ...: the LayerNorm-fold form of the epilogue (timing only: zero statistics)
     if (ln) tile -= 2000;
     const bool want_stamps = tile >= 1000;   // 1000 + tile: also print the block timeline statistics
@@ -246,6 +249,7 @@ extern "C" int cbas_debug_gemm_bench(int M, int N, int K, int tile, int iters, f
     if (resid) tile -= 100;
     if (qkv && (N % 3 || (N / 3) % 64)) return cbas_fail(CBAS_EINVAL, "q|k|v bench needs N = 3 D, D a multiple of 64");
     if (M <= 0 || N % 128 || K % 64 || iters <= 0) return cbas_fail(CBAS_EINVAL, "bad GEMM bench shape");
+    if (swiglu && (tile >= 100 || ln)) return cbas_fail(CBAS_EINVAL, "the gated bench form is an fp16 up-projection form of its own");
     const int64_t M_pad = round_up(M, 256);
     f16 *A = nullptr, *Wt = nullptr, *out = nullptr;
     float* bias = nullptr;
@@ -300,7 +304,8 @@ extern "C" int cbas_debug_gemm_bench(int M, int N, int K, int tile, int iters, f
         p.ln_ld = (int)M_pad;
         if (!p.tile) p.tile = GEMM_TILE_PP_AUTO;
     }
-    const GemmEpilogue epi = qkv ? (ln ? EPI_QKV_LN : EPI_QKV) : resid ? (ln ? EPI_RESID_LN : EPI_RESID) : f8 ? EPI_GELU_F8 : (ln ? EPI_GELU_LN : EPI_GELU);
+    if (swiglu) p.ldo = N / 2;
+    const GemmEpilogue epi = swiglu ? EPI_SWIGLU : qkv ? (ln ? EPI_QKV_LN : EPI_QKV) : resid ? (ln ? EPI_RESID_LN : EPI_RESID) : f8 ? EPI_GELU_F8 : (ln ? EPI_GELU_LN : EPI_GELU);
     int rc = launch_gemm(epi, p, 0);
     if (rc) return cbas_fail(CBAS_EINVAL, "launch_gemm failed for tile %d (rc=%d)", tile, rc);
     HIP_TRY(hipDeviceSynchronize());
@@ -542,6 +547,75 @@ extern "C" int cbas_debug_gemm_gelu_forms(int M, int N, int K, int tile, int a_f
         if (W8_host) HIP_TRY(hipMemcpy(W8_host, W8, (int64_t)N * K, hipMemcpyDeviceToHost));
         if (Wsc_host) HIP_TRY(hipMemcpy(Wsc_host, Wsc, (int64_t)N * K / 32, hipMemcpyDeviceToHost));
     }
+    return CBAS_OK;
+}
+
+// ONE gate | up GEMM of a gated MLP (EPI_SWIGLU) on host operands: the harness interleaves W_g / W_u and their biases with the
+// library's own routine (launch_interleave_gate_up), converts / splits them as cbas_enc_create_mlp does, and returns what the
+// launch stored (see the header).
+extern "C" int cbas_debug_gemm_swiglu(int arith, int tile, int forms, int M, int M_alloc, int F, int K, int lda, const float* A_host,
+                                      const float* Wg_host, const float* Wu_host, const float* bg_host, const float* bu_host,
+                                      float a_scale, float w_scale, float out_scale, void* out_host) {
+    if (arith != 0 && arith != 3 && arith != 4) return cbas_fail(CBAS_EINVAL, "arith %d: 0, 3 or 4", arith);
+    if (M <= 0 || M_alloc < M || F <= 0 || F % 64 || K <= 0 || K % 64 || lda < K || lda % 32 || !A_host || !Wg_host || !Wu_host || !bg_host ||
+        !bu_host || !out_host)
+        return cbas_fail(CBAS_EINVAL, "bad gated GEMM test shape / pointers (F %% 64, K %% 64, lda %% 32 must be 0)");
+    if (arith == 4 && !(a_scale > 0.f && w_scale > 0.f && out_scale > 0.f)) return cbas_fail(CBAS_EINVAL, "split operands need positive scales");
+    const size_t na = (size_t)M_alloc * lda, nw = (size_t)F * K, osz = (size_t)M * F * (arith == 0 ? 2 : 4);
+    DevBufs B;
+    float *A32, *Wg, *Wu, *bg, *bu, *Wgu, *bgu;
+    void* out;
+    HIP_TRY(B.alloc(&A32, na * 4));
+    HIP_TRY(B.alloc(&Wg, nw * 4));
+    HIP_TRY(B.alloc(&Wu, nw * 4));
+    HIP_TRY(B.alloc(&bg, (size_t)F * 4));
+    HIP_TRY(B.alloc(&bu, (size_t)F * 4));
+    HIP_TRY(B.alloc(&Wgu, 2 * nw * 4));
+    HIP_TRY(B.alloc(&bgu, 2 * (size_t)F * 4));
+    HIP_TRY(B.alloc(&out, osz));
+    HIP_TRY(hipMemcpy(A32, A_host, na * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(Wg, Wg_host, nw * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(Wu, Wu_host, nw * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(bg, bg_host, (size_t)F * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(bu, bu_host, (size_t)F * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(out, out_host, osz, hipMemcpyHostToDevice));          // the caller's canaries: rows >= M of a tile must not be stored
+    LAUNCH_TRY(launch_interleave_gate_up(Wg, Wu, Wgu, F, K, 0));
+    LAUNCH_TRY(launch_interleave_gate_up(bg, bu, bgu, F, 1, 0));
+    int rcode = 0;
+    if (arith == 0) {
+        f16 *A16, *W16;
+        HIP_TRY(B.alloc(&A16, na * 2));
+        HIP_TRY(B.alloc(&W16, 2 * nw * 2));
+        LAUNCH_TRY(launch_convert_f16(A32, A16, nullptr, (int64_t)na, 0));
+        LAUNCH_TRY(launch_convert_f16(Wgu, W16, nullptr, (int64_t)(2 * nw), 0));
+        GemmParams p{};
+        p.tile = tile; p.A = A16; p.lda = lda; p.W = W16; p.M = M; p.M_pad = M_alloc; p.N = 2 * F; p.K = K; p.bias = bgu;
+        p.out_f16 = (f16*)out; p.ldo = F;
+        rcode = launch_gemm(EPI_SWIGLU, p, 0);
+    } else {
+        const bool split = arith == 4;
+        const float *Ag = A32, *Wq = Wgu;
+        if (split) {
+            float *As, *Ws;
+            HIP_TRY(B.alloc(&As, na * 4));
+            HIP_TRY(B.alloc(&Ws, 2 * nw * 4));
+            LAUNCH_TRY(launch_pack_split_weight(A32, As, M_alloc, lda, a_scale, 0));
+            LAUNCH_TRY(launch_pack_split_weight(Wgu, Ws, 2 * (int64_t)F, K, w_scale, 0));
+            Ag = As; Wq = Ws;
+        }
+        Gemm32VitParams p{};
+        p.A = Ag; p.lda = lda; p.W = Wq; p.M = M; p.N = 2 * F; p.K = K; p.bias = bgu; p.out = (float*)out; p.ldo = F;
+        p.split = split; p.a_scale = split ? a_scale : 1.f; p.w_scale = split ? w_scale : 1.f; p.out_scale = out_scale;
+        if (split) {
+            vit32_split_set_forms(forms);
+            gemm_split_pp_set_tile(tile > 0 ? tile : 0, nullptr);
+        }
+        rcode = launch_gemm_f32_vit(EPI_SWIGLU, p, 0);
+        if (split) { gemm_split_pp_set_tile(0, nullptr); vit32_split_set_forms(-1); }
+    }
+    if (rcode) return cbas_fail(CBAS_EINVAL, "gated GEMM launch failed (arith %d, tile %d, forms %d: rc=%d)", arith, tile, forms, rcode);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out_host, out, osz, hipMemcpyDeviceToHost));
     return CBAS_OK;
 }
 

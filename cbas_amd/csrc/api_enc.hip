@@ -67,6 +67,12 @@ struct cbas_enc {
     cbas_enc_config cfg;
     int device;
     int D, F, L, NH, R, NP;            // NP = prefix tokens
+    // CBAS_MLP_GELU / CBAS_MLP_SWIGLU (cbas_enc_create_mlp).  A gated handle keeps gate_proj | up_proj as ONE weight of 2F rows,
+    // interleaved in blocks of 32 (EPI_SWIGLU, kernels.h): LayerW::wup / wup32 / up_b point at it and the up GEMM runs with N = 2F;
+    // its output, the workspace u16 and the down projection are [rows][F] as for a GELU handle.
+    int mlp = 0;
+    float* gu_bias_all = nullptr;      // gated: [L][2F] interleaved gate | up biases
+    float* gu_scratch = nullptr;       // gated, create only: one layer's interleaved fp32 weight on its way to the fp16 / split copy
     float* blob = nullptr;             // all fp32 parameters on device
     std::vector<LayerW> layers;
     const float *prefix, *patch_b, *norm_w, *norm_b;
@@ -171,13 +177,13 @@ int64_t cnx_weights_count(const cbas_enc_config& c) {
     return n + 2 * prev;
 }
 
-int64_t weights_count(const cbas_enc_config& c) {
+int64_t weights_count(const cbas_enc_config& c, int mlp = CBAS_MLP_GELU) {
     if (c.family == 1) return cnx_weights_count(c);
     const int64_t D = c.hidden_size, F = c.intermediate_size, R = c.num_register_tokens, p = c.patch_size;
     const int64_t G = c.pos_embed_grid;
     int64_t n = D + R * D + (G > 0 ? (1 + G * G) * D : 0) + D * 3 * p * p + D;
     const int64_t per = 2 * D + (D * D + D) + (D * D + D) + (D * D + D) + (D * D + D) + D + 2 * D + (F * D + F) + (D * F + D) + D;
-    n += per * c.num_layers;
+    n += (per + (mlp == CBAS_MLP_SWIGLU ? F * D + F : 0)) * c.num_layers;      // gated: + gate_proj weight and bias
     n += 2 * D;
     return n;
 }
@@ -436,11 +442,12 @@ struct ProfScope {
 // rows, read and written in place in the residual stream with a row stride of T*D.
 int run_last_layer_cls(cbas_enc* h, const LayerW& w, int n, int T, hipStream_t st, bool fold) {
     const int D = h->D, F = h->F, M = n * T, M_pad = (int)round_up(M, 128);
+    const int NU = h->mlp ? 2 * F : F;      // columns of the up GEMM: gate | up interleaved for a gated MLP
     const int64_t cap = round_up(h->cfg.max_batch, 128);
     f16* qc = h->cls16;                     // [n][D] CLS queries (bias added, scaled by 1/8; no RoPE on prefix rows)
     f16* cc = qc + cap * D;                 // [n][D] attention context of the CLS rows
     f16* hc = cc + cap * D;                 // [n][D] LayerNorm 2 of the CLS rows
-    f16* uc = hc + cap * D;                 // [n][F] GELU(up_proj)
+    f16* uc = hc + cap * D;                 // [n][F] GELU(up_proj) / silu(gate_proj) * up_proj
     // precision 2: the k | v projection of all rows follows the plan's q|k|v bit; the CLS tail is fp16 in every plan
     const bool split = h->cfg.precision == 1, f8 = h->cfg.precision == 2 && (h->fp8_plan & CBAS_FP8_PLAN_QKV);
     const int sc_ld = (int)h->rows_cap;
@@ -480,8 +487,8 @@ int run_last_layer_cls(cbas_enc* h, const LayerW& w, int n, int T, hipStream_t s
     { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f16(h->x, (int64_t)T * D, w.ln2_w, w.ln2_b, hc, n, D, h->cfg.layer_norm_eps, st)); }
     GemmParams u{};
     u.A = hc; u.W = w.wup; u.W_lo = split ? w.wup_lo : nullptr;
-    u.M = n; u.M_pad = n; u.N = F; u.K = D; u.bias = w.up_b; u.out_f16 = uc; u.ldo = F;
-    { PROF(CBAS_PROF_UP, 2.0 * n * (double)F * D); LAUNCH_TRY(launch_gemm(EPI_GELU, u, st)); }
+    u.M = n; u.M_pad = n; u.N = NU; u.K = D; u.bias = w.up_b; u.out_f16 = uc; u.ldo = F;
+    { PROF(CBAS_PROF_UP, 2.0 * n * (double)NU * D); LAUNCH_TRY(launch_gemm(h->mlp ? EPI_SWIGLU : EPI_GELU, u, st)); }
     GemmParams d{};
     d.A = uc; d.W = w.wdown; d.W_lo = split ? w.wdown_lo : nullptr;
     d.M = n; d.M_pad = n; d.N = D; d.K = F; d.bias = w.down_b; d.lambda = w.ls2; d.out_f32 = h->x; d.ldo = T * D;
@@ -496,6 +503,8 @@ int run_blocks_f32(cbas_enc* h, int n, int height, int width, float* cls_f32, f1
     const int ps = h->cfg.patch_size;
     const int nh = height / ps, nw = width / ps, P = nh * nw, T = P + h->NP;
     const int D = h->D, F = h->F;
+    const int NU = h->mlp ? 2 * F : F;      // columns of the up GEMM: gate | up interleaved for a gated MLP
+    const GemmEpilogue EU = h->mlp ? EPI_SWIGLU : EPI_GELU;
     const int M = n * T;
     h->last_rows = M;
     int rc = ensure_rope(h, nh, nw);
@@ -507,7 +516,7 @@ int run_blocks_f32(cbas_enc* h, int n, int height, int width, float* cls_f32, f1
     const float eps = h->cfg.layer_norm_eps;
 
     // precision 4: the same schedule with every GEMM's products on the fp16 pipe as three-term splits; operand scales:
-    // LayerNorm rows and pixels as they are, attention context x 16, GELU output x 4 (typical magnitudes ~0.05 / ~0.3:
+    // LayerNorm rows and pixels as they are, attention context x 16, GELU / gated-MLP output x 4 (typical magnitudes ~0.05 / ~0.3:
     // keeps their low halves out of fp16's subnormal range), weights by their per-tensor power of two
     const int split = h->cfg.precision == 4;
     auto sp = [&](Gemm32VitParams& q, float a_scale, float w_scale) { q.split = split; q.a_scale = a_scale; q.w_scale = w_scale; };
@@ -562,8 +571,8 @@ int run_blocks_f32(cbas_enc* h, int n, int height, int width, float* cls_f32, f1
             Gemm32VitParams u{};
             sp(u, 1.f, w.sc_up);
             u.out_scale = 4.f;
-            u.A = hc; u.lda = D; u.W = w.wup32; u.M = n; u.N = F; u.K = D; u.bias = w.up_b; u.out = uc; u.ldo = F;
-            { PROF(CBAS_PROF_UP, 2.0 * n * (double)F * D); LAUNCH_TRY(launch_gemm_f32_vit(EPI_GELU, u, st)); }
+            u.A = hc; u.lda = D; u.W = w.wup32; u.M = n; u.N = NU; u.K = D; u.bias = w.up_b; u.out = uc; u.ldo = F;
+            { PROF(CBAS_PROF_UP, 2.0 * n * (double)NU * D); LAUNCH_TRY(launch_gemm_f32_vit(EU, u, st)); }
             Gemm32VitParams d{};
             sp(d, 4.f, w.sc_down);
             d.A = uc; d.lda = F; d.W = w.wdown32; d.M = n; d.N = D; d.K = F; d.bias = w.down_b; d.lambda = w.ls2; d.out = h->x; d.ldo = (int64_t)T * D;
@@ -590,8 +599,8 @@ int run_blocks_f32(cbas_enc* h, int n, int height, int width, float* cls_f32, f1
         Gemm32VitParams u{};
         sp(u, 1.f, w.sc_up);
         u.out_scale = 4.f;
-        u.A = h32; u.lda = D; u.W = w.wup32; u.M = M; u.N = F; u.K = D; u.bias = w.up_b; u.out = u32; u.ldo = F;
-        { PROF(CBAS_PROF_UP, 2.0 * M * (double)F * D); LAUNCH_TRY(launch_gemm_f32_vit(EPI_GELU, u, st)); }
+        u.A = h32; u.lda = D; u.W = w.wup32; u.M = M; u.N = NU; u.K = D; u.bias = w.up_b; u.out = u32; u.ldo = F;
+        { PROF(CBAS_PROF_UP, 2.0 * M * (double)NU * D); LAUNCH_TRY(launch_gemm_f32_vit(EU, u, st)); }
         if (stop(6)) return CBAS_OK;
         Gemm32VitParams d{};
         sp(d, 4.f, w.sc_down);
@@ -725,8 +734,8 @@ int run_blocks(cbas_enc* h, int n, int height, int width, int patch_k, float in_
         else { u.A = h->h16; u.W = w.wup; u.W_lo = split ? w.wup_lo : nullptr; }
         if (f8_down) { u.out_f8 = u8; u.out_sc = h->sc_u; u.sc_ldo = sc_ld; }
         else u.out_f16 = h->u16;
-        u.M = M; u.M_pad = M_pad; u.N = F; u.K = D; u.bias = w.up_b; u.ldo = F;
-        { PROF(CBAS_PROF_UP, 2.0 * M * (double)F * D); LAUNCH_TRY(launch_gemm(f8_down ? EPI_GELU_F8 : EPI_GELU, u, st)); }
+        u.M = M; u.M_pad = M_pad; u.N = h->mlp ? 2 * F : F; u.K = D; u.bias = w.up_b; u.ldo = F;      // gated: gate | up interleaved
+        { PROF(CBAS_PROF_UP, 2.0 * M * (double)u.N * D); LAUNCH_TRY(launch_gemm(h->mlp ? EPI_SWIGLU : f8_down ? EPI_GELU_F8 : EPI_GELU, u, st)); }
         if (stop(6)) return CBAS_OK;
 
         GemmParams d{};
@@ -845,6 +854,30 @@ int forward_u8(cbas_enc* h, const uint8_t* frames_dev, int n, int height, int wi
 
 extern "C" int64_t cbas_enc_weights_count(const cbas_enc_config* cfg) { return cfg ? weights_count(*cfg) : -1; }
 
+namespace {
+// why a gated MLP cannot be built for this configuration, or nullptr
+const char* mlp_refusal(const cbas_enc_config& c, int mlp) {
+    if (mlp == CBAS_MLP_GELU) return nullptr;
+    if (mlp != CBAS_MLP_SWIGLU) return "mlp must be CBAS_MLP_GELU (0) or CBAS_MLP_SWIGLU (1)";
+    if (c.family != 0) return "a gated MLP (CBAS_MLP_SWIGLU) exists for ViT handles only; ConvNeXt blocks have none";
+    if (c.precision == 2) return "precision 2 (MX-fp8) has no gated-MLP GEMM; a gated handle runs in precision 0, 3 or 4";
+    if (c.precision == 1) return "precision 1 (fp16 hi+lo weights) has no gated-MLP GEMM; a gated handle runs in precision 0, 3 or 4";
+    return nullptr;
+}
+}  // namespace
+
+extern "C" int64_t cbas_enc_weights_count_mlp(const cbas_enc_config* cfg, int32_t mlp) {
+    if (!cfg) return -1;
+    if (const char* why = mlp_refusal(*cfg, mlp)) { cbas_fail(CBAS_EINVAL, "%s", why); return -1; }
+    return weights_count(*cfg, mlp);
+}
+
+extern "C" int cbas_enc_get_mlp(const cbas_enc* h, int32_t* mlp) {
+    if (!h || !mlp) return cbas_fail(CBAS_EINVAL, "null argument");
+    *mlp = h->mlp;
+    return CBAS_OK;
+}
+
 extern "C" void cbas_enc_destroy(cbas_enc* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
@@ -875,7 +908,7 @@ extern "C" void cbas_enc_destroy(cbas_enc* h) {
     for (auto& t : h->pos_tables) { if (t.cos) (void)hipFree(t.cos); if (t.sin) (void)hipFree(t.sin); if (t.fac) (void)hipFree(t.fac); if (t.pos) (void)hipFree(t.pos); }
     void* bufs[] = {h->blob, h->w16, h->w16_lo, h->qkv_bias_all, h->prefix_dev,
                     h->A_patch, h->h16, h->qkv16, h->u16, h->x, h->cls16, h->w8, h->w8_sc, h->sc_h, h->sc_u,
-                    h->w16_fold, h->fold_vec, h->x16, h->lnst, h->w32, h->cnx_arena};
+                    h->w16_fold, h->fold_vec, h->x16, h->lnst, h->w32, h->cnx_arena, h->gu_bias_all, h->gu_scratch};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (h->compute) (void)hipStreamDestroy(h->compute);
@@ -1066,9 +1099,15 @@ int cnx_build(cbas_enc* h, const float* wh) {
 
 extern "C" int cbas_enc_create(const cbas_enc_config* cfg, const float* weights_host, int64_t n_weights,
                                int device_id, cbas_enc** out) {
+    return cbas_enc_create_mlp(cfg, CBAS_MLP_GELU, weights_host, n_weights, device_id, out);
+}
+
+extern "C" int cbas_enc_create_mlp(const cbas_enc_config* cfg, int32_t mlp, const float* weights_host, int64_t n_weights,
+                                   int device_id, cbas_enc** out) {
     if (!cfg || !weights_host || !out) return cbas_fail(CBAS_EINVAL, "null argument");
     *out = nullptr;
     const cbas_enc_config& c = *cfg;
+    if (const char* why = mlp_refusal(c, mlp)) return cbas_fail(CBAS_EINVAL, "%s", why);
     if (c.family == 1) {
         int rc = cnx_check_config(c);
         if (rc) return rc;
@@ -1103,7 +1142,7 @@ extern "C" int cbas_enc_create(const cbas_enc_config* cfg, const float* weights_
                          c.hidden_size, c.num_heads);
     if (c.intermediate_size <= 0 || c.intermediate_size % 128)
         return cbas_fail(CBAS_EINVAL, "intermediate_size=%d must be a multiple of 128", c.intermediate_size);
-    if (c.hidden_size > 1024) return cbas_fail(CBAS_EINVAL, "hidden_size > 1024 not supported");
+    if (c.hidden_size > 1280) return cbas_fail(CBAS_EINVAL, "hidden_size > 1280 not supported");
     if (c.patch_size != 16 && c.patch_size != 14) return cbas_fail(CBAS_EINVAL, "patch_size must be 14 or 16");
     if (c.precision < 0 || c.precision > 4)
         return cbas_fail(CBAS_EINVAL, "precision=%d: 0 (fp16), 1 (fp16 hi+lo weights), 2 (MX-fp8), 3 (fp32, the reference's CPU arithmetic) "
@@ -1111,18 +1150,20 @@ extern "C" int cbas_enc_create(const cbas_enc_config* cfg, const float* weights_
     if (c.precision == 2 && (c.hidden_size % 256 || c.intermediate_size % 256))
         return cbas_fail(CBAS_EINVAL, "precision 2 (MX-fp8) needs hidden_size and intermediate_size to be multiples of 256 "
                                       "(K-tiles of 128 consumed in pairs); got %d / %d", c.hidden_size, c.intermediate_size);
+    if (c.precision == 2 && c.hidden_size > 1024)
+        return cbas_fail(CBAS_EINVAL, "precision 2 (MX-fp8) stops at hidden_size 1024 (its LayerNorm has no wider form); got %d", c.hidden_size);
     if ((c.use_rope != 0) == (c.pos_embed_grid > 0))
         return cbas_fail(CBAS_EINVAL, "exactly one of use_rope / pos_embed_grid must be set");
     if (c.num_layers <= 0 || c.num_register_tokens < 0 || c.max_batch <= 0 || c.max_height < c.patch_size || c.max_width < c.patch_size)
         return cbas_fail(CBAS_EINVAL, "bad layer/register/batch/frame-size field");
-    if (n_weights != weights_count(c))
+    if (n_weights != weights_count(c, mlp))
         return cbas_fail(CBAS_EINVAL, "weights blob has %lld floats, config needs %lld", (long long)n_weights,
-                         (long long)weights_count(c));
+                         (long long)weights_count(c, mlp));
     HIP_TRY(hipSetDevice(device_id));
 
     cbas_enc* h = new (std::nothrow) cbas_enc();
     if (!h) return cbas_fail(CBAS_ENOMEM, "out of host memory");
-    h->cfg = c; h->device = device_id;
+    h->cfg = c; h->device = device_id; h->mlp = mlp;
     h->D = c.hidden_size; h->F = c.intermediate_size; h->L = c.num_layers; h->NH = c.num_heads;
     h->R = c.num_register_tokens; h->NP = 1 + h->R;
     const int64_t D = h->D, F = h->F;
@@ -1143,18 +1184,21 @@ extern "C" int cbas_enc_create(const cbas_enc_config* cfg, const float* weights_
     CREATE_TRY(hipMalloc(&h->blob, n_weights * sizeof(float)));
     CREATE_TRY(hipMemcpy(h->blob, weights_host, n_weights * sizeof(float), hipMemcpyHostToDevice));
 
-    // fp16 weight arena: patch (D*256 + D*512) + per layer (3DD + DD + FD + DF)
-    const int64_t n16 = D * 256 + D * 512 + (int64_t)h->L * (4 * D * D + 2 * F * D);
+    // fp16 weight arena: patch (D*256 + D*512) + per layer (3DD + DD + FD + DF); a gated MLP's gate | up weight is 2FD
+    const bool gated = mlp == CBAS_MLP_SWIGLU;
+    const int64_t FU = gated ? 2 * F : F;      // rows of the up GEMM's weight
+    const int64_t n16 = D * 256 + D * 512 + (int64_t)h->L * (4 * D * D + FU * D + F * D);
     const bool p3 = c.precision >= 3;         // fp32 end to end (3: fp32 MFMA; 4: three-term fp16 split of the same operands): no fp16 copies, every workspace 4 bytes per element
     if (!p3) CREATE_TRY(hipMalloc(&h->w16, n16 * sizeof(f16)));
     if (c.precision == 1) CREATE_TRY(hipMalloc(&h->w16_lo, n16 * sizeof(f16)));
     float* w32p = nullptr;
     if (c.precision == 4) {
         // every weight once more in the split hi | lo format (same byte size as fp32) + a scratch patch weight
-        CREATE_TRY(hipMalloc(&h->w32, (2 * D * 256 + (int64_t)h->L * (4 * D * D + 2 * F * D)) * sizeof(float)));
+        CREATE_TRY(hipMalloc(&h->w32, (2 * D * 256 + (int64_t)h->L * (4 * D * D + FU * D + F * D)) * sizeof(float)));
         w32p = h->w32;
     } else if (p3) {
-        CREATE_TRY(hipMalloc(&h->w32, (D * 256 + (int64_t)h->L * 3 * D * D) * sizeof(float)));
+        // (gated: + the interleaved gate | up weight of every layer, which precision 3 reads as it is)
+        CREATE_TRY(hipMalloc(&h->w32, (D * 256 + (int64_t)h->L * (3 * D * D + (gated ? FU * D : 0))) * sizeof(float)));
         w32p = h->w32;
     }
     uint8_t* w8p = nullptr;
@@ -1172,8 +1216,14 @@ extern "C" int cbas_enc_create(const cbas_enc_config* cfg, const float* weights_
     // NON-BLOCKING stream (every stream of this library) touches the buffer - found by running training beside the encoder (r5)
     CREATE_TRY(hipMemsetAsync(h->qkv_bias_all, 0, (int64_t)h->L * 3 * D * sizeof(float), h->compute));
 
-    // LayerNorm fold: folded copies of the q|k|v and up_proj weights (+ column sums and biases), fp16 path only
-    h->fold_ok = c.precision == 0 && D % 256 == 0 && D <= 1024 && F % 256 == 0;
+    if (gated) {
+        CREATE_TRY(hipMalloc(&h->gu_bias_all, (int64_t)h->L * FU * sizeof(float)));
+        if (c.precision != 3) CREATE_TRY(hipMalloc(&h->gu_scratch, FU * D * sizeof(float)));
+    }
+
+    // LayerNorm fold: folded copies of the q|k|v and up_proj weights (+ column sums and biases), fp16 path only; not for a
+    // gated MLP (no folded EPI_SWIGLU) or D > 1024 (the statistics are pooled over at most four 256-column blocks)
+    h->fold_ok = c.precision == 0 && !gated && D % 256 == 0 && D <= 1024 && F % 256 == 0;
     f16* wf = nullptr;
     float* fv = nullptr;
     if (h->fold_ok) {
@@ -1261,6 +1311,8 @@ extern "C" int cbas_enc_create(const cbas_enc_config* cfg, const float* weights_
         lw.ls1 = p; p += D;
         lw.ln2_w = p; p += D;
         lw.ln2_b = p; p += D;
+        const float *gw = nullptr, *gb = nullptr;      // gated: gate_proj sits immediately before up_proj
+        if (gated) { gw = p; p += F * D; gb = p; p += F; }
         const float* uw = p; p += F * D;
         lw.up_b = p; p += F;
         const float* dw = p; p += D * F;
@@ -1268,13 +1320,13 @@ extern "C" int cbas_enc_create(const cbas_enc_config* cfg, const float* weights_
         lw.ls2 = p; p += D;
         lw.wqkv = w; w += 3 * D * D;
         lw.wo = w; w += D * D;
-        lw.wup = w; w += F * D;
+        lw.wup = w; w += FU * D;
         lw.wdown = w; w += D * F;
         lw.wqkv_lo = lo(lw.wqkv); lw.wo_lo = lo(lw.wo); lw.wup_lo = lo(lw.wup); lw.wdown_lo = lo(lw.wdown);
         if (c.precision == 4) {
             lw.sc_qkv = pow2_scale(std::max(host_max(qw, D * D), std::max(host_max(kw, D * D), host_max(vw, D * D))));
             lw.sc_o = pow2_scale(host_max(ow, D * D));
-            lw.sc_up = pow2_scale(host_max(uw, F * D));
+            lw.sc_up = pow2_scale(gated ? std::max(host_max(gw, F * D), host_max(uw, F * D)) : host_max(uw, F * D));
             lw.sc_down = pow2_scale(host_max(dw, D * F));
         }
         if (c.precision == 4) {
@@ -1284,8 +1336,9 @@ extern "C" int cbas_enc_create(const cbas_enc_config* cfg, const float* weights_
             lw.wqkv32 = w32p; w32p += 3 * D * D;
             rc |= launch_pack_split_weight(ow, w32p, D, (int)D, lw.sc_o, st);
             lw.wo32 = w32p; w32p += D * D;
-            rc |= launch_pack_split_weight(uw, w32p, F, (int)D, lw.sc_up, st);
-            lw.wup32 = w32p; w32p += F * D;
+            if (gated) rc |= launch_interleave_gate_up(gw, uw, h->gu_scratch, F, (int)D, st);      // same stream: the scratch is reused per layer
+            rc |= launch_pack_split_weight(gated ? h->gu_scratch : uw, w32p, FU, (int)D, lw.sc_up, st);
+            lw.wup32 = w32p; w32p += FU * D;
             rc |= launch_pack_split_weight(dw, w32p, D, (int)F, lw.sc_down, st);
             lw.wdown32 = w32p; w32p += D * F;
         } else if (p3) {
@@ -1295,12 +1348,17 @@ extern "C" int cbas_enc_create(const cbas_enc_config* cfg, const float* weights_
             CREATE_TRY(hipMemcpyAsync(w32p + 2 * D * D, vw, D * D * sizeof(float), hipMemcpyDeviceToDevice, st));
             lw.wqkv32 = w32p; w32p += 3 * D * D;
             lw.wo32 = ow; lw.wup32 = uw; lw.wdown32 = dw;
+            if (gated) {
+                rc |= launch_interleave_gate_up(gw, uw, w32p, F, (int)D, st);
+                lw.wup32 = w32p; w32p += FU * D;
+            }
         } else {
             rc |= launch_convert_f16(qw, lw.wqkv, lw.wqkv_lo, D * D, st);
             rc |= launch_convert_f16(kw, lw.wqkv + D * D, lw.wqkv_lo ? lw.wqkv_lo + D * D : nullptr, D * D, st);
             rc |= launch_convert_f16(vw, lw.wqkv + 2 * D * D, lw.wqkv_lo ? lw.wqkv_lo + 2 * D * D : nullptr, D * D, st);
             rc |= launch_convert_f16(ow, lw.wo, lw.wo_lo, D * D, st);
-            rc |= launch_convert_f16(uw, lw.wup, lw.wup_lo, F * D, st);
+            if (gated) rc |= launch_interleave_gate_up(gw, uw, h->gu_scratch, F, (int)D, st);      // same stream: the scratch is reused per layer
+            rc |= launch_convert_f16(gated ? h->gu_scratch : uw, lw.wup, lw.wup_lo, FU * D, st);
             rc |= launch_convert_f16(dw, lw.wdown, lw.wdown_lo, D * F, st);
         }
         if (c.precision == 2) {
@@ -1326,6 +1384,11 @@ extern "C" int cbas_enc_create(const cbas_enc_config* cfg, const float* weights_
             rc |= launch_fold_ln_weight(kw, lw.ln1_w, lw.ln1_b, kb, lw.wqkv_f + D * D, lw.qkv_cs + D, lw.qkv_bf + D, (int)D, (int)D, st);
             rc |= launch_fold_ln_weight(vw, lw.ln1_w, lw.ln1_b, vb, lw.wqkv_f + 2 * D * D, lw.qkv_cs + 2 * D, lw.qkv_bf + 2 * D, (int)D, (int)D, st);
             rc |= launch_fold_ln_weight(uw, lw.ln2_w, lw.ln2_b, lw.up_b, lw.wup_f, lw.up_cs, lw.up_bf, (int)F, (int)D, st);
+        }
+        if (gated) {
+            float* gub = h->gu_bias_all + (int64_t)l * FU;
+            rc |= launch_interleave_gate_up(gb, lw.up_b, gub, F, 1, st);
+            lw.up_b = gub;
         }
         CREATE_TRY(hipMemcpyAsync(lw.qkv_b, qb, D * sizeof(float), hipMemcpyDeviceToDevice, st));
         CREATE_TRY(hipMemcpyAsync(lw.qkv_b + D, kb, D * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -1420,6 +1483,7 @@ extern "C" int cbas_enc_create(const cbas_enc_config* cfg, const float* weights_
         return rc;
     }
     CREATE_TRY(hipStreamSynchronize(st));
+    if (h->gu_scratch) { (void)hipFree(h->gu_scratch); h->gu_scratch = nullptr; }
 #undef CREATE_TRY
     *out = h;
     return CBAS_OK;
@@ -1755,7 +1819,7 @@ extern "C" int cbas_enc_check_finite(cbas_enc* h) {
     HIP_TRY(hipStreamSynchronize(h->aux));
     return cbas_fail(CBAS_ERANGE, "%u frame(s) produced a non-finite CLS row: an activation left the range of precision %d%s",
                      n, h->cfg.precision,
-                     h->cfg.precision == 4 ? " (operands are split into fp16 halves after power-of-two scaling: |GELU output| < 16 376, "
+                     h->cfg.precision == 4 ? " (operands are split into fp16 halves after power-of-two scaling: |GELU / gated-MLP output| < 16 376, "
                                              "|k|, |v| < 16 376, ... - include/cbas_mi355x.h); precision 3 (CBAS_PRECISION=3) computes "
                                              "the same rows in fp32 without a range limit"
                                            : h->cfg.precision == 3 ? "" : " (fp16 activations: |value| < 65 504); precisions 3 / 4 keep them in fp32");

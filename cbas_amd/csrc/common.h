@@ -158,6 +158,19 @@ static __device__ __forceinline__ f32x4 gelu_fast4(f32x4 x) {
     return r - a * (poly * t * e);
 }
 
+// silu(g) * u for the fp16 encoder path's gated MLP ([tf]:360-373), four values at once: silu(g) = g / (1 + exp(-g)) on
+// v_exp_f32 / v_rcp_f32.  exp2's argument -g log2(e) is rounded once, so exp(-g) carries a relative error of about
+// |g| 2^-24 (2^-19.5 at |g| = 20, where silu itself is below 5e-8 or within 2e-9 of g); v_rcp_f32 adds one ulp: three
+// orders below the fp16 rounding applied to the result.  Finite g never gives a NaN: g -> -inf makes exp(-g) = +inf,
+// rcp = 0 and the product -0; g -> +inf makes exp(-g) = 0 and the product g.
+static __device__ __forceinline__ f32x4 swiglu_fast4(f32x4 g, f32x4 u) {
+    const f32x4 a = g * -1.44269504088896341f;
+    const f32x4 e = {__builtin_amdgcn_exp2f(a[0]), __builtin_amdgcn_exp2f(a[1]), __builtin_amdgcn_exp2f(a[2]), __builtin_amdgcn_exp2f(a[3])};
+    const f32x4 d = e + 1.0f;
+    const f32x4 r = {__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1]), __builtin_amdgcn_rcpf(d[2]), __builtin_amdgcn_rcpf(d[3])};
+    return (g * r) * u;
+}
+
 // ---- MX-fp8 (OCP e4m3 elements, E8M0 scale per 32-element block) -------------------------------------------------
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));

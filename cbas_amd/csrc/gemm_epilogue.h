@@ -3,7 +3,7 @@
 // accumulator tiles that make up a 64-column group (= one attention head for the QKV projection):
 //     v[j][e]  <->  C[m][head_col0 + j*16 + (lane>>4)*4 + e],   j = 0..3, e = 0..3
 // Reference arithmetic: bias adds of nn.Linear, RoPE [tf]:238-268 (rotate_half :203-207),
-// LayerScale :342-343 + residual :432-443, exact-erf GELU :356, conv bias / token scatter :82-89.
+// LayerScale :342-343 + residual :432-443, exact-erf GELU :356, gated MLP :360-373, conv bias / token scatter :82-89.
 #pragma once
 #include "kernels.h"
 
@@ -101,6 +101,15 @@ __device__ __forceinline__ void gemm_epilogue_row(const GemmParams& p, int m, in
             float* xp = p.out_f32 + (size_t)m * p.ldo + n;
             const f32x4 xv = *reinterpret_cast<const f32x4*>(xp);
             *reinterpret_cast<f32x4*>(xp) = (acc[j] + bv) * lv + xv;
+        }
+    } else if (EPI == EPI_SWIGLU) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int n = ncol + j * 16;
+            const f32x4 gv = swiglu_fast4(acc[j] + *reinterpret_cast<const f32x4*>(p.bias + n),
+                                          acc[j + 2] + *reinterpret_cast<const f32x4*>(p.bias + n + 32));
+            const f16x4 hv = {(f16)gv[0], (f16)gv[1], (f16)gv[2], (f16)gv[3]};
+            *reinterpret_cast<f16x4*>(p.out_f16 + (size_t)m * p.ldo + (head_col0 >> 1) + (lane >> 4) * 4 + j * 16) = hv;
         }
     } else {  // EPI_GELU
 #pragma unroll
@@ -276,6 +285,33 @@ __device__ __forceinline__ void gemm_epilogue_tile(const GemmParams& p, int row_
                 const int m = row_base + half * 64 + r;
                 if (m < p.M) *reinterpret_cast<uint4*>(p.out_f8 + (size_t)m * p.ldo + head_col0 + c * 16) = q;
             }
+            asm volatile("" ::: "memory");
+        }
+    } else if (EPI == EPI_SWIGLU) {
+        // gated MLP: columns j = 0, 1 of the group are 32 gate columns, j = 2, 3 the up columns of the same outputs (the weight
+        // rows are interleaved that way at create), so silu(g) * u is formed in-lane, the pairing RoPE uses.  The 32 output
+        // columns of a row are 64 bytes: one 16-row slab = 1 KiB of scratch (two regions, alternating), left as 16-byte pieces
+        // of whole 64-byte row segments.
+        f32x4 bv[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) bv[j] = *reinterpret_cast<const f32x4*>(p.bias + head_col0 + j * 16 + g * 4);
+        pre();
+        f16* const obase = p.out_f16 + (head_col0 >> 1);
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            char* const sc = scratch + (i & 1) * 1024;
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const f32x4 hv4 = swiglu_fast4(acc[i][j] + bv[j], acc[i][j + 2] + bv[j + 2]);
+                const f16x4 hv = {(f16)hv4[0], (f16)hv4[1], (f16)hv4[2], (f16)hv4[3]};
+                const int c = 2 * j + (g >> 1);                         // 16-byte chunk of the row, swizzled by row pair
+                *reinterpret_cast<f16x4*>(sc + li * 64 + ((c ^ ((li >> 1) & 3)) << 4) + (g & 1) * 8) = hv;
+            }
+            asm volatile("" ::: "memory");
+            const int r = lane >> 2, c = lane & 3;                      // 16 rows x 64 bytes per wave store
+            const f16x8 hv = *reinterpret_cast<const f16x8*>(sc + r * 64 + ((c ^ ((r >> 1) & 3)) << 4));
+            const int m = row_base + i * 16 + r;
+            if (m < p.M) __builtin_nontemporal_store(hv, reinterpret_cast<f16x8*>(obase + (size_t)m * p.ldo + c * 8));
             asm volatile("" ::: "memory");
         }
     } else {                                     // EPI_QKV / EPI_GELU: fp16 out, whole 64x(TM*16) tile at once

@@ -1,7 +1,7 @@
 // fp16 MFMA GEMM for the ViT projections on gfx950 (MI355X).
 //
 //   C[M,N] = A[M,K] * W[N,K]^T,  A/W fp16 row-major (K contiguous), fp32 accumulate,
-//   epilogue fused per GemmEpilogue (bias, RoPE, LayerScale+residual, exact GELU).
+//   epilogue fused per GemmEpilogue (bias, RoPE, LayerScale+residual, exact GELU, gated silu).
 //
 // Structure (v1): 128x128x64 tile per 256-thread workgroup (2x2 waves, each 64x64 = 4x4 MFMA
 // 16x16x32 tiles), both operands staged global->LDS with 16-byte LDS-DMA (global_load_lds), two
@@ -222,6 +222,7 @@ static int dispatch_gemm(GemmEpilogue epi, const GemmParams& p, int tile, hipStr
         case EPI_QKV:   return launch_epi<EPI_QKV>(p, tile, stream);
         case EPI_RESID: return launch_epi<EPI_RESID>(p, tile, stream);
         case EPI_GELU:  return launch_epi<EPI_GELU>(p, tile, stream);
+        case EPI_SWIGLU: return p.W_lo ? -1 : launch_epi<EPI_SWIGLU>(p, tile, stream);
     }
     return -1;
 }

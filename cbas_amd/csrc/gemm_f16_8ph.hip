@@ -710,6 +710,7 @@ int launch_gemm_split_pp(GemmEpilogue epi, const Gemm32VitParams& sp_in, hipStre
         case EPI_QKV:   return launch_split_pp_epi<EPI_QKV>(p, sp, stream);
         case EPI_RESID: return launch_split_pp_epi<EPI_RESID>(p, sp, stream);
         case EPI_GELU:  return launch_split_pp_epi<EPI_GELU>(p, sp, stream);
+        case EPI_SWIGLU: return launch_split_pp_epi<EPI_SWIGLU>(p, sp, stream);
         default: return -1;
     }
 }
@@ -738,6 +739,7 @@ int launch_gemm_8ph(GemmEpilogue epi, const GemmParams& p_in, int tile, hipStrea
         case EPI_QKV:   return launch_8ph_epi<EPI_QKV, false>(p, tile, stream);
         case EPI_RESID: return launch_8ph_epi<EPI_RESID, false>(p, tile, stream);
         case EPI_GELU:  return launch_8ph_epi<EPI_GELU, false>(p, tile, stream);
+        case EPI_SWIGLU: return launch_8ph_epi<EPI_SWIGLU, false>(p, tile, stream);
         // LayerNorm fold (fp16 only): the statistics are pooled over N tiles of 256 columns, at most four of them
         case EPI_QKV_LN:   return p.ln_in && p.ln_colsum && p.ln_parts >= 1 && p.ln_parts <= 4 && p.K == p.ln_parts * 256
                                   ? launch_8ph_epi<EPI_QKV_LN, false>(p, tile, stream) : -1;

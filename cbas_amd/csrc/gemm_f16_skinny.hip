@@ -104,6 +104,7 @@ int launch_gemm_skinny(GemmEpilogue epi, const GemmParams& p, hipStream_t stream
         case EPI_QKV:   return launch_skinny<EPI_QKV>(p, stream);
         case EPI_RESID: return launch_skinny<EPI_RESID>(p, stream);
         case EPI_GELU:  return launch_skinny<EPI_GELU>(p, stream);
+        case EPI_SWIGLU: return launch_skinny<EPI_SWIGLU>(p, stream);
         default: return -1;
     }
 }

@@ -19,6 +19,11 @@ enum GemmEpilogue {
     // fp8 plans (gemm_f16_8ph.hip only): what EPI_GELU_F8 becomes on fp16 operands - the GELU value is rounded to fp16 first, so
     // the bytes and scales are the quantisation of exactly what EPI_GELU would have stored (callers pass EPI_GELU_F8)
     EPI_GELU_F8_H = 8,
+    // gated MLP (DINOv3 S+ / H+, [tf]:360-373): W = gate | up interleaved in blocks of 32 rows (launch_interleave_gate_up), N = 2F;
+    // a 64-column group holds 32 gate columns, then the up columns of the same 32 outputs, and writes 32 output columns:
+    //   h[m][n / 2 + c] = silu(acc[n + c] + bias[n + c]) * (acc[n + 32 + c] + bias[n + 32 + c]),  n % 64 == 0, c < 32
+    // in the format EPI_GELU writes (fp16; fp32; the split image with out_scale), leading dimension ldo >= N / 2
+    EPI_SWIGLU = 9,
 };
 constexpr int epi_base(int epi) {
     return epi == EPI_QKV_LN ? EPI_QKV : epi == EPI_GELU_LN ? EPI_GELU : epi == EPI_RESID_LN ? EPI_RESID : epi == EPI_GELU_F8_H ? EPI_GELU_F8 : epi;
@@ -61,7 +66,7 @@ struct GemmParams {
     const float* bias;   // [N]
     const float* lambda; // [N]   (EPI_RESID)
     float* out_f32;      // EPI_PATCH / EPI_RESID: residual stream x, leading dim ldo
-    f16* out_f16;        // EPI_QKV / EPI_GELU
+    f16* out_f16;        // EPI_QKV / EPI_GELU / EPI_SWIGLU
     int ldo;
     // EPI_PATCH
     int patches_per_frame;   // P
@@ -139,6 +144,9 @@ int launch_final_norm_cls(const float* x, const float* gamma, const float* beta,
 int launch_attention(const f16* qkv, const f16* q_cls, void* out, uint32_t* out_sc, int sc_ld, int n, int T, int D,
                      int n_heads, hipStream_t stream);
 
+// gated MLP, create time: out [2F][K] = rows of gate [F][K] and up [F][K] interleaved in blocks of 32 - out rows [64 b, 64 b + 32)
+// are gate rows [32 b, 32 b + 32), out rows [64 b + 32, 64 b + 64) the up rows of the same outputs (K = 1: the biases); F % 32 == 0
+int launch_interleave_gate_up(const float* gate, const float* up, float* out, int64_t F, int K, hipStream_t stream);
 // fp32 -> fp16 weight conversion (optionally also the fp16 residual), n elements
 int launch_convert_f16(const float* src, f16* hi, f16* lo, int64_t n, hipStream_t stream);
 // patch weight (D,3,16,16) fp32 -> sum over the 3 identical input channels -> (D,256) fp16 hi (+lo),
@@ -158,7 +166,7 @@ struct Gemm32VitParams {
     int M, N, K;                   // N % 128 == 0, K % 32 == 0
     const float* bias;             // [N]
     const float* lambda;           // [N]   (EPI_RESID)
-    float* out; int64_t ldo;       // EPI_PATCH / EPI_RESID: the residual stream x; EPI_QKV / EPI_GELU: qkv / u
+    float* out; int64_t ldo;       // EPI_PATCH / EPI_RESID: the residual stream x; EPI_QKV / EPI_GELU / EPI_SWIGLU: qkv / u
     // EPI_PATCH
     int patches_per_frame, tokens_per_frame, n_prefix;
     const float* pos;              // DINOv2 position embedding [P][N], or nullptr
@@ -172,9 +180,9 @@ struct Gemm32VitParams {
     // precision 4: the same fp32 operands, products on the fp16 matrix pipe as a three-term split (vit_f32.hip).
     // a_scale / w_scale: powers of two the operands are multiplied by before the split (keeps the low halves out of
     // fp16's subnormal range); the accumulators are multiplied by 1 / (a_scale * w_scale) - all exact.
-    int split;                     // A and W are in the split format (vit_f32.hip); EPI_GELU then writes its output split too
+    int split;                     // A and W are in the split format (vit_f32.hip); EPI_GELU / EPI_SWIGLU then write their output split too
     float a_scale, w_scale;        // the scales A and W were split with
-    float out_scale;               // EPI_GELU with split: scale of the split output (the down projection's a_scale)
+    float out_scale;               // EPI_GELU / EPI_SWIGLU with split: scale of the split output (the down projection's a_scale)
 };
 int launch_gemm_f32_vit(GemmEpilogue epi, const Gemm32VitParams& p, hipStream_t stream);
 // precision 4, M > 256, N % 256 == 0: the ping-pong kernel's split-operand form (gemm_f16_8ph.hip); -1 = not its shape

@@ -101,6 +101,17 @@ __device__ __forceinline__ f32x4 gelu_erf4(f32x4 x) {
     return (0.5f * x) * (1.0f + erf4(z));
 }
 
+// gated MLP ([tf]:360-373: down_proj(act_fn(gate_proj(x)) * up_proj(x)), act_fn = silu): torch's CPU silu x / (1 + exp(-x))
+// and the product as separately rounded fp32 steps; expf from the device library (accurate form).  No NaN from finite
+// operands: exp(-g) = +inf for g -> -inf gives g / inf = -0, exp(-g) = 0 for g -> +inf gives g.
+__device__ __forceinline__ f32x4 swiglu4(f32x4 g, f32x4 u) {
+#pragma clang fp contract(off)
+    const f32x4 e = {expf(-g[0]), expf(-g[1]), expf(-g[2]), expf(-g[3])};
+    const f32x4 d = 1.0f + e;
+    const f32x4 s = g / d;
+    return s * u;
+}
+
 // hi / lo halves of four values (x scale): x ~ hi + lo to 22 bits
 __device__ __forceinline__ void split4(f32x4 v, float scale, f16x4v& hi, f16x4v& lo) {
 #pragma unroll
@@ -170,6 +181,18 @@ __device__ __forceinline__ void vit32_epilogue_row(const Gemm32VitParams& p, int
             const f32x4 hsc = (acc[j] + bv) * lv;       // layer_scale(linear(.)), rounded as its own op
             *reinterpret_cast<f32x4*>(xp) = hsc + xv;   // + residual
         }
+    } else if (EPI == EPI_SWIGLU) {
+        // columns j = 0, 1 of the group: 32 gate columns; j = 2, 3: the up columns of the same outputs (kernels.h).  The 32 output
+        // columns are one K-tile of the down projection's split image.
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const f32x4 gg = acc[j] + *reinterpret_cast<const f32x4*>(p.bias + ncol + j * 16);
+            const f32x4 uu = acc[j + 2] + *reinterpret_cast<const f32x4*>(p.bias + ncol + 32 + j * 16);
+            const f32x4 hv = swiglu4(gg, uu);
+            const int n = (head_col0 >> 1) + (lane >> 4) * 4 + j * 16;
+            if (p.split) store_split4(p.out + (int64_t)m * p.ldo, n, hv, p.out_scale);      // the down projection's A operand
+            else *reinterpret_cast<f32x4*>(p.out + (int64_t)m * p.ldo + n) = hv;
+        }
     } else {  // EPI_GELU
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -191,6 +214,7 @@ __device__ __forceinline__ void vit32_epilogue_row(const Gemm32VitParams& p, int
 //   EPI_RESID  fp32 x read / written in 256-byte row segments, rows prefetched two slabs ahead
 //   EPI_GELU   the split image of 64 columns = two K-tiles of the down projection = 256 contiguous bytes per row
 //   EPI_QKV    one head of q, k or v = [hi 128 B | lo 128 B] = 256 contiguous bytes per row
+//   EPI_SWIGLU the split image of the 32 output columns = one K-tile of the down projection = 128 contiguous bytes per row
 // `pre` is called once after the first global loads are issued (the persistent kernel's next-tile LDS-DMA).
 // ---------------------------------------------------------------------------------------------------------------------
 template <int EPI, int TM, typename Pre>
@@ -253,6 +277,34 @@ __device__ __forceinline__ void vit32_epilogue_tile(const Gemm32VitParams& p, in
     f32x4 bv[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) bv[j] = *reinterpret_cast<const f32x4*>(p.bias + head_col0 + j * 16 + g * 4);
+    if (EPI == EPI_SWIGLU) {
+        // 32 output columns = ONE K-tile of the down projection = 128 contiguous bytes per row [hi 64 B | lo 64 B]: lane group g
+        // holds k = 4 g + e (j = 0) and 16 + 4 g + e (j = 1), i.e. chunk g of the hi half and chunk 4 + g of the lo half.
+        // A 16-row slab is 2 KiB of scratch (two regions, alternating) and leaves as 8 rows x 128 bytes per wave store.
+        pre();
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            char* sc = scratch + (i & 1) * 2048;
+            f16x4v hi[2], lo[2];
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                split4(swiglu4(acc[i][j] * unscale + bv[j], acc[i][j + 2] * unscale + bv[j + 2]), p.out_scale, hi[j], lo[j]);
+            const f16x8 h8 = __builtin_shufflevector(hi[0], hi[1], 0, 1, 2, 3, 4, 5, 6, 7);
+            const f16x8 l8 = __builtin_shufflevector(lo[0], lo[1], 0, 1, 2, 3, 4, 5, 6, 7);
+            *reinterpret_cast<f16x8*>(sc + li * 128 + ((g ^ (li & 7)) << 4)) = h8;
+            *reinterpret_cast<f16x8*>(sc + li * 128 + (((4 + g) ^ (li & 7)) << 4)) = l8;
+            asm volatile("" ::: "memory");
+#pragma unroll
+            for (int it = 0; it < 2; ++it) {
+                const int r = it * 8 + (lane >> 3), c = lane & 7;
+                const f32x4 y = *reinterpret_cast<const f32x4*>(sc + r * 128 + ((c ^ (r & 7)) << 4));
+                const int m = row_base + i * 16 + r;
+                if (m < p.M) *reinterpret_cast<f32x4*>(reinterpret_cast<char*>(p.out + (int64_t)m * p.ldo + (head_col0 >> 1)) + c * 16) = y;
+            }
+            asm volatile("" ::: "memory");
+        }
+        return;
+    }
     const int sec = EPI == EPI_QKV ? head_col0 / p.D + p.sec0 : 2;      // 0 q, 1 k, 2 v: uniform over the 64-column group
     const bool rope_sec = EPI == EPI_QKV && p.rope_cos && sec < 2;
     const float qsc = sec == 0 ? 0.125f * ATT_QS : (sec == 1 ? ATT_KS : ATT_VS);

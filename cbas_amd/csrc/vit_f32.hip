@@ -14,6 +14,7 @@
 //        EPI_QKV    + bias, RoPE on the patch rows of q and k ([tf]:238-268, rotate_half :203-207), q * 1/8 (exact)
 //        EPI_RESID  x += (acc + bias) * lambda                                        [tf]:342-343, :432-443
 //        EPI_GELU   exact-erf GELU(acc + bias)                                        [tf]:356
+//        EPI_SWIGLU silu(gate + bias) * (up + bias) of the gated MLP, gate | up interleaved  [tf]:360-373
 //   attention_f32_kernel       softmax(q k^T) v per (frame, head), online softmax over 64-key blocks   [tf]:210-234
 //   layernorm_f32_kernel       [tf]:404,410
 //   im2col_*_f32, pack_patch_weight_f32   backend/cbas.py:431 (green / 255.0 in double, then float), :674
@@ -962,6 +963,7 @@ int launch_gemm_f32_vit(GemmEpilogue epi, const Gemm32VitParams& p, hipStream_t 
         case EPI_QKV:   return launch_vit32<EPI_QKV>(p, stream);
         case EPI_RESID: return launch_vit32<EPI_RESID>(p, stream);
         case EPI_GELU:  return launch_vit32<EPI_GELU>(p, stream);
+        case EPI_SWIGLU: return launch_vit32<EPI_SWIGLU>(p, stream);
         default: return -1;
     }
 }
@@ -1013,6 +1015,7 @@ int launch_layernorm_f32(const float* x, int64_t ldx, const float* gamma, const 
         case 2: hipLaunchKernelGGL(layernorm_f32_kernel<2>, grid, block, 0, stream, x, ldx, gamma, beta, out, M, D, eps, split); break;
         case 3: hipLaunchKernelGGL(layernorm_f32_kernel<3>, grid, block, 0, stream, x, ldx, gamma, beta, out, M, D, eps, split); break;
         case 4: hipLaunchKernelGGL(layernorm_f32_kernel<4>, grid, block, 0, stream, x, ldx, gamma, beta, out, M, D, eps, split); break;
+        case 5: hipLaunchKernelGGL(layernorm_f32_kernel<5>, grid, block, 0, stream, x, ldx, gamma, beta, out, M, D, eps, split); break;      // D = 1280 (ViT-H+)
         default: return -1;
     }
     return CHECK_LAUNCH();

@@ -820,6 +820,18 @@ __global__ void convert_f16_kernel(const float* __restrict__ src, f16* __restric
     if (lo) lo[i] = (f16)(v - (float)h);
 }
 
+// gated MLP: out row r of [2F][K] = gate row 32 (r / 64) + r % 64 when r % 64 < 32, else up row 32 (r / 64) + r % 64 - 32
+// (EPI_SWIGLU, kernels.h); n = 2 F K elements
+__global__ void interleave_gate_up_kernel(const float* __restrict__ gate, const float* __restrict__ up, float* __restrict__ out,
+                                          int64_t n, int K) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t r = i / K;
+    const int k = (int)(i - r * K), in = (int)(r & 63);
+    const int64_t src = ((r >> 6) * 32 + (in & 31)) * K + k;
+    out[i] = in < 32 ? gate[src] : up[src];
+}
+
 // One thread per 32-element block of a [N][K] weight: E8M0 scale (no clipping) + 32 e4m3 bytes.
 __global__ void pack_fp8_weight_kernel(const float* __restrict__ src, uint8_t* __restrict__ w8, uint32_t* __restrict__ sc,
                                        int N, int K, int n_total, int n0) {
@@ -901,6 +913,7 @@ int launch_layernorm_f16(const float* x, int64_t ldx, const float* gamma, const 
         case 2: hipLaunchKernelGGL(layernorm_f16_kernel<2>, grid, block, 0, stream, x, ldx, gamma, beta, out, M, D, eps); break;
         case 3: hipLaunchKernelGGL(layernorm_f16_kernel<3>, grid, block, 0, stream, x, ldx, gamma, beta, out, M, D, eps); break;
         case 4: hipLaunchKernelGGL(layernorm_f16_kernel<4>, grid, block, 0, stream, x, ldx, gamma, beta, out, M, D, eps); break;
+        case 5: hipLaunchKernelGGL(layernorm_f16_kernel<5>, grid, block, 0, stream, x, ldx, gamma, beta, out, M, D, eps); break;      // D = 1280 (ViT-H+)
         default: return -1;
     }
     return CHECK_LAUNCH();
@@ -926,7 +939,7 @@ int launch_fold_ln_weight(const float* W, const float* gamma, const float* beta,
 
 int launch_layernorm_f8(const float* x, int64_t ldx, const float* gamma, const float* beta, uint8_t* out8,
                         uint32_t* out_sc, int sc_ld, int M, int D, float eps, hipStream_t stream) {
-    if (D % 128) return -1;
+    if (D % 128 || D > 1024) return -1;             // precision 2 stops at D = 1024 (cbas_enc_create refuses wider handles)
     const int nv = (D / 4 + 63) / 64;
     const dim3 grid((M + 3) / 4), block(256);
     switch (nv) {
@@ -947,6 +960,7 @@ int launch_final_norm_cls(const float* x, const float* gamma, const float* beta,
         case 2: hipLaunchKernelGGL(final_norm_cls_kernel<2>, grid, block, 0, stream, x, gamma, beta, cls_f32, cls_f16, n, T, D, eps, nonfinite); break;
         case 3: hipLaunchKernelGGL(final_norm_cls_kernel<3>, grid, block, 0, stream, x, gamma, beta, cls_f32, cls_f16, n, T, D, eps, nonfinite); break;
         case 4: hipLaunchKernelGGL(final_norm_cls_kernel<4>, grid, block, 0, stream, x, gamma, beta, cls_f32, cls_f16, n, T, D, eps, nonfinite); break;
+        case 5: hipLaunchKernelGGL(final_norm_cls_kernel<5>, grid, block, 0, stream, x, gamma, beta, cls_f32, cls_f16, n, T, D, eps, nonfinite); break;      // D = 1280 (ViT-H+)
         default: return -1;
     }
     return CHECK_LAUNCH();
@@ -990,6 +1004,13 @@ int launch_attention(const f16* qkv, const f16* q_cls, void* out, uint32_t* out_
     }
     hipLaunchKernelGGL(attention_stream_kernel, dim3(n * n_heads, nqb), dim3(512), 0, stream, qkv, q_cls, out, out_sc, sc_ld, T, D, n_heads);
     return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int launch_interleave_gate_up(const float* gate, const float* up, float* out, int64_t F, int K, hipStream_t stream) {
+    if (F <= 0 || F % 32 || K <= 0) return -1;
+    const int64_t n = 2 * F * K;
+    hipLaunchKernelGGL(interleave_gate_up_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, gate, up, out, n, K);
+    return CHECK_LAUNCH();
 }
 
 int launch_convert_f16(const float* src, f16* hi, f16* lo, int64_t n, hipStream_t stream) {

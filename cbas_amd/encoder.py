@@ -40,13 +40,14 @@ def pack_encoder_weights(cfg: ViTConfig, w: Dict[str, np.ndarray]) -> np.ndarray
         parts.append(w["embeddings.position_embeddings"].reshape(-1))
     parts += [w["embeddings.patch_embeddings.weight"].reshape(-1), w["embeddings.patch_embeddings.bias"].reshape(-1)]
     zero_kb = np.zeros(D, np.float32)
+    gate = ("mlp.gate_proj.weight", "mlp.gate_proj.bias") if cfg.use_gated_mlp else ()     # immediately before up_proj
     for i in range(cfg.num_hidden_layers):
         p = f"model.layer.{i}."
         w.setdefault(p + "attention.k_proj.bias", zero_kb)       # DINOv3 has no key bias ([tf] key_bias=False)
         for k in ("norm1.weight", "norm1.bias", "attention.q_proj.weight", "attention.q_proj.bias",
                   "attention.k_proj.weight", "attention.k_proj.bias", "attention.v_proj.weight", "attention.v_proj.bias",
                   "attention.o_proj.weight", "attention.o_proj.bias", "layer_scale1.lambda1",
-                  "norm2.weight", "norm2.bias", "mlp.up_proj.weight", "mlp.up_proj.bias",
+                  "norm2.weight", "norm2.bias", *gate, "mlp.up_proj.weight", "mlp.up_proj.bias",
                   "mlp.down_proj.weight", "mlp.down_proj.bias", "layer_scale2.lambda1"):
             parts.append(np.asarray(w[p + k], np.float32).reshape(-1))
     parts += [w["norm.weight"].reshape(-1), w["norm.bias"].reshape(-1)]
@@ -123,6 +124,12 @@ class DinoEncoder:
         if convnext and int(precision) not in (3, 4):
             raise ValueError(f"precision {int(precision)}: DINOv3 ConvNeXt encoders run in precision 3 (fp32) or 4 (the default: "
                              "fp32 with split-fp16 GEMM products) only")
+        # the MLP kind travels beside the config struct (cbas_enc_create_mlp): every handle of this encoder - the one rebuilt
+        # for larger frames and the precision-3 range-fallback twin included - is created through _create with it
+        self._mlp = _lib.MLP_SWIGLU if getattr(cfg, "use_gated_mlp", False) else _lib.MLP_GELU
+        if self._mlp == _lib.MLP_SWIGLU and int(precision) not in (0, 3, 4):
+            raise ValueError(f"precision {int(precision)}: a gated-MLP encoder (DINOv3 ViT-S+ / H+) runs in precision 0, 3 or 4 "
+                             "(there is no MX-fp8 and no hi+lo form of the gated GEMM)")
         self.config = cfg
         self.device = torch.device(device)
         self._dev = _device_index(self.device)
@@ -140,7 +147,7 @@ class DinoEncoder:
                                          cfg.layer_norm_eps, cfg.rope_theta, self.max_batch, self.max_frame[0],
                                          self.max_frame[1], int(precision), int(cfg.use_rope), int(cfg.pos_embed_grid))
         blob = pack_encoder_weights(cfg, weights)
-        need = self._lib.cbas_enc_weights_count(C.byref(self._cfg_c))
+        need = self._lib.cbas_enc_weights_count_mlp(C.byref(self._cfg_c), self._mlp)
         if need != blob.shape[0]:
             raise RuntimeError(f"weight blob has {blob.shape[0]} floats, library expects {need}")
         self._blob = blob                 # kept so that the handle can be rebuilt for larger frames
@@ -149,8 +156,8 @@ class DinoEncoder:
 
     def _create(self) -> None:
         h = C.c_void_p()
-        _lib.check(self._lib.cbas_enc_create(C.byref(self._cfg_c), self._blob.ctypes.data, self._blob.shape[0], self._dev,
-                                             C.byref(h)), "cbas_enc_create")
+        _lib.check(self._lib.cbas_enc_create_mlp(C.byref(self._cfg_c), self._mlp, self._blob.ctypes.data, self._blob.shape[0],
+                                                 self._dev, C.byref(h)), "cbas_enc_create_mlp")
         self._h = h
         if getattr(self.config, "model_type", None) == "dinov2":
             # plain DINOv2 resamples its position table without antialiasing (HF modeling_dinov2.py:86-91).  Set on EVERY handle
@@ -220,6 +227,7 @@ class DinoEncoder:
             twin._lib, twin._blob = self._lib, self._blob
             twin._cfg_c = _lib.EncConfig.from_buffer_copy(self._cfg_c)       # every field, the family's included
             twin._cfg_c.precision = 3
+            twin._mlp = self._mlp                # a gated encoder's twin is gated
             twin._fp8_plan = self._fp8_plan      # carried, not applied: the fp32 twin has no fp8 GEMM (its fp8_plan reads 0)
             twin._h = None
             twin.model_identifier = getattr(self, "model_identifier", "<in-memory>")

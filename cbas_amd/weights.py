@@ -207,6 +207,9 @@ def encoder_param_shapes(cfg: ViTConfig) -> Dict[str, Tuple[int, ...]]:
         s[pre + "layer_scale1.lambda1"] = (D,)
         s[pre + "norm2.weight"] = (D,)
         s[pre + "norm2.bias"] = (D,)
+        if cfg.use_gated_mlp:                      # DINOv3ViTGatedMLP ([tf]:360-373): gate_proj, up_proj, down_proj
+            s[pre + "mlp.gate_proj.weight"] = (F, D)
+            s[pre + "mlp.gate_proj.bias"] = (F,)
         s[pre + "mlp.up_proj.weight"] = (F, D)
         s[pre + "mlp.up_proj.bias"] = (F,)
         s[pre + "mlp.down_proj.weight"] = (D, F)

@@ -64,8 +64,8 @@ typedef struct cbas_head cbas_head;
 
 /* Mirrors the HF config.json fields of a DINOv3 ViT ([tf] configuration_dinov3_vit.py:74-101). */
 typedef struct cbas_enc_config {
-    int32_t hidden_size;          /* D: 384 / 768 / 1024                       */
-    int32_t intermediate_size;    /* F: 4*D                                    */
+    int32_t hidden_size;          /* D: 384 / 768 / 1024 / 1280 (a multiple of 128, at most 1280; precision 2: at most 1024) */
+    int32_t intermediate_size;    /* F: 4*D (a multiple of 128)                */
     int32_t num_layers;           /* L                                         */
     int32_t num_heads;            /* D / 64 (head_dim must be 64)              */
     int32_t num_register_tokens;  /* R (4 for the released checkpoints)        */
@@ -102,7 +102,11 @@ typedef struct cbas_enc_config {
                                         halves are fp16: after the fixed power-of-two scales an activation must stay below
                                         65 504 - LayerNorm rows as they are, |attention context| and |q| / 8 < 4 094, |k|, |v|
                                         and |GELU output| < 16 376 (far above what ViT checkpoints with "massive activation"
-                                        channels produce: tests/test_gpu_fp32.py); precision 3 has no such bound. */
+                                        channels produce: tests/test_gpu_fp32.py); precision 3 has no such bound.  A gated MLP
+                                        (cbas_enc_create_mlp) stores silu(gate) * up where a GELU handle stores the GELU output,
+                                        with the same scale of 4: |silu(gate) * up| < 16 376.  A value outside it becomes an
+                                        infinite fp16 half, reaches the CLS row as a non-finite value and is reported as
+                                        CBAS_ERANGE (cbas_enc_check_finite). */
     int32_t use_rope;             /* 1: DINOv3 (RoPE on patch rows, no additive position embedding)     */
     int32_t pos_embed_grid;       /* G > 0: DINOv2 (with registers, or plain with num_register_tokens = 0), learned (1+G*G, D)
                                      position embedding, bicubic-antialias interpolated to each frame's patch grid unless
@@ -136,6 +140,26 @@ int64_t cbas_enc_weights_count(const cbas_enc_config* cfg);
 
 int cbas_enc_create(const cbas_enc_config* cfg, const float* weights_host, int64_t n_weights,
                     int device_id, cbas_enc** out);
+
+/* The MLP of a ViT layer.  cbas_enc_config has no field for it (its size is part of ABI 11), so the kind travels beside it:
+ *   CBAS_MLP_GELU    down(gelu(up(x))): every ViT the two calls above build; cbas_enc_weights_count_mlp / cbas_enc_create_mlp with
+ *                    this value ARE cbas_enc_weights_count / cbas_enc_create.
+ *   CBAS_MLP_SWIGLU  down(silu(gate(x)) * up(x)): DINOv3ViTGatedMLP ([tf] modeling_dinov3_vit.py:360-373; use_gated_mlp = true,
+ *                    hidden_act = "silu": ViT-S+/16 with D 384 / F 1536, ViT-H+/16 with D 1280 / F 5120).  family = 0, precision 0,
+ *                    3 or 4.  Refused with CBAS_EINVAL and a message that says why: precision 2 (no MX-fp8 form of the gated
+ *                    GEMM), precision 1 (no hi+lo form either - its use is bring-up, and no test would hold it to anything),
+ *                    ConvNeXt, any other value of `mlp`.
+ * Blob order for CBAS_MLP_SWIGLU: as documented above, with gate.w[F*D] gate.b[F] immediately before up.w[F*D] up.b[F] in every
+ * layer (the HF state_dict order: mlp.gate_proj, mlp.up_proj, mlp.down_proj).  gate and up run as ONE GEMM of 2F columns whose
+ * epilogue forms silu(gate) * up; neither is written to memory.  intermediate_size is F, as in the HF config.
+ * cbas_enc_weights_count_mlp returns -1 (and sets cbas_last_error) where cbas_enc_create_mlp would refuse the combination. */
+#define CBAS_MLP_GELU   0
+#define CBAS_MLP_SWIGLU 1
+int64_t cbas_enc_weights_count_mlp(const cbas_enc_config* cfg, int32_t mlp);
+int cbas_enc_create_mlp(const cbas_enc_config* cfg, int32_t mlp, const float* weights_host, int64_t n_weights,
+                        int device_id, cbas_enc** out);
+/* The MLP kind the handle was created with. */
+int cbas_enc_get_mlp(const cbas_enc* h, int32_t* mlp);
 void cbas_enc_destroy(cbas_enc* h);
 
 /* ConvNeXt handles take every forward / submit / wait / fused-session entry point below unchanged; frames must be at least

@@ -62,7 +62,8 @@ int cbas_head_debug_read(cbas_head* h, int which, float* host_out, int64_t n_flo
 
 /* Bring-up: time the fp16 GEMM kernel alone on random operands (GELU epilogue, M x N x K,
  * tile: 0 auto, 1 128x128, 2 256x128, 3 128x256, 4 256x256, 5+ experimental variants) and return a
- * position-weighted checksum of the fp16 output, so tile variants can be compared bit for bit. */
+ * position-weighted checksum of the fp16 output, so tile variants can be compared bit for bit.  3000 + tile: the gated MLP's
+ * gate | up epilogue (EPI_SWIGLU) on the same N = 2 F columns, F columns stored (scripts/gated_rate.py). */
 int cbas_debug_gemm_bench(int M, int N, int K, int tile, int iters, float* ms_out,
                           unsigned long long* checksum_out);
 
@@ -87,6 +88,21 @@ int cbas_debug_gemm_f8(int M, int N, int K, int tile, const float* A_host, const
 int cbas_debug_gemm_gelu_forms(int M, int N, int K, int tile, int a_fp8, int out_fp8, const float* A_host, const float* W_host,
                                const float* bias_host, uint16_t* out16_host, uint8_t* out8_host, uint32_t* outsc_host,
                                uint8_t* A8_host, uint32_t* Asc_host, uint8_t* W8_host, uint32_t* Wsc_host);
+
+/* Tests: ONE gate | up GEMM of a gated MLP (EPI_SWIGLU: h = silu(A W_g^T + b_g) * (A W_u^T + b_u), neither factor stored) on host
+ * operands, in a chosen arithmetic and form (tests/test_gpu_gated_mlp.py compares it with a float64 reference).
+ *   arith  0: fp16 operands, h stored as fp16 [M][F];  3: fp32, h stored as fp32 [M][F];
+ *          4: split operands (A x a_scale, W x w_scale), h stored as the down projection's split image: per row and 32 columns 128
+ *             bytes [hi 32 x fp16 | lo 32 x fp16] of h x out_scale, column 16 h + 4 g + e at position 8 g + 4 h + e of each half
+ *   tile   arith 0: a GemmTile (0 the planner's choice - skinny for M <= 64; 1 / 2 / 3 / 4 / 7 the 16-wave 128x128 / 256x128 /
+ *          128x256 / 256x256 / 192x256 tiles, 8 its 64x128 tile, 9 skinny, 13..17 the ping-pong tiles 256 / 192 / 160 / 128 rows /
+ *          planner with tail, persistent once there are more tiles than CUs);  arith 4: the ping-pong form's tile height (0 planner)
+ *   forms  arith 4: bit 0 the ping-pong form (M > 256), bit 1 the skinny form (M <= 256), 0 the 128 x 128 kernels, -1 the environment
+ * A_host [M_alloc][lda] (lda >= K: lda = T * D reads one row per frame, the pruned last layer's CLS rows), W_g / W_u [F][K],
+ * b_g / b_u [F]; F % 64 == 0, K % 64 == 0, lda % 32 == 0.  out_host [M][F] goes up first (canaries) and comes back. */
+int cbas_debug_gemm_swiglu(int arith, int tile, int forms, int M, int M_alloc, int F, int K, int lda, const float* A_host,
+                           const float* Wg_host, const float* Wu_host, const float* bg_host, const float* bu_host,
+                           float a_scale, float w_scale, float out_scale, void* out_host);
 
 /* Tests: ONE library GEMM launch on host operands (tests/test_gpu_kernel_reference.py compares it with a float64 reference).
  * The harness converts / splits the fp32 host operands on the device with the library's own routines (launch_convert_f16,
