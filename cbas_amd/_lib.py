@@ -102,6 +102,9 @@ SIGNATURES = {
     "cbas_head_score_rows": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                      c_void_p]),
     "cbas_logits_nll": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_float, c_void_p, c_void_p]),
+    "cbas_probs_top1": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cbas_disagreement_runs": (c_int64, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                         c_void_p, c_int32, c_void_p, c_int64, C.POINTER(c_int64), c_void_p]),
     "cbas_head_train_read": (c_int, [c_void_p, c_int32, c_void_p, c_int64]),
     "cbas_head_train_last_outputs": (c_int, [c_void_p, c_void_p, c_void_p, c_int32]),
     "cbas_csv_format_f32": (c_int64, [c_void_p, c_int64, c_int32, c_void_p, c_int64]),

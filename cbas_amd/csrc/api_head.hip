@@ -1,6 +1,7 @@
 // C-ABI: classifier-head handle (ClassifierLSTMDeltas + the window loop of infer_file).
 // See include/cbas_mi355x.h for the contract and the reference lines each entry point replaces.
 #include <math.h>
+#include <stddef.h>
 #include <string.h>
 #include <mutex>
 #include <new>
@@ -455,6 +456,83 @@ extern "C" int cbas_logits_nll(const float* logits_dev, const int32_t* labels_de
     s.last = st;
     s.used = true;
     return CBAS_OK;
+}
+
+extern "C" int cbas_probs_top1(const float* probs_dev, int64_t n, int32_t n_classes, int32_t* pred_dev, float* conf_dev,
+                               uint32_t* flags_dev, void* stream) {
+    if (!probs_dev || !pred_dev || !conf_dev || !flags_dev)
+        return cbas_fail(CBAS_EINVAL, "probs_dev / pred_dev / conf_dev / flags_dev NULL");
+    if (n < 1 || n_classes < 1 || n_classes > HEAD_SCORE_MAX_CLASSES)
+        return cbas_fail(CBAS_EINVAL, "n=%lld, n_classes=%d: n >= 1 and 1 <= n_classes <= %d", (long long)n, n_classes,
+                         HEAD_SCORE_MAX_CLASSES);
+    LAUNCH_TRY(launch_probs_top1(probs_dev, n, n_classes, pred_dev, conf_dev, flags_dev, (hipStream_t)stream));
+    return CBAS_OK;
+}
+
+static_assert(sizeof(cbas_disagreement_run) == sizeof(RunRecord) && sizeof(RunRecord) == 24 &&
+              offsetof(cbas_disagreement_run, model_confidence) == offsetof(RunRecord, model_confidence),
+              "cbas_disagreement_run is the record the kernels write");
+
+namespace {
+// the scratch of one cbas_disagreement_runs call; freed on every way out
+struct RunsScratch {
+    void* p = nullptr;
+    ~RunsScratch() {
+        if (p) (void)hipFree(p);
+    }
+};
+}  // namespace
+
+extern "C" int64_t cbas_disagreement_runs(const int32_t* pred_dev, const float* conf_dev, int64_t n_frames_total,
+                                          const int64_t* clip_table_dev, int32_t n_clips, const int32_t* inst_clip_dev,
+                                          const int32_t* inst_start_dev, const int32_t* inst_end_dev, const int32_t* inst_label_dev,
+                                          int32_t n_instances, const int32_t* name_rank_dev, int32_t n_classes,
+                                          cbas_disagreement_run* records_dev, int64_t capacity, int64_t* needed_host,
+                                          void* stream) {
+    if (needed_host) *needed_host = 0;
+    if (!pred_dev || !conf_dev || !clip_table_dev || !inst_clip_dev || !inst_start_dev || !inst_end_dev || !inst_label_dev ||
+        !name_rank_dev)
+        return cbas_fail(CBAS_EINVAL, "cbas_disagreement_runs: a NULL pointer among pred / conf / clip_table / inst_* / name_rank");
+    if (n_frames_total < 0 || n_clips < 1 || n_instances < 1 || n_classes < 1 || n_classes > HEAD_SCORE_MAX_CLASSES)
+        return cbas_fail(CBAS_EINVAL, "n_frames_total=%lld, n_clips=%d, n_instances=%d, n_classes=%d: n_frames_total >= 0, n_clips >= 1, "
+                         "n_instances >= 1 and 1 <= n_classes <= %d", (long long)n_frames_total, n_clips, n_instances, n_classes,
+                         HEAD_SCORE_MAX_CLASSES);
+    if (capacity < 0 || (capacity > 0 && !records_dev)) return cbas_fail(CBAS_EINVAL, "capacity=%lld with records_dev %s",
+                                                                         (long long)capacity, records_dev ? "set" : "NULL");
+    hipPointerAttribute_t attr;
+    HIP_TRY(hipPointerGetAttributes(&attr, pred_dev));
+    HIP_TRY(hipSetDevice(attr.device));
+    hipStream_t st = (hipStream_t)stream;
+    // scratch: [flags: 16 bytes][offsets: n_instances + 1 int64][counts: n_instances int32]
+    RunsScratch scratch;
+    const size_t off_bytes = ((size_t)n_instances + 1) * sizeof(long long);
+    HIP_TRY(hipMalloc(&scratch.p, 16 + off_bytes + (size_t)n_instances * sizeof(int)));
+    unsigned* flags = reinterpret_cast<unsigned*>(scratch.p);
+    long long* offsets = reinterpret_cast<long long*>(reinterpret_cast<char*>(scratch.p) + 16);
+    int* counts = reinterpret_cast<int*>(reinterpret_cast<char*>(scratch.p) + 16 + off_bytes);
+    HIP_TRY(hipMemsetAsync(flags, 0, 16, st));
+    const RunsParams p{pred_dev, conf_dev, n_frames_total, clip_table_dev, n_clips, inst_clip_dev, inst_start_dev, inst_end_dev,
+                       inst_label_dev, n_instances, name_rank_dev, n_classes};
+    LAUNCH_TRY(launch_runs_count(p, counts, offsets, flags, st));
+    unsigned bad = 0;
+    long long total = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, flags, sizeof(bad), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&total, offsets + n_instances, sizeof(total), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (bad & RUNS_FLAG_CLIP) return cbas_fail(CBAS_EINVAL, "cbas_disagreement_runs: an instance names a clip outside [0, %d)", n_clips);
+    if (bad & RUNS_FLAG_LABEL) return cbas_fail(CBAS_EINVAL, "cbas_disagreement_runs: a label lies outside [-1, %d)", n_classes);
+    if (bad & RUNS_FLAG_RANGE) return cbas_fail(CBAS_EINVAL, "cbas_disagreement_runs: an instance has start < 0 or end < start");
+    if (bad & RUNS_FLAG_TABLE)
+        return cbas_fail(CBAS_EINVAL, "cbas_disagreement_runs: a clip table entry reaches outside the %lld frames of pred / conf",
+                         (long long)n_frames_total);
+    if (bad & RUNS_FLAG_PRED) return cbas_fail(CBAS_EINVAL, "cbas_disagreement_runs: a prediction lies outside [-1, %d)", n_classes);
+    if (needed_host) *needed_host = total;
+    if (total > capacity)
+        return cbas_fail(CBAS_EINVAL, "cbas_disagreement_runs: %lld records, the buffer holds %lld", total, (long long)capacity);
+    if (total == 0) return 0;
+    LAUNCH_TRY(launch_runs_emit(p, offsets, reinterpret_cast<RunRecord*>(records_dev), total, flags, st));
+    HIP_TRY(hipStreamSynchronize(st));                         // the scratch is freed on return
+    return total;
 }
 
 // rows: the clip's CLS rows as IEEE half (what _cls.h5 holds) or float32 (a foreign `cls` dataset, which the reference

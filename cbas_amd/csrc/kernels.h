@@ -351,3 +351,35 @@ int launch_head_score(const float* logits, const int* labels, int64_t n, int C, 
 constexpr int LOGITS_NLL_MAX_BLOCKS = 128;
 int launch_logits_nll(const float* logits, const int* labels, int64_t n, int C, float temp, unsigned long long* partials,
                       unsigned* ticket, float* out2, hipStream_t st);
+
+// head_report_kernels.hip: the disagreement report of a training job (backend/workthreads.py:760-803) on device probabilities.
+// launch_probs_top1: pred[r] = first index of the row maximum of probs (n, C) and conf[r] = that maximum; a row with a NaN gets
+// pred -1, conf NaN and *flags |= HEAD_SCORE_FLAG_NAN.
+int launch_probs_top1(const float* probs, int64_t n, int C, int* pred, float* conf, unsigned* flags, hipStream_t st);
+// The run scan.  All pointers are device pointers; clip_table is (n_clips, 2) = (first frame in pred / conf, frames).
+struct RunsParams {
+    const int* pred;
+    const float* conf;
+    int64_t n_frames_total;
+    const int64_t* clip_table;
+    int n_clips;
+    const int *inst_clip, *inst_start, *inst_end, *inst_label;
+    int n_instances;
+    const int* name_rank;
+    int n_classes;
+};
+struct RunRecord {          // = cbas_disagreement_run of include/cbas_mi355x.h
+    int instance, start_frame, end_frame, model_prediction;
+    double model_confidence;
+};
+constexpr unsigned RUNS_FLAG_CLIP = 1u;     // an instance names a clip outside the table
+constexpr unsigned RUNS_FLAG_LABEL = 2u;    // a label outside [-1, C)
+constexpr unsigned RUNS_FLAG_RANGE = 4u;    // start < 0 or end < start
+constexpr unsigned RUNS_FLAG_TABLE = 8u;    // a table entry outside the n_frames_total frames
+constexpr unsigned RUNS_FLAG_PRED = 16u;    // a prediction outside [-1, C)
+// launch_runs_count: counts[i] = runs of instance i, offsets[0 .. n_instances] = their exclusive scan and the total; *flags |= the
+// bits above (a refused instance counts 0 runs).  launch_runs_emit: the n_records = offsets[n_instances] records, ordered by
+// (instance, run start); the caller has checked the flags and the room in `records`.
+int launch_runs_count(const RunsParams& p, int* counts, long long* offsets, unsigned* flags, hipStream_t st);
+int launch_runs_emit(const RunsParams& p, const long long* offsets, RunRecord* records, long long n_records, unsigned* flags,
+                     hipStream_t st);

@@ -1183,6 +1183,13 @@ def _as_mi355x_head(model, device) -> ClassifierLSTMDeltas:
 INFER_CHUNK = 20000                  # backend/cbas.py:482: frames per read of the `cls` dataset
 
 
+def infer_spans(total: int, half: int, chunk: int = INFER_CHUNK) -> list:
+    """``(start, end, first row read, last row read + 1)`` of the pieces ``classify_cls_file`` classifies a clip of
+    ``total`` frames in: ``chunk`` frames each, read with a halo of ``half`` real rows on both sides."""
+    return [(start, min(start + chunk, total), max(0, start - half), min(total, min(start + chunk, total) + half))
+            for start in range(0, total, chunk)]
+
+
 def classify_cls_file(reader: "h5io.ClsReader", head: ClassifierLSTMDeltas, temperature: float, device,
                       chunk: int = INFER_CHUNK) -> np.ndarray:
     """The read + window loop of infer_file (backend/cbas.py:497-551): the `cls` dataset is read in ``chunk``-frame pieces
@@ -1190,13 +1197,10 @@ def classify_cls_file(reader: "h5io.ClsReader", head: ClassifierLSTMDeltas, temp
     piece being read while the head works on the current one, so a day-long file needs a chunk of host memory, not the
     whole clip.  Returns (N, C) float32 probabilities.  Any numeric dataset is accepted: IEEE half rows are consumed as
     they are, everything else as float32 (the reference's ``.float()``, :507-508)."""
-    total, half = reader.shape[0], head.seq_len // 2
+    total = reader.shape[0]
     device = torch.device(device)
     probs_dev = torch.empty((total, head.out_features), dtype=torch.float32, device=device)
-    spans = []
-    for start in range(0, total, chunk):
-        end = min(start + chunk, total)
-        spans.append((start, end, max(0, start - half), min(total, end + half)))
+    spans = infer_spans(total, head.seq_len // 2, chunk)
 
     def read(k):
         _s, _e, r0, r1 = spans[k]

@@ -21,6 +21,10 @@ The tail of a training job runs from the same rows: ``evaluate_on_split`` (backe
 the logits on the device and evaluates the L-BFGS closure with ``cbas_logits_nll``; inside ``keep_rows()`` they and
 ``train_lstm_model`` share one store.
 
+The last step of a job, the disagreement report (backend/workthreads.py:728-811), runs from them too: ``disagreement_report``
+classifies every training clip that has no ``_outputs.csv`` yet from its resident rows, keeps the probabilities on the device
+for ``cbas_probs_top1`` and ``cbas_disagreement_runs`` and writes the CSV the reference writes on a thread beside them.
+
 Dropout keep-masks come from a counter-based hash (seed, step, layer, element) instead of torch's
 global RNG, so a run is reproducible from its seed; the masks have the reference's rates (0.1 after
 the three bottleneck GELUs, 0.15 after lin0's GELU).
@@ -28,8 +32,10 @@ the three bottleneck GELUs, 0.15 after lin0's GELU).
 from __future__ import annotations
 
 import contextlib
+import csv
 import ctypes as C
 import os
+import queue
 import threading
 from typing import Dict, List, Mapping, Optional, Sequence
 
@@ -855,3 +861,336 @@ def fit_temperature(model, val_loader, device):
         logits, labels = torch.cat(all_logits).detach(), torch.cat(all_labels)
     temperature, _, _ = fit_temperature_from(device_nll(logits, labels))
     return temperature
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the disagreement report (backend/workthreads.py:728-811): where the trained head and the human labels differ
+# ---------------------------------------------------------------------------------------------------------------
+RUN_DTYPE = np.dtype([("instance", "<i4"), ("start_frame", "<i4"), ("end_frame", "<i4"), ("model_prediction", "<i4"),
+                      ("model_confidence", "<f8")])          # cbas_disagreement_run of include/cbas_mi355x.h
+TOP1_FLAG_NAN = 1                                           # CBAS_TOP1_FLAG_NAN
+
+
+def name_ranks(behaviors: Sequence[str]) -> np.ndarray:
+    """``rank[c]`` = position of ``behaviors[c]`` among the sorted names: pandas' ``mode()`` returns its values sorted and the
+    reference takes the first (workthreads.py:794), so equally frequent predictions are decided by name."""
+    rank = np.empty(len(behaviors), np.int32)
+    rank[sorted(range(len(behaviors)), key=lambda c: behaviors[c])] = np.arange(len(behaviors), dtype=np.int32)
+    return rank
+
+
+def disagreement_runs_host(pred: np.ndarray, conf: np.ndarray, start: int, end: int, label: int, name_rank: np.ndarray) -> list:
+    """workthreads.py:777-803 for ONE instance of a clip whose per-frame prediction (class index, -1 for none) and confidence
+    are ``pred`` / ``conf``: ``[(start_frame, end_frame, model_prediction, model_confidence)]``, one entry per maximal run of
+    consecutive frames of ``iloc[start:end+1]`` (negative bounds count from the end, as there) whose prediction is not
+    ``label`` (-1: a label that is no behaviour, every frame differs).  The prediction of a run is its most frequent one, ties
+    to the smallest ``name_rank``; its confidence the float64 mean, summed in ascending frame order."""
+    frames = np.arange(len(pred))[start:end + 1]
+    if frames.size == 0:
+        return []
+    wrong = frames[np.ones(frames.size, bool) if label < 0 else pred[frames] != label]
+    if wrong.size == 0:
+        return []
+    out = []
+    for run in np.split(wrong, np.flatnonzero(np.diff(wrong) != 1) + 1):
+        p = pred[run]
+        counts = np.bincount(p[p >= 0], minlength=len(name_rank))
+        best = np.flatnonzero(counts == counts.max()) if counts.max() > 0 else np.empty(0, np.int64)
+        winner = int(best[np.argmin(name_rank[best])]) if best.size else -1
+        mean = float(np.cumsum(np.asarray(conf[run], np.float64))[-1] / run.size)
+        out.append((int(run[0]), int(run[-1]), winner, mean))
+    return out
+
+
+def probs_top1(probs: torch.Tensor, pred: Optional[torch.Tensor] = None, conf: Optional[torch.Tensor] = None,
+               flags: Optional[torch.Tensor] = None):
+    """``cbas_probs_top1``: ``(pred int32 (n,), conf float32 (n,), flags int32 (1,))`` of device probabilities (n, C): the first
+    index of each row's maximum and the maximum; a row with a NaN gets -1 / NaN and sets ``TOP1_FLAG_NAN`` in ``flags``
+    (OR-ed into a word the caller passes).  Asynchronous on the current stream."""
+    if probs.dim() != 2 or probs.dtype != torch.float32 or not probs.is_cuda or not probs.is_contiguous() or probs.shape[0] < 1:
+        raise ValueError(f"probs must be a contiguous float32 (n >= 1, C) tensor on a GPU, got {probs.dtype} {tuple(probs.shape)} on {probs.device}")
+    n = int(probs.shape[0])
+    pred = torch.empty(n, dtype=torch.int32, device=probs.device) if pred is None else pred
+    conf = torch.empty(n, dtype=torch.float32, device=probs.device) if conf is None else conf
+    flags = torch.zeros(1, dtype=torch.int32, device=probs.device) if flags is None else flags
+    for t, dt in ((pred, torch.int32), (conf, torch.float32)):
+        if t.dtype != dt or t.device != probs.device or tuple(t.shape) != (n,) or not t.is_contiguous():
+            raise ValueError(f"pred / conf must be contiguous ({n},) int32 / float32 tensors on {probs.device}")
+    if flags.dtype != torch.int32 or flags.device != probs.device or flags.numel() != 1:
+        raise ValueError(f"flags must be one int32 word on {probs.device}")
+    with torch.cuda.device(probs.device):
+        stream = torch.cuda.current_stream(probs.device).cuda_stream
+        _lib.check(_lib.load().cbas_probs_top1(probs.data_ptr(), n, int(probs.shape[1]), pred.data_ptr(), conf.data_ptr(),
+                                               flags.data_ptr(), stream), "cbas_probs_top1")
+    return pred, conf, flags
+
+
+def disagreement_runs(pred: torch.Tensor, conf: torch.Tensor, clip_table, clip, start, end, label, name_rank) -> np.ndarray:
+    """``cbas_disagreement_runs``: the records (``RUN_DTYPE``, ordered by instance and run start) of the instances
+    ``(clip[i], start[i], end[i], label[i])`` over the per-frame ``pred`` (int32) / ``conf`` (float32) of all clips back to back
+    on one GPU; ``clip_table`` (n_clips, 2) = (first frame, frames) per clip.  The semantics are those of
+    ``disagreement_runs_host`` for ``0 <= start <= end``; anything else is refused."""
+    dev = pred.device
+    if pred.dtype != torch.int32 or conf.dtype != torch.float32 or not pred.is_cuda or conf.device != dev or pred.shape != conf.shape \
+            or pred.dim() != 1 or not pred.is_contiguous() or not conf.is_contiguous():
+        raise ValueError("pred (int32) and conf (float32) must be contiguous 1-d tensors of one length on one GPU")
+    table = np.ascontiguousarray(np.asarray(clip_table, np.int64).reshape(-1, 2))
+    arrays = [np.ascontiguousarray(np.asarray(a, np.int32)) for a in (clip, start, end, label)]
+    rank = np.ascontiguousarray(np.asarray(name_rank, np.int32))
+    n_inst = int(arrays[0].shape[0])
+    if any(a.shape != (n_inst,) for a in arrays) or n_inst < 1 or table.shape[0] < 1:
+        raise ValueError("clip, start, end and label must be four 1-d arrays of one length >= 1, the table (n_clips >= 1, 2)")
+    # a run needs an error frame and, before the next run, a frame that is none: at most (frames + 1) // 2 per instance
+    frames_of = table[np.clip(arrays[0], 0, table.shape[0] - 1), 1]
+    length = np.clip(np.minimum(arrays[2].astype(np.int64), frames_of - 1) - arrays[1] + 1, 0, None)
+    capacity = max(1, int(((length + 1) // 2).sum()))
+    dev_arrays = [torch.from_numpy(a).to(dev) for a in [table] + arrays + [rank]]
+    records = torch.empty(capacity * RUN_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    needed = C.c_int64(0)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        n = _lib.load().cbas_disagreement_runs(pred.data_ptr(), conf.data_ptr(), int(pred.shape[0]), dev_arrays[0].data_ptr(),
+                                               int(table.shape[0]), dev_arrays[1].data_ptr(), dev_arrays[2].data_ptr(),
+                                               dev_arrays[3].data_ptr(), dev_arrays[4].data_ptr(), n_inst, dev_arrays[5].data_ptr(),
+                                               int(rank.shape[0]), records.data_ptr(), capacity, C.byref(needed), stream)
+    if n < 0:
+        _lib.check(int(n), "cbas_disagreement_runs")
+    return records[:n * RUN_DTYPE.itemsize].cpu().numpy().view(RUN_DTYPE).copy()
+
+
+def _read_outputs_csv(path: str, behaviors: Sequence[str]) -> np.ndarray:
+    """The behaviour columns of an ``_outputs.csv`` as float64 (n, C), selected by name as ``pred_df[task.behaviors]`` does
+    (workthreads.py:761-763); an empty field is NaN.  Raises when a column is missing or a field is no number."""
+    with open(path, newline="", encoding="utf-8") as f:
+        header = next(csv.reader(f), None)
+        if header is None:
+            raise ValueError("empty file")
+        cols = [header.index(b) for b in behaviors]                   # ValueError: a behaviour without a column
+        try:
+            values = np.loadtxt(f, delimiter=",", dtype=np.float64, ndmin=2, usecols=cols)
+        except ValueError:
+            values = None                                             # an empty or quoted field: the slow reader below
+    if values is None:
+        with open(path, newline="", encoding="utf-8") as f:
+            rows = csv.reader(f)
+            next(rows)
+            values = np.array([[float(r[c]) if r[c] != "" else np.nan for c in cols] for r in rows if r], np.float64)
+    return values.reshape(-1, len(behaviors))
+
+
+class _CsvWriter:
+    """The thread that writes the ``_outputs.csv`` files while the device classifies the next clip: it waits for the event
+    behind a clip's device-to-host copy, then runs the native writer.  ``failed``: the clips whose file could not be written."""
+
+    def __init__(self, behaviors):
+        self.behaviors = list(behaviors)
+        self.failed: Dict[int, Exception] = {}
+        self._q: "queue.Queue" = queue.Queue()
+        self._t = threading.Thread(target=self._run, name="cbas-report-csv", daemon=True)
+        self._t.start()
+
+    def _run(self):
+        from .pipeline import write_probs_csv
+        while True:
+            item = self._q.get()
+            if item is None:
+                return
+            k, path, host, event = item
+            try:
+                event.synchronize()
+                write_probs_csv(path, host.numpy(), self.behaviors)
+            except Exception as e:  # noqa: BLE001 - reported by the caller, which drops the clip as infer_file's failure does
+                self.failed[k] = e
+
+    def put(self, k: int, path: str, host: torch.Tensor, event) -> None:
+        self._q.put((k, path, host, event))
+
+    def close(self) -> None:
+        self._q.put(None)
+        self._t.join()
+
+
+def _kept_rows_of(path: str, dim: int, device):
+    """``(store, (base, n))`` for ``path`` in the store kept by the enclosing ``keep_rows()`` when that store holds the file as
+    it is on disk now, else None."""
+    with _row_cache_lock:
+        cache = _row_cache
+        if cache is None or cache.store is None:
+            return None
+        store = cache.store
+        held = store.files.get(path)
+        if held is None or torch.device(store.device) != torch.device(device) or store.dim != dim:
+            return None
+        if cache.stamps.get(path) is None or cache.stamps[path] != _file_stamp(path):
+            return None
+        return store, held
+
+
+def _clip_rows(path: str, dim: int, device, log):
+    """The half-precision rows of one ``_cls.h5`` on ``device``: a view of the kept store, or the file uploaded once.  None
+    (with the reason logged) when the file is not what the device path takes: the caller hands the clip to ``infer_file``."""
+    kept = _kept_rows_of(path, dim, device)
+    if kept is not None:
+        store, (base, n) = kept
+        return store.rows[base:base + n]
+    try:
+        with h5io.ClsReader(path) as r:
+            shape, half = tuple(r.shape), bool(r.is_half)
+            if len(shape) != 2 or shape[1] != dim or not half or shape[0] == 0:
+                return None
+            if shape[0] * dim * 2 > _resident_budget(device):
+                log(f"disagreement report: {path} does not fit in device memory, classified through infer_file")
+                return None
+            rows = torch.empty((shape[0], dim), dtype=torch.float16, device=device)
+            for a in range(0, shape[0], ResidentRows.READ_ROWS):
+                b = min(shape[0], a + ResidentRows.READ_ROWS)
+                rows[a:b].copy_(torch.from_numpy(r.read(a, b)))
+            return rows
+    except Exception:  # noqa: BLE001 - infer_file reports what is wrong with the file
+        return None
+
+
+def disagreement_report(model, train_insts, behaviors, seq_len: int, project_path: str, task_name: str, device=None,
+                        log=print) -> List[dict]:
+    """``TrainingThread._generate_disagreement_report`` (backend/workthreads.py:728-805) up to the sort: for every training
+    instance ``{"video", "start", "end", "label"}`` the runs of frames where ``model`` disagrees with the label, as
+    ``{"video_path", "start_frame", "end_frame", "human_label", "model_prediction", "model_confidence"}``, sorted by
+    confidence, highest first (stable: videos by first appearance, instances in list order, runs ascending).
+
+    A clip that has a ``<video>_<task_name>_outputs.csv`` is read from it, as the reference does.  Any other clip is classified
+    at temperature 1.0 (:753-756 passes none) and its CSV is written, byte for byte what ``infer_file`` writes: on a GPU with
+    this package's head the rows come from the store kept by ``keep_rows()`` (or are uploaded once), the probabilities stay on
+    the device for ``cbas_probs_top1`` and ONE ``cbas_disagreement_runs`` call over all clips, and a thread writes the files
+    meanwhile.  ``CBAS_TRAIN_RESIDENT=0``, another device or head, or a file the store cannot take, go through ``infer_file``
+    and the numpy routine on the parsed file; the records are the same, the confidences within 2^-24 relative (the file holds
+    the shortest decimals of the float32 values)."""
+    from . import pipeline as _pl
+
+    device = torch.device(device) if device is not None else torch.device("cuda" if torch.cuda.is_available() else "cpu")
+    behaviors = list(behaviors)
+    n_classes = len(behaviors)
+    rank = name_ranks(behaviors)
+    on_device = (device.type == "cuda" and isinstance(model, ClassifierLSTMDeltas) and model.seq_len == seq_len
+                 and model.out_features == n_classes and 1 <= n_classes <= 64
+                 and os.environ.get("CBAS_TRAIN_RESIDENT", "1").strip() != "0")
+
+    by_video: Dict[str, list] = {}
+    for inst in train_insts:
+        video = inst.get("video")
+        if video:
+            by_video.setdefault(video, []).append(inst)
+
+    # per clip that yields records: the parsed instances and where its predictions are
+    clips = []                    # dicts: video, insts [(start, end, label, label index)], and "host": (pred, conf) or "dev": (base, n)
+    pred_parts, conf_parts, total = [], [], 0
+    writer = _CsvWriter(behaviors) if on_device else None
+    flags = None
+    try:
+        for video, instances in by_video.items():
+            h5_path = os.path.splitext(os.path.join(project_path, video))[0] + "_cls.h5"
+            if not os.path.exists(h5_path):
+                continue
+            csv_path = h5_path.replace("_cls.h5", f"_{task_name}_outputs.csv")
+            clip = {"video": video, "insts": []}
+            rows = None
+            if not os.path.exists(csv_path):
+                rows = _clip_rows(h5_path, model.in_features, device, log) if on_device else None
+                if rows is None:
+                    csv_path = _pl.infer_file(file_path=h5_path, model=model, dataset_name=task_name, behaviors=behaviors,
+                                              seq_len=seq_len, device=device)
+                    if not csv_path:
+                        continue
+            if rows is not None:
+                n = int(rows.shape[0])
+                model.to(device)
+                probs = torch.empty((n, n_classes), dtype=torch.float32, device=device)
+                for a, b, r0, r1 in _pl.infer_spans(n, model.seq_len // 2):      # the calls infer_file makes, on resident rows
+                    model.infer_range_into(rows[r0:r1], r1 - r0, a - r0, b - a, probs[r0:], 1.0)
+                if flags is None:
+                    flags = torch.zeros(len(by_video), dtype=torch.int32, device=device)
+                k = len(clips)
+                pred = torch.empty(n, dtype=torch.int32, device=device)
+                conf = torch.empty(n, dtype=torch.float32, device=device)
+                probs_top1(probs, pred, conf, flags[k:k + 1])
+                host = torch.empty((n, n_classes), dtype=torch.float32, pin_memory=True)
+                host.copy_(probs, non_blocking=True)
+                event = torch.cuda.Event()
+                event.record(torch.cuda.current_stream(device))
+                writer.put(k, csv_path, host, event)
+                pred_parts.append(pred)
+                conf_parts.append(conf)
+                clip.update(dev=(total, n), csv=csv_path, probs=host, event=event)
+                total += n
+            else:
+                try:
+                    values = _read_outputs_csv(csv_path, behaviors)
+                    if np.isnan(values).any():
+                        raise ValueError("a probability is NaN")
+                    if values.shape[0] == 0:
+                        raise ValueError("no rows")
+                except Exception as e:  # noqa: BLE001 - workthreads.py:764-766
+                    log(f"Could not read or process CSV {csv_path}: {e}")
+                    continue
+                clip["host"] = (values.argmax(axis=1).astype(np.int64), values.max(axis=1))
+            for inst in instances:
+                try:
+                    start, end, label = int(inst["start"]), int(inst["end"]), inst["label"]
+                except (ValueError, KeyError, TypeError) as e:
+                    log(f"Skipping malformed instance in disagreement report: {inst}. Error: {e}")
+                    continue
+                clip["insts"].append((start, end, label, behaviors.index(label) if label in behaviors else -1))
+            if "probs" in clip and all(0 <= a <= b for a, b, _l, _i in clip["insts"]):
+                del clip["probs"]                           # only the host routine (negative bounds) reads them again
+            clips.append(clip)
+
+        # the device clips: one scan over all their instances; what pandas' negative bounds mean is left to the host routine
+        runs_of: Dict[tuple, list] = {}                     # (clip, instance) -> [(start, end, prediction index, confidence)]
+        dev_clips = [(k, c) for k, c in enumerate(clips) if "dev" in c]
+        if dev_clips:
+            nan = flags.cpu().numpy()                       # synchronises: every clip has been classified
+            table, ic, ia, ib, il, where = [], [], [], [], [], []
+            for k, c in dev_clips:
+                if nan[k] & TOP1_FLAG_NAN:
+                    log(f"Could not read or process CSV {c['csv']}: a probability is NaN")
+                    c["insts"] = []
+                    continue
+                n = c["dev"][1]
+                for j, (start, end, _label, index) in enumerate(c["insts"]):
+                    if 0 <= start <= end:
+                        if start < n:
+                            ic.append(len(table)), ia.append(start), ib.append(min(end, n - 1)), il.append(index), where.append((k, j))
+                    else:
+                        c["event"].synchronize()
+                        p = c["probs"].numpy()
+                        runs_of[(k, j)] = disagreement_runs_host(p.argmax(axis=1), p.max(axis=1), start, end, index, rank)
+                table.append(c["dev"])
+            if ic:
+                records = disagreement_runs(torch.cat(pred_parts), torch.cat(conf_parts), table, ic, ia, ib, il, rank)
+                for r in records:
+                    runs_of.setdefault(where[int(r["instance"])], []).append(
+                        (int(r["start_frame"]), int(r["end_frame"]), int(r["model_prediction"]), float(r["model_confidence"])))
+    finally:
+        if writer is not None:
+            writer.close()
+    if writer is not None:
+        for k, e in writer.failed.items():
+            log(f"Error during buffered inference on {clips[k]['csv']}: {e}")
+            clips[k]["insts"] = []
+
+    disagreements = []
+    for k, c in enumerate(clips):
+        for j, (start, end, label, index) in enumerate(c["insts"]):
+            runs = runs_of.get((k, j), []) if "dev" in c else disagreement_runs_host(c["host"][0], c["host"][1], start, end, index, rank)
+            for a, b, winner, confidence in runs:
+                disagreements.append({"video_path": c["video"], "start_frame": int(a), "end_frame": int(b), "human_label": label,
+                                      "model_prediction": behaviors[winner] if winner >= 0 else None,
+                                      "model_confidence": float(confidence)})
+    disagreements.sort(key=lambda x: x["model_confidence"], reverse=True)
+    return disagreements
+
+
+def write_disagreement_report(path: str, items: List[dict]) -> None:
+    """workthreads.py:807-809: ``disagreement_report.yaml`` as the labelling UI reads it."""
+    import yaml
+    with open(path, "w") as f:
+        yaml.dump(items, f, allow_unicode=True)

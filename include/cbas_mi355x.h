@@ -53,7 +53,7 @@ extern "C" {
 #define CBAS_ERANGE       -5   /* a frame's CLS row came out NaN / infinite: an activation left the arithmetic mode's range */
 
 /* Still 11 with cbas_rows_gather_windows / cbas_head_train_step_rows, with cbas_head_score_rows / cbas_logits_nll, with
- * cbas_enc_set_pos_interp and with cbas_enc_set_fp8_plan: they are additions.  No structure and no existing signature changed, so a caller built against the earlier version 11 header
+ * cbas_enc_set_pos_interp, with cbas_enc_set_fp8_plan and with cbas_probs_top1 / cbas_disagreement_runs: they are additions.  No structure and no existing signature changed, so a caller built against the earlier version 11 header
  * runs unchanged. */
 #define CBAS_ABI_VERSION   11
 
@@ -478,6 +478,55 @@ int cbas_head_score_rows(cbas_head* h, const uint16_t* rows_f16_dev, int64_t n_r
  * CBAS_EINVAL: a NULL pointer, n < 1, n_classes outside [1, 64], temp <= 0 or NaN. */
 int cbas_logits_nll(const float* logits_dev, const int32_t* labels_dev, int64_t n, int32_t n_classes, float temp,
                     float* out2_dev, void* stream);
+
+/* The disagreement report of a training job (TrainingThread._generate_disagreement_report, backend/workthreads.py:728-811)
+ * from probabilities that are on the device (cbas_head_infer_f16 over the resident rows of a training clip), instead of
+ * writing `_outputs.csv`, reading it back with pandas and scanning it per instance.
+ *
+ * cbas_probs_top1 replaces :762-763 (`idxmax(axis=1)` and `max(axis=1)` over the behaviour columns): for each of the n rows
+ * of probs_dev (n, n_classes) float32
+ *   pred_dev[r] = index of the FIRST maximum (int32), conf_dev[r] = that maximum (float32).
+ * A row that holds a NaN gets pred -1 and conf NaN, and CBAS_TOP1_FLAG_NAN is OR-ed into *flags_dev (a device word the caller
+ * zeroes and reads; the reference's `except` at :764 drops such a clip).  Asynchronous on `stream`; nothing is copied.
+ * CBAS_EINVAL: a NULL pointer, n < 1, n_classes outside [1, 64]. */
+#define CBAS_TOP1_FLAG_NAN 1u
+int cbas_probs_top1(const float* probs_dev, int64_t n, int32_t n_classes, int32_t* pred_dev, float* conf_dev,
+                    uint32_t* flags_dev, void* stream);
+/* cbas_disagreement_runs replaces :777-803, for all instances of all clips in one call.  pred_dev / conf_dev hold the frames of
+ * all clips back to back (n_frames_total of them), clip_table_dev (n_clips, 2) int64 gives each clip's (first frame, frames).
+ * Instance i is (inst_clip[i], inst_start[i], inst_end[i], inst_label[i]), all int32: its frames are
+ * [start, min(end, frames - 1)] of its clip (`iloc[start:end+1]`; an empty range yields no record); label is the class index of
+ * the human label, or -1 for a label that is no behaviour - then every frame is an error frame, as under the string
+ * comparison of :781.  An error frame is one with pred != label.  One record per maximal run of consecutive error frames
+ * INSIDE one instance (runs of abutting or overlapping instances never merge; overlapping instances each report theirs):
+ *   model_prediction  the most frequent pred of the run; among equally frequent ones the class with the smallest
+ *                     name_rank_dev[class] (int32[n_classes], the rank of the class NAME in sorted order: pandas mode()
+ *                     returns sorted values and :794 takes [0]).  Frames with pred -1 are error frames but are not counted
+ *                     here (mode() drops NaN); -1 when the run has no other frame.
+ *   model_confidence  the mean of conf over the run in float64.  The sum is formed in a fixed order that depends on the run
+ *                     alone (64 interleaved partial sums, each in ascending frame order, then a fixed tree), without
+ *                     floating-point atomics; for top-1 probabilities (>= 1/64) of up to 2^22 frames every partial sum is
+ *                     exact, so it is the sum in ascending frame order bit for bit.
+ * Records are ordered by (instance, start_frame) whatever the order of execution (count, exclusive scan, emit; nothing is
+ * appended with an atomic), so equal inputs give equal bytes.  Returns the number of records (>= 0) or a negative CBAS_E*
+ * code; *needed_host (may be NULL) receives the number of records whenever the instances were accepted.  records_dev holds
+ * `capacity` records; fewer than needed is CBAS_EINVAL and writes nothing (capacity 0 with records_dev NULL asks for the
+ * count).  CBAS_EINVAL also for: a NULL pointer, n_clips / n_instances < 1, n_classes outside [1, 64], an instance whose clip
+ * lies outside the table, whose label lies outside [-1, n_classes), with start < 0 or end < start, a table entry that reaches
+ * outside the n_frames_total frames, a pred outside [-1, n_classes) - each checked on the device before anything is indexed
+ * with it.  The call synchronises `stream`. */
+typedef struct cbas_disagreement_run {
+    int32_t instance;          /* index into the inst_* arrays */
+    int32_t start_frame;       /* first and last frame of the run, in frames of the instance's clip */
+    int32_t end_frame;
+    int32_t model_prediction;
+    double  model_confidence;
+} cbas_disagreement_run;
+int64_t cbas_disagreement_runs(const int32_t* pred_dev, const float* conf_dev, int64_t n_frames_total,
+                               const int64_t* clip_table_dev, int32_t n_clips, const int32_t* inst_clip_dev,
+                               const int32_t* inst_start_dev, const int32_t* inst_end_dev, const int32_t* inst_label_dev,
+                               int32_t n_instances, const int32_t* name_rank_dev, int32_t n_classes,
+                               cbas_disagreement_run* records_dev, int64_t capacity, int64_t* needed_host, void* stream);
 
 /* Copy the current parameters (what = 0) or the gradients of the last step (what = 1) to the host, in the
  * blob order of cbas_head_create (n = cbas_head_weights_count).  Synchronises the device. */
