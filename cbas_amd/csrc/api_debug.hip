@@ -784,3 +784,120 @@ extern "C" int cbas_debug_attention_run(const cbas_debug_attention_args* a) {
     HIP_TRY(hipMemcpy(a->out, out, osz, hipMemcpyDeviceToHost));
     return CBAS_OK;
 }
+
+// ---- tests: one launch of a row-wise kernel (LayerNorm forms, the MX-fp8 row, the ConvNeXt producers) on host operands ----
+extern "C" int cbas_debug_rows_run(const cbas_debug_rows_args* a) {
+    if (!a || a->struct_bytes != (int64_t)sizeof(cbas_debug_rows_args))
+        return cbas_fail(CBAS_EINVAL, "cbas_debug_rows_args: struct_bytes %lld, library expects %lld", a ? (long long)a->struct_bytes : -1ll,
+                         (long long)sizeof(cbas_debug_rows_args));
+    const int op = a->op, D = a->D, M = a->M, n = a->n, h = a->h, w = a->w;
+    const int64_t ld = a->ld;
+    const bool vit_ln = op >= CBAS_DEBUG_ROWS_LN_F16 && op <= CBAS_DEBUG_ROWS_LN_F8;
+    const bool cls = op == CBAS_DEBUG_ROWS_FINAL_CLS || op == CBAS_DEBUG_ROWS_CNX_POOL_LN;
+    const bool stem = op == CBAS_DEBUG_ROWS_CNX_STEM_U8 || op == CBAS_DEBUG_ROWS_CNX_STEM_F32;
+    const bool cnx = op >= CBAS_DEBUG_ROWS_CNX_LN_ROWS && op <= CBAS_DEBUG_ROWS_CNX_POOL_LN;
+    if (op < CBAS_DEBUG_ROWS_LN_F16 || op > CBAS_DEBUG_ROWS_CNX_POOL_LN) return cbas_fail(CBAS_EINVAL, "op %d", op);
+    // what the launch reads (x_need) and writes (out_need, out2_need), in bytes: the images must hold it
+    int64_t x_need = 0, out_need = 0, out2_need = 0;
+    if (!stem) {
+        if (D <= 0 || D % 4 || !a->gamma || !a->beta) return cbas_fail(CBAS_EINVAL, "D = %d: a positive multiple of 4; gamma / beta", D);
+        if ((vit_ln || op == CBAS_DEBUG_ROWS_FINAL_CLS) && D > 1280) return cbas_fail(CBAS_EINVAL, "D = %d: the ViT LayerNorms stop at 1280", D);
+        if (op == CBAS_DEBUG_ROWS_LN_SPLIT && D % 32) return cbas_fail(CBAS_EINVAL, "LN_SPLIT: D %% 32");
+        if (op == CBAS_DEBUG_ROWS_LN_F8 && (D % 128 || D < 256 || D > 1024)) return cbas_fail(CBAS_EINVAL, "LN_F8: D = 256 .. 1024 in steps of 128");
+        if (cnx && (D % 32 || D > 1536)) return cbas_fail(CBAS_EINVAL, "ConvNeXt width %d: a multiple of 32 up to 1536", D);
+    }
+    if (vit_ln || op == CBAS_DEBUG_ROWS_CNX_LN_ROWS) {
+        if (M <= 0 || ld < D) return cbas_fail(CBAS_EINVAL, "M = %d, ld = %lld: M > 0 and ld >= D", M, (long long)ld);
+        const int64_t span = ((int64_t)(M - 1) * ld + D) * 4;
+        if (vit_ln) x_need = span; else out_need = span;
+        if (op == CBAS_DEBUG_ROWS_LN_F16) out_need = (int64_t)M * D * 2;
+        if (op == CBAS_DEBUG_ROWS_LN_F32 || op == CBAS_DEBUG_ROWS_LN_SPLIT) out_need = (int64_t)M * D * 4;
+        if (op == CBAS_DEBUG_ROWS_LN_F8) {
+            if (a->sc_ld < M) return cbas_fail(CBAS_EINVAL, "sc_ld %d < M %d", a->sc_ld, M);
+            out_need = (int64_t)M * D;
+            out2_need = (int64_t)(D / 128) * a->sc_ld * 4;
+        }
+    } else {
+        if (n <= 0) return cbas_fail(CBAS_EINVAL, "n = %d", n);
+        if (op == CBAS_DEBUG_ROWS_FINAL_CLS) {
+            if (a->T <= 0) return cbas_fail(CBAS_EINVAL, "T = %d", a->T);
+            x_need = ((int64_t)(n - 1) * a->T * D + D) * 4;
+        } else if (stem) {
+            if (h < 4 || w < 4) return cbas_fail(CBAS_EINVAL, "stem: a %d x %d frame is smaller than one 4 x 4 patch", h, w);
+            const int ho = h / 4, wo = w / 4;
+            if (op == CBAS_DEBUG_ROWS_CNX_STEM_U8) {
+                if (a->frame_stride <= 0 || a->row_stride <= 0 || a->pixel_stride <= 0) return cbas_fail(CBAS_EINVAL, "stem: strides must be positive");
+                x_need = (int64_t)(n - 1) * a->frame_stride + (int64_t)(4 * ho - 1) * a->row_stride + (int64_t)(4 * wo - 1) * a->pixel_stride + 1;
+            } else {
+                x_need = (int64_t)n * h * w * 4;
+            }
+            out_need = (int64_t)n * ho * wo * 32 * 4;
+        } else {
+            if (h <= 0 || w <= 0 || ld < D) return cbas_fail(CBAS_EINVAL, "grid %d x %d, ld = %lld: positive, ld >= C", h, w, (long long)ld);
+            x_need = (((int64_t)n * h * w - 1) * ld + D) * 4;
+            if (op == CBAS_DEBUG_ROWS_CNX_DOWNSAMPLE) {
+                if (h < 2 || w < 2) return cbas_fail(CBAS_EINVAL, "downsample: a %d x %d grid has no 2 x 2 window", h, w);
+                out_need = (int64_t)n * (h / 2) * (w / 2) * 4 * D * 4;
+            } else if (op == CBAS_DEBUG_ROWS_CNX_DWCONV_LN) {
+                if (!a->wt || !a->bias) return cbas_fail(CBAS_EINVAL, "dwconv: wt / bias");
+                out_need = (int64_t)n * h * w * D * 4;
+            }
+        }
+        if (cls) {
+            if (!a->out && !a->out2) return cbas_fail(CBAS_EINVAL, "cls_f32 and cls_f16 both NULL");
+            out_need = a->out ? (int64_t)n * D * 4 : 0;
+            out2_need = a->out2 ? (int64_t)n * D * 2 : 0;
+        }
+    }
+    if ((x_need && (!a->x || a->x_bytes < x_need)) || (out_need && (!a->out || a->out_bytes < out_need)) ||
+        (out2_need && (!a->out2 || a->out2_bytes < out2_need)))
+        return cbas_fail(CBAS_EINVAL, "op %d: an image is missing or too small (x %lld of %lld, out %lld of %lld, out2 %lld of %lld bytes)", op,
+                         (long long)a->x_bytes, (long long)x_need, (long long)a->out_bytes, (long long)out_need, (long long)a->out2_bytes,
+                         (long long)out2_need);
+    DevBufs B;
+    char *x = nullptr, *out = nullptr, *out2 = nullptr;
+    float *gamma = nullptr, *beta = nullptr, *wt = nullptr, *bias = nullptr;
+    unsigned* counter = nullptr;
+    const auto upload = [&B](auto** dev, const void* host, size_t bytes) -> hipError_t {
+        const hipError_t e = B.alloc(dev, bytes);
+        return e != hipSuccess ? e : hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice);
+    };
+    if (x_need) HIP_TRY(upload(&x, a->x, (size_t)a->x_bytes));
+    if (out_need) HIP_TRY(upload(&out, a->out, (size_t)a->out_bytes));
+    if (out2_need) HIP_TRY(upload(&out2, a->out2, (size_t)a->out2_bytes));
+    if (!stem) {
+        HIP_TRY(upload(&gamma, a->gamma, (size_t)D * 4));
+        HIP_TRY(upload(&beta, a->beta, (size_t)D * 4));
+    }
+    if (op == CBAS_DEBUG_ROWS_CNX_DWCONV_LN) {
+        HIP_TRY(upload(&wt, a->wt, (size_t)49 * D * 4));
+        HIP_TRY(upload(&bias, a->bias, (size_t)D * 4));
+    }
+    if (cls && a->counter) HIP_TRY(upload(&counter, a->counter, 4));
+    const float* xf = reinterpret_cast<const float*>(x);
+    float* of = reinterpret_cast<float*>(out);
+    const float eps = a->eps;
+    const int split = a->split ? 1 : 0;
+    int rc = -1;
+    switch (op) {
+        case CBAS_DEBUG_ROWS_LN_F16: rc = launch_layernorm_f16(xf, ld, gamma, beta, (f16*)out, M, D, eps, 0); break;
+        case CBAS_DEBUG_ROWS_LN_F32: rc = launch_layernorm_f32(xf, ld, gamma, beta, of, M, D, eps, 0, 0); break;
+        case CBAS_DEBUG_ROWS_LN_SPLIT: rc = launch_layernorm_f32(xf, ld, gamma, beta, of, M, D, eps, 1, 0); break;
+        case CBAS_DEBUG_ROWS_LN_F8: rc = launch_layernorm_f8(xf, ld, gamma, beta, (uint8_t*)out, (uint32_t*)out2, a->sc_ld, M, D, eps, 0); break;
+        case CBAS_DEBUG_ROWS_FINAL_CLS: rc = launch_final_norm_cls(xf, gamma, beta, of, (f16*)out2, n, a->T, D, eps, 0, counter); break;
+        case CBAS_DEBUG_ROWS_CNX_STEM_U8:
+            rc = launch_cnx_stem_im2col_u8((const uint8_t*)x, n, h, w, a->frame_stride, a->row_stride, a->pixel_stride, of, split, 0);
+            break;
+        case CBAS_DEBUG_ROWS_CNX_STEM_F32: rc = launch_cnx_stem_im2col_f32(xf, n, h, w, of, split, 0); break;
+        case CBAS_DEBUG_ROWS_CNX_LN_ROWS: rc = launch_cnx_ln_rows(of, ld, gamma, beta, M, D, eps, 0); break;
+        case CBAS_DEBUG_ROWS_CNX_DOWNSAMPLE: rc = launch_cnx_downsample(xf, ld, n, h, w, gamma, beta, D, eps, of, split, 0); break;
+        case CBAS_DEBUG_ROWS_CNX_DWCONV_LN: rc = launch_cnx_dwconv_ln(xf, ld, n, h, w, wt, bias, gamma, beta, D, eps, of, split, 0); break;
+        case CBAS_DEBUG_ROWS_CNX_POOL_LN: rc = launch_cnx_pool_ln(xf, ld, n, h * w, gamma, beta, D, eps, of, (f16*)out2, counter, 0); break;
+    }
+    if (rc) return cbas_fail(CBAS_EINVAL, "row kernel launch failed (op %d, D %d: rc=%d)", op, D, rc);
+    HIP_TRY(hipDeviceSynchronize());
+    if (out_need) HIP_TRY(hipMemcpy(a->out, out, (size_t)a->out_bytes, hipMemcpyDeviceToHost));
+    if (out2_need) HIP_TRY(hipMemcpy(a->out2, out2, (size_t)a->out2_bytes, hipMemcpyDeviceToHost));
+    if (counter) HIP_TRY(hipMemcpy(a->counter, counter, 4, hipMemcpyDeviceToHost));
+    return CBAS_OK;
+}

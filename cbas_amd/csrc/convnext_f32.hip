@@ -23,9 +23,10 @@
 
 namespace {
 
-// LayerNorm of one row held as NV f32x4 per lane (groups lane + 64 k < C / 4), the reference's two-pass form
+// LayerNorm of one row held as NV f32x4 per lane (groups lane + 64 k < C / 4), the reference's two-pass form; returns rstd
+// (0 when the variance overflowed fp32, NaN for a non-finite row)
 template <int NV>
-__device__ __forceinline__ void cnx_ln(f32x4 (&v)[NV], int C, float eps, const float* __restrict__ gamma,
+__device__ __forceinline__ float cnx_ln(f32x4 (&v)[NV], int C, float eps, const float* __restrict__ gamma,
                                        const float* __restrict__ beta, int lane) {
     const int nvec = C >> 2;
     float s = 0.f;
@@ -54,6 +55,7 @@ __device__ __forceinline__ void cnx_ln(f32x4 (&v)[NV], int C, float eps, const f
             v[k] = (v[k] - mean) * rstd * g + b;
         }
     }
+    return rstd;
 }
 
 // one thread = one output pixel of the stem: 16 pixels in, 32 floats out (plain or split)
@@ -217,9 +219,9 @@ __global__ __launch_bounds__(256) void cnx_pool_ln_kernel(const float* __restric
         const int idx = lane + 64 * k;
         v[k] = (((part[0][idx] + part[1][idx]) + part[2][idx]) + part[3][idx]) / inv;
     }
-    cnx_ln<NV>(v, C, eps, gamma, beta, lane);
+    const float rstd = cnx_ln<NV>(v, C, eps, gamma, beta, lane);
     if (nonfinite) {
-        bool bad = false;
+        bool bad = !(rstd > 0.f);          // an overflowed variance gives rstd = 0 and a finite row (beta)
 #pragma unroll
         for (int k = 0; k < NV; ++k)
             if (lane + 64 * k < nvec) {
@@ -263,7 +265,7 @@ int launch_cnx_stem_im2col_u8(const uint8_t* frames, int n, int height, int widt
                               int64_t pixel_stride, float* A, int split, hipStream_t stream) {
     const int ho = height / 4, wo = width / 4;
     const int64_t total = (int64_t)n * ho * wo;
-    if (total <= 0) return -1;
+    if (n <= 0 || height < 4 || width < 4 || frame_stride <= 0 || row_stride <= 0 || pixel_stride <= 0) return -1;
     hipLaunchKernelGGL(cnx_stem_im2col_kernel<uint8_t>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, frames, n,
                        frame_stride, row_stride, pixel_stride, ho, wo, A, split);
     return CHECK_LAUNCH();
@@ -272,7 +274,7 @@ int launch_cnx_stem_im2col_u8(const uint8_t* frames, int n, int height, int widt
 int launch_cnx_stem_im2col_f32(const float* frames, int n, int height, int width, float* A, int split, hipStream_t stream) {
     const int ho = height / 4, wo = width / 4;
     const int64_t total = (int64_t)n * ho * wo;
-    if (total <= 0) return -1;
+    if (n <= 0 || height < 4 || width < 4) return -1;
     hipLaunchKernelGGL(cnx_stem_im2col_kernel<float>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, frames, n,
                        (int64_t)height * width, (int64_t)width, (int64_t)1, ho, wo, A, split);
     return CHECK_LAUNCH();
@@ -288,7 +290,7 @@ int launch_cnx_downsample(const float* x, int64_t ldx, int n, int hi, int wi, co
                           float* A, int split, hipStream_t stream) {
     const int ho = hi / 2, wo = wi / 2;
     const int64_t M = (int64_t)n * ho * wo;
-    if (!cnx_ok(C) || ldx < C || M <= 0 || M > 0x7fffffff) return -1;
+    if (!cnx_ok(C) || ldx < C || n <= 0 || hi < 2 || wi < 2 || M > 0x7fffffff) return -1;
     CNX_NV_SWITCH(cnx_nv(C), cnx_downsample_kernel, dim3((unsigned)M), dim3(256), 0, stream, x, ldx, hi, wi, n, ho, wo, gamma, beta, C,
                   eps, A, split);
     return CHECK_LAUNCH();
@@ -297,7 +299,7 @@ int launch_cnx_downsample(const float* x, int64_t ldx, int n, int hi, int wi, co
 int launch_cnx_dwconv_ln(const float* x, int64_t ld, int n, int hh, int ww, const float* wt, const float* bias, const float* gamma,
                          const float* beta, int C, float eps, float* A, int split, hipStream_t stream) {
     const int64_t M = (int64_t)n * hh * ww;
-    if (!cnx_ok(C) || ld < C || M <= 0) return -1;
+    if (!cnx_ok(C) || ld < C || n <= 0 || hh <= 0 || ww <= 0) return -1;
     CNX_NV_SWITCH(cnx_nv(C), cnx_dwconv_ln_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, stream, x, ld, n, hh, ww, wt, bias, gamma,
                   beta, C, eps, A, split);
     return CHECK_LAUNCH();

@@ -133,7 +133,8 @@ int launch_ln_stats_x16(const float* x, f16* x16, float2* ln_out, int ln_ld, int
 int launch_fold_ln_weight(const float* W, const float* gamma, const float* beta, const float* b, f16* Wf, float* colsum,
                           float* biasf, int N, int K, hipStream_t stream);
 // Final LayerNorm on the CLS row of every frame: x[b*T] -> cls_f32[b][D] / cls_f16[b][D]
-// `nonfinite` (may be NULL): incremented once per frame whose CLS row holds a NaN / infinity
+// `nonfinite` (may be NULL): incremented once per frame whose CLS row holds a NaN / infinity or a finite value whose square
+// overflows the variance (rstd = 0: the row would come out as beta)
 int launch_final_norm_cls(const float* x, const float* gamma, const float* beta, float* cls_f32,
                           f16* cls_f16, int n, int T, int D, float eps, hipStream_t stream, unsigned* nonfinite = nullptr);
 

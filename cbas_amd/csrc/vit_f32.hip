@@ -1007,7 +1007,7 @@ int launch_pack_patch_weight_f32(const float* w, float* out, int D, int ps, hipS
 
 int launch_layernorm_f32(const float* x, int64_t ldx, const float* gamma, const float* beta, float* out, int M, int D,
                          float eps, int split, hipStream_t stream) {
-    if (split && D % 32) return -1;
+    if (M <= 0 || D <= 0 || D % 4 || ldx < D || (split && D % 32)) return -1;     // 16-byte vectors; split: whole 32-column tiles
     const int nv = (D / 4 + 63) / 64;
     const dim3 grid((M + 3) / 4), block(256);
     switch (nv) {

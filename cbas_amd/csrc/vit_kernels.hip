@@ -84,8 +84,9 @@ __global__ void write_prefix_kernel(float* __restrict__ x, const float* __restri
 // LayerNorm: one wave per row, two-pass statistics in registers (matches the reference's
 // mean / biased-variance formulation), fp32 in, fp16 out.
 // ---------------------------------------------------------------------------------------------
+// Returns rstd: 0 when the variance overflowed fp32, NaN when the row holds a NaN / infinity (the range checks below read it).
 template <int NV>
-__device__ __forceinline__ void ln_row(const float* __restrict__ xr, const float* __restrict__ gamma,
+__device__ __forceinline__ float ln_row(const float* __restrict__ xr, const float* __restrict__ gamma,
                                        const float* __restrict__ beta, int D, float eps, int lane,
                                        f32x4 (&y)[NV]) {
     const int nvec = D >> 2;
@@ -117,6 +118,7 @@ __device__ __forceinline__ void ln_row(const float* __restrict__ xr, const float
             y[k] = (v[k] - mean) * rstd * g + bb;
         }
     }
+    return rstd;
 }
 
 template <int NV>
@@ -234,14 +236,15 @@ __global__ __launch_bounds__(256) void final_norm_cls_kernel(const float* __rest
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= n) return;
     f32x4 y[NV];
-    ln_row<NV>(x + (size_t)b * T * D, gamma, beta, D, eps, lane, y);
+    const float rstd = ln_row<NV>(x + (size_t)b * T * D, gamma, beta, D, eps, lane, y);
     const int nvec = D >> 2;
     // A non-finite value anywhere in the encoder reaches the CLS row (every query attends to every key): one test per
     // frame here watches the whole forward pass.  The reference's fp32 arithmetic has no range limit; the split-fp16 operands
     // of precision 4 (|x| scale < 65 504, vit32_epilogue.h) and the fp16 activations of precision 0 do - a violation is
     // counted and turned into CBAS_ERANGE at the next wait instead of NaN rows in a `_cls.h5`.
+    // A finite value whose square overflows the variance gives rstd = 0 and a finite row (beta): counted through rstd.
     if (nonfinite) {
-        bool bad = false;
+        bool bad = !(rstd > 0.f);
 #pragma unroll
         for (int k = 0; k < NV; ++k)
             if (lane + 64 * k < nvec) {
@@ -906,6 +909,7 @@ int launch_im2col_f32(const float* frames, int n, int height, int width, f16* A,
 
 int launch_layernorm_f16(const float* x, int64_t ldx, const float* gamma, const float* beta, f16* out, int M, int D,
                          float eps, hipStream_t stream) {
+    if (M <= 0 || D <= 0 || D % 4 || ldx < D) return -1;     // rows are read as 16-byte vectors
     const int nv = (D / 4 + 63) / 64;
     const dim3 grid((M + 3) / 4), block(256);
     switch (nv) {
@@ -939,10 +943,12 @@ int launch_fold_ln_weight(const float* W, const float* gamma, const float* beta,
 
 int launch_layernorm_f8(const float* x, int64_t ldx, const float* gamma, const float* beta, uint8_t* out8,
                         uint32_t* out_sc, int sc_ld, int M, int D, float eps, hipStream_t stream) {
-    if (D % 128 || D > 1024) return -1;             // precision 2 stops at D = 1024 (cbas_enc_create refuses wider handles)
+    // precision 2 runs D = 256 .. 1024 (cbas_enc_create refuses other handles; the fp8 GEMMs take K-tiles of 128 in pairs)
+    if (D % 128 || D < 256 || D > 1024 || M <= 0 || ldx < D || sc_ld < M) return -1;
     const int nv = (D / 4 + 63) / 64;
     const dim3 grid((M + 3) / 4), block(256);
     switch (nv) {
+        case 1: hipLaunchKernelGGL(layernorm_f8_kernel<1>, grid, block, 0, stream, x, ldx, gamma, beta, out8, out_sc, sc_ld, M, D, eps); break;      // D = 256
         case 2: hipLaunchKernelGGL(layernorm_f8_kernel<2>, grid, block, 0, stream, x, ldx, gamma, beta, out8, out_sc, sc_ld, M, D, eps); break;
         case 3: hipLaunchKernelGGL(layernorm_f8_kernel<3>, grid, block, 0, stream, x, ldx, gamma, beta, out8, out_sc, sc_ld, M, D, eps); break;
         case 4: hipLaunchKernelGGL(layernorm_f8_kernel<4>, grid, block, 0, stream, x, ldx, gamma, beta, out8, out_sc, sc_ld, M, D, eps); break;
@@ -953,6 +959,7 @@ int launch_layernorm_f8(const float* x, int64_t ldx, const float* gamma, const f
 
 int launch_final_norm_cls(const float* x, const float* gamma, const float* beta, float* cls_f32,
                           f16* cls_f16, int n, int T, int D, float eps, hipStream_t stream, unsigned* nonfinite) {
+    if (n <= 0 || T <= 0 || D <= 0 || D % 4) return -1;
     const int nv = (D / 4 + 63) / 64;
     const dim3 grid((n + 3) / 4), block(256);
     switch (nv) {

@@ -149,6 +149,57 @@ typedef struct cbas_debug_attention_args {
 } cbas_debug_attention_args;
 int cbas_debug_attention_run(const cbas_debug_attention_args* a);
 
+/* Tests: ONE launch of a row-wise encoder kernel on host operands (tests/test_gpu_rows_reference.py compares it with the float64
+ * references of oracle/kernel_ref.py).  The harness uploads x (x_bytes) and the caller's pre-filled output images (out_bytes /
+ * out2_bytes / *counter), runs exactly one launcher on the default stream and copies the whole output images back: whatever
+ * the launch does not own is the caller's canary.  It refuses (CBAS_EINVAL, nothing launched) every shape a launcher would
+ * mis-handle: M or n <= 0, D % 4 != 0 (LN_SPLIT and the ConvNeXt ops: D % 32) or beyond the launcher's switch (ViT 1280, LN_F8
+ * 256 .. 1024 in steps of 128, ConvNeXt 1536), ld < D, sc_ld < M, null pointers, and any row / frame / pixel stride whose last
+ * read or write would leave x_bytes / out_bytes / out2_bytes.
+ *   op                launcher                              x                          out (out2)
+ *   LN_F16            launch_layernorm_f16                  [M][ld] f32                [M][D] fp16
+ *   LN_F32, LN_SPLIT  launch_layernorm_f32 (split 0 / 1)    [M][ld] f32                [M][D] f32 / split image
+ *   LN_F8             launch_layernorm_f8                   [M][ld] f32                [M][D] e4m3 bytes (out2: [D/128][sc_ld] dwords)
+ *   FINAL_CLS         launch_final_norm_cls                 [n][T][D] f32 (row 0 read) cls_f32 [n][D] (out2: cls_f16 [n][D]); either may be NULL
+ *   CNX_STEM_U8       launch_cnx_stem_im2col_u8 (split)     bytes, the three strides   A [n (h/4) (w/4)][32]
+ *   CNX_STEM_F32      launch_cnx_stem_im2col_f32 (split)    [n][h][w] f32              A [n (h/4) (w/4)][32]
+ *   CNX_LN_ROWS       launch_cnx_ln_rows                    -                          in place: [M][ld] f32
+ *   CNX_DOWNSAMPLE    launch_cnx_downsample (split)         [n][h][w][ld] f32          A [n (h/2) (w/2)][4 D]
+ *   CNX_DWCONV_LN     launch_cnx_dwconv_ln (split)          [n][h][w][ld] f32          A [n h w][D]; wt [49][D], bias [D]
+ *   CNX_POOL_LN       launch_cnx_pool_ln                    [n][h w][ld] f32           as FINAL_CLS
+ * counter (FINAL_CLS / CNX_POOL_LN): the non-finite counter, in / out; NULL hands the launcher nonfinite = NULL. */
+enum {
+    CBAS_DEBUG_ROWS_LN_F16 = 0, CBAS_DEBUG_ROWS_LN_F32 = 1, CBAS_DEBUG_ROWS_LN_SPLIT = 2, CBAS_DEBUG_ROWS_LN_F8 = 3,
+    CBAS_DEBUG_ROWS_FINAL_CLS = 4, CBAS_DEBUG_ROWS_CNX_STEM_U8 = 5, CBAS_DEBUG_ROWS_CNX_STEM_F32 = 6,
+    CBAS_DEBUG_ROWS_CNX_LN_ROWS = 7, CBAS_DEBUG_ROWS_CNX_DOWNSAMPLE = 8, CBAS_DEBUG_ROWS_CNX_DWCONV_LN = 9,
+    CBAS_DEBUG_ROWS_CNX_POOL_LN = 10
+};
+typedef struct cbas_debug_rows_args {
+    int64_t struct_bytes;        /* sizeof(cbas_debug_rows_args): a mismatch is rejected */
+    int op, split;               /* split: the split = 1 form of the CNX_STEM_* / CNX_DOWNSAMPLE / CNX_DWCONV_LN operand */
+    int M;                       /* rows (LN_*, CNX_LN_ROWS) */
+    int n;                       /* frames (every other op) */
+    int D;                       /* D, resp. the ConvNeXt width C */
+    int T;                       /* FINAL_CLS: tokens per frame */
+    int h, w;                    /* frame height / width in pixels (stem), resp. the grid of the spatial ops */
+    int sc_ld;                   /* LN_F8: rows of a K-tile's scale image */
+    float eps;
+    int64_t ld;                  /* row stride of x (CNX_LN_ROWS: of out) in elements */
+    int64_t frame_stride, row_stride, pixel_stride;     /* CNX_STEM_U8, bytes */
+    const void* x;
+    int64_t x_bytes;
+    const float* gamma;          /* [D] */
+    const float* beta;           /* [D] */
+    const float* wt;             /* CNX_DWCONV_LN: [49][D] */
+    const float* bias;           /* CNX_DWCONV_LN: [D] */
+    void* out;                   /* in / out */
+    int64_t out_bytes;
+    void* out2;                  /* in / out: LN_F8 scales, cls_f16 */
+    int64_t out2_bytes;
+    uint32_t* counter;           /* in / out, or NULL */
+} cbas_debug_rows_args;
+int cbas_debug_rows_run(const cbas_debug_rows_args* a);
+
 /* Root-cause probe (round 5): run a kernel from a separately built code object IN PLACE of the library's head_expand_kernel
  * on this handle (same grid, block, dynamic LDS and arguments: scripts/probes/expand_r4/expand_r4.hip has the signature).
  * hsaco_path = NULL restores the library's kernel.  scripts/expand_rootcause.py builds instruction-level variants of the

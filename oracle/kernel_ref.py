@@ -1,8 +1,10 @@
 """ORACLE (test infrastructure, not product code): float64 references of single GEMM and attention launches, the
-exact precision-3 accumulator, and element-wise error bounds derived from where each kernel rounds.
+exact precision-3 accumulator, the row-wise kernels between the GEMMs (LayerNorm forms, the MX-fp8 row, the ConvNeXt
+producers), and element-wise error bounds derived from where each kernel rounds.
 
-Used by tests/test_gpu_kernel_reference.py (the kernels through cbas_debug_gemm_run / cbas_debug_attention_run) and
-tests/test_kernel_reference_bounds.py (the references and bounds themselves, on the CPU).
+Used by tests/test_gpu_kernel_reference.py (the kernels through cbas_debug_gemm_run / cbas_debug_attention_run),
+tests/test_gpu_rows_reference.py (cbas_debug_rows_run) and tests/test_kernel_reference_bounds.py (the references and
+bounds themselves, on the CPU).
 
 Units: u32 = 2^-24 (fp32 unit roundoff), u16 = 2^-11 (fp16).  A bound is a float64 array shaped like the output; a kernel
 output y passes when |y - ref| <= bound everywhere (non-finite y never passes).  Every bound is a sum of the terms its
@@ -269,6 +271,201 @@ def attention_ref(arith: int, qkv: np.ndarray, n: int, T: int, D: int, q_cls=Non
         bound = bound + U32 * np.abs(O)
     to_rows = lambda x: x.transpose(0, 2, 1, 3).reshape(n * nq, D)   # noqa: E731
     return to_rows(O), to_rows(bound)
+
+
+# ---- row-wise kernels: LayerNorm forms, the MX-fp8 row, the ConvNeXt producers -----------------------------------------
+# Accuracy of the device's fp32 division and sqrtf, in units of u32 (half an ulp).  The library is built with hipcc -O3 and
+# no fast-math switch (cbas_amd/build.py), so -fhip-fp32-correctly-rounded-divide-sqrt holds (hipcc's default): `/` is
+# IEEE-correct (half an ulp = 1 u32); for sqrtf the HIP math API documents 1 ulp (= 2 u32), which is what is budgeted.
+DIV_U = 1.0
+SQRT_U = 2.0
+DW_TAPS = 49
+
+
+def ln_levels(D: int) -> int:
+    """Depth of the kernels' sum over D terms (ln_row / layernorm_f32_kernel / cnx_ln): pairwise inside a 4-vector (2
+    levels), one accumulation per vector a lane holds (NV = ceil(D / 256)), then the 6-step xor butterfly.  A value passes
+    through at most that many fp32 additions, so the sum is off by at most levels u32 sum |x| to first order."""
+    return 2 + (D // 4 + 63) // 64 + 6
+
+
+def ln_ref(x, gamma, beta, eps, Ex=None):
+    """LayerNorm over the last axis with the biased variance, float64: y = (x - mean) / sqrt(var + eps) gamma + beta, eps
+    the fp32 value the kernel receives.  Returns (y, bound); the bound follows the kernels' two-pass form, L = ln_levels(D):
+      mean   fp32 sum of D terms, then a division:         K = L u32 sum |x| / D + DIV_U u32 |mean|  (+ mean(Ex))
+      centre d_i = fl(x_i - mean^): off by the common K (its effect on sum d^2 is D K^2 exactly, as sum c_i = 0) and by
+             r_i = u32 (|c_i| + K) (+ Ex_i) of its own
+      var    Eq = D K^2 + sum r_i (2 |c_i| + 2 K + r_i) + (L + 1) u32 sum (|c_i| + K + r_i)^2   (squares, sum), then
+             t = fl(fl(q / D) + eps): Et = Eq / D + (DIV_U + 1) u32 (t + Eq / D)
+      rstd   1 / sqrtf(t): relative rel = |sqrt(t / (t -+ Et)) - 1| + (SQRT_U + DIV_U) u32
+      out    y = fl(fl(fl(d rstd) g) + b): E = |g| rstd ((1 + rel) (K + r_i) + |c_i| rel), + 2 u32 (|c rstd g| + E)
+             + u32 (|y| + E) for the two products and the sum (a fused multiply-add only removes one of them)
+    Ex (optional, shaped like x): what the kernel's input is already off by when x itself is computed on the device (the
+    pooled mean, the depthwise convolution).  The output format's rounding is the caller's (out_rounding)."""
+    x = np.asarray(x, np.float64)
+    g = np.asarray(gamma, np.float64)
+    b = np.asarray(beta, np.float64)
+    D = x.shape[-1]
+    L = ln_levels(D)
+    e = float(np.float32(eps))
+    ex = np.zeros_like(x) if Ex is None else np.asarray(Ex, np.float64)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        mean = x.mean(-1, keepdims=True)
+        K = (L * U32 * (np.abs(x) + ex).sum(-1, keepdims=True) / D + DIV_U * U32 * np.abs(mean)) * (1 + 2 * L * U32) \
+            + ex.mean(-1, keepdims=True)
+        c = x - mean
+        ac = np.abs(c)
+        r = U32 * (ac + K + ex) + ex
+        var = (c * c).mean(-1, keepdims=True)
+        Eq = D * K * K + (r * (2 * ac + 2 * K + r)).sum(-1, keepdims=True) + (L + 1) * U32 * ((ac + K + r) ** 2).sum(-1, keepdims=True)
+        t = var + e
+        Et = Eq / D + (DIV_U + 1) * U32 * (t + Eq / D)
+        lo = np.where(t > Et, t - Et, np.nan)                       # the bound is infinite where the variance is lost
+        rel = np.maximum(np.sqrt(t / lo) - 1.0, 1.0 - np.sqrt(t / (t + Et))) + (SQRT_U + DIV_U) * U32 * (1 + 2.0 ** -20)
+        rel = np.where(np.isfinite(rel), rel, np.inf)
+        rstd = 1.0 / np.sqrt(t)
+        y = c * rstd * g + b
+        E = np.abs(g) * rstd * ((1 + rel) * (K + r) + ac * rel)
+        E = E + 2 * U32 * (np.abs(c * rstd * g) + E) + U32 * (np.abs(y) + E)
+    return y, E
+
+
+def stored_bound(ref, E, kind: str) -> np.ndarray:
+    """Bound of a row kernel's stored output: E, plus the format's rounding of a value within E of ref ('f16', 'f32', or
+    'split' at scale 1: 2^-22 relative and 2^-25 where a half falls below fp16's normal range)."""
+    return E + out_rounding(np.abs(ref) + E, kind) + (F16_SUB if kind == "split" else 0.0)
+
+
+def rows_case(M: int, D: int, seed: int, ld: int | None = None, traps: bool = True):
+    """The inputs of a LayerNorm case, shared by the GPU tests and the CPU validation: M random rows [M][ld] (columns past D
+    hold 7.0 and are never read), gains and offsets that differ per column, and - when there is room - the trap rows: a
+    large mean with a small spread (1e3, sd 1), a constant row, a row with one massive channel."""
+    rng = np.random.default_rng(seed)
+    ld = ld or D
+    x = np.full((M, ld), 7.0, np.float32)
+    x[:, :D] = (rng.standard_normal((M, D)) * rng.uniform(0.2, 3.0, (M, 1)) + rng.standard_normal((M, 1))).astype(np.float32)
+    if traps:
+        x[0, :D] = (1e3 + rng.standard_normal(D)).astype(np.float32)
+        if M > 1:
+            x[1, :D] = np.float32(2.7182817)
+        if M > 2:
+            x[2, int(rng.integers(D))] = np.float32(1.0e4)
+    gamma = (1.0 + 0.5 * rng.standard_normal(D)).astype(np.float32)
+    beta = (0.3 * rng.standard_normal(D)).astype(np.float32)
+    return x, gamma, beta
+
+
+def mx_row_seed(D: int, M: int) -> int:
+    """Seed of the LN_F8 GPU case (D, M): tests/test_kernel_reference_bounds.py checks on the CPU that the reference alone
+    leaves at most 1 % of a case's blocks within the bound of a scale boundary."""
+    return 3000 + D + M + (10000 if (D, M) == (384, 4) else 0)      # 3388 puts 1 of that case's 48 blocks at a boundary
+
+
+# MX-fp8 row (layernorm_f8_kernel): e4m3 elements, one E8M0 scale byte per 32 columns
+def e4m3_half_step(a) -> np.ndarray:
+    """Half the spacing of e4m3 at magnitude a (in units of the block scale): 2^(floor(log2 a) - 4), 2^-10 in the subnormal
+    range below 2^-6; a value that lands exactly on a power of two from below still rounds within the lower binade's step."""
+    a = np.asarray(a, np.float64)
+    with np.errstate(divide="ignore"):
+        e = np.floor(np.log2(np.maximum(a, 2.0 ** -6)))
+    return 2.0 ** (np.clip(e, -6, 8) - 4)
+
+
+def mx_row_decode(bytes8: np.ndarray, sc: np.ndarray, M: int, D: int):
+    """out8 [M][D] e4m3 bytes + out_sc [D/128][sc_ld] dwords (byte b of dword (kt, row) = block 4 kt + b) ->
+    (values float64 [M][D], scale bytes [M][D/32])."""
+    from oracle.mx_oracle import e4m3_decode
+    sb = np.ascontiguousarray(sc).view(np.uint8).reshape(D // 128, -1, 4)[:, :M, :]          # [kt][row][b]
+    sb = sb.transpose(1, 0, 2).reshape(M, D // 32).astype(np.int32)
+    s = 2.0 ** (sb.astype(np.float64) - 127.0)
+    v = e4m3_decode(bytes8[:M, :D]).astype(np.float64).reshape(M, D // 32, 32) * s[:, :, None]
+    return v.reshape(M, D), sb
+
+
+def mx_row_bound(y: np.ndarray, E: np.ndarray, sb: np.ndarray) -> np.ndarray:
+    """LayerNorm bound E plus the e4m3 half-step at the scale the kernel chose (sb [M][D/32]): the element rounded is
+    within E of y, so its magnitude in scale units is at most (|y| + E) / s."""
+    s = np.repeat(2.0 ** (sb.astype(np.float64) - 127.0), 32, axis=1)
+    return E + s * e4m3_half_step((np.abs(y) + E) / s)
+
+
+def mx_scale_window(y: np.ndarray, E: np.ndarray):
+    """Scale bytes of the reference's 32-column block maxima, pushed down / up by the LayerNorm bound:
+    (expected, lowest accepted, highest accepted) [M][D/32]; lowest != highest marks a block within the bound of a boundary."""
+    from oracle.mx_oracle import mx_scale_exp
+    M, D = y.shape
+    a = np.abs(y).reshape(M, D // 32, 32)
+    e = E.reshape(M, D // 32, 32)
+    return mx_scale_exp(a.max(-1)), mx_scale_exp(np.maximum(a - e, 0.0).max(-1)), mx_scale_exp((a + e).max(-1))
+
+
+# ConvNeXt producers.  Activations are channels-last [n][h][w][C] float64 views of the fp32 rows.
+def cnx_stem_ref(frames: np.ndarray, u8: bool) -> np.ndarray:
+    """Stem gather of [n][h][w] green planes: A[(b, oy, ox)][4 i + j] = pixel (4 oy + i, 4 ox + j), u8 as
+    np.float32(px / 255.0); columns 16 .. 31 zero.  Exact: returns float32 [n (h/4) (w/4)][32]."""
+    n, h, w = frames.shape
+    ho, wo = h // 4, w // 4
+    v = frames[:, :4 * ho, :4 * wo].reshape(n, ho, 4, wo, 4).transpose(0, 1, 3, 2, 4).reshape(n * ho * wo, 16)
+    v = (v.astype(np.float64) / 255.0).astype(np.float32) if u8 else v.astype(np.float32)
+    return np.concatenate([v, np.zeros_like(v)], axis=1)
+
+
+def cnx_downsample_ref(x, gamma, beta, eps):
+    """A[(b, oy, ox)][(2 kh + kw) C + c] = LayerNorm(x[b, 2 oy + kh, 2 ox + kw])[c]; the last row / column of an odd grid is
+    not read.  Returns (A [n ho wo][4 C], bound)."""
+    n, h, w, C = x.shape
+    ho, wo = h // 2, w // 2
+    y, E = ln_ref(x[:, :2 * ho, :2 * wo], gamma, beta, eps)
+    win = lambda t: t.reshape(n, ho, 2, wo, 2, C).transpose(0, 1, 3, 2, 4, 5).reshape(n * ho * wo, 4 * C)   # noqa: E731
+    return win(y), win(E)
+
+
+def cnx_dwconv_ref(x, wt, bias):
+    """Depthwise 7 x 7, zero padding 3, taps tap-major wt [49][C] (tap = 7 ky + kx reads pixel (y + ky - 3, x + kx - 3)),
+    plus bias.  Returns (conv [n][h][w][C], Ex): the kernel's fmaf chain over at most 49 taps and the bias addition are off
+    by at most (49 + 1) u32 (sum |w a| + |b|)."""
+    x = np.asarray(x, np.float64)
+    wt = np.asarray(wt, np.float64)
+    n, h, w, C = x.shape
+    xp = np.zeros((n, h + 6, w + 6, C))
+    xp[:, 3:3 + h, 3:3 + w] = x
+    acc = np.zeros_like(x)
+    mag = np.zeros_like(x)
+    for ky in range(7):
+        for kx in range(7):
+            p = xp[:, ky:ky + h, kx:kx + w] * wt[7 * ky + kx]
+            acc += p
+            mag += np.abs(p)
+    b = np.asarray(bias, np.float64)
+    return acc + b, (DW_TAPS + 1) * U32 * (mag + np.abs(b))
+
+
+def cnx_dwconv_ln_ref(x, wt, bias, gamma, beta, eps):
+    conv, Ex = cnx_dwconv_ref(x, wt, bias)
+    n, h, w, C = conv.shape
+    y, E = ln_ref(conv.reshape(n * h * w, C), gamma, beta, eps, Ex.reshape(n * h * w, C))
+    return y, E
+
+
+def cnx_pool_ln_ref(x, gamma, beta, eps):
+    """LayerNorm(mean over the hw pixels of a frame), x [n][hw][C].  The kernel sums ceil(hw / 4) pixels per wave in order,
+    adds the four partial sums in order and divides: Ex = (ceil(hw / 4) + 3) u32 sum |x| / hw + DIV_U u32 |mean|."""
+    x = np.asarray(x, np.float64)
+    hw = x.shape[1]
+    p = x.mean(1)
+    Ex = ((hw + 3) // 4 + 3) * U32 * np.abs(x).sum(1) / hw + DIV_U * U32 * np.abs(p)
+    return ln_ref(p, gamma, beta, eps, Ex)
+
+
+def pool_order_f32(x32: np.ndarray) -> np.ndarray:
+    """The pooled mean in the kernel's own order, float32: wave w sums pixels w, w + 4, ... in order from +0, then
+    ((p0 + p1) + p2) + p3, divided by hw.  x32 [n][hw][C]."""
+    x32 = np.asarray(x32, np.float32)
+    n, hw, C = x32.shape
+    part = np.zeros((4, n, C), np.float32)
+    for p in range(hw):
+        part[p % 4] = part[p % 4] + x32[:, p]
+    return (((part[0] + part[1]) + part[2]) + part[3]) / np.float32(hw)
 
 
 def ratio(y, ref, bound) -> float:

@@ -225,3 +225,248 @@ def test_attention_bound_accepts_the_simulated_kernel_and_rejects_planted_defect
                      ("q's 1/8 missing", dict(no_q_scale=True))):
         r = R.ratio(_sim_attention(qkv, n, T, D, **kw), ref, bound)
         assert r > 1.0, (name, r)
+
+
+# ---- row-wise kernels: LayerNorm forms, the MX-fp8 row, the ConvNeXt producers ----------------------------------------
+F32 = np.float32
+
+
+def _sim_ln(x, gamma, beta, eps, *, unbiased=False, no_eps=False, one_pass=False, drop_last_vec=False):
+    """ln_row / layernorm_f32_kernel / cnx_ln in numpy float32 with the kernels' reduction order: a lane adds its 4-vectors
+    pairwise, accumulates them in order, then the xor butterfly 32, 16, .., 1 over the 64 lanes.  Optional planted defects."""
+    x = np.asarray(x, F32)
+    M, D = x.shape
+    nvec = D // 4
+    NV = (nvec + 63) // 64
+    valid = (np.arange(NV * 64) < nvec).reshape(NV, 64)
+    xp = np.zeros((M, NV * 256), F32)
+    xp[:, :D] = x
+    xp = xp.reshape(M, NV, 64, 4)
+
+    def wave_sum(vec4, mask):                                     # vec4 [M][NV][64][4] -> [M]
+        pair = (vec4[..., 0] + vec4[..., 1]) + (vec4[..., 2] + vec4[..., 3])
+        s = np.zeros((M, 64), F32)
+        for k in range(NV):
+            s = s + np.where(mask[k], pair[:, k], F32(0))
+        for o in (32, 16, 8, 4, 2, 1):
+            s = s + s[:, np.arange(64) ^ o]
+        return s[:, 0]
+
+    mmask = valid.copy()
+    if drop_last_vec:
+        mmask[NV - 1] = False
+    with np.errstate(all="ignore"):
+        mean = (wave_sum(xp, mmask) / F32(D))[:, None, None, None]
+        d = xp - mean
+        if one_pass:
+            q = wave_sum(xp * xp, valid) / F32(D) - mean[:, 0, 0, 0] * mean[:, 0, 0, 0]
+        else:
+            q = wave_sum(d * d, valid) / F32(D - 1 if unbiased else D)
+        rstd = F32(1) / np.sqrt(q + (F32(0) if no_eps else F32(eps)))
+        g = np.zeros(NV * 256, F32)
+        g[:D] = gamma
+        b = np.zeros(NV * 256, F32)
+        b[:D] = beta
+        y = d * rstd[:, None, None, None] * g.reshape(NV, 64, 4) + b.reshape(NV, 64, 4)
+    return y.reshape(M, NV * 256)[:, :D]
+
+
+def _store(y32, kind):
+    """The output format's rounding of an fp32 row: fp16, fp32, or the split pair at scale 1."""
+    if kind == "f16":
+        return y32.astype(np.float16).astype(np.float64)
+    if kind == "split":
+        return R.split_value(y32, 1.0)
+    return y32.astype(np.float64)
+
+
+LN_DEFECTS = ("unbiased", "no_eps", "one_pass", "drop_last_vec")
+
+
+@pytest.mark.parametrize("kind", ["f16", "f32", "split"])
+@pytest.mark.parametrize("D", [128, 256, 384, 768, 1024, 1280, 96, 800, 1536])
+def test_layernorm_bound_accepts_the_simulated_kernel_and_rejects_planted_defects(kind, D):
+    """ViT widths (NV 1 .. 5) and ConvNeXt widths (96: a partial only vector, 800: a partial vector at NV 4, 1536: NV 6)."""
+    rejected = set()
+    for eps in (1e-5, 1e-6):
+        x, gamma, beta = R.rows_case(9, D, 1000 + D)
+        ref, E = R.ln_ref(x, gamma, beta, eps)
+        bound = R.stored_bound(ref, E, kind)
+        r = R.ratio(_store(_sim_ln(x, gamma, beta, eps), kind), ref, bound)
+        print(f"[ln {kind} D {D} eps {eps:g}] simulated kernel: max err / bound {r:.3f}")
+        assert r <= 1.0
+        for name in LN_DEFECTS:
+            if name == "drop_last_vec" and (D // 4) % 64 == 0:
+                continue
+            if R.ratio(_store(_sim_ln(x, gamma, beta, eps, **{name: True}), kind), ref, bound) > 1.0:
+                rejected.add(name)
+    expect = set(LN_DEFECTS) - ({"drop_last_vec"} if (D // 4) % 64 == 0 else set())
+    if kind == "f16" and D >= 1024:
+        expect.discard("unbiased")           # 1 / (2 D) of the value is below fp16's own rounding there; caught at every D < 1024
+    assert rejected >= expect, expect - rejected
+
+
+def test_each_layernorm_defect_is_caught_where_it_should_be():
+    """Per trap row: the constant row catches the dropped eps, the mean-1e3 row the one-pass variance."""
+    D = 384
+    x, gamma, beta = R.rows_case(4, D, 7)
+    ref, E = R.ln_ref(x, gamma, beta, 1e-6)
+    bound = R.stored_bound(ref, E, "f32")
+    err = lambda **kw: np.abs(_sim_ln(x, gamma, beta, 1e-6, **kw) - ref) / bound    # noqa: E731
+    with np.errstate(invalid="ignore"):
+        assert not (np.nan_to_num(err(no_eps=True)[1], nan=np.inf) <= 1.0).all()
+        assert err(one_pass=True)[0].max() > 1.0
+        assert err(drop_last_vec=True).max(axis=1).min() > 1.0                     # every row
+        assert err(unbiased=True)[3].max() > 1.0                                   # a plain random row
+
+
+# MX-fp8 row
+def _sim_mx_row(y32, *, neighbour_block=False):
+    """layernorm_f8_kernel's store on the fp32 LayerNorm rows: block maximum -> scale byte -> e4m3 bytes, and the scale
+    image [D/128][sc_ld] dwords.  neighbour_block: each scale byte lands in the next 32-column block's slot."""
+    from oracle import mx_oracle as MX
+    M, D = y32.shape
+    sc_ld = M + 3
+    yb = y32.reshape(M, D // 32, 32)
+    sb = MX.mx_scale_exp(np.abs(yb).max(-1))
+    inv = np.exp2(127.0 - sb).astype(F32)
+    q = MX.e4m3_round(yb * inv[:, :, None])
+    # e4m3 value -> byte: sign | exponent | mantissa
+    a = np.abs(q).astype(np.float64)
+    e = np.where(a >= 2.0 ** -6, np.floor(np.log2(np.maximum(a, 2.0 ** -9))), -7)
+    ef = (e + 7).astype(np.int64)
+    m = np.where(ef > 0, a / 2.0 ** e * 8 - 8, a * 2.0 ** 9).astype(np.int64)
+    byte = ((np.signbit(q).astype(np.int64) << 7) | (ef << 3) | m).astype(np.uint8).reshape(M, D)
+    img = np.full((D // 128, sc_ld, 4), 0xA5, np.uint8)
+    for blk in range(D // 32):
+        dst = (blk + 1) % (D // 32) if neighbour_block else blk
+        img[dst // 4, :M, dst % 4] = sb[:, blk]
+    return byte, img.view(np.uint32).reshape(D // 128, sc_ld)
+
+
+@pytest.mark.parametrize("D", [256, 384, 768, 1024])
+def test_mx_row_bound_and_scale_bytes(D):
+    M = 64
+    tolerated = total = 0
+    for eps in (1e-5, 1e-6):
+        x, gamma, beta = R.rows_case(M, D, 2000 + D)
+        ref, E = R.ln_ref(x, gamma, beta, eps)
+        y32 = _sim_ln(x, gamma, beta, eps)
+        byte, img = _sim_mx_row(y32)
+        val, sb = R.mx_row_decode(byte, img, M, D)
+        r = R.ratio(val, ref, R.mx_row_bound(ref, E, sb))
+        print(f"[ln f8 D {D} eps {eps:g}] simulated kernel: max err / bound {r:.3f}")
+        assert r <= 1.0
+        want, lo, hi = R.mx_scale_window(ref, E)
+        assert ((sb >= lo) & (sb <= hi)).all()
+        tolerated += int((lo != hi).sum())
+        total += lo.size
+        # planted: the scale byte written to the neighbouring 32-column block
+        byte2, img2 = _sim_mx_row(y32, neighbour_block=True)
+        val2, sb2 = R.mx_row_decode(byte2, img2, M, D)
+        assert not ((sb2 >= lo) & (sb2 <= hi)).all()
+        assert R.ratio(val2, ref, R.mx_row_bound(ref, E, sb2)) > 1.0
+    assert tolerated <= 0.01 * total, (tolerated, total)
+
+
+def test_the_gpu_cases_of_the_mx_row_have_few_blocks_at_a_scale_boundary():
+    """tests/test_gpu_rows_reference.py accepts either neighbour where the reference's block maximum lies within the bound of
+    a scale boundary; with its seeds (kernel_ref.mx_row_seed) the reference alone keeps such blocks under 1 % per case."""
+    for D in (256, 384, 768, 1024):
+        for M in (1, 3, 4, 5, 1023):
+            x, gamma, beta = R.rows_case(M, D, R.mx_row_seed(D, M))
+            ref, E = R.ln_ref(x, gamma, beta, 1e-5 if M % 2 else 1e-6)
+            _, lo, hi = R.mx_scale_window(ref, E)
+            assert (lo != hi).sum() <= 0.01 * lo.size, (D, M, int((lo != hi).sum()), lo.size)
+
+
+# ConvNeXt producers
+def _cnx_case(n, h, w, C, seed):
+    rng = np.random.default_rng(seed)
+    x = (rng.standard_normal((n, h, w, C)) * 1.5 + 0.3).astype(F32)
+    gamma = (1.0 + 0.5 * rng.standard_normal(C)).astype(F32)
+    beta = (0.3 * rng.standard_normal(C)).astype(F32)
+    wt = (rng.standard_normal((49, C)) / 7.0).astype(F32)
+    bias = (0.2 * rng.standard_normal(C)).astype(F32)
+    return x, gamma, beta, wt, bias
+
+
+def _sim_dwconv(x, wt, bias, *, shift=False, clamp=False):
+    """The kernel's fmaf chain over the taps inside the frame (ky, then kx), then the bias: each step's exact product and
+    sum in float64, rounded once to fp32.  shift: the taps read one pixel to the right; clamp: edge clamping for zero padding."""
+    n, h, w, C = x.shape
+    acc = np.zeros((n, h, w, C), F32)
+    ys, xs = np.arange(h)[:, None], np.arange(w)[None, :]
+    for ky in range(7):
+        for kx in range(7):
+            iy, ix = ys + ky - 3, xs + kx - 3 + (1 if shift else 0)
+            inside = ((iy >= 0) & (iy < h) & (ix >= 0) & (ix < w))[None, :, :, None]
+            a = x[:, np.clip(iy, 0, h - 1), np.clip(ix, 0, w - 1)]
+            step = (acc.astype(np.float64) + a.astype(np.float64) * wt[7 * ky + kx].astype(np.float64)).astype(F32)
+            acc = step if clamp else np.where(inside, step, acc)
+    return acc + bias
+
+
+@pytest.mark.parametrize("C", [32, 96, 800])
+def test_dwconv_ln_bound_accepts_the_simulated_kernel_and_rejects_planted_defects(C):
+    for (h, w) in ((1, 1), (2, 3), (7, 7), (8, 5)):
+        x, gamma, beta, wt, bias = _cnx_case(2, h, w, C, 10 * h + w)
+        ref, E = R.cnx_dwconv_ln_ref(x, wt, bias, gamma, beta, 1e-6)
+        bound = R.stored_bound(ref, E, "f32")
+        sim = lambda **kw: _sim_ln(_sim_dwconv(x, wt, bias, **kw).reshape(-1, C), gamma, beta, 1e-6).astype(np.float64)   # noqa: E731
+        r = R.ratio(sim(), ref, bound)
+        print(f"[dwconv C {C} {h}x{w}] simulated kernel: max err / bound {r:.3f}")
+        assert r <= 1.0
+        if h * w > 1:                           # a 1 x 1 frame has one tap: nothing to shift or clamp to
+            assert R.ratio(sim(shift=True), ref, bound) > 1.0
+            assert R.ratio(sim(clamp=True), ref, bound) > 1.0
+    # the 1 x 1 frame's only tap is the centre one: a kernel that took tap 0 instead is rejected
+    x, gamma, beta, wt, bias = _cnx_case(2, 1, 1, C, 11)
+    ref, E = R.cnx_dwconv_ln_ref(x, wt, bias, gamma, beta, 1e-6)
+    wrong = _sim_ln((x * wt[0] + bias).reshape(-1, C), gamma, beta, 1e-6)
+    assert R.ratio(wrong, ref, R.stored_bound(ref, E, "f32")) > 1.0
+
+
+@pytest.mark.parametrize("C", [32, 192, 1536])
+def test_downsample_bound_accepts_the_simulated_kernel_and_rejects_swapped_kh_kw(C):
+    x, gamma, beta, _, _ = _cnx_case(2, 5, 7, C, 5)
+    x[:, 4], x[:, :, 6] = np.nan, np.nan                                  # the odd grid's last row / column: never read
+    ref, E = R.cnx_downsample_ref(x, gamma, beta, 1e-6)
+    assert np.isfinite(ref).all() and np.isfinite(E).all()
+    bound = R.stored_bound(ref, E, "f32")
+    y = _sim_ln(x[:, :4, :6].reshape(-1, C), gamma, beta, 1e-6).reshape(2, 2, 2, 3, 2, C)       # [b][oy][kh][ox][kw][C]
+    good = y.transpose(0, 1, 3, 2, 4, 5).reshape(-1, 4 * C)
+    swapped = y.transpose(0, 1, 3, 4, 2, 5).reshape(-1, 4 * C)
+    assert R.ratio(good, ref, bound) <= 1.0
+    assert R.ratio(swapped, ref, bound) > 1.0
+    assert R.ratio(_store(good, "split"), ref, R.stored_bound(ref, E, "split")) <= 1.0
+
+
+@pytest.mark.parametrize("hw", [1, 3, 4, 5, 49, 196])
+def test_pool_ln_bound_accepts_the_kernel_order_and_rejects_a_dropped_pixel(hw):
+    C = 384
+    x, gamma, beta, _, _ = _cnx_case(3, 1, hw, C, hw)
+    x = x.reshape(3, hw, C)
+    ref, E = R.cnx_pool_ln_ref(x, gamma, beta, 1e-6)
+    bound = R.stored_bound(ref, E, "f32")
+    r = R.ratio(_sim_ln(R.pool_order_f32(x), gamma, beta, 1e-6), ref, bound)
+    print(f"[pool hw {hw}] simulated kernel: max err / bound {r:.3f}")
+    assert r <= 1.0
+    if hw > 1:
+        dropped = R.pool_order_f32(x[:, :-1]) * F32(hw - 1) / F32(hw)       # the last pixel (a partial round of 4) left out
+        assert R.ratio(_sim_ln(dropped, gamma, beta, 1e-6), ref, bound) > 1.0
+    # (a wrong divisor is no defect here: LayerNorm undoes a common factor)  The next frame's first pixel summed as well:
+    leak = R.pool_order_f32(np.concatenate([x, np.roll(x, -1, axis=0)[:, :1]], axis=1)) * F32(hw + 1) / F32(hw)
+    assert R.ratio(_sim_ln(leak, gamma, beta, 1e-6), ref, bound) > 1.0
+
+
+def test_stem_reference_gathers_4x4_patches_and_ignores_the_remainder():
+    rng = np.random.default_rng(3)
+    f = rng.integers(0, 256, (2, 9, 14), dtype=np.uint8)
+    f[:, 8:], f[:, :, 12:] = 255, 255                                      # the remainder of a 9 x 14 frame: never read
+    A = R.cnx_stem_ref(f, True)
+    assert A.shape == (2 * 2 * 3, 32) and not A[:, 16:].any()
+    m = (1 * 2 + 1) * 3 + 2                                               # frame 1, oy 1, ox 2
+    assert np.array_equal(A[m, :16].reshape(4, 4), (f[1, 4:8, 8:12] / 255.0).astype(F32))
+    g = rng.standard_normal((2, 9, 14)).astype(F32)
+    assert np.array_equal(R.cnx_stem_ref(g, False)[m, :16].reshape(4, 4), g[1, 4:8, 8:12])
