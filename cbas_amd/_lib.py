@@ -99,6 +99,7 @@ SIGNATURES = {
     "cbas_rows_gather_windows": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "cbas_head_train_step_rows": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32,
                                           c_void_p, c_void_p]),
+    "cbas_head_train_step_rows_multi": (c_int, [c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cbas_head_score_rows": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                      c_void_p]),
     "cbas_logits_nll": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_float, c_void_p, c_void_p]),
@@ -147,6 +148,7 @@ DEBUG_SIGNATURES = {
 }
 
 ENC_SLOTS = 3
+TRAIN_MULTI_MAX = 8                                   # CBAS_TRAIN_MULTI_MAX of include/cbas_mi355x.h
 POS_INTERP_BICUBIC_AA, POS_INTERP_BICUBIC = 0, 1      # CBAS_POS_INTERP_* of include/cbas_mi355x.h
 MLP_GELU, MLP_SWIGLU = 0, 1                           # CBAS_MLP_* of include/cbas_mi355x.h
 EXPECTED_ABI = 11         # CBAS_ABI_VERSION of include/cbas_mi355x.h these ctypes structures mirror

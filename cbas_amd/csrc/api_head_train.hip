@@ -51,6 +51,10 @@ struct cbas_head_trainer {
         *XT, *dprojT, *augT, *dZT, *dginT, *xinT, *hprevT, *latentT, *dlogT, *Rc, *RcT, *cov, *Gm, *sq, *dlat_cov, *wlin0T, *wihT,
         *skbuf;                                                          // split-K partial tiles
     float* xg = nullptr;             // [max_batch][T][I] windows gathered by cbas_head_train_step_rows (the step's operand)
+    // cbas_head_train_step_rows_multi: the trainer's own stream and the event that orders it against the other trainers of a
+    // call; made by the first such call (a trainer stepped on its caller's stream never has them)
+    hipStream_t own = nullptr;
+    hipEvent_t ev = nullptr;
     std::vector<void*> allocs;
 };
 
@@ -149,6 +153,8 @@ extern "C" void cbas_head_train_destroy(cbas_head_trainer* t) {
     if (!t) return;
     (void)hipSetDevice(t->device);
     (void)hipDeviceSynchronize();
+    if (t->ev) (void)hipEventDestroy(t->ev);
+    if (t->own) (void)hipStreamDestroy(t->own);
     for (void* p : t->allocs)
         if (p) (void)hipFree(p);
     delete t;
@@ -263,6 +269,251 @@ extern "C" int cbas_head_train_create(const cbas_head_config* cfg, const cbas_tr
     return CBAS_OK;
 }
 
+namespace {
+
+// One trainer's part of a step.  cbas_head_train_step runs one Job on the caller's stream; cbas_head_train_step_rows_multi
+// runs k of them in lockstep, each on its trainer's own stream.
+struct Job {
+    cbas_head_trainer* t;
+    const float* x;                  // [B][T][I]
+    const int32_t* labels;
+    hipStream_t st;
+    int64_t B, R, Rp, Bp;
+    bool use_cov;                    // cbas.py:1340
+    float cov_inv;                   // 1 / (B - 1)
+    unsigned long long key[4];       // dropout streams of this step (oracle/head_train_oracle.py: dropout_keep)
+    unsigned thr_b, thr_l;
+    float sc_b, sc_l;
+    TrainExpandParams ep;
+    TrainPoolParams pp;
+    float *dh_cur, *dh_next;
+};
+
+void bind_job(Job& c) {
+    cbas_head_trainer* t = c.t;
+    c.R = c.B * t->T; c.Rp = round_up(c.R, K_PAD); c.Bp = round_up(c.B, 32); c.use_cov = c.B > 1;
+    c.cov_inv = c.use_cov ? 1.0f / (float)(c.B - 1) : 0.f;
+    const bool drop = t->tcfg.dropout != 0;
+    for (int s = 0; s < 4; ++s) c.key[s] = mix64h(t->tcfg.seed ^ mix64h((unsigned long long)t->step * 4ull + (unsigned long long)s));
+    c.thr_b = drop ? (unsigned)floor(0.1 * 16777216.0) : 0u; c.thr_l = drop ? (unsigned)floor(0.15 * 16777216.0) : 0u;
+    c.sc_b = drop ? (float)(1.0 / (1.0 - 0.1)) : 1.0f; c.sc_l = drop ? (float)(1.0 / (1.0 - 0.15)) : 1.0f;
+    float* P = t->P;
+    TrainExpandParams& ep = c.ep;
+    ep = TrainExpandParams{};
+    ep.proj = t->proj; ep.tmat = t->tmat; ep.lin_vec = t->lin_vec; ep.b_bott = P + t->o_bbott; ep.ln_w = P + t->o_lnw;
+    ep.ln_b = P + t->o_lnb; ep.b_lin1 = P + t->o_blin1; ep.T = t->T; ep.Bn = t->Bn; ep.NPROJ = t->NPROJ; ep.C = t->C; ep.NS = t->NS;
+    for (int s = 0; s < 3; ++s) ep.key[s] = c.key[s];
+    ep.thr = c.thr_b; ep.scale = c.sc_b;
+    TrainPoolParams& pp = c.pp;
+    pp = TrainPoolParams{};
+    pp.hout = t->hout[t->NL - 1]; pp.lin_logits = t->lin_logits; pp.w_att = P + t->o_watt; pp.b_att = P + t->o_batt;
+    pp.att_temp = P + t->o_temp; pp.w_lin2 = P + t->o_wlin2; pp.b_lin2 = P + t->o_blin2; pp.gate = P + t->o_gate;
+    pp.T = t->T; pp.H2 = t->H2; pp.C = t->C; pp.lo = t->lo; pp.hi = t->hi;
+    c.dh_cur = t->dhA; c.dh_next = t->dhB;
+}
+
+// The step of k trainers that share one head configuration (k = 1: the one trainer of cbas_head_train_step, and exactly its
+// launches in its order).  The LSTM, expand and pool kernels, the transposes and the GEMMs are queued per trainer on
+// jobs[j].st and overlap there.  For k > 1 the small kernels - Adam, the column sums, the cross-entropy pair, cov_offdiag,
+// add / copy, GELU + dropout - go out as ONE trial-batched launch for all k on the leading stream jobs[0].st: `join` orders
+// that stream behind every trainer's with one event each, `fork` orders every trainer's stream behind it again.  Batched
+// launches that follow each other need neither.  The call returns forked, so each stream alone orders the next step.
+int step_jobs(Job* jobs, const int k, const int update) {
+    const cbas_head_trainer* cfg = jobs[0].t;
+    const int I = cfg->I, C = cfg->C, T = cfg->T, L0 = cfg->L0, h = cfg->h, F = cfg->F, H2 = cfg->H2, NP = cfg->NPROJ, NL = cfg->NL;
+    const hipStream_t lead = jobs[0].st;
+    bool joined = false;
+    auto join = [&]() -> int {
+        if (joined || k == 1) return CBAS_OK;
+        for (int j = 1; j < k; ++j) {
+            HIP_TRY(hipEventRecord(jobs[j].t->ev, jobs[j].st));
+            HIP_TRY(hipStreamWaitEvent(lead, jobs[j].t->ev, 0));
+        }
+        joined = true;
+        return CBAS_OK;
+    };
+    auto fork = [&]() -> int {
+        if (!joined) return CBAS_OK;
+        HIP_TRY(hipEventRecord(jobs[0].t->ev, lead));
+        for (int j = 1; j < k; ++j) HIP_TRY(hipStreamWaitEvent(jobs[j].st, jobs[0].t->ev, 0));
+        joined = false;
+        return CBAS_OK;
+    };
+#define TRY_RC(expr)                       \
+    do {                                   \
+        const int rc_ = (expr);            \
+        if (rc_ != CBAS_OK) return rc_;    \
+    } while (0)
+// the statements once per trainer j, with c / t / P / G / st naming that trainer's job, handle, parameters, gradients, stream
+#define PER_JOB(...)                                                                                       \
+    for (int j = 0; j < k; ++j) {                                                                          \
+        Job& c = jobs[j];                                                                                  \
+        cbas_head_trainer* const t = c.t;                                                                  \
+        float* const P = t->P;                                                                             \
+        float* const G = t->G;                                                                             \
+        const hipStream_t st = c.st;                                                                       \
+        (void)P; (void)G; (void)st;                                                                        \
+        __VA_ARGS__;                                                                                       \
+    }
+#define EACH(...)       do { TRY_RC(fork()); PER_JOB(__VA_ARGS__) } while (0)      /* queued on every trainer's own stream */
+#define FILL(...)       do { TRY_RC(join()); PER_JOB(__VA_ARGS__) } while (0)      /* entry j of a table for the leading stream */
+// the small kernels: the single-trial launcher for k = 1, else one batched launch; ON: does trainer j take part
+#define COLSUM(ON, SRC, ROWS, COLS, DST)                                                                                        \
+    do {                                                                                                                        \
+        if (k == 1) { EACH(if (ON) LAUNCH_TRY(launch_colsum(SRC, ROWS, COLS, COLS, 1.0f, t->cs_tmp, DST, st))); }               \
+        else {                                                                                                                  \
+            ColsumBatch b_{};                                                                                                   \
+            FILL(if (ON) { b_.src[j] = SRC; b_.rows[j] = ROWS; b_.cols[j] = COLS; b_.ld[j] = COLS; b_.tmp[j] = t->cs_tmp; b_.dst[j] = DST; }); \
+            LAUNCH_TRY(launch_colsum_multi(b_, k, lead));                                                                       \
+        }                                                                                                                       \
+    } while (0)
+#define ADD_VEC(A, B_, OUT, N)                                                                                                  \
+    do {                                                                                                                        \
+        if (k == 1) { EACH(LAUNCH_TRY(launch_add_vec(A, B_, OUT, N, st))); }                                                    \
+        else {                                                                                                                  \
+            VecBatch b_{};                                                                                                      \
+            FILL(b_.a[j] = A; b_.b[j] = B_; b_.out[j] = OUT; b_.n[j] = N);                                                      \
+            LAUNCH_TRY(launch_add_vec_multi(b_, k, lead));                                                                      \
+        }                                                                                                                       \
+    } while (0)
+#define GELU_DROPOUT(Z_, IO, BACKWARD)                                                                                          \
+    do {                                                                                                                        \
+        if (k == 1) { EACH(LAUNCH_TRY(launch_gelu_dropout(Z_, IO, c.R * L0, c.key[3], c.thr_l, c.sc_l, BACKWARD, st))); }       \
+        else {                                                                                                                  \
+            GeluBatch b_{};                                                                                                     \
+            FILL(b_.Z[j] = Z_; b_.io[j] = IO; b_.n[j] = c.R * L0; b_.key[j] = c.key[3]; b_.thr[j] = c.thr_l; b_.scale[j] = c.sc_l); \
+            LAUNCH_TRY(launch_gelu_dropout_multi(b_, k, BACKWARD, lead));                                                       \
+        }                                                                                                                       \
+    } while (0)
+
+    // ---------------- forward ----------------
+    EACH(LAUNCH_TRY(gemm_nt(c.x, I, P + t->o_wproj, NP, nullptr, t->proj, NP, c.R, NP, I, st));
+         LAUNCH_TRY(launch_train_expand_fwd(c.ep, c.B, t->Y, t->aug, t->lin_logits, st));
+         LAUNCH_TRY(gemm_nt(t->aug, F, P + t->o_wlin0, L0, P + t->o_blin0, t->Z, L0, c.R, L0, F, st)));
+    GELU_DROPOUT(t->Z, t->xl, 0);
+    EACH(LAUNCH_TRY(launch_head_centre(t->xl, c.B, T, L0, st)));
+    for (int l = 0; l < NL; ++l) {
+        const int in = l == 0 ? L0 : H2;
+        ADD_VEC(P + t->o_bih[l], P + t->o_bhh[l], t->b_gate, 8 * h);
+        EACH(LAUNCH_TRY(gemm_nt(l == 0 ? t->xl : t->hout[l - 1], in, P + t->o_wih[l], 8 * h, t->b_gate, t->gin, 8 * h, c.R, 8 * h, in, st));
+             LAUNCH_TRY(launch_lstm_train_fwd(t->gin, P + t->o_whh[l], h, T, c.B, t->act[l], t->cst[l], t->hout[l], st)));
+    }
+    EACH(LAUNCH_TRY(launch_pool_train_fwd(c.pp, c.B, t->attw, t->scores, t->latent, t->lstm_logits, t->final_logits, st)));
+
+    // ---------------- loss ----------------
+    if (k == 1) {
+        EACH(LAUNCH_TRY(launch_ce_terms(t->final_logits, c.labels, t->cw, c.B, C, t->tcfg.label_smoothing, t->terms, st)));
+    } else {
+        CeBatch b{};
+        FILL(b.logits[j] = t->final_logits; b.labels[j] = c.labels; b.cw[j] = t->cw; b.n[j] = c.B; b.C[j] = C;
+             b.eps[j] = t->tcfg.label_smoothing; b.out[j] = t->terms);
+        LAUNCH_TRY(launch_ce_multi(b, k, 0, lead));
+    }
+    COLSUM(true, t->terms, c.B, 2, t->sums);                                                    // sums[0..1]
+    if (k == 1) {
+        EACH(LAUNCH_TRY(launch_ce_grad(t->final_logits, c.labels, t->cw, t->sums, c.B, C, t->tcfg.label_smoothing, t->dfinal, st)));
+    } else {
+        CeBatch b{};
+        FILL(b.logits[j] = t->final_logits; b.labels[j] = c.labels; b.cw[j] = t->cw; b.sums[j] = t->sums; b.n[j] = c.B; b.C[j] = C;
+             b.eps[j] = t->tcfg.label_smoothing; b.out[j] = t->dfinal);
+        LAUNCH_TRY(launch_ce_multi(b, k, 1, lead));
+    }
+    COLSUM(c.use_cov, t->latent, c.B, H2, t->sq);                                               // column sums (sq as scratch)
+    EACH(if (c.use_cov) {
+        LAUNCH_TRY(launch_sub_colmean(t->latent, t->sq, c.B, H2, t->Rc, st));
+        LAUNCH_TRY(launch_transpose_pad(t->Rc, c.B, H2, H2, t->RcT, c.Bp, st));
+        LAUNCH_TRY(gemm_nt(t->RcT, c.Bp, t->RcT, H2, nullptr, t->cov, H2, H2, H2, (int)c.Bp, st));
+    });
+    if (k == 1) {
+        EACH(if (c.use_cov) LAUNCH_TRY(launch_cov_offdiag(t->cov, H2, c.cov_inv, 4.0f * c.cov_inv, t->Gm, t->sq, st)));
+    } else {
+        CovBatch b{};
+        FILL(if (c.use_cov) {
+            b.cov[j] = t->cov; b.n[j] = H2; b.cscale[j] = c.cov_inv; b.gscale[j] = 4.0f * c.cov_inv; b.G[j] = t->Gm; b.sq[j] = t->sq;
+        });
+        LAUNCH_TRY(launch_cov_offdiag_multi(b, k, lead));
+    }
+    COLSUM(c.use_cov, t->sq, H2, 1, t->sums + 2);                                               // sums[2] = covariance penalty
+    EACH(if (c.use_cov) LAUNCH_TRY(gemm_nt(t->Rc, H2, t->Gm, H2, nullptr, t->dlat_cov, H2, c.B, H2, H2, st));
+         else HIP_TRY(hipMemsetAsync(t->sums + 2, 0, sizeof(float), st)));
+
+    // ---------------- backward ----------------
+    EACH(LAUNCH_TRY(launch_pool_train_bwd(c.pp, c.B, t->attw, t->scores, t->lstm_logits, t->dfinal, c.use_cov ? t->dlat_cov : nullptr,
+                                          t->dhA, t->dlstm, t->dlin, t->part_pool, st)));
+    // w_att | b_att | gate | att_temp are contiguous in the layout and in part_pool's row
+    COLSUM(true, t->part_pool, c.B, H2 + 12, G + t->o_watt);
+    COLSUM(true, t->dlstm, c.B, C, G + t->o_blin2);
+    COLSUM(true, t->dlin, c.B, C, G + t->o_blin1);
+    EACH(LAUNCH_TRY(launch_transpose_pad(t->dlstm, c.B, C, C, t->dlogT, c.Bp, st));
+         LAUNCH_TRY(launch_transpose_pad(t->latent, c.B, H2, H2, t->latentT, c.Bp, st));
+         LAUNCH_TRY(gemm_nt(t->dlogT, c.Bp, t->latentT, H2, nullptr, G + t->o_wlin2, H2, C, H2, (int)c.Bp, st)));
+
+    for (int l = NL - 1; l >= 0; --l) {
+        const int in = l == 0 ? L0 : H2;
+        EACH(LAUNCH_TRY(launch_lstm_train_bwd(c.dh_cur, t->act[l], t->cst[l], t->hout[l], P + t->o_whh[l], h, T, c.B, t->dgin, t->hprev, st)));
+        COLSUM(true, t->dgin, c.R, 8 * h, G + t->o_bih[l]);
+        ADD_VEC(G + t->o_bih[l], nullptr, G + t->o_bhh[l], 8 * h);
+        EACH(const float* xin = l == 0 ? t->xl : t->hout[l - 1];
+             LAUNCH_TRY(launch_transpose_pad(t->dgin, c.R, 8 * h, 8 * h, t->dginT, c.Rp, st));
+             LAUNCH_TRY(launch_transpose_pad(t->hprev, c.R, H2, H2, t->hprevT, c.Rp, st));
+             LAUNCH_TRY(launch_transpose_pad(xin, c.R, in, in, t->xinT, c.Rp, st));
+             for (int dir = 0; dir < 2; ++dir)
+                 LAUNCH_TRY(gemm_nt_longk(t->dginT + (int64_t)dir * 4 * h * c.Rp, t->hprevT + (int64_t)dir * h * c.Rp, h,
+                                          G + t->o_whh[l] + (int64_t)dir * 4 * h * h, 4 * h, h, c.Rp, t->skbuf, st));
+             LAUNCH_TRY(gemm_nt_longk(t->dginT, t->xinT, in, G + t->o_wih[l], 8 * h, in, c.Rp, t->skbuf, st));
+             LAUNCH_TRY(launch_transpose_pad(P + t->o_wih[l], 8 * h, in, in, t->wihT, 8 * h, st));   /* [in][8h] */
+             LAUNCH_TRY(gemm_nt(t->dgin, 8 * h, t->wihT, in, nullptr, l == 0 ? t->dxl : c.dh_next, in, c.R, in, 8 * h, st));
+             float* tmp = c.dh_cur; c.dh_cur = c.dh_next; c.dh_next = tmp);
+    }
+    // centring (classifier_head.py:166-167) is its own adjoint: d x = d xc - mean_t(d xc)
+    EACH(LAUNCH_TRY(launch_head_centre(t->dxl, c.B, T, L0, st)));
+    GELU_DROPOUT(t->Z, t->dxl, 1);                                                              // dxl is now dZ
+    COLSUM(true, t->dxl, c.R, L0, G + t->o_blin0);
+    EACH(LAUNCH_TRY(launch_transpose_pad(t->dxl, c.R, L0, L0, t->dZT, c.Rp, st));
+         LAUNCH_TRY(launch_transpose_pad(t->aug, c.R, F, F, t->augT, c.Rp, st));
+         LAUNCH_TRY(gemm_nt_longk(t->dZT, t->augT, F, G + t->o_wlin0, L0, F, c.Rp, t->skbuf, st));
+         LAUNCH_TRY(launch_transpose_pad(P + t->o_wlin0, L0, F, F, t->wlin0T, L0, st));         /* [F][L0] */
+         LAUNCH_TRY(gemm_nt(t->dxl, L0, t->wlin0T, F, nullptr, t->daug, F, c.R, F, L0, st));
+         LAUNCH_TRY(launch_train_expand_bwd(c.ep, c.B, t->Y, t->daug, t->dlin, t->dproj, t->part_exp, st)));
+    // b_bott | ln_w | ln_b are contiguous in the layout and in part_exp's row
+    COLSUM(true, t->part_exp, c.B, 3 * F, G + t->o_bbott);
+    EACH(LAUNCH_TRY(launch_transpose_pad(t->dproj, c.R, NP, NP, t->dprojT, c.Rp, st));
+         LAUNCH_TRY(launch_transpose_pad(c.x, c.R, I, I, t->XT, c.Rp, st));
+         LAUNCH_TRY(gemm_nt_longk(t->dprojT, t->XT, I, G + t->o_wproj, NP, I, c.Rp, t->skbuf, st)));
+
+    if (update) {
+        if (k == 1) {
+            EACH(LAUNCH_TRY(launch_adam_step(P, G, t->M, t->V, t->n_train, t->tcfg.lr, t->tcfg.weight_decay, t->o_gate, t->o_gate + 1,
+                                             1e-3f /* cbas.py:1307 */, t->step + 1, st)));
+        } else {
+            AdamBatch b{};
+            b.wd_special = 1e-3f;                                                               // cbas.py:1307
+            FILL(b.p[j] = P; b.g[j] = G; b.m[j] = t->M; b.v[j] = t->V; b.n[j] = t->n_train; b.wd[j] = t->tcfg.weight_decay;
+                 b.wd_lo[j] = t->o_gate; b.wd_hi[j] = t->o_gate + 1;
+                 adam_bias_corrections(t->tcfg.lr, t->step + 1, &b.lr_c1[j], &b.inv_sqrt_c2[j]));
+            LAUNCH_TRY(launch_adam_step_multi(b, k, lead));
+        }
+        for (int j = 0; j < k; ++j) jobs[j].t->step += 1;
+    }
+    TRY_RC(fork());
+    return CBAS_OK;
+#undef GELU_DROPOUT
+#undef ADD_VEC
+#undef COLSUM
+#undef FILL
+#undef EACH
+#undef PER_JOB
+#undef TRY_RC
+}
+
+void read_loss(const float* s, float* loss_host) {
+    loss_host[1] = s[0] / s[1];
+    loss_host[2] = s[2];
+    loss_host[0] = loss_host[1] + loss_host[2];
+}
+
+}  // namespace
+
 extern "C" int cbas_head_train_step(cbas_head_trainer* t, const float* x_dev, const int32_t* labels_dev, int32_t n_windows,
                                     int32_t update, float* loss_host, void* stream) {
     if (!t) return cbas_fail(CBAS_EINVAL, "null trainer handle");
@@ -270,120 +521,16 @@ extern "C" int cbas_head_train_step(cbas_head_trainer* t, const float* x_dev, co
     if (n_windows < 1 || n_windows > t->Bcap) return cbas_fail(CBAS_EINVAL, "n_windows=%d outside [1, max_batch=%lld]", n_windows, (long long)t->Bcap);
     HIP_TRY(hipSetDevice(t->device));
     hipStream_t st = (hipStream_t)stream;
-    const int I = t->I, C = t->C, T = t->T, Bn = t->Bn, L0 = t->L0, h = t->h, F = t->F, H2 = t->H2, NP = t->NPROJ, NL = t->NL;
-    const int64_t B = n_windows, R = B * T, Rp = round_up(R, K_PAD), Bp = round_up(B, 32);
-    float* P = t->P;
-    float* G = t->G;
-
-    // dropout streams of this step (oracle/head_train_oracle.py: dropout_keep)
-    const bool drop = t->tcfg.dropout != 0;
-    unsigned long long key[4];
-    for (int s = 0; s < 4; ++s) key[s] = mix64h(t->tcfg.seed ^ mix64h((unsigned long long)t->step * 4ull + (unsigned long long)s));
-    const unsigned thr_b = drop ? (unsigned)floor(0.1 * 16777216.0) : 0u, thr_l = drop ? (unsigned)floor(0.15 * 16777216.0) : 0u;
-    const float sc_b = drop ? (float)(1.0 / (1.0 - 0.1)) : 1.0f, sc_l = drop ? (float)(1.0 / (1.0 - 0.15)) : 1.0f;
-
-    // ---------------- forward ----------------
-    LAUNCH_TRY(gemm_nt(x_dev, I, P + t->o_wproj, NP, nullptr, t->proj, NP, R, NP, I, st));
-    TrainExpandParams ep{};
-    ep.proj = t->proj; ep.tmat = t->tmat; ep.lin_vec = t->lin_vec; ep.b_bott = P + t->o_bbott; ep.ln_w = P + t->o_lnw;
-    ep.ln_b = P + t->o_lnb; ep.b_lin1 = P + t->o_blin1; ep.T = T; ep.Bn = Bn; ep.NPROJ = NP; ep.C = C; ep.NS = t->NS;
-    for (int s = 0; s < 3; ++s) ep.key[s] = key[s];
-    ep.thr = thr_b; ep.scale = sc_b;
-    LAUNCH_TRY(launch_train_expand_fwd(ep, B, t->Y, t->aug, t->lin_logits, st));
-    LAUNCH_TRY(gemm_nt(t->aug, F, P + t->o_wlin0, L0, P + t->o_blin0, t->Z, L0, R, L0, F, st));
-    LAUNCH_TRY(launch_gelu_dropout(t->Z, t->xl, R * L0, key[3], thr_l, sc_l, 0, st));
-    LAUNCH_TRY(launch_head_centre(t->xl, B, T, L0, st));
-    for (int l = 0; l < NL; ++l) {
-        const float* xin = l == 0 ? t->xl : t->hout[l - 1];
-        const int in = l == 0 ? L0 : H2;
-        LAUNCH_TRY(launch_add_vec(P + t->o_bih[l], P + t->o_bhh[l], t->b_gate, 8 * h, st));
-        LAUNCH_TRY(gemm_nt(xin, in, P + t->o_wih[l], 8 * h, t->b_gate, t->gin, 8 * h, R, 8 * h, in, st));
-        LAUNCH_TRY(launch_lstm_train_fwd(t->gin, P + t->o_whh[l], h, T, B, t->act[l], t->cst[l], t->hout[l], st));
-    }
-    TrainPoolParams pp{};
-    pp.hout = t->hout[NL - 1]; pp.lin_logits = t->lin_logits; pp.w_att = P + t->o_watt; pp.b_att = P + t->o_batt;
-    pp.att_temp = P + t->o_temp; pp.w_lin2 = P + t->o_wlin2; pp.b_lin2 = P + t->o_blin2; pp.gate = P + t->o_gate;
-    pp.T = T; pp.H2 = H2; pp.C = C; pp.lo = t->lo; pp.hi = t->hi;
-    LAUNCH_TRY(launch_pool_train_fwd(pp, B, t->attw, t->scores, t->latent, t->lstm_logits, t->final_logits, st));
-
-    // ---------------- loss ----------------
-    const float eps = t->tcfg.label_smoothing;
-    LAUNCH_TRY(launch_ce_terms(t->final_logits, labels_dev, t->cw, B, C, eps, t->terms, st));
-    LAUNCH_TRY(launch_colsum(t->terms, B, 2, 2, 1.0f, t->cs_tmp, t->sums, st));                 // sums[0..1]
-    LAUNCH_TRY(launch_ce_grad(t->final_logits, labels_dev, t->cw, t->sums, B, C, eps, t->dfinal, st));
-    const bool use_cov = B > 1;                                                                // cbas.py:1340
-    if (use_cov) {
-        LAUNCH_TRY(launch_colsum(t->latent, B, H2, H2, 1.0f, t->cs_tmp, t->sq, st));            // column sums (sq as scratch)
-        LAUNCH_TRY(launch_sub_colmean(t->latent, t->sq, B, H2, t->Rc, st));
-        LAUNCH_TRY(launch_transpose_pad(t->Rc, B, H2, H2, t->RcT, Bp, st));
-        LAUNCH_TRY(gemm_nt(t->RcT, Bp, t->RcT, H2, nullptr, t->cov, H2, H2, H2, (int)Bp, st));
-        const float inv = 1.0f / (float)(B - 1);
-        LAUNCH_TRY(launch_cov_offdiag(t->cov, H2, inv, 4.0f * inv, t->Gm, t->sq, st));
-        LAUNCH_TRY(launch_colsum(t->sq, H2, 1, 1, 1.0f, t->cs_tmp, t->sums + 2, st));           // sums[2] = covariance penalty
-        LAUNCH_TRY(gemm_nt(t->Rc, H2, t->Gm, H2, nullptr, t->dlat_cov, H2, B, H2, H2, st));
-    } else {
-        HIP_TRY(hipMemsetAsync(t->sums + 2, 0, sizeof(float), st));
-    }
-
-    // ---------------- backward ----------------
-    LAUNCH_TRY(launch_pool_train_bwd(pp, B, t->attw, t->scores, t->lstm_logits, t->dfinal, use_cov ? t->dlat_cov : nullptr, t->dhA,
-                                     t->dlstm, t->dlin, t->part_pool, st));
-    // w_att | b_att | gate | att_temp are contiguous in the layout and in part_pool's row
-    LAUNCH_TRY(launch_colsum(t->part_pool, B, H2 + 12, H2 + 12, 1.0f, t->cs_tmp, G + t->o_watt, st));
-    LAUNCH_TRY(launch_colsum(t->dlstm, B, C, C, 1.0f, t->cs_tmp, G + t->o_blin2, st));
-    LAUNCH_TRY(launch_colsum(t->dlin, B, C, C, 1.0f, t->cs_tmp, G + t->o_blin1, st));
-    LAUNCH_TRY(launch_transpose_pad(t->dlstm, B, C, C, t->dlogT, Bp, st));
-    LAUNCH_TRY(launch_transpose_pad(t->latent, B, H2, H2, t->latentT, Bp, st));
-    LAUNCH_TRY(gemm_nt(t->dlogT, Bp, t->latentT, H2, nullptr, G + t->o_wlin2, H2, C, H2, (int)Bp, st));
-
-    float* dh_cur = t->dhA;
-    float* dh_next = t->dhB;
-    for (int l = NL - 1; l >= 0; --l) {
-        const float* xin = l == 0 ? t->xl : t->hout[l - 1];
-        const int in = l == 0 ? L0 : H2;
-        LAUNCH_TRY(launch_lstm_train_bwd(dh_cur, t->act[l], t->cst[l], t->hout[l], P + t->o_whh[l], h, T, B, t->dgin, t->hprev, st));
-        LAUNCH_TRY(launch_colsum(t->dgin, R, 8 * h, 8 * h, 1.0f, t->cs_tmp, G + t->o_bih[l], st));
-        LAUNCH_TRY(launch_add_vec(G + t->o_bih[l], nullptr, G + t->o_bhh[l], 8 * h, st));
-        LAUNCH_TRY(launch_transpose_pad(t->dgin, R, 8 * h, 8 * h, t->dginT, Rp, st));
-        LAUNCH_TRY(launch_transpose_pad(t->hprev, R, H2, H2, t->hprevT, Rp, st));
-        LAUNCH_TRY(launch_transpose_pad(xin, R, in, in, t->xinT, Rp, st));
-        for (int dir = 0; dir < 2; ++dir)
-            LAUNCH_TRY(gemm_nt_longk(t->dginT + (int64_t)dir * 4 * h * Rp, t->hprevT + (int64_t)dir * h * Rp, h,
-                                     G + t->o_whh[l] + (int64_t)dir * 4 * h * h, 4 * h, h, Rp, t->skbuf, st));
-        LAUNCH_TRY(gemm_nt_longk(t->dginT, t->xinT, in, G + t->o_wih[l], 8 * h, in, Rp, t->skbuf, st));
-        LAUNCH_TRY(launch_transpose_pad(P + t->o_wih[l], 8 * h, in, in, t->wihT, 8 * h, st));   // [in][8h]
-        float* dx = l == 0 ? t->dxl : dh_next;
-        LAUNCH_TRY(gemm_nt(t->dgin, 8 * h, t->wihT, in, nullptr, dx, in, R, in, 8 * h, st));
-        float* tmp = dh_cur; dh_cur = dh_next; dh_next = tmp;
-    }
-    // centring (classifier_head.py:166-167) is its own adjoint: d x = d xc - mean_t(d xc)
-    LAUNCH_TRY(launch_head_centre(t->dxl, B, T, L0, st));
-    LAUNCH_TRY(launch_gelu_dropout(t->Z, t->dxl, R * L0, key[3], thr_l, sc_l, 1, st));       // dxl is now dZ
-    LAUNCH_TRY(launch_colsum(t->dxl, R, L0, L0, 1.0f, t->cs_tmp, G + t->o_blin0, st));
-    LAUNCH_TRY(launch_transpose_pad(t->dxl, R, L0, L0, t->dZT, Rp, st));
-    LAUNCH_TRY(launch_transpose_pad(t->aug, R, F, F, t->augT, Rp, st));
-    LAUNCH_TRY(gemm_nt_longk(t->dZT, t->augT, F, G + t->o_wlin0, L0, F, Rp, t->skbuf, st));
-    LAUNCH_TRY(launch_transpose_pad(P + t->o_wlin0, L0, F, F, t->wlin0T, L0, st));             // [F][L0]
-    LAUNCH_TRY(gemm_nt(t->dxl, L0, t->wlin0T, F, nullptr, t->daug, F, R, F, L0, st));
-    LAUNCH_TRY(launch_train_expand_bwd(ep, B, t->Y, t->daug, t->dlin, t->dproj, t->part_exp, st));
-    // b_bott | ln_w | ln_b are contiguous in the layout and in part_exp's row
-    LAUNCH_TRY(launch_colsum(t->part_exp, B, 3 * F, 3 * F, 1.0f, t->cs_tmp, G + t->o_bbott, st));
-    LAUNCH_TRY(launch_transpose_pad(t->dproj, R, NP, NP, t->dprojT, Rp, st));
-    LAUNCH_TRY(launch_transpose_pad(x_dev, R, I, I, t->XT, Rp, st));
-    LAUNCH_TRY(gemm_nt_longk(t->dprojT, t->XT, I, G + t->o_wproj, NP, I, Rp, t->skbuf, st));
-
-    if (update) {
-        LAUNCH_TRY(launch_adam_step(P, G, t->M, t->V, t->n_train, t->tcfg.lr, t->tcfg.weight_decay, t->o_gate, t->o_gate + 1,
-                                    1e-3f /* cbas.py:1307 */, t->step + 1, st));
-        t->step += 1;
-    }
+    Job job{};
+    job.t = t; job.x = x_dev; job.labels = labels_dev; job.st = st; job.B = n_windows;
+    bind_job(job);
+    const int rc = step_jobs(&job, 1, update);
+    if (rc != CBAS_OK) return rc;
     if (loss_host) {
         float s[3];
         HIP_TRY(hipMemcpyAsync(s, t->sums, sizeof(s), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        loss_host[1] = s[0] / s[1];
-        loss_host[2] = s[2];
-        loss_host[0] = loss_host[1] + loss_host[2];
+        read_loss(s, loss_host);
     }
     return CBAS_OK;
 }
@@ -417,14 +564,69 @@ extern "C" int cbas_head_train_step_rows(cbas_head_trainer* t, const uint16_t* r
     return cbas_head_train_step(t, t->xg, labels_dev, n_windows, update, loss_host, stream);
 }
 
+extern "C" int cbas_head_train_step_rows_multi(cbas_head_trainer** trainers, int32_t k, const uint16_t* rows_f16_dev,
+                                               int64_t n_rows, int32_t dim, const int64_t* const* first_row_dev,
+                                               const int32_t* const* labels_dev, const int32_t* n_windows, float* losses_host) {
+    static_assert(CBAS_TRAIN_MULTI_MAX == TRAIN_MULTI_MAX, "the header's cap is the batched kernels' table size");
+    if (!trainers || !rows_f16_dev || !first_row_dev || !labels_dev || !n_windows)
+        return cbas_fail(CBAS_EINVAL, "trainers / rows_f16_dev / first_row_dev / labels_dev / n_windows NULL");
+    if (k < 1 || k > CBAS_TRAIN_MULTI_MAX) return cbas_fail(CBAS_EINVAL, "k=%d outside [1, %d]", k, CBAS_TRAIN_MULTI_MAX);
+    if (n_rows < 0) return cbas_fail(CBAS_EINVAL, "n_rows=%lld is negative", (long long)n_rows);
+    // everything is checked before anything is queued: a refused call leaves every trainer as it was
+    for (int j = 0; j < k; ++j) {
+        const cbas_head_trainer* t = trainers[j];
+        if (!t) return cbas_fail(CBAS_EINVAL, "trainer %d is NULL", j);
+        if (!first_row_dev[j] || !labels_dev[j]) return cbas_fail(CBAS_EINVAL, "first_row_dev[%d] / labels_dev[%d] NULL", j, j);
+        if (dim != t->I) return cbas_fail(CBAS_EINVAL, "rows of width %d: trainer %d was created for in_features=%d", dim, j, t->I);
+        if (n_windows[j] < 1 || n_windows[j] > t->Bcap)
+            return cbas_fail(CBAS_EINVAL, "n_windows[%d]=%d outside [1, max_batch=%lld]", j, n_windows[j], (long long)t->Bcap);
+        const cbas_head_trainer* a = trainers[0];
+        if (t->device != a->device || t->C != a->C || t->T != a->T || t->Bn != a->Bn || t->L0 != a->L0 || t->h != a->h ||
+            t->NS != a->NS || t->NL != a->NL || t->lo != a->lo || t->hi != a->hi)
+            return cbas_fail(CBAS_EINVAL, "trainer %d has another head configuration or device than trainer 0", j);
+        for (int i = 0; i < j; ++i)
+            if (trainers[i] == t) return cbas_fail(CBAS_EINVAL, "trainer %d is trainer %d again", j, i);
+    }
+    HIP_TRY(hipSetDevice(trainers[0]->device));
+    Job jobs[CBAS_TRAIN_MULTI_MAX] = {};
+    for (int j = 0; j < k; ++j) {
+        cbas_head_trainer* t = trainers[j];
+        if (!t->own) HIP_TRY(hipStreamCreateWithFlags(&t->own, hipStreamNonBlocking));
+        if (!t->ev) HIP_TRY(hipEventCreateWithFlags(&t->ev, hipEventDisableTiming));
+        jobs[j].t = t; jobs[j].x = t->xg; jobs[j].labels = labels_dev[j]; jobs[j].st = t->own; jobs[j].B = n_windows[j];
+        bind_job(jobs[j]);
+    }
+    for (int j = 0; j < k; ++j) {
+        const int rc = cbas_rows_gather_windows(rows_f16_dev, n_rows, dim, first_row_dev[j], n_windows[j], jobs[j].t->T, jobs[j].t->xg,
+                                                jobs[j].st);
+        if (rc != CBAS_OK) return rc;
+    }
+    const int rc = step_jobs(jobs, k, 1);
+    if (rc != CBAS_OK) return rc;
+    if (losses_host) {
+        // the one wait of the call: the leading stream behind every trainer's, the k copies on it, one synchronisation
+        float s[CBAS_TRAIN_MULTI_MAX][3];
+        const hipStream_t lead = jobs[0].st;
+        for (int j = 1; j < k; ++j) {
+            HIP_TRY(hipEventRecord(jobs[j].t->ev, jobs[j].st));
+            HIP_TRY(hipStreamWaitEvent(lead, jobs[j].t->ev, 0));
+        }
+        for (int j = 0; j < k; ++j) HIP_TRY(hipMemcpyAsync(s[j], jobs[j].t->sums, sizeof(s[j]), hipMemcpyDeviceToHost, lead));
+        HIP_TRY(hipStreamSynchronize(lead));
+        for (int j = 0; j < k; ++j) read_loss(s[j], losses_host + 3 * j);
+    }
+    return CBAS_OK;
+}
+
 extern "C" int cbas_head_train_read(cbas_head_trainer* t, int32_t what, float* blob_host, int64_t n) {
     if (!t || !blob_host) return cbas_fail(CBAS_EINVAL, "null argument");
     if (n != t->n_blob) return cbas_fail(CBAS_EINVAL, "blob has %lld floats, config needs %lld", (long long)n, (long long)t->n_blob);
-    if (what != 0 && what != 1) return cbas_fail(CBAS_EINVAL, "what=%d (0 parameters, 1 gradients)", what);
+    if (what < 0 || what > 3) return cbas_fail(CBAS_EINVAL, "what=%d (0 parameters, 1 gradients, 2 / 3 Adam's first / second moment)", what);
     HIP_TRY(hipSetDevice(t->device));
     HIP_TRY(hipDeviceSynchronize());
     std::vector<float> host((size_t)t->n_train);
-    HIP_TRY(hipMemcpy(host.data(), what == 0 ? t->P : t->G, host.size() * sizeof(float), hipMemcpyDeviceToHost));
+    const float* const src[4] = {t->P, t->G, t->M, t->V};
+    HIP_TRY(hipMemcpy(host.data(), src[what], host.size() * sizeof(float), hipMemcpyDeviceToHost));
     for (const MapEntry& e : t->map) memcpy(blob_host + e.blob_off, host.data() + e.train_off, (size_t)e.n * sizeof(float));
     return CBAS_OK;
 }

@@ -241,6 +241,17 @@ __global__ void gelu_dropout_fwd_kernel(const float* __restrict__ Z, float* __re
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = gelu_erf_lib(Z[i]) * drop_scale(key, (unsigned long long)i, thr, scale);
 }
+// trial-batched forms (blockIdx.y = trial): the single-trial expressions, element for element
+__global__ void gelu_dropout_fwd_multi_kernel(GeluBatch b) {
+    const int j = blockIdx.y;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < b.n[j]) b.io[j][i] = gelu_erf_lib(b.Z[j][i]) * drop_scale(b.key[j], (unsigned long long)i, b.thr[j], b.scale[j]);
+}
+__global__ void gelu_dropout_bwd_multi_kernel(GeluBatch b) {
+    const int j = blockIdx.y;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < b.n[j]) b.io[j][i] = b.io[j][i] * drop_scale(b.key[j], (unsigned long long)i, b.thr[j], b.scale[j]) * gelu_erf_grad(b.Z[j][i]);
+}
 __global__ void gelu_dropout_bwd_kernel(const float* __restrict__ Z, float* __restrict__ d, int64_t n,
                                         unsigned long long key, unsigned thr, float scale) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -455,10 +466,9 @@ __global__ __launch_bounds__(256) void pool_train_bwd_kernel(PoolArgs a, const f
 // cross entropy with class weights and label smoothing (nn.CrossEntropyLoss, reduction 'mean')
 // terms[w] = [ loss numerator of window w | w[y_w] ]
 // ---------------------------------------------------------------------------------------------
-__global__ void ce_terms_kernel(const float* __restrict__ logits, const int* __restrict__ labels, const float* __restrict__ cw,
-                                int64_t n, int C, float eps, float* __restrict__ terms) {
-    const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (w >= n) return;
+__device__ __forceinline__ void ce_terms_window(const float* __restrict__ logits, const int* __restrict__ labels,
+                                                const float* __restrict__ cw, int64_t w, int C, float eps,
+                                                float* __restrict__ terms) {
     const float* z = logits + w * C;
     float mx = z[0];
     for (int c = 1; c < C; ++c) mx = fmaxf(mx, z[c]);
@@ -472,11 +482,20 @@ __global__ void ce_terms_kernel(const float* __restrict__ logits, const int* __r
     terms[w * 2 + 0] = (1.0f - eps) * wy * (lse - z[y]) + (eps / (float)C) * smooth;
     terms[w * 2 + 1] = wy;
 }
-// sums[0] = sum of numerators, sums[1] = sum of w[y]
-__global__ void ce_grad_kernel(const float* __restrict__ logits, const int* __restrict__ labels, const float* __restrict__ cw,
-                               const float* __restrict__ sums, int64_t n, int C, float eps, float* __restrict__ dlogits) {
+__global__ void ce_terms_kernel(const float* __restrict__ logits, const int* __restrict__ labels, const float* __restrict__ cw,
+                                int64_t n, int C, float eps, float* __restrict__ terms) {
     const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (w >= n) return;
+    if (w < n) ce_terms_window(logits, labels, cw, w, C, eps, terms);
+}
+__global__ void ce_terms_multi_kernel(CeBatch b) {
+    const int j = blockIdx.y;
+    const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w < b.n[j]) ce_terms_window(b.logits[j], b.labels[j], b.cw[j], w, b.C[j], b.eps[j], b.out[j]);
+}
+// sums[0] = sum of numerators, sums[1] = sum of w[y]
+__device__ __forceinline__ void ce_grad_window(const float* __restrict__ logits, const int* __restrict__ labels,
+                                               const float* __restrict__ cw, const float* __restrict__ sums, int64_t w, int C,
+                                               float eps, float* __restrict__ dlogits) {
     const float* z = logits + w * C;
     float mx = z[0];
     for (int c = 1; c < C; ++c) mx = fmaxf(mx, z[c]);
@@ -493,11 +512,21 @@ __global__ void ce_grad_kernel(const float* __restrict__ logits, const int* __re
         dlogits[w * C + c] = ((1.0f - eps) * wy * (p - (c == y ? 1.0f : 0.f)) + (eps / (float)C) * (p * wsum - wc)) * inv;
     }
 }
+__global__ void ce_grad_kernel(const float* __restrict__ logits, const int* __restrict__ labels, const float* __restrict__ cw,
+                               const float* __restrict__ sums, int64_t n, int C, float eps, float* __restrict__ dlogits) {
+    const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w < n) ce_grad_window(logits, labels, cw, sums, w, C, eps, dlogits);
+}
+__global__ void ce_grad_multi_kernel(CeBatch b) {
+    const int j = blockIdx.y;
+    const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w < b.n[j]) ce_grad_window(b.logits[j], b.labels[j], b.cw[j], b.sums[j], w, b.C[j], b.eps[j], b.out[j]);
+}
 
 // covariance penalty: raw Rc^T Rc (n x n) -> cov = cscale * it; G' = gscale * offdiag(cov), sq[i] = row sums of offdiag(cov)^2
-__global__ void cov_offdiag_kernel(const float* __restrict__ cov, int n, float cscale, float gscale, float* __restrict__ G,
-                                   float* __restrict__ sq) {
-    const int i = blockIdx.x, lane = threadIdx.x;
+__device__ __forceinline__ void cov_offdiag_row(const float* __restrict__ cov, int n, float cscale, float gscale,
+                                                float* __restrict__ G, float* __restrict__ sq, int i) {
+    const int lane = threadIdx.x;
     float s = 0.f;
     for (int j = lane; j < n; j += 64) {
         const float v = i == j ? 0.f : cov[i * n + j] * cscale;
@@ -506,6 +535,14 @@ __global__ void cov_offdiag_kernel(const float* __restrict__ cov, int n, float c
     }
     s = wave_sum(s);
     if (lane == 0) sq[i] = s;
+}
+__global__ void cov_offdiag_kernel(const float* __restrict__ cov, int n, float cscale, float gscale, float* __restrict__ G,
+                                   float* __restrict__ sq) {
+    cov_offdiag_row(cov, n, cscale, gscale, G, sq, blockIdx.x);
+}
+__global__ void cov_offdiag_multi_kernel(CovBatch b) {
+    const int j = blockIdx.y;
+    if ((int)blockIdx.x < b.n[j]) cov_offdiag_row(b.cov[j], b.n[j], b.cscale[j], b.gscale[j], b.G[j], b.sq[j], blockIdx.x);
 }
 
 // rows x cols -> centred copy (column means removed); means from colsum
@@ -517,10 +554,8 @@ __global__ void sub_colmean_kernel(const float* __restrict__ src, const float* _
 
 // deterministic column sums, two stages of fixed shape: stage 1 splits the rows into `chunks` contiguous
 // ranges (tmp [chunks][cols]), stage 2 adds the chunks in order.
-__global__ void colsum_stage1_kernel(const float* __restrict__ src, int64_t rows, int cols, int64_t ld, int chunks,
-                                     float* __restrict__ tmp) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    const int ch = blockIdx.y;
+__device__ __forceinline__ void colsum_stage1_col(const float* __restrict__ src, int64_t rows, int cols, int64_t ld, int chunks,
+                                                  float* __restrict__ tmp, int c, int ch) {
     if (c >= cols) return;
     const int64_t per = (rows + chunks - 1) / chunks;
     const int64_t r0 = ch * per, r1 = r0 + per < rows ? r0 + per : rows;
@@ -528,12 +563,28 @@ __global__ void colsum_stage1_kernel(const float* __restrict__ src, int64_t rows
     for (int64_t r = r0; r < r1; ++r) s += src[r * ld + c];
     tmp[(int64_t)ch * cols + c] = s;
 }
-__global__ void colsum_stage2_kernel(const float* __restrict__ tmp, int cols, int chunks, float scale, float* __restrict__ dst) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+__global__ void colsum_stage1_kernel(const float* __restrict__ src, int64_t rows, int cols, int64_t ld, int chunks,
+                                     float* __restrict__ tmp) {
+    colsum_stage1_col(src, rows, cols, ld, chunks, tmp, blockIdx.x * blockDim.x + threadIdx.x, blockIdx.y);
+}
+__device__ __forceinline__ void colsum_stage2_col(const float* __restrict__ tmp, int cols, int chunks, float scale,
+                                                  float* __restrict__ dst, int c) {
     if (c >= cols) return;
     float s = 0.f;
     for (int ch = 0; ch < chunks; ++ch) s += tmp[(int64_t)ch * cols + c];
     dst[c] = s * scale;
+}
+__global__ void colsum_stage2_kernel(const float* __restrict__ tmp, int cols, int chunks, float scale, float* __restrict__ dst) {
+    colsum_stage2_col(tmp, cols, chunks, scale, dst, blockIdx.x * blockDim.x + threadIdx.x);
+}
+// trial-batched column sums (blockIdx.z = trial): each trial keeps its own rows / chunks split and its own tmp
+__global__ void colsum_stage1_multi_kernel(ColsumBatch b, int chunks) {
+    const int j = blockIdx.z;
+    colsum_stage1_col(b.src[j], b.rows[j], b.cols[j], b.ld[j], chunks, b.tmp[j], blockIdx.x * blockDim.x + threadIdx.x, blockIdx.y);
+}
+__global__ void colsum_stage2_multi_kernel(ColsumBatch b, int chunks) {
+    const int j = blockIdx.z;
+    colsum_stage2_col(b.tmp[j], b.cols[j], chunks, 1.0f, b.dst[j], blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 __global__ void add_vec_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, int n) {
@@ -544,19 +595,36 @@ __global__ void copy_vec_kernel(const float* __restrict__ a, float* __restrict__
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = a[i];
 }
+__global__ void add_vec_multi_kernel(VecBatch v) {                 // b == nullptr: copy
+    const int j = blockIdx.y;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= v.n[j]) return;
+    v.out[j][i] = v.b[j] ? v.a[j][i] + v.b[j][i] : v.a[j][i];
+}
 
 // torch.optim.Adam (L2 weight decay added to the gradient); [wd_lo, wd_hi) uses wd_special (the gate group)
-__global__ void adam_step_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                 int64_t n, float lr_c1, float inv_sqrt_c2, float b1, float b2, float eps, float wd,
-                                 int64_t wd_lo, int64_t wd_hi, float wd_special) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+__device__ __forceinline__ void adam_element(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                             float* __restrict__ v, int64_t i, float lr_c1, float inv_sqrt_c2, float b1, float b2,
+                                             float eps, float wd, int64_t wd_lo, int64_t wd_hi, float wd_special) {
     const float pw = p[i];
     const float gi = g[i] + ((i >= wd_lo && i < wd_hi) ? wd_special : wd) * pw;
     const float mi = b1 * m[i] + (1.0f - b1) * gi;
     const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
     m[i] = mi; v[i] = vi;
     p[i] = pw - lr_c1 * mi / (sqrtf(vi) * inv_sqrt_c2 + eps);
+}
+__global__ void adam_step_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                 int64_t n, float lr_c1, float inv_sqrt_c2, float b1, float b2, float eps, float wd,
+                                 int64_t wd_lo, int64_t wd_hi, float wd_special) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) adam_element(p, g, m, v, i, lr_c1, inv_sqrt_c2, b1, b2, eps, wd, wd_lo, wd_hi, wd_special);
+}
+__global__ void adam_step_multi_kernel(AdamBatch a, float b1, float b2, float eps) {       // blockIdx.y = trial
+    const int j = blockIdx.y;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < a.n[j])
+        adam_element(a.p[j], a.g[j], a.m[j], a.v[j], i, a.lr_c1[j], a.inv_sqrt_c2[j], b1, b2, eps, a.wd[j], a.wd_lo[j], a.wd_hi[j],
+                     a.wd_special);
 }
 
 }  // namespace
@@ -719,12 +787,80 @@ int launch_add_vec(const float* a, const float* b, float* out, int n, hipStream_
     else hipLaunchKernelGGL(copy_vec_kernel, dim3((n + 255) / 256), dim3(256), 0, st, a, out, n);
     return CHECK_LAUNCH();
 }
+void adam_bias_corrections(float lr, int step, float* lr_c1, float* inv_sqrt_c2) {
+    const double b1 = 0.9, b2 = 0.999;
+    *lr_c1 = (float)((double)lr / (1.0 - pow(b1, step)));
+    *inv_sqrt_c2 = (float)(1.0 / sqrt(1.0 - pow(b2, step)));
+}
 int launch_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float wd, int64_t wd_lo, int64_t wd_hi,
                      float wd_special, int step, hipStream_t st) {
-    const double b1 = 0.9, b2 = 0.999;
-    const float lr_c1 = (float)((double)lr / (1.0 - pow(b1, step)));
-    const float inv_sqrt_c2 = (float)(1.0 / sqrt(1.0 - pow(b2, step)));
+    float lr_c1, inv_sqrt_c2;
+    adam_bias_corrections(lr, step, &lr_c1, &inv_sqrt_c2);
     hipLaunchKernelGGL(adam_step_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p, g, m, v, n, lr_c1, inv_sqrt_c2,
                        0.9f, 0.999f, 1e-8f, wd, wd_lo, wd_hi, wd_special);
+    return CHECK_LAUNCH();
+}
+
+// ---------------------------------------------------------------------------------------------
+// trial-batched launchers: one launch serves the k <= TRAIN_MULTI_MAX trainers of a cbas_head_train_step_rows_multi call.
+// The grid's x (and, for the column sums, y) extent is that of the largest trial and the trial index is the next grid
+// dimension; a trial whose count is 0 takes no part.  Block shapes are those of the single-trial launchers.
+// ---------------------------------------------------------------------------------------------
+namespace {
+template <typename T>
+T max_of(const T* v, int k) {
+    T m = 0;
+    for (int j = 0; j < k; ++j) m = v[j] > m ? v[j] : m;
+    return m;
+}
+}  // namespace
+
+int launch_gelu_dropout_multi(const GeluBatch& b, int k, int backward, hipStream_t st) {
+    const int64_t n = max_of(b.n, k);
+    if (k < 1 || k > TRAIN_MULTI_MAX) return -1;
+    if (n == 0) return 0;
+    const dim3 grid((unsigned)((n + 255) / 256), (unsigned)k);
+    if (backward) hipLaunchKernelGGL(gelu_dropout_bwd_multi_kernel, grid, dim3(256), 0, st, b);
+    else hipLaunchKernelGGL(gelu_dropout_fwd_multi_kernel, grid, dim3(256), 0, st, b);
+    return CHECK_LAUNCH();
+}
+int launch_ce_multi(const CeBatch& b, int k, int grad, hipStream_t st) {
+    const int64_t n = max_of(b.n, k);
+    if (k < 1 || k > TRAIN_MULTI_MAX) return -1;
+    if (n == 0) return 0;
+    const dim3 grid((unsigned)((n + 127) / 128), (unsigned)k);
+    if (grad) hipLaunchKernelGGL(ce_grad_multi_kernel, grid, dim3(128), 0, st, b);
+    else hipLaunchKernelGGL(ce_terms_multi_kernel, grid, dim3(128), 0, st, b);
+    return CHECK_LAUNCH();
+}
+int launch_cov_offdiag_multi(const CovBatch& b, int k, hipStream_t st) {
+    const int n = max_of(b.n, k);
+    if (k < 1 || k > TRAIN_MULTI_MAX) return -1;
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(cov_offdiag_multi_kernel, dim3((unsigned)n, (unsigned)k), dim3(64), 0, st, b);
+    return CHECK_LAUNCH();
+}
+int launch_colsum_multi(const ColsumBatch& b, int k, hipStream_t st) {
+    const int cols = max_of(b.cols, k);
+    if (k < 1 || k > TRAIN_MULTI_MAX) return -1;
+    if (cols == 0) return 0;
+    const int chunks = COLSUM_CHUNKS;
+    hipLaunchKernelGGL(colsum_stage1_multi_kernel, dim3((cols + 63) / 64, chunks, (unsigned)k), dim3(64), 0, st, b, chunks);
+    hipLaunchKernelGGL(colsum_stage2_multi_kernel, dim3((cols + 63) / 64, 1, (unsigned)k), dim3(64), 0, st, b, chunks);
+    return CHECK_LAUNCH();
+}
+int launch_add_vec_multi(const VecBatch& v, int k, hipStream_t st) {
+    const int n = max_of(v.n, k);
+    if (k < 1 || k > TRAIN_MULTI_MAX) return -1;
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(add_vec_multi_kernel, dim3((n + 255) / 256, (unsigned)k), dim3(256), 0, st, v);
+    return CHECK_LAUNCH();
+}
+int launch_adam_step_multi(const AdamBatch& a, int k, hipStream_t st) {
+    const int64_t n = max_of(a.n, k);
+    if (k < 1 || k > TRAIN_MULTI_MAX) return -1;
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(adam_step_multi_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)k), dim3(256), 0, st, a, 0.9f, 0.999f,
+                       1e-8f);
     return CHECK_LAUNCH();
 }

@@ -331,6 +331,44 @@ int launch_colsum(const float* src, int64_t rows, int cols, int64_t ld, float sc
 int launch_add_vec(const float* a, const float* b, float* out, int n, hipStream_t st);      // b == nullptr: copy
 int launch_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float wd, int64_t wd_lo, int64_t wd_hi,
                      float wd_special, int step, hipStream_t st);
+void adam_bias_corrections(float lr, int step, float* lr_c1, float* inv_sqrt_c2);      // what launch_adam_step hands its kernel
+
+// Trial-batched forms of the small kernels above, for the k <= TRAIN_MULTI_MAX trainers of one
+// cbas_head_train_step_rows_multi call: entry j of each table is trainer j's operands of the single-trial launcher, and the
+// result is bit for bit what that launcher writes (same per-element expressions, same COLSUM_CHUNKS split of the rows).
+// An entry whose count (n / cols) is 0 takes no part.  The tables travel as kernel arguments.
+constexpr int TRAIN_MULTI_MAX = 8;
+struct GeluBatch {
+    const float* Z[TRAIN_MULTI_MAX]; float* io[TRAIN_MULTI_MAX]; int64_t n[TRAIN_MULTI_MAX]; unsigned long long key[TRAIN_MULTI_MAX];
+    unsigned thr[TRAIN_MULTI_MAX]; float scale[TRAIN_MULTI_MAX];
+};
+struct CeBatch {      // out: terms (launch_ce_terms) or dlogits (launch_ce_grad, which also reads sums)
+    const float* logits[TRAIN_MULTI_MAX]; const int* labels[TRAIN_MULTI_MAX]; const float* cw[TRAIN_MULTI_MAX];
+    const float* sums[TRAIN_MULTI_MAX]; float* out[TRAIN_MULTI_MAX]; int64_t n[TRAIN_MULTI_MAX]; int C[TRAIN_MULTI_MAX];
+    float eps[TRAIN_MULTI_MAX];
+};
+struct CovBatch {
+    const float* cov[TRAIN_MULTI_MAX]; float* G[TRAIN_MULTI_MAX]; float* sq[TRAIN_MULTI_MAX]; int n[TRAIN_MULTI_MAX];
+    float cscale[TRAIN_MULTI_MAX], gscale[TRAIN_MULTI_MAX];
+};
+struct ColsumBatch {  // scale 1
+    const float* src[TRAIN_MULTI_MAX]; float* tmp[TRAIN_MULTI_MAX]; float* dst[TRAIN_MULTI_MAX]; int64_t rows[TRAIN_MULTI_MAX];
+    int64_t ld[TRAIN_MULTI_MAX]; int cols[TRAIN_MULTI_MAX];
+};
+struct VecBatch {     // b[j] == nullptr: copy
+    const float* a[TRAIN_MULTI_MAX]; const float* b[TRAIN_MULTI_MAX]; float* out[TRAIN_MULTI_MAX]; int n[TRAIN_MULTI_MAX];
+};
+struct AdamBatch {    // lr_c1 / inv_sqrt_c2 from adam_bias_corrections
+    float* p[TRAIN_MULTI_MAX]; const float* g[TRAIN_MULTI_MAX]; float* m[TRAIN_MULTI_MAX]; float* v[TRAIN_MULTI_MAX];
+    int64_t n[TRAIN_MULTI_MAX], wd_lo[TRAIN_MULTI_MAX], wd_hi[TRAIN_MULTI_MAX];
+    float lr_c1[TRAIN_MULTI_MAX], inv_sqrt_c2[TRAIN_MULTI_MAX], wd[TRAIN_MULTI_MAX]; float wd_special;
+};
+int launch_gelu_dropout_multi(const GeluBatch& b, int k, int backward, hipStream_t st);
+int launch_ce_multi(const CeBatch& b, int k, int grad, hipStream_t st);
+int launch_cov_offdiag_multi(const CovBatch& b, int k, hipStream_t st);
+int launch_colsum_multi(const ColsumBatch& b, int k, hipStream_t st);
+int launch_add_vec_multi(const VecBatch& v, int k, hipStream_t st);
+int launch_adam_step_multi(const AdamBatch& a, int k, hipStream_t st);
 
 // rows_gather.hip: x_out[w][t][:] = float(rows_f16[first_row[w] + t][:]); rows outside [0, n_rows) read as zeros.
 // Returns -1 for a null pointer, a non-positive size or a window beyond the limits below.

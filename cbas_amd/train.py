@@ -32,6 +32,7 @@ the three bottleneck GELUs, 0.15 after lin0's GELU).
 from __future__ import annotations
 
 import contextlib
+import copy
 import csv
 import ctypes as C
 import os
@@ -155,6 +156,7 @@ class HeadTrainer:
     def _read(self, what: int) -> Dict[str, np.ndarray]:
         blob = np.empty(self.n_blob, np.float32)
         _lib.check(self._lib.cbas_head_train_read(self._h, what, blob.ctypes.data, self.n_blob), "cbas_head_train_read")
+        self._keep_multi = []          # the read synchronised the device: no queued step reads its inputs any more
         return unpack_head_weights(self.cfg, blob)
 
     def weights(self) -> Dict[str, np.ndarray]:
@@ -162,6 +164,10 @@ class HeadTrainer:
 
     def grads(self) -> Dict[str, np.ndarray]:
         return self._read(1)
+
+    def adam_moments(self):
+        """(first moment, second moment) of Adam, named like the parameters."""
+        return self._read(2), self._read(3)
 
     def last_outputs(self, n: int):
         logits = np.empty((n, self.cfg.out_features), np.float32)
@@ -180,6 +186,46 @@ class HeadTrainer:
             self.close()
         except Exception:
             pass
+
+
+def step_rows_multi(rows: torch.Tensor, jobs, want_loss: bool = True):
+    """One optimisation step for each of up to ``_lib.TRAIN_MULTI_MAX`` trainers from one store of rows
+    (``cbas_head_train_step_rows_multi``): ``jobs`` is a sequence of ``(HeadTrainer, first_row, labels)`` as
+    ``HeadTrainer.step_rows`` takes them, all trainers of one head configuration on the device of ``rows``.  Every trainer
+    steps on its own stream and ends, bit for bit, where ``step_rows`` on the same windows leaves it.  Returns one
+    ``(loss, cross_entropy, covariance_penalty)`` per job when ``want_loss`` (one wait for all), else None."""
+    jobs = list(jobs)
+    k = len(jobs)
+    if not 1 <= k <= _lib.TRAIN_MULTI_MAX:
+        raise ValueError(f"{k} trainers in one call: 1 to {_lib.TRAIN_MULTI_MAX} are possible")
+    lead = jobs[0][0]
+    if rows.dim() != 2 or rows.dtype != torch.float16 or rows.device != lead._index_device() or not rows.is_contiguous():
+        raise ValueError(f"rows must be a contiguous float16 (N, {lead.cfg.in_features}) tensor on {lead.device}, got "
+                         f"{rows.dtype} {tuple(rows.shape)} on {rows.device}")
+    held = []
+    for trainer, first_row, labels in jobs:
+        B = int(first_row.shape[0])
+        if first_row.dim() != 1 or labels.shape != (B,):
+            raise ValueError(f"first_row {tuple(first_row.shape)} and labels {tuple(labels.shape)} must both be ({B},)")
+        # a copy from pageable host memory has completed when .to() returns, so the trainer's own stream may read it
+        held.append((first_row.to(trainer.device, torch.int64).contiguous(), labels.to(trainer.device, torch.int32).contiguous()))
+    if any(f.device != rows.device for f, _ in held):
+        raise ValueError(f"every trainer must be on the device of rows, {rows.device}")
+    torch.cuda.current_stream(rows.device).synchronize()       # what the caller queued for rows / first_row / labels is done
+    handles = (C.c_void_p * k)(*[t._h.value for t, _, _ in jobs])
+    firsts = (C.c_void_p * k)(*[f.data_ptr() for f, _ in held])
+    labs = (C.c_void_p * k)(*[y.data_ptr() for _, y in held])
+    counts = (C.c_int32 * k)(*[int(f.shape[0]) for f, _ in held])
+    out = (C.c_float * (3 * k))() if want_loss else None
+    for (trainer, _, _), pair in zip(jobs, held):       # alive until the step that reads them has run
+        trainer._keep_multi = (getattr(trainer, "_keep_multi", None) or []) + [(rows,) + pair]
+    _lib.check(lead._lib.cbas_head_train_step_rows_multi(handles, k, rows.data_ptr(), int(rows.shape[0]), int(rows.shape[1]), firsts,
+                                                         labs, counts, out), "cbas_head_train_step_rows_multi")
+    if not want_loss:
+        return None
+    for (trainer, _, _), pair in zip(jobs, held):       # the call waited for every trainer: earlier inputs are free
+        trainer._keep_multi = [(rows,) + pair]
+    return [(float(out[3 * j]), float(out[3 * j + 1]), float(out[3 * j + 2])) for j in range(k)]
 
 
 class PerformanceReport:
@@ -503,24 +549,43 @@ def train_lstm_model(train_set, test_set, seq_len: int, behaviors: list, cancel_
                      lstm_layers=1, seed: int = 0, in_features: int = 768, log=print):
     """Same signature, control flow and return value as backend/cbas.py:1274-1422 (plus ``seed`` for the
     dropout stream / shuffling / initialisation, ``in_features`` for non-768 encoders, and ``log``)."""
-    from sklearn.metrics import classification_report, confusion_matrix
-
     if len(train_set) == 0:
         return None, None, -1
     device = torch.device(device) if device is not None else torch.device("cuda")
     if device.type != "cuda":
         raise RuntimeError("cbas_amd.train.train_lstm_model runs on a GPU device only")
-    gen = torch.Generator()
-    gen.manual_seed(int(seed))
     has_test = test_set is not None and len(test_set) > 0
     store = open_store([train_set] + ([test_set] if has_test else []), ("training", "test"), seq_len, in_features, device, log)
-    xbuf = None
-    collate = collate_fn
     if store is not None:
         # the same loaders over an index-only view: the sampler's randperm, the loader's per-iterator seed draw and the
         # balanced counter are consumed exactly as on the host path, so the batches are the same, draw for draw
         train_set = _IndexView(train_set, seq_len, store.files)
         test_set = _IndexView(test_set, seq_len, store.files) if test_set is not None and len(test_set) > 0 else None
+    trial = _trial(train_set, test_set, store, seq_len, behaviors, cancel_event, batch_size, lr, epochs, device, class_weights,
+                   patience, progress_callback, optimization_target, weight_decay, label_smoothing, lstm_hidden_size, lstm_layers,
+                   seed, in_features, log, defer_steps=False)
+    try:
+        next(trial)
+    except StopIteration as done:
+        return done.value
+    raise AssertionError("a trial that takes its own steps has nothing to hand out")
+
+
+def _trial(train_set, test_set, store, seq_len, behaviors, cancel_event, batch_size, lr, epochs, device, class_weights, patience,
+           progress_callback, optimization_target, weight_decay, label_smoothing, lstm_hidden_size, lstm_layers, seed,
+           in_features, log, defer_steps):
+    """One trial of ``train_lstm_model`` as a generator whose return value is the trial's.  ``store``: the resident rows
+    (``train_set`` / ``test_set`` are then ``_IndexView``s) or None for the host loader.  With ``defer_steps`` a step from
+    resident rows is not taken here: the generator yields ``(trainer, first_row, labels, want_loss)`` and is sent the
+    loss triple (or None), so that ``train_lstm_trials`` can take the steps of several trials in one call.  Everything else -
+    the seed's three streams of randomness, scoring, selection, patience, cancel - is this one code path for both."""
+    from sklearn.metrics import classification_report, confusion_matrix
+
+    gen = torch.Generator()
+    gen.manual_seed(int(seed))
+    xbuf = None
+    collate = collate_fn
+    if store is not None:
         xbuf = torch.empty((batch_size, seq_len, in_features), dtype=torch.float32, device=device)
         collate = _collate_index
     train_loader = torch.utils.data.DataLoader(train_set, batch_size, shuffle=True, collate_fn=collate, num_workers=0,
@@ -580,7 +645,10 @@ def train_lstm_model(train_set, test_set, seq_len: int, behaviors: list, cancel_
                     continue
                 if store is not None:                   # `windows` are first rows in the resident store
                     store.check(windows.numpy(), seq_len)
-                    loss = trainer.step_rows(store.rows, windows, labels, want_loss=(i % 50 == 0))
+                    if defer_steps:
+                        loss = yield trainer, windows, labels, i % 50 == 0
+                    else:
+                        loss = trainer.step_rows(store.rows, windows, labels, want_loss=(i % 50 == 0))
                 else:
                     loss = trainer.step(windows.float(), labels, want_loss=(i % 50 == 0))
                 if loss is not None:
@@ -617,6 +685,109 @@ def train_lstm_model(train_set, test_set, seq_len: int, behaviors: list, cancel_
         final_model.load_state_dict(best_state)
         return final_model.to(device).eval(), epoch_reports, best_epoch
     return None, None, -1
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the trials of a run, beside each other (backend/workthreads.py:596-690 trains num_runs x num_trials heads in sequence)
+# ---------------------------------------------------------------------------------------------------------------
+def _own_counter(dataset):
+    """``dataset`` for one trial: a balanced dataset draws its classes round-robin from a ``counter`` on the instance, so
+    every trial counts on a shallow copy of its own (manifest and buckets shared) from where the caller's stands."""
+    return copy.copy(dataset) if _ds.manifest_kind(dataset) == "balanced" else dataset
+
+
+def _run_trial_slots(seeds, max_concurrent: int, start, step_many) -> list:
+    """The slot scheduler of ``train_lstm_trials``.  ``start(seed)`` gives a ``_trial``-style generator: it yields step
+    requests, is sent each step's loss and returns the trial's result.  At most ``max_concurrent`` generators are alive; in
+    every round ``step_many([request, ...])`` takes one step for each of them (in seed order) and returns their losses; a
+    trial that returns frees its slot for the next seed.  Returns the results in seed order."""
+    results = [None] * len(seeds)
+    waiting = list(enumerate(seeds))
+    alive: Dict[int, list] = {}                     # position in seeds -> [generator, its pending request]
+
+    def advance(i, trial, loss):
+        try:
+            alive[i] = [trial, trial.send(loss)]
+        except StopIteration as done:
+            alive.pop(i, None)
+            results[i] = done.value
+
+    try:
+        while waiting or alive:
+            while waiting and len(alive) < max_concurrent:
+                i, seed = waiting.pop(0)
+                advance(i, start(seed), None)
+            if alive:
+                order = sorted(alive)
+                losses = step_many([alive[i][1] for i in order])
+                for i, loss in zip(order, losses):
+                    advance(i, alive[i][0], loss)
+    finally:
+        for trial, _ in alive.values():             # an exception: every trial still releases its trainer
+            trial.close()
+    return results
+
+
+def train_lstm_trials(train_set, test_set, seq_len: int, behaviors: list, cancel_event, *, trial_seeds: Sequence[int],
+                      max_concurrent: int = 4, batch_size=512, lr=1e-4, epochs=10, device=None, class_weights=None, patience=3,
+                      progress_callback=None, optimization_target="weighted avg", weight_decay=0.0, label_smoothing=0.0,
+                      lstm_hidden_size=64, lstm_layers=1, in_features: int = 768, log=print) -> list:
+    """The trials of one run - same sets and hyper-parameters, one seed each - trained beside each other from ONE resident row
+    store: ``[(model | None, epoch_reports | None, best_epoch), ...]`` in the order of ``trial_seeds``, entry i being what
+    ``train_lstm_model(..., seed=trial_seeds[i])`` returns when it is called alone (weights bit for bit, reports, best
+    epoch; "alone" for a balanced dataset: with its ``counter`` where it stands at this call).
+
+    Up to ``max_concurrent`` (1..8) trainers are alive at a time, each on a stream of its own in this process; their steps go
+    out together (``cbas_head_train_step_rows_multi``); a trial that ends - its epochs, its patience, ``cancel_event`` - frees
+    its slot for the next seed.  When the rows cannot be resident (``CBAS_TRAIN_RESIDENT=0``, rows that do not fit, datasets
+    that are no manifest datasets) the trials run one after another through ``train_lstm_model`` and ``log`` gets one line
+    that says why."""
+    seeds = [int(s) for s in trial_seeds]
+    if isinstance(max_concurrent, bool) or int(max_concurrent) != max_concurrent or not 1 <= max_concurrent <= _lib.TRAIN_MULTI_MAX:
+        raise ValueError(f"max_concurrent={max_concurrent!r}: 1 to {_lib.TRAIN_MULTI_MAX} trials can train beside each other")
+    if not seeds:
+        return []
+    if len(train_set) == 0:
+        return [(None, None, -1) for _ in seeds]
+    device = torch.device(device) if device is not None else torch.device("cuda")
+    if device.type != "cuda":
+        raise RuntimeError("cbas_amd.train.train_lstm_trials runs on a GPU device only")
+    has_test = test_set is not None and len(test_set) > 0
+    said = []
+    store = open_store([train_set] + ([test_set] if has_test else []), ("training", "test"), seq_len, in_features, device, said.append)
+    if store is None:
+        why = said[-1][said[-1].index("(") + 1:said[-1].rindex(")")]
+        log(f"training trials: {len(seeds)} one after another ({why})")
+        return [train_lstm_model(_own_counter(train_set), _own_counter(test_set), seq_len, behaviors, cancel_event,
+                                 batch_size=batch_size, lr=lr, epochs=epochs, device=device, class_weights=class_weights,
+                                 patience=patience, progress_callback=progress_callback, optimization_target=optimization_target,
+                                 weight_decay=weight_decay, label_smoothing=label_smoothing, lstm_hidden_size=lstm_hidden_size,
+                                 lstm_layers=lstm_layers, seed=seed, in_features=in_features, log=log) for seed in seeds]
+    for line in said:
+        log(line)
+    log(f"training trials: {len(seeds)} on one row store, up to {int(max_concurrent)} beside each other")
+    # one window table per set, shared by all trials
+    train_view = _IndexView(train_set, seq_len, store.files)
+    test_view = _IndexView(test_set, seq_len, store.files) if has_test else None
+
+    def view_of(view):
+        if view is None:
+            return None
+        mine = copy.copy(view)
+        mine.dataset = _own_counter(view.dataset)
+        return mine
+
+    def start(seed):
+        return _trial(view_of(train_view), view_of(test_view), store, seq_len, behaviors, cancel_event, batch_size, lr, epochs,
+                      device, class_weights, patience, progress_callback, optimization_target, weight_decay, label_smoothing,
+                      lstm_hidden_size, lstm_layers, seed, in_features, log, defer_steps=True)
+
+    def step_many(requests):
+        wanted = [want for _, _, _, want in requests]
+        losses = step_rows_multi(store.rows, [(t, first, labels) for t, first, labels, _ in requests], want_loss=any(wanted))
+        return [loss if want else None for loss, want in zip(losses or [None] * len(requests), wanted)]
+
+    return _run_trial_slots(seeds, int(max_concurrent), start, step_many)
 
 
 # ---------------------------------------------------------------------------------------------------------------

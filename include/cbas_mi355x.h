@@ -446,6 +446,29 @@ int cbas_rows_gather_windows(const uint16_t* rows_f16_dev, int64_t n_rows, int32
 int cbas_head_train_step_rows(cbas_head_trainer* t, const uint16_t* rows_f16_dev, int64_t n_rows, int32_t dim,
                               const int64_t* first_row_dev, const int32_t* labels_dev, int32_t n_windows, int32_t seq_len,
                               int32_t update, float* loss_host, void* stream);
+/* One optimisation step (update = 1) for each of k trainers from ONE such store: the trials of a run (TrainingThread,
+ * backend/workthreads.py:596-690, trains them one after another) differ in their random draws alone, and a step of this head
+ * is launch latency and a serial LSTM recurrence more than arithmetic.  Trainer j steps on the n_windows[j] windows named by
+ * first_row_dev[j] with labels labels_dev[j] (device pointers in host tables of k entries) and ends with the parameters, the
+ * gradients and the Adam moments, bit for bit, that cbas_head_train_step_rows leaves for the same windows.
+ *   - Every trainer has a stream of its own (made by its first call here, released by cbas_head_train_destroy) and owns every
+ *     buffer its step writes; the store is only read.  The gather, the LSTM, expand and pool kernels, the transposes and the
+ *     GEMMs of trainer j are queued on trainer j's stream, where they overlap with the other trainers'.
+ *   - For k > 1 the small kernels (Adam, the column sums, the cross-entropy pair, the covariance off-diagonal, add / copy,
+ *     GELU + dropout) are ONE launch for all k on trainer 0's stream, ordered against the others with events; per element
+ *     and per reduction they are the single-trial kernels.  k = 1 queues exactly what cbas_head_train_step_rows queues.
+ *   - Nothing is synchronised between trainers on the host.  losses_host (k x 3 floats: total, cross-entropy, covariance
+ *     penalty per trainer) is filled after ONE wait at the end; NULL: no wait, the call returns with everything queued.
+ * The caller orders these streams against its own: the pointers must be valid and their contents complete when the call is
+ * made, and stay so until the trainers are read (cbas_head_train_read synchronises the device).  A trainer is stepped either
+ * here or on a caller's stream; changing over needs a device synchronisation in between.
+ * CBAS_EINVAL, with nothing queued and no trainer changed: k outside [1, CBAS_TRAIN_MULTI_MAX], a NULL table, trainer or
+ * table entry, the same trainer twice, dim != in_features, trainers that differ in head configuration or device,
+ * n_windows[j] outside [1, max_batch of trainer j], n_rows < 0. */
+#define CBAS_TRAIN_MULTI_MAX 8
+int cbas_head_train_step_rows_multi(cbas_head_trainer** trainers, int32_t k, const uint16_t* rows_f16_dev, int64_t n_rows,
+                                    int32_t dim, const int64_t* const* first_row_dev, const int32_t* const* labels_dev,
+                                    const int32_t* n_windows, float* losses_host);
 
 /* The tail of a training job on the device: scoring a split and fitting the calibration temperature from such a store.
  *
@@ -528,8 +551,8 @@ int64_t cbas_disagreement_runs(const int32_t* pred_dev, const float* conf_dev, i
                                int32_t n_instances, const int32_t* name_rank_dev, int32_t n_classes,
                                cbas_disagreement_run* records_dev, int64_t capacity, int64_t* needed_host, void* stream);
 
-/* Copy the current parameters (what = 0) or the gradients of the last step (what = 1) to the host, in the
- * blob order of cbas_head_create (n = cbas_head_weights_count).  Synchronises the device. */
+/* Copy the current parameters (what = 0), the gradients of the last step (what = 1) or Adam's first / second moment
+ * (what = 2 / 3) to the host, in the blob order of cbas_head_create (n = cbas_head_weights_count).  Synchronises the device. */
 int cbas_head_train_read(cbas_head_trainer* t, int32_t what, float* blob_host, int64_t n);
 /* Logits (n_windows, C) and latent (n_windows, 2h) of the LAST step's forward pass (device -> host). */
 int cbas_head_train_last_outputs(cbas_head_trainer* t, float* logits_host, float* latent_host, int32_t n_windows);
