@@ -33,7 +33,16 @@ static inline int cbas_fail(int code, const char* fmt, ...) {
                              __FILE__, __LINE__);                                              \
     } while (0)
 
-#define LAUNCH_TRY(expr)                                                                       \
+// HIP_TRY for the calls of a create path: running out of memory is CBAS_ENOMEM, every other failure CBAS_EHIP
+#define ALLOC_TRY(expr)                                                                                            \
+    do {                                                                                                           \
+        hipError_t _e = (expr);                                                                                    \
+        if (_e != hipSuccess)                                                                                      \
+            return cbas_fail(_e == hipErrorOutOfMemory ? CBAS_ENOMEM : CBAS_EHIP, "%s failed: %s (%s:%d)", #expr,  \
+                             hipGetErrorString(_e), __FILE__, __LINE__);                                           \
+    } while (0)
+
+#define LAUNCH_TRY(expr)                                                                      \
     do {                                                                                       \
         int _r = (expr);                                                                       \
         if (_r != 0)                                                                           \

@@ -61,6 +61,24 @@ struct Slot {
     bool dev_mode = false;        // submitted by cbas_enc_submit_u8 (device in/out) rather than ..._host
 };
 
+// One compute lane: the activation workspace of one batch in flight and the stream its asynchronous batches run on.  The
+// forward functions take the lane they work in as a parameter; nothing else in the handle points into a workspace.
+// Precisions 3 / 4 and ConvNeXt keep floats in the buffers declared f16*.  A buffer the handle's mode has no use for is null.
+struct Lane {
+    f16 *A_patch = nullptr, *h16 = nullptr, *qkv16 = nullptr, *u16 = nullptr;
+    float* x = nullptr;
+    // compact per-frame rows of the pruned last layer (only the CLS row is consumed: [tf]:540-541, cbas.py:677):
+    // cls16 = [q | ctx | LN2 | (pad)] x [max_batch][D] fp16, then GELU(up) [max_batch][F]
+    f16* cls16 = nullptr;
+    uint32_t *sc_h = nullptr, *sc_u = nullptr; // precision 2: block scales of the fp8 activations in h16 / u16 ([K/128][rows_cap])
+    f16* x16 = nullptr;                // LayerNorm fold: [rows_cap][D] fp16 copy of the residual stream (the folded GEMMs' A operand)
+    float2* lnst = nullptr;            //                 [4][rows_cap] per-row LayerNorm statistics by 256-column block
+    hipStream_t stream = nullptr;      // lane 0: the handle's `compute`; lane 1: its own
+};
+
+// bytes of each buffer of a lane, 0 for one the mode does not have: vit_lane_bytes / cnx_lane_bytes -> alloc_lane
+struct LaneBytes { size_t A_patch = 0, h16 = 0, qkv16 = 0, u16 = 0, x = 0, cls16 = 0, sc_h = 0, sc_u = 0, x16 = 0, lnst = 0; };
+
 }  // namespace
 
 struct cbas_enc {
@@ -79,7 +97,6 @@ struct cbas_enc {
     f16 *w16 = nullptr, *w16_lo = nullptr;     // all fp16 weights (hi / lo)
     uint8_t* w8 = nullptr;                     // precision 2: all MX-fp8 weights
     uint32_t* w8_sc = nullptr;                 //              and their block scales
-    uint32_t *sc_h = nullptr, *sc_u = nullptr; // precision 2: block scales of the fp8 activations in h16 / u16 ([K/128][rows_cap])
     f16 *wpatch, *wpatch2, *wpatch_lo, *wpatch2_lo;
     float* w32 = nullptr;                      // precision 3 / 4: packed q|k|v weights of every layer + the (D,256) patch weight
     const float* wpatch32 = nullptr;
@@ -107,13 +124,7 @@ struct cbas_enc {
     float* rope_fac = nullptr;          // the same angles by axis, [nh + nw][cos(16) | sin(16)] (GemmParams::rope_fac)
     int rope_nh = 0, rope_nw = 0;
     int rope_cap = 0;
-    // workspaces
-    int64_t rows_cap = 0, prow_cap = 0;
-    f16 *A_patch = nullptr, *h16 = nullptr, *qkv16 = nullptr, *u16 = nullptr;
-    float* x = nullptr;
-    // compact per-frame rows of the pruned last layer (only the CLS row is consumed: [tf]:540-541, cbas.py:677):
-    // cls16 = [q | ctx | LN2 | (pad)] x [max_batch][D] fp16, then GELU(up) [max_batch][F]
-    f16* cls16 = nullptr;
+    int64_t rows_cap = 0, prow_cap = 0;      // token / patch rows a lane's workspace holds
     bool prune_last = true;
     bool rope_in_lds = true;           // cbas_enc_debug_option("rope_lds"): q|k|v epilogue reads the by-axis RoPE table from LDS
     // LayerNorm fold: see run_blocks.  fold_ok = the folded weights exist; ln_fold = use them (debug option "ln_fold").
@@ -122,8 +133,6 @@ struct cbas_enc {
     bool fold_ok = false, ln_fold = false;
     f16* w16_fold = nullptr;
     float* fold_vec = nullptr;
-    f16* x16 = nullptr;                // [rows_cap][D] fp16 copy of the residual stream (the folded GEMMs' A operand)
-    float2* lnst = nullptr;            // [4][rows_cap] per-row LayerNorm statistics by 256-column block
     int last_rows = 0;
     hipStream_t compute = nullptr, copy = nullptr;
     hipStream_t aux = nullptr;          // cbas_enc_check_finite's 4-byte copies: not the NULL stream (torch's default stream is one: a copy there would wait for the caller's own work)
@@ -132,9 +141,9 @@ struct cbas_enc {
     // Two batches in flight: the asynchronous entry points (cbas_enc_submit_u8 / ..._host) alternate two
     // compute lanes, each a full workspace + its own stream, so that one batch's partial tile rounds,
     // LayerNorm and attention run under the other batch's GEMMs (+10 % measured; outputs bit-identical).
-    // lane 0 = the buffers above on `compute`; the synchronous cbas_enc_forward_* always use lane 0.
-    struct Lane { f16 *A_patch, *h16, *qkv16, *u16, *cls16; float* x; uint32_t *sc_h, *sc_u; hipStream_t stream; f16* x16; float2* lnst; };
-    Lane lanes[2] = {};
+    // The lanes own every activation buffer of the handle (alloc_lane / free_lane).  The synchronous cbas_enc_forward_* and the
+    // debug taps work in lanes[0] on the caller's stream / on `compute`; a handle created under CBAS_LANES=1 has no lanes[1].
+    Lane lanes[2];
     int n_lanes = 1;
     uint64_t submit_count = 0;
     // ordering between the synchronous calls (lane 0 workspace on the CALLER's stream) and asynchronous batches
@@ -440,11 +449,11 @@ struct ProfScope {
 // Last transformer layer when only the CLS rows are consumed.  K and V are still projected for every row
 // (the CLS query attends to all tokens); the query, attention, o_proj, LayerNorm 2 and the MLP run on the n CLS
 // rows, read and written in place in the residual stream with a row stride of T*D.
-int run_last_layer_cls(cbas_enc* h, const LayerW& w, int n, int T, hipStream_t st, bool fold) {
+int run_last_layer_cls(cbas_enc* h, const Lane& ws, const LayerW& w, int n, int T, hipStream_t st, bool fold) {
     const int D = h->D, F = h->F, M = n * T, M_pad = (int)round_up(M, 128);
     const int NU = h->mlp ? 2 * F : F;      // columns of the up GEMM: gate | up interleaved for a gated MLP
     const int64_t cap = round_up(h->cfg.max_batch, 128);
-    f16* qc = h->cls16;                     // [n][D] CLS queries (bias added, scaled by 1/8; no RoPE on prefix rows)
+    f16* qc = ws.cls16;                     // [n][D] CLS queries (bias added, scaled by 1/8; no RoPE on prefix rows)
     f16* cc = qc + cap * D;                 // [n][D] attention context of the CLS rows
     f16* hc = cc + cap * D;                 // [n][D] LayerNorm 2 of the CLS rows
     f16* uc = hc + cap * D;                 // [n][F] GELU(up_proj) / silu(gate_proj) * up_proj
@@ -453,52 +462,52 @@ int run_last_layer_cls(cbas_enc* h, const LayerW& w, int n, int T, hipStream_t s
     const int sc_ld = (int)h->rows_cap;
     GemmParams kv{};                        // k | v sections of the fused QKV weight, all rows
     if (f8) {
-        { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f8(h->x, D, w.ln1_w, w.ln1_b, (uint8_t*)h->h16, h->sc_h, sc_ld, M, D, h->cfg.layer_norm_eps, st)); }
+        { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f8(ws.x, D, w.ln1_w, w.ln1_b, (uint8_t*)ws.h16, ws.sc_h, sc_ld, M, D, h->cfg.layer_norm_eps, st)); }
         // the CLS tail of this layer stays fp16 (fp16 weights, n rows): its LayerNorm 1 rows go to the LN2 slot for now
-        { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f16(h->x, (int64_t)T * D, w.ln1_w, w.ln1_b, hc, n, D, h->cfg.layer_norm_eps, st)); }
-        kv.A8 = (const uint8_t*)h->h16; kv.A_sc = h->sc_h; kv.sc_lda = sc_ld;
+        { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f16(ws.x, (int64_t)T * D, w.ln1_w, w.ln1_b, hc, n, D, h->cfg.layer_norm_eps, st)); }
+        kv.A8 = (const uint8_t*)ws.h16; kv.A_sc = ws.sc_h; kv.sc_lda = sc_ld;
         kv.W8 = w.wqkv8 + (size_t)D * D; kv.W_sc = w.sqkv + D; kv.sc_ldw = 3 * D;
     } else if (fold) {
         // LayerNorm fold: the k | v rows of the folded weight on the raw fp16 residual stream; the n CLS rows' LayerNorm 1
         // (for the query) is computed on its own, into the LN2 slot for now
-        { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f16(h->x, (int64_t)T * D, w.ln1_w, w.ln1_b, hc, n, D, h->cfg.layer_norm_eps, st)); }
-        kv.A = h->x16; kv.W = w.wqkv_f + (size_t)D * D;
+        { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f16(ws.x, (int64_t)T * D, w.ln1_w, w.ln1_b, hc, n, D, h->cfg.layer_norm_eps, st)); }
+        kv.A = ws.x16; kv.W = w.wqkv_f + (size_t)D * D;
         kv.tile = (long)((M + 255) / 256) * (2 * D / 256) >= 120 ? GEMM_TILE_PP_AUTO : GEMM_TILE_PP_128x256;
-        kv.ln_in = h->lnst; kv.ln_colsum = w.qkv_cs + D; kv.ln_parts = D / 256; kv.ln_ld = (int)h->rows_cap; kv.ln_eps = h->cfg.layer_norm_eps;
+        kv.ln_in = ws.lnst; kv.ln_colsum = w.qkv_cs + D; kv.ln_parts = D / 256; kv.ln_ld = (int)h->rows_cap; kv.ln_eps = h->cfg.layer_norm_eps;
     } else {
-        { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f16(h->x, D, w.ln1_w, w.ln1_b, h->h16, M, D, h->cfg.layer_norm_eps, st)); }
-        kv.A = h->h16; kv.W = w.wqkv + (size_t)D * D; kv.W_lo = split ? w.wqkv_lo + (size_t)D * D : nullptr;
+        { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f16(ws.x, D, w.ln1_w, w.ln1_b, ws.h16, M, D, h->cfg.layer_norm_eps, st)); }
+        kv.A = ws.h16; kv.W = w.wqkv + (size_t)D * D; kv.W_lo = split ? w.wqkv_lo + (size_t)D * D : nullptr;
     }
-    kv.M = M; kv.M_pad = M_pad; kv.N = 2 * D; kv.K = D; kv.bias = (fold ? w.qkv_bf : w.qkv_b) + D; kv.out_f16 = h->qkv16 + D; kv.ldo = 3 * D;
+    kv.M = M; kv.M_pad = M_pad; kv.N = 2 * D; kv.K = D; kv.bias = (fold ? w.qkv_bf : w.qkv_b) + D; kv.out_f16 = ws.qkv16 + D; kv.ldo = 3 * D;
     kv.tokens_per_frame = T; kv.n_prefix = h->NP; kv.D = D; kv.sec0 = 1;
     set_rope(h, kv);
     { PROF(CBAS_PROF_QKV, 2.0 * M * 2.0 * D * D); LAUNCH_TRY(launch_gemm(fold ? EPI_QKV_LN : EPI_QKV, kv, st)); }
     const bool compact_q = f8 || fold;      // the CLS rows' LayerNorm 1 sits in hc
     GemmParams q{};                         // q section, CLS rows only (row b*T of h16; the compact fp16 rows when f8 / folded)
-    q.A = compact_q ? hc : h->h16; q.lda = compact_q ? D : T * D; q.W = w.wqkv; q.W_lo = split ? w.wqkv_lo : nullptr;
+    q.A = compact_q ? hc : ws.h16; q.lda = compact_q ? D : T * D; q.W = w.wqkv; q.W_lo = split ? w.wqkv_lo : nullptr;
     q.M = n; q.M_pad = n; q.N = D; q.K = D; q.bias = w.qkv_b; q.out_f16 = qc; q.ldo = D;
     q.tokens_per_frame = 1; q.n_prefix = 1; q.D = D; q.sec0 = 0;      // every row is token 0: no RoPE
     { PROF(CBAS_PROF_QKV, 2.0 * n * (double)D * D); LAUNCH_TRY(launch_gemm(EPI_QKV, q, st)); }
-    { PROF(CBAS_PROF_ATTENTION, 4.0 * n * (double)T * D); LAUNCH_TRY(launch_attention(h->qkv16, qc, cc, nullptr, 0, n, T, D, h->NH, st)); }
+    { PROF(CBAS_PROF_ATTENTION, 4.0 * n * (double)T * D); LAUNCH_TRY(launch_attention(ws.qkv16, qc, cc, nullptr, 0, n, T, D, h->NH, st)); }
     GemmParams o{};
     o.A = cc; o.W = w.wo; o.W_lo = split ? w.wo_lo : nullptr;
-    o.M = n; o.M_pad = n; o.N = D; o.K = D; o.bias = w.o_b; o.lambda = w.ls1; o.out_f32 = h->x; o.ldo = T * D;
+    o.M = n; o.M_pad = n; o.N = D; o.K = D; o.bias = w.o_b; o.lambda = w.ls1; o.out_f32 = ws.x; o.ldo = T * D;
     { PROF(CBAS_PROF_OPROJ, 2.0 * n * (double)D * D); LAUNCH_TRY(launch_gemm(EPI_RESID, o, st)); }
-    { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f16(h->x, (int64_t)T * D, w.ln2_w, w.ln2_b, hc, n, D, h->cfg.layer_norm_eps, st)); }
+    { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f16(ws.x, (int64_t)T * D, w.ln2_w, w.ln2_b, hc, n, D, h->cfg.layer_norm_eps, st)); }
     GemmParams u{};
     u.A = hc; u.W = w.wup; u.W_lo = split ? w.wup_lo : nullptr;
     u.M = n; u.M_pad = n; u.N = NU; u.K = D; u.bias = w.up_b; u.out_f16 = uc; u.ldo = F;
     { PROF(CBAS_PROF_UP, 2.0 * n * (double)NU * D); LAUNCH_TRY(launch_gemm(h->mlp ? EPI_SWIGLU : EPI_GELU, u, st)); }
     GemmParams d{};
     d.A = uc; d.W = w.wdown; d.W_lo = split ? w.wdown_lo : nullptr;
-    d.M = n; d.M_pad = n; d.N = D; d.K = F; d.bias = w.down_b; d.lambda = w.ls2; d.out_f32 = h->x; d.ldo = T * D;
+    d.M = n; d.M_pad = n; d.N = D; d.K = F; d.bias = w.down_b; d.lambda = w.ls2; d.out_f32 = ws.x; d.ldo = T * D;
     { PROF(CBAS_PROF_DOWN, 2.0 * n * (double)F * D); LAUNCH_TRY(launch_gemm(EPI_RESID, d, st)); }
     return CBAS_OK;
 }
 
 // precision 3: the same schedule with every buffer and every contraction in fp32 (vit_f32.hip).  The workspace pointers
 // (A_patch, h16, qkv16, u16, cls16) are allocated at 4 bytes per element in this mode and hold floats.
-int run_blocks_f32(cbas_enc* h, int n, int height, int width, float* cls_f32, f16* cls_f16, hipStream_t st,
+int run_blocks_f32(cbas_enc* h, const Lane& ws, int n, int height, int width, float* cls_f32, f16* cls_f16, hipStream_t st,
                    int stop_layer, int stop_stage) {
     const int ps = h->cfg.patch_size;
     const int nh = height / ps, nw = width / ps, P = nh * nw, T = P + h->NP;
@@ -509,10 +518,10 @@ int run_blocks_f32(cbas_enc* h, int n, int height, int width, float* cls_f32, f1
     h->last_rows = M;
     int rc = ensure_rope(h, nh, nw);
     if (rc) return rc;
-    float* const A32 = reinterpret_cast<float*>(h->A_patch);
-    float* const h32 = reinterpret_cast<float*>(h->h16);
-    float* const qkv32 = reinterpret_cast<float*>(h->qkv16);
-    float* const u32 = reinterpret_cast<float*>(h->u16);
+    float* const A32 = reinterpret_cast<float*>(ws.A_patch);
+    float* const h32 = reinterpret_cast<float*>(ws.h16);
+    float* const qkv32 = reinterpret_cast<float*>(ws.qkv16);
+    float* const u32 = reinterpret_cast<float*>(ws.u16);
     const float eps = h->cfg.layer_norm_eps;
 
     // precision 4: the same schedule with every GEMM's products on the fp16 pipe as three-term splits; operand scales:
@@ -522,7 +531,7 @@ int run_blocks_f32(cbas_enc* h, int n, int height, int width, float* cls_f32, f1
     auto sp = [&](Gemm32VitParams& q, float a_scale, float w_scale) { q.split = split; q.a_scale = a_scale; q.w_scale = w_scale; };
     Gemm32VitParams g{};
     sp(g, 1.f, h->sc_patch);
-    g.A = A32; g.lda = 256; g.W = h->wpatch32; g.M = n * P; g.N = D; g.K = 256; g.bias = h->patch_b; g.out = h->x; g.ldo = D;
+    g.A = A32; g.lda = 256; g.W = h->wpatch32; g.M = n * P; g.N = D; g.K = 256; g.bias = h->patch_b; g.out = ws.x; g.ldo = D;
     g.patches_per_frame = P; g.tokens_per_frame = T; g.n_prefix = h->NP; g.pos = h->cfg.use_rope ? nullptr : h->pos_tab;
     { PROF(CBAS_PROF_PATCH, 2.0 * g.M * g.N * g.K); LAUNCH_TRY(launch_gemm_f32_vit(EPI_PATCH, g, st)); }
     if (stop_layer == 0 && stop_stage == 0) return CBAS_OK;
@@ -545,11 +554,11 @@ int run_blocks_f32(cbas_enc* h, int n, int height, int width, float* cls_f32, f1
             // the last layer feeds only the final norm of the CLS rows (see run_last_layer_cls): K | V for every row,
             // everything else for the n CLS rows, read and written in place with a row stride of T*D
             const int64_t cap = round_up(h->cfg.max_batch, 128);
-            float* qc = reinterpret_cast<float*>(h->cls16);      // [n][D] CLS queries
+            float* qc = reinterpret_cast<float*>(ws.cls16);      // [n][D] CLS queries
             float* cc = qc + cap * D;                            // [n][D] attention context
             float* hc = cc + cap * D;                            // [n][D] LayerNorm rows
             float* uc = hc + cap * D;                            // [n][F] GELU(up_proj)
-            { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f32(h->x, D, w.ln1_w, w.ln1_b, h32, M, D, eps, split, st)); }
+            { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f32(ws.x, D, w.ln1_w, w.ln1_b, h32, M, D, eps, split, st)); }
             Gemm32VitParams kv{};
             qkv_params(w, kv);
             sp(kv, 1.f, w.sc_qkv);
@@ -565,9 +574,9 @@ int run_blocks_f32(cbas_enc* h, int n, int height, int width, float* cls_f32, f1
             { PROF(CBAS_PROF_ATTENTION, 4.0 * n * (double)T * D); LAUNCH_TRY(launch_attention_f32(qkv32, qc, cc, n, T, D, h->NH, split ? 16.f : 0.f, st)); }
             Gemm32VitParams o{};
             sp(o, 16.f, w.sc_o);
-            o.A = cc; o.lda = D; o.W = w.wo32; o.M = n; o.N = D; o.K = D; o.bias = w.o_b; o.lambda = w.ls1; o.out = h->x; o.ldo = (int64_t)T * D;
+            o.A = cc; o.lda = D; o.W = w.wo32; o.M = n; o.N = D; o.K = D; o.bias = w.o_b; o.lambda = w.ls1; o.out = ws.x; o.ldo = (int64_t)T * D;
             { PROF(CBAS_PROF_OPROJ, 2.0 * n * (double)D * D); LAUNCH_TRY(launch_gemm_f32_vit(EPI_RESID, o, st)); }
-            { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f32(h->x, (int64_t)T * D, w.ln2_w, w.ln2_b, hc, n, D, eps, split, st)); }
+            { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f32(ws.x, (int64_t)T * D, w.ln2_w, w.ln2_b, hc, n, D, eps, split, st)); }
             Gemm32VitParams u{};
             sp(u, 1.f, w.sc_up);
             u.out_scale = 4.f;
@@ -575,11 +584,11 @@ int run_blocks_f32(cbas_enc* h, int n, int height, int width, float* cls_f32, f1
             { PROF(CBAS_PROF_UP, 2.0 * n * (double)NU * D); LAUNCH_TRY(launch_gemm_f32_vit(EU, u, st)); }
             Gemm32VitParams d{};
             sp(d, 4.f, w.sc_down);
-            d.A = uc; d.lda = F; d.W = w.wdown32; d.M = n; d.N = D; d.K = F; d.bias = w.down_b; d.lambda = w.ls2; d.out = h->x; d.ldo = (int64_t)T * D;
+            d.A = uc; d.lda = F; d.W = w.wdown32; d.M = n; d.N = D; d.K = F; d.bias = w.down_b; d.lambda = w.ls2; d.out = ws.x; d.ldo = (int64_t)T * D;
             { PROF(CBAS_PROF_DOWN, 2.0 * n * (double)F * D); LAUNCH_TRY(launch_gemm_f32_vit(EPI_RESID, d, st)); }
             break;
         }
-        { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f32(h->x, D, w.ln1_w, w.ln1_b, h32, M, D, eps, split, st)); }
+        { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f32(ws.x, D, w.ln1_w, w.ln1_b, h32, M, D, eps, split, st)); }
         if (stop(1)) return CBAS_OK;
         Gemm32VitParams q{};
         qkv_params(w, q);
@@ -591,10 +600,10 @@ int run_blocks_f32(cbas_enc* h, int n, int height, int width, float* cls_f32, f1
         if (stop(3)) return CBAS_OK;
         Gemm32VitParams o{};
         sp(o, 16.f, w.sc_o);
-        o.A = h32; o.lda = D; o.W = w.wo32; o.M = M; o.N = D; o.K = D; o.bias = w.o_b; o.lambda = w.ls1; o.out = h->x; o.ldo = D;
+        o.A = h32; o.lda = D; o.W = w.wo32; o.M = M; o.N = D; o.K = D; o.bias = w.o_b; o.lambda = w.ls1; o.out = ws.x; o.ldo = D;
         { PROF(CBAS_PROF_OPROJ, 2.0 * M * (double)D * D); LAUNCH_TRY(launch_gemm_f32_vit(EPI_RESID, o, st)); }
         if (stop(4)) return CBAS_OK;
-        { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f32(h->x, D, w.ln2_w, w.ln2_b, h32, M, D, eps, split, st)); }
+        { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f32(ws.x, D, w.ln2_w, w.ln2_b, h32, M, D, eps, split, st)); }
         if (stop(5)) return CBAS_OK;
         Gemm32VitParams u{};
         sp(u, 1.f, w.sc_up);
@@ -604,19 +613,19 @@ int run_blocks_f32(cbas_enc* h, int n, int height, int width, float* cls_f32, f1
         if (stop(6)) return CBAS_OK;
         Gemm32VitParams d{};
         sp(d, 4.f, w.sc_down);
-        d.A = u32; d.lda = F; d.W = w.wdown32; d.M = M; d.N = D; d.K = F; d.bias = w.down_b; d.lambda = w.ls2; d.out = h->x; d.ldo = D;
+        d.A = u32; d.lda = F; d.W = w.wdown32; d.M = M; d.N = D; d.K = F; d.bias = w.down_b; d.lambda = w.ls2; d.out = ws.x; d.ldo = D;
         { PROF(CBAS_PROF_DOWN, 2.0 * M * (double)F * D); LAUNCH_TRY(launch_gemm_f32_vit(EPI_RESID, d, st)); }
         if (stop(7)) return CBAS_OK;
     }
     if (cls_f32 || cls_f16)
-        LAUNCH_TRY(launch_final_norm_cls(h->x, h->norm_w, h->norm_b, cls_f32, cls_f16, n, T, D, eps, st, h->nonfinite_dev));
+        LAUNCH_TRY(launch_final_norm_cls(ws.x, h->norm_w, h->norm_b, cls_f32, cls_f16, n, T, D, eps, st, h->nonfinite_dev));
     return CBAS_OK;
 }
 
 // Everything after ingest: patch GEMM, L transformer blocks, final CLS norm.
-int run_blocks(cbas_enc* h, int n, int height, int width, int patch_k, float in_scale, float* cls_f32,
+int run_blocks(cbas_enc* h, const Lane& ws, int n, int height, int width, int patch_k, float in_scale, float* cls_f32,
                f16* cls_f16, hipStream_t st, int stop_layer, int stop_stage) {
-    if (h->cfg.precision >= 3) return run_blocks_f32(h, n, height, width, cls_f32, cls_f16, st, stop_layer, stop_stage);
+    if (h->cfg.precision >= 3) return run_blocks_f32(h, ws, n, height, width, cls_f32, cls_f16, st, stop_layer, stop_stage);
     const int ps = h->cfg.patch_size;
     const int nh = height / ps, nw = width / ps, P = nh * nw, T = P + h->NP;
     const int D = h->D, F = h->F;
@@ -626,11 +635,11 @@ int run_blocks(cbas_enc* h, int n, int height, int width, int patch_k, float in_
     if (rc) return rc;
 
     GemmParams g{};
-    g.A = h->A_patch;
+    g.A = ws.A_patch;
     g.W = patch_k == 256 ? h->wpatch : h->wpatch2;
     g.W_lo = h->cfg.precision == 1 ? (patch_k == 256 ? h->wpatch_lo : h->wpatch2_lo) : nullptr;
     g.M = n * P; g.M_pad = (int)round_up(n * P, 128); g.N = D; g.K = patch_k;
-    g.bias = h->patch_b; g.out_f32 = h->x; g.ldo = D;
+    g.bias = h->patch_b; g.out_f32 = ws.x; g.ldo = D;
     g.patches_per_frame = P; g.tokens_per_frame = T; g.n_prefix = h->NP; g.in_scale = in_scale;
     g.pos = h->cfg.use_rope ? nullptr : h->pos_tab;
     { PROF(CBAS_PROF_PATCH, 2.0 * g.M * g.N * g.K); LAUNCH_TRY(launch_gemm(EPI_PATCH, g, st)); }
@@ -656,97 +665,97 @@ int run_blocks(cbas_enc* h, int n, int height, int width, int patch_k, float in_
     const bool fold = h->ln_fold && h->fold_ok && stop_layer < 0;
     const int ln_ld = (int)h->rows_cap;
     auto pp_tile = [&](int N) { return (long)((M + 255) / 256) * (N / 256) >= 120 ? GEMM_TILE_PP_AUTO : GEMM_TILE_PP_128x256; };
-    if (fold) { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_ln_stats_x16(h->x, h->x16, h->lnst, ln_ld, M, D, st)); }
+    if (fold) { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_ln_stats_x16(ws.x, ws.x16, ws.lnst, ln_ld, M, D, st)); }
     if (f8 && stop_layer >= 0) return cbas_fail(CBAS_EINVAL, "debug taps read fp16 buffers; not available with precision 2");
     const int sc_ld = (int)h->rows_cap;
-    uint8_t* const h8 = reinterpret_cast<uint8_t*>(h->h16);      // fp8 activations live in the fp16 buffers' memory
-    uint8_t* const u8 = reinterpret_cast<uint8_t*>(h->u16);
+    uint8_t* const h8 = reinterpret_cast<uint8_t*>(ws.h16);      // fp8 activations live in the fp16 buffers' memory
+    uint8_t* const u8 = reinterpret_cast<uint8_t*>(ws.u16);
     for (int l = 0; l < h->L; ++l) {
         const LayerW& w = h->layers[l];
         auto stop = [&](int stage) { return stop_layer == l && stop_stage == stage; };
         if (prune && l == h->L - 1) {
-            rc = run_last_layer_cls(h, w, n, T, st, fold);
+            rc = run_last_layer_cls(h, ws, w, n, T, st, fold);
             if (rc) return rc;
             break;
         }
         if (fold) {
             auto ln_consumer = [&](GemmParams& g, const float* colsum) {
-                g.ln_in = h->lnst; g.ln_colsum = colsum; g.ln_parts = D / 256; g.ln_ld = ln_ld; g.ln_eps = h->cfg.layer_norm_eps;
+                g.ln_in = ws.lnst; g.ln_colsum = colsum; g.ln_parts = D / 256; g.ln_ld = ln_ld; g.ln_eps = h->cfg.layer_norm_eps;
             };
-            auto ln_producer = [&](GemmParams& g) { g.x16_out = h->x16; g.ln_out = h->lnst; g.ln_ld = ln_ld; };
+            auto ln_producer = [&](GemmParams& g) { g.x16_out = ws.x16; g.ln_out = ws.lnst; g.ln_ld = ln_ld; };
             const bool more = l + 1 < h->L;             // the last layer's down_proj feeds the final norm only
             GemmParams q{};
             q.tile = pp_tile(3 * D);
-            q.A = h->x16; q.W = w.wqkv_f; q.M = M; q.M_pad = M_pad; q.N = 3 * D; q.K = D; q.bias = w.qkv_bf; q.out_f16 = h->qkv16; q.ldo = 3 * D;
+            q.A = ws.x16; q.W = w.wqkv_f; q.M = M; q.M_pad = M_pad; q.N = 3 * D; q.K = D; q.bias = w.qkv_bf; q.out_f16 = ws.qkv16; q.ldo = 3 * D;
             q.tokens_per_frame = T; q.n_prefix = h->NP; q.D = D;
             ln_consumer(q, w.qkv_cs);
             set_rope(h, q);
             { PROF(CBAS_PROF_QKV, 2.0 * M * 3.0 * D * D); LAUNCH_TRY(launch_gemm(EPI_QKV_LN, q, st)); }
             { PROF(CBAS_PROF_ATTENTION, 4.0 * n * (double)T * T * D);
-              LAUNCH_TRY(launch_attention(h->qkv16, nullptr, h->h16, nullptr, sc_ld, n, T, D, h->NH, st)); }
+              LAUNCH_TRY(launch_attention(ws.qkv16, nullptr, ws.h16, nullptr, sc_ld, n, T, D, h->NH, st)); }
             GemmParams o{};
             o.tile = pp_tile(D);
-            o.A = h->h16; o.W = w.wo; o.M = M; o.M_pad = M_pad; o.N = D; o.K = D; o.bias = w.o_b; o.lambda = w.ls1; o.out_f32 = h->x; o.ldo = D;
+            o.A = ws.h16; o.W = w.wo; o.M = M; o.M_pad = M_pad; o.N = D; o.K = D; o.bias = w.o_b; o.lambda = w.ls1; o.out_f32 = ws.x; o.ldo = D;
             ln_producer(o);
             { PROF(CBAS_PROF_OPROJ, 2.0 * M * (double)D * D); LAUNCH_TRY(launch_gemm(EPI_RESID_LN, o, st)); }
             GemmParams u{};
             u.tile = pp_tile(F);
-            u.A = h->x16; u.W = w.wup_f; u.out_f16 = h->u16; u.M = M; u.M_pad = M_pad; u.N = F; u.K = D; u.bias = w.up_bf; u.ldo = F;
+            u.A = ws.x16; u.W = w.wup_f; u.out_f16 = ws.u16; u.M = M; u.M_pad = M_pad; u.N = F; u.K = D; u.bias = w.up_bf; u.ldo = F;
             ln_consumer(u, w.up_cs);
             { PROF(CBAS_PROF_UP, 2.0 * M * (double)F * D); LAUNCH_TRY(launch_gemm(EPI_GELU_LN, u, st)); }
             GemmParams d{};
             d.tile = pp_tile(D);
-            d.A = h->u16; d.W = w.wdown; d.M = M; d.M_pad = M_pad; d.N = D; d.K = F; d.bias = w.down_b; d.lambda = w.ls2; d.out_f32 = h->x; d.ldo = D;
+            d.A = ws.u16; d.W = w.wdown; d.M = M; d.M_pad = M_pad; d.N = D; d.K = F; d.bias = w.down_b; d.lambda = w.ls2; d.out_f32 = ws.x; d.ldo = D;
             if (more) ln_producer(d);
             { PROF(CBAS_PROF_DOWN, 2.0 * M * (double)F * D); LAUNCH_TRY(launch_gemm(more ? EPI_RESID_LN : EPI_RESID, d, st)); }
             continue;
         }
-        if (f8_qkv) { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f8(h->x, D, w.ln1_w, w.ln1_b, h8, h->sc_h, sc_ld, M, D, h->cfg.layer_norm_eps, st)); }
-        else { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f16(h->x, D, w.ln1_w, w.ln1_b, h->h16, M, D, h->cfg.layer_norm_eps, st)); }
+        if (f8_qkv) { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f8(ws.x, D, w.ln1_w, w.ln1_b, h8, ws.sc_h, sc_ld, M, D, h->cfg.layer_norm_eps, st)); }
+        else { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f16(ws.x, D, w.ln1_w, w.ln1_b, ws.h16, M, D, h->cfg.layer_norm_eps, st)); }
         if (stop(1)) return CBAS_OK;
 
         GemmParams q{};
-        if (f8_qkv) { q.A8 = h8; q.A_sc = h->sc_h; q.sc_lda = sc_ld; q.W8 = w.wqkv8; q.W_sc = w.sqkv; }
-        else { q.A = h->h16; q.W = w.wqkv; q.W_lo = split ? w.wqkv_lo : nullptr; }
-        q.M = M; q.M_pad = M_pad; q.N = 3 * D; q.K = D; q.bias = w.qkv_b; q.out_f16 = h->qkv16; q.ldo = 3 * D;
+        if (f8_qkv) { q.A8 = h8; q.A_sc = ws.sc_h; q.sc_lda = sc_ld; q.W8 = w.wqkv8; q.W_sc = w.sqkv; }
+        else { q.A = ws.h16; q.W = w.wqkv; q.W_lo = split ? w.wqkv_lo : nullptr; }
+        q.M = M; q.M_pad = M_pad; q.N = 3 * D; q.K = D; q.bias = w.qkv_b; q.out_f16 = ws.qkv16; q.ldo = 3 * D;
         q.tokens_per_frame = T; q.n_prefix = h->NP; q.D = D;
         set_rope(h, q);
         { PROF(CBAS_PROF_QKV, 2.0 * M * 3.0 * D * D); LAUNCH_TRY(launch_gemm(EPI_QKV, q, st)); }
         if (stop(2)) return CBAS_OK;
 
         { PROF(CBAS_PROF_ATTENTION, 4.0 * n * (double)T * T * D);
-          LAUNCH_TRY(launch_attention(h->qkv16, nullptr, h->h16, f8_proj ? h->sc_h : nullptr, sc_ld, n, T, D, h->NH, st)); }
+          LAUNCH_TRY(launch_attention(ws.qkv16, nullptr, ws.h16, f8_proj ? ws.sc_h : nullptr, sc_ld, n, T, D, h->NH, st)); }
         if (stop(3)) return CBAS_OK;
 
         GemmParams o{};
-        if (f8_proj) { o.A8 = h8; o.A_sc = h->sc_h; o.sc_lda = sc_ld; o.W8 = w.wo8; o.W_sc = w.so; }
-        else { o.A = h->h16; o.W = w.wo; o.W_lo = split ? w.wo_lo : nullptr; }
-        o.M = M; o.M_pad = M_pad; o.N = D; o.K = D; o.bias = w.o_b; o.lambda = w.ls1; o.out_f32 = h->x; o.ldo = D;
+        if (f8_proj) { o.A8 = h8; o.A_sc = ws.sc_h; o.sc_lda = sc_ld; o.W8 = w.wo8; o.W_sc = w.so; }
+        else { o.A = ws.h16; o.W = w.wo; o.W_lo = split ? w.wo_lo : nullptr; }
+        o.M = M; o.M_pad = M_pad; o.N = D; o.K = D; o.bias = w.o_b; o.lambda = w.ls1; o.out_f32 = ws.x; o.ldo = D;
         { PROF(CBAS_PROF_OPROJ, 2.0 * M * (double)D * D); LAUNCH_TRY(launch_gemm(EPI_RESID, o, st)); }
         if (stop(4)) return CBAS_OK;
 
-        if (f8_up) { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f8(h->x, D, w.ln2_w, w.ln2_b, h8, h->sc_h, sc_ld, M, D, h->cfg.layer_norm_eps, st)); }
-        else { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f16(h->x, D, w.ln2_w, w.ln2_b, h->h16, M, D, h->cfg.layer_norm_eps, st)); }
+        if (f8_up) { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f8(ws.x, D, w.ln2_w, w.ln2_b, h8, ws.sc_h, sc_ld, M, D, h->cfg.layer_norm_eps, st)); }
+        else { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f16(ws.x, D, w.ln2_w, w.ln2_b, ws.h16, M, D, h->cfg.layer_norm_eps, st)); }
         if (stop(5)) return CBAS_OK;
 
         GemmParams u{};                     // operands by the plan's `up` bit, result in the format `down` consumes
-        if (f8_up) { u.A8 = h8; u.A_sc = h->sc_h; u.sc_lda = sc_ld; u.W8 = w.wup8; u.W_sc = w.sup; }
-        else { u.A = h->h16; u.W = w.wup; u.W_lo = split ? w.wup_lo : nullptr; }
-        if (f8_down) { u.out_f8 = u8; u.out_sc = h->sc_u; u.sc_ldo = sc_ld; }
-        else u.out_f16 = h->u16;
+        if (f8_up) { u.A8 = h8; u.A_sc = ws.sc_h; u.sc_lda = sc_ld; u.W8 = w.wup8; u.W_sc = w.sup; }
+        else { u.A = ws.h16; u.W = w.wup; u.W_lo = split ? w.wup_lo : nullptr; }
+        if (f8_down) { u.out_f8 = u8; u.out_sc = ws.sc_u; u.sc_ldo = sc_ld; }
+        else u.out_f16 = ws.u16;
         u.M = M; u.M_pad = M_pad; u.N = h->mlp ? 2 * F : F; u.K = D; u.bias = w.up_b; u.ldo = F;      // gated: gate | up interleaved
         { PROF(CBAS_PROF_UP, 2.0 * M * (double)u.N * D); LAUNCH_TRY(launch_gemm(h->mlp ? EPI_SWIGLU : f8_down ? EPI_GELU_F8 : EPI_GELU, u, st)); }
         if (stop(6)) return CBAS_OK;
 
         GemmParams d{};
-        if (f8_down) { d.A8 = u8; d.A_sc = h->sc_u; d.sc_lda = sc_ld; d.W8 = w.wdown8; d.W_sc = w.sdown; }
-        else { d.A = h->u16; d.W = w.wdown; d.W_lo = split ? w.wdown_lo : nullptr; }
-        d.M = M; d.M_pad = M_pad; d.N = D; d.K = F; d.bias = w.down_b; d.lambda = w.ls2; d.out_f32 = h->x; d.ldo = D;
+        if (f8_down) { d.A8 = u8; d.A_sc = ws.sc_u; d.sc_lda = sc_ld; d.W8 = w.wdown8; d.W_sc = w.sdown; }
+        else { d.A = ws.u16; d.W = w.wdown; d.W_lo = split ? w.wdown_lo : nullptr; }
+        d.M = M; d.M_pad = M_pad; d.N = D; d.K = F; d.bias = w.down_b; d.lambda = w.ls2; d.out_f32 = ws.x; d.ldo = D;
         { PROF(CBAS_PROF_DOWN, 2.0 * M * (double)F * D); LAUNCH_TRY(launch_gemm(EPI_RESID, d, st)); }
         if (stop(7)) return CBAS_OK;
     }
     if (cls_f32 || cls_f16)
-        LAUNCH_TRY(launch_final_norm_cls(h->x, h->norm_w, h->norm_b, cls_f32, cls_f16, n, T, D,
+        LAUNCH_TRY(launch_final_norm_cls(ws.x, h->norm_w, h->norm_b, cls_f32, cls_f16, n, T, D,
                                          h->cfg.layer_norm_eps, st, h->nonfinite_dev));
     return CBAS_OK;
 }
@@ -754,11 +763,11 @@ int run_blocks(cbas_enc* h, int n, int height, int width, int patch_k, float in_
 // DINOv3 ConvNeXt ([cx] = transformers models/dinov3_convnext/modeling_dinov3_convnext.py, DINOv3ConvNextModel.forward), after
 // the stem's im2col has been written to h16: the whole network on the fp32 GEMMs of the ViT (precision 4: split operands) and
 // the kernels of convnext_f32.hip.  stop >= 0 (debug taps): 0 ends after the stem's LayerNorm, 1 + i after stage i.
-int run_cnx(cbas_enc* h, int n, int height, int width, float* cls_f32, f16* cls_f16, hipStream_t st, int stop) {
+int run_cnx(cbas_enc* h, const Lane& ws, int n, int height, int width, float* cls_f32, f16* cls_f16, hipStream_t st, int stop) {
     const int split = h->cfg.precision == 4;
     const float eps = h->cfg.layer_norm_eps;
-    float* const A32 = reinterpret_cast<float*>(h->h16);
-    float* const u32 = reinterpret_cast<float*>(h->u16);
+    float* const A32 = reinterpret_cast<float*>(ws.h16);
+    float* const u32 = reinterpret_cast<float*>(ws.u16);
     auto gemm = [&](const float* A, int64_t lda, const float* W, int M, int N, int K, const float* bias,
                     float* out, int64_t ldo, float a_scale, float w_scale) {
         Gemm32VitParams g{};
@@ -771,9 +780,9 @@ int run_cnx(cbas_enc* h, int n, int height, int width, float* cls_f32, f16* cls_
     int M = n * hh * ww;
     const cbas_enc::CnxStage& S0 = h->cnx[0];
     {
-        Gemm32VitParams g = gemm(A32, 32, S0.ds_w, M, S0.Cp, 32, S0.ds_b, h->x, S0.Cp, 1.f, S0.sc_ds);
+        Gemm32VitParams g = gemm(A32, 32, S0.ds_w, M, S0.Cp, 32, S0.ds_b, ws.x, S0.Cp, 1.f, S0.sc_ds);
         { PROF(CBAS_PROF_PATCH, 2.0 * M * S0.C * 48); LAUNCH_TRY(launch_gemm_f32_vit(EPI_PATCH, g, st)); }
-        { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_cnx_ln_rows(h->x, S0.Cp, S0.ds_ln_w, S0.ds_ln_b, M, S0.C, eps, st)); }
+        { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_cnx_ln_rows(ws.x, S0.Cp, S0.ds_ln_w, S0.ds_ln_b, M, S0.C, eps, st)); }
     }
     h->cnx_tap_rows = M;
     if (stop == 0) return CBAS_OK;
@@ -783,19 +792,19 @@ int run_cnx(cbas_enc* h, int n, int height, int width, float* cls_f32, f16* cls_
         if (i > 0) {
             const cbas_enc::CnxStage& P = h->cnx[i - 1];
             { PROF(CBAS_PROF_LAYERNORM, 0.0);
-              LAUNCH_TRY(launch_cnx_downsample(h->x, P.Cp, n, hh, ww, S.ds_ln_w, S.ds_ln_b, P.C, eps, A32, split, st)); }
+              LAUNCH_TRY(launch_cnx_downsample(ws.x, P.Cp, n, hh, ww, S.ds_ln_w, S.ds_ln_b, P.C, eps, A32, split, st)); }
             hh /= 2; ww /= 2;
             M = n * hh * ww;
-            Gemm32VitParams g = gemm(A32, 4 * P.C, S.ds_w, M, S.Cp, 4 * P.C, S.ds_b, h->x, S.Cp, 1.f, S.sc_ds);
+            Gemm32VitParams g = gemm(A32, 4 * P.C, S.ds_w, M, S.Cp, 4 * P.C, S.ds_b, ws.x, S.Cp, 1.f, S.sc_ds);
             { PROF(CBAS_PROF_PATCH, 2.0 * M * C * 4.0 * P.C); LAUNCH_TRY(launch_gemm_f32_vit(EPI_PATCH, g, st)); }
         }
         for (const cbas_enc::CnxBlock& b : S.blocks) {
             { PROF(CBAS_PROF_LAYERNORM, 0.0);
-              LAUNCH_TRY(launch_cnx_dwconv_ln(h->x, S.Cp, n, hh, ww, b.dw_t, b.dw_b, b.ln_w, b.ln_b, C, eps, A32, split, st)); }
+              LAUNCH_TRY(launch_cnx_dwconv_ln(ws.x, S.Cp, n, hh, ww, b.dw_t, b.dw_b, b.ln_w, b.ln_b, C, eps, A32, split, st)); }
             Gemm32VitParams u = gemm(A32, C, b.pw1_w, M, 4 * C, C, b.pw1_b, u32, 4 * C, 1.f, b.sc1);
             u.out_scale = 4.f;                                        // the GELU output as pointwise_conv2's split A operand
             { PROF(CBAS_PROF_UP, 2.0 * M * 4.0 * C * C); LAUNCH_TRY(launch_gemm_f32_vit(EPI_GELU, u, st)); }
-            Gemm32VitParams d = gemm(u32, 4 * C, b.pw2_w, M, S.Cp, 4 * C, b.pw2_b, h->x, S.Cp, 4.f, b.sc2);
+            Gemm32VitParams d = gemm(u32, 4 * C, b.pw2_w, M, S.Cp, 4 * C, b.pw2_b, ws.x, S.Cp, 4.f, b.sc2);
             d.lambda = b.gamma;                                       // x += (pointwise_conv2 + b) * gamma
             { PROF(CBAS_PROF_DOWN, 2.0 * M * 4.0 * C * C); LAUNCH_TRY(launch_gemm_f32_vit(EPI_RESID, d, st)); }
         }
@@ -804,50 +813,67 @@ int run_cnx(cbas_enc* h, int n, int height, int width, float* cls_f32, f16* cls_
     }
     if (cls_f32 || cls_f16) {
         PROF(CBAS_PROF_LAYERNORM, 0.0);
-        LAUNCH_TRY(launch_cnx_pool_ln(h->x, h->cnx[3].Cp, n, hh * ww, h->cnx_norm_w, h->cnx_norm_b, h->cnx[3].C, eps, cls_f32,
+        LAUNCH_TRY(launch_cnx_pool_ln(ws.x, h->cnx[3].Cp, n, hh * ww, h->cnx_norm_w, h->cnx_norm_b, h->cnx[3].C, eps, cls_f32,
                                       cls_f16, h->nonfinite_dev, st));
     }
     return CBAS_OK;
 }
 
-int forward_u8_one(cbas_enc* h, const uint8_t* frames_dev, int n, int height, int width, int64_t frame_stride,
+int forward_u8_one(cbas_enc* h, const Lane& ws, const uint8_t* frames_dev, int n, int height, int width, int64_t frame_stride,
                    int64_t row_stride, int64_t pixel_stride, float* cls_f32, f16* cls_f16, hipStream_t st,
                    int stop_layer, int stop_stage) {
     if (h->cfg.family == 1) {
         LAUNCH_TRY(launch_cnx_stem_im2col_u8(frames_dev, n, height, width, frame_stride, row_stride, pixel_stride,
-                                             reinterpret_cast<float*>(h->h16), h->cfg.precision == 4, st));
+                                             reinterpret_cast<float*>(ws.h16), h->cfg.precision == 4, st));
         h->cnx_tap = stop_layer;
-        return run_cnx(h, n, height, width, cls_f32, cls_f16, st, stop_layer);
+        return run_cnx(h, ws, n, height, width, cls_f32, cls_f16, st, stop_layer);
     }
     const int ps = h->cfg.patch_size;
     const int T = (height / ps) * (width / ps) + h->NP;
     if (h->cfg.precision >= 3)
         LAUNCH_TRY(launch_im2col_u8_f32(frames_dev, n, height, width, frame_stride, row_stride, pixel_stride,
-                                        reinterpret_cast<float*>(h->A_patch), h->x, h->prefix, h->NP, h->D, T, ps,
+                                        reinterpret_cast<float*>(ws.A_patch), ws.x, h->prefix, h->NP, h->D, T, ps,
                                         h->cfg.precision == 4, st));
     else
-        LAUNCH_TRY(launch_im2col_u8(frames_dev, n, height, width, frame_stride, row_stride, pixel_stride, h->A_patch,
-                                    h->x, h->prefix, h->NP, h->D, T, ps, st));
-    return run_blocks(h, n, height, width, 256, 1.0f / 255.0f, cls_f32, cls_f16, st, stop_layer, stop_stage);
+        LAUNCH_TRY(launch_im2col_u8(frames_dev, n, height, width, frame_stride, row_stride, pixel_stride, ws.A_patch,
+                                    ws.x, h->prefix, h->NP, h->D, T, ps, st));
+    return run_blocks(h, ws, n, height, width, 256, 1.0f / 255.0f, cls_f32, cls_f16, st, stop_layer, stop_stage);
 }
 
-// Point the handle's workspace pointers at lane `l` (kernel arguments are captured at launch, so the
-// host-side switch is safe while the other lane's kernels are still running).
-void use_lane(cbas_enc* h, int l) {
-    const cbas_enc::Lane& L = h->lanes[l];
-    h->A_patch = L.A_patch; h->x = L.x; h->h16 = L.h16; h->qkv16 = L.qkv16; h->u16 = L.u16; h->cls16 = L.cls16;
-    h->sc_h = L.sc_h; h->sc_u = L.sc_u; h->x16 = L.x16; h->lnst = L.lnst;
-}
-
-int forward_u8(cbas_enc* h, const uint8_t* frames_dev, int n, int height, int width, int64_t frame_stride,
+int forward_u8(cbas_enc* h, const Lane& ws, const uint8_t* frames_dev, int n, int height, int width, int64_t frame_stride,
                int64_t row_stride, int64_t pixel_stride, float* cls_f32, f16* cls_f16, hipStream_t st,
                int stop_layer, int stop_stage) {
     int rc = check_frame(h, n, height, width);
     if (rc) return rc;
     if (!frames_dev) return cbas_fail(CBAS_EINVAL, "frames_dev is NULL");
     HIP_TRY(hipSetDevice(h->device));
-    return forward_u8_one(h, frames_dev, n, height, width, frame_stride, row_stride, pixel_stride, cls_f32, cls_f16, st,
+    return forward_u8_one(h, ws, frames_dev, n, height, width, frame_stride, row_stride, pixel_stride, cls_f32, cls_f16, st,
                           stop_layer, stop_stage);
+}
+
+// The buffers of lanes[lane], each zero-filled whole on `st` (the handle's compute stream: see the note at qkv_bias_all in
+// vit_build).  ConvNeXt's padding columns of x stay zero from here on.
+int alloc_lane(cbas_enc* h, int lane, const LaneBytes& sz, hipStream_t st) {
+    Lane& ws = h->lanes[lane];
+#define LANE_BUF(name)                                              \
+    if (sz.name) {                                                  \
+        ALLOC_TRY(hipMalloc(&ws.name, sz.name));                    \
+        ALLOC_TRY(hipMemsetAsync(ws.name, 0, sz.name, st));         \
+    }
+    LANE_BUF(A_patch); LANE_BUF(x); LANE_BUF(h16); LANE_BUF(qkv16); LANE_BUF(u16); LANE_BUF(cls16);
+    LANE_BUF(sc_h); LANE_BUF(sc_u); LANE_BUF(x16); LANE_BUF(lnst);
+#undef LANE_BUF
+    return CBAS_OK;
+}
+
+// Safe on a lane that was never or only partly allocated (a failed create); lane 0's stream belongs to the handle.
+void free_lane(cbas_enc* h, int lane) {
+    Lane& ws = h->lanes[lane];
+    if (ws.stream && ws.stream != h->compute) { (void)hipStreamSynchronize(ws.stream); (void)hipStreamDestroy(ws.stream); }
+    void* bufs[] = {ws.A_patch, ws.x, ws.h16, ws.qkv16, ws.u16, ws.cls16, ws.sc_h, ws.sc_u, ws.x16, ws.lnst};
+    for (void* b : bufs)
+        if (b) (void)hipFree(b);
+    ws = Lane{};
 }
 
 }  // namespace
@@ -896,19 +922,12 @@ extern "C" void cbas_enc_destroy(cbas_enc* h) {
         if (s.ev_in) (void)hipEventDestroy(s.ev_in);
     }
     for (auto& r : h->prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-    if (h->lanes[0].x) use_lane(h, 0);
-    if (h->lanes[1].stream) { (void)hipStreamSynchronize(h->lanes[1].stream); (void)hipStreamDestroy(h->lanes[1].stream); }
+    for (int l = 0; l < 2; ++l) free_lane(h, l);
     if (h->lane0_async_done) (void)hipEventDestroy(h->lane0_async_done);
     if (h->sync_done) (void)hipEventDestroy(h->sync_done);
-    {
-        void* b1[] = {h->lanes[1].A_patch, h->lanes[1].x, h->lanes[1].h16, h->lanes[1].qkv16, h->lanes[1].u16, h->lanes[1].cls16,
-                      h->lanes[1].sc_h, h->lanes[1].sc_u, h->lanes[1].x16, h->lanes[1].lnst};
-        for (void* b : b1) if (b) (void)hipFree(b);
-    }
     for (auto& t : h->pos_tables) { if (t.cos) (void)hipFree(t.cos); if (t.sin) (void)hipFree(t.sin); if (t.fac) (void)hipFree(t.fac); if (t.pos) (void)hipFree(t.pos); }
-    void* bufs[] = {h->blob, h->w16, h->w16_lo, h->qkv_bias_all, h->prefix_dev,
-                    h->A_patch, h->h16, h->qkv16, h->u16, h->x, h->cls16, h->w8, h->w8_sc, h->sc_h, h->sc_u,
-                    h->w16_fold, h->fold_vec, h->x16, h->lnst, h->w32, h->cnx_arena, h->gu_bias_all, h->gu_scratch};
+    void* bufs[] = {h->blob, h->w16, h->w16_lo, h->qkv_bias_all, h->prefix_dev, h->w8, h->w8_sc,
+                    h->w16_fold, h->fold_vec, h->w32, h->cnx_arena, h->gu_bias_all, h->gu_scratch};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (h->compute) (void)hipStreamDestroy(h->compute);
@@ -921,28 +940,20 @@ namespace {
 
 // host-streaming slots (both families)
 int create_slots(cbas_enc* h) {
-#define SLOT_TRY(expr)                                                                                              \
-    do {                                                                                                           \
-        hipError_t _e = (expr);                                                                                    \
-        if (_e != hipSuccess)                                                                                      \
-            return cbas_fail(_e == hipErrorOutOfMemory ? CBAS_ENOMEM : CBAS_EHIP, "%s failed: %s (%s:%d)", #expr,  \
-                             hipGetErrorString(_e), __FILE__, __LINE__);                                           \
-    } while (0)
     const cbas_enc_config& c = h->cfg;
     h->slot_bytes = (int64_t)c.max_batch * c.max_height * c.max_width * 4;
     for (Slot& s : h->slots) {
-        SLOT_TRY(hipHostMalloc(&s.in_host, h->slot_bytes, hipHostMallocDefault));
-        SLOT_TRY(hipHostMalloc(&s.out16_host, (int64_t)c.max_batch * h->D * 2, hipHostMallocDefault));
-        SLOT_TRY(hipHostMalloc(&s.out32_host, (int64_t)c.max_batch * h->D * 4, hipHostMallocDefault));
-        SLOT_TRY(hipMalloc(&s.in_dev, h->slot_bytes));
-        SLOT_TRY(hipMalloc(&s.out16_dev, (int64_t)c.max_batch * h->D * 2));
-        SLOT_TRY(hipMalloc(&s.out32_dev, (int64_t)c.max_batch * h->D * 4));
-        SLOT_TRY(hipEventCreateWithFlags(&s.ev_copied, hipEventDisableTiming));
-        SLOT_TRY(hipEventCreateWithFlags(&s.ev_done, hipEventDisableTiming));
-        SLOT_TRY(hipEventCreateWithFlags(&s.ev_in, hipEventDisableTiming));
+        ALLOC_TRY(hipHostMalloc(&s.in_host, h->slot_bytes, hipHostMallocDefault));
+        ALLOC_TRY(hipHostMalloc(&s.out16_host, (int64_t)c.max_batch * h->D * 2, hipHostMallocDefault));
+        ALLOC_TRY(hipHostMalloc(&s.out32_host, (int64_t)c.max_batch * h->D * 4, hipHostMallocDefault));
+        ALLOC_TRY(hipMalloc(&s.in_dev, h->slot_bytes));
+        ALLOC_TRY(hipMalloc(&s.out16_dev, (int64_t)c.max_batch * h->D * 2));
+        ALLOC_TRY(hipMalloc(&s.out32_dev, (int64_t)c.max_batch * h->D * 4));
+        ALLOC_TRY(hipEventCreateWithFlags(&s.ev_copied, hipEventDisableTiming));
+        ALLOC_TRY(hipEventCreateWithFlags(&s.ev_done, hipEventDisableTiming));
+        ALLOC_TRY(hipEventCreateWithFlags(&s.ev_in, hipEventDisableTiming));
     }
     return CBAS_OK;
-#undef SLOT_TRY
 }
 
 int cnx_check_config(const cbas_enc_config& c) {
@@ -1069,73 +1080,21 @@ int cnx_build(cbas_enc* h, const float* wh) {
                 if (f.second == g.off) *f.first = h->w32 + g.off;
         }
     }
-    // workspaces: lane 0 on the handle's compute stream, lane 1 on its own
-    cnx_sizes(h, c.max_batch, c.max_height, c.max_width, &h->cnx_x_cap, &h->cnx_a_cap, &h->cnx_u_cap);
-    const char* e = getenv("CBAS_LANES");
-    h->n_lanes = (e && atoi(e) == 1) ? 1 : 2;
-    for (int l = 0; l < h->n_lanes; ++l) {
-        cbas_enc::Lane& L = h->lanes[l];
-        HIP_TRY(hipMalloc(&L.x, h->cnx_x_cap * sizeof(float)));
-        HIP_TRY(hipMalloc(&L.h16, h->cnx_a_cap * sizeof(float)));
-        HIP_TRY(hipMalloc(&L.u16, h->cnx_u_cap * sizeof(float)));
-        HIP_TRY(hipMemsetAsync(L.x, 0, h->cnx_x_cap * sizeof(float), st));      // the padding columns stay 0 from here on
-        HIP_TRY(hipMemsetAsync(L.h16, 0, h->cnx_a_cap * sizeof(float), st));
-        HIP_TRY(hipMemsetAsync(L.u16, 0, h->cnx_u_cap * sizeof(float), st));
-        if (l == 0) L.stream = h->compute;
-        else HIP_TRY(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
-    }
-    use_lane(h, 0);
-    HIP_TRY(hipEventCreateWithFlags(&h->lane0_async_done, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&h->sync_done, hipEventDisableTiming));
-    HIP_TRY(hipMalloc(&h->nonfinite_dev, sizeof(unsigned)));
-    HIP_TRY(hipMemsetAsync(h->nonfinite_dev, 0, sizeof(unsigned), st));
-    int rc = create_slots(h);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(st));
     return CBAS_OK;
 }
 
-}  // namespace
-
-extern "C" int cbas_enc_create(const cbas_enc_config* cfg, const float* weights_host, int64_t n_weights,
-                               int device_id, cbas_enc** out) {
-    return cbas_enc_create_mlp(cfg, CBAS_MLP_GELU, weights_host, n_weights, device_id, out);
+// floats per lane of a ConvNeXt handle's three buffers (kept for check_frame) and their bytes
+LaneBytes cnx_lane_bytes(cbas_enc* h) {
+    const cbas_enc_config& c = h->cfg;
+    cnx_sizes(h, c.max_batch, c.max_height, c.max_width, &h->cnx_x_cap, &h->cnx_a_cap, &h->cnx_u_cap);
+    LaneBytes sz;
+    sz.x = h->cnx_x_cap * sizeof(float);
+    sz.h16 = h->cnx_a_cap * sizeof(float);
+    sz.u16 = h->cnx_u_cap * sizeof(float);
+    return sz;
 }
 
-extern "C" int cbas_enc_create_mlp(const cbas_enc_config* cfg, int32_t mlp, const float* weights_host, int64_t n_weights,
-                                   int device_id, cbas_enc** out) {
-    if (!cfg || !weights_host || !out) return cbas_fail(CBAS_EINVAL, "null argument");
-    *out = nullptr;
-    const cbas_enc_config& c = *cfg;
-    if (const char* why = mlp_refusal(c, mlp)) return cbas_fail(CBAS_EINVAL, "%s", why);
-    if (c.family == 1) {
-        int rc = cnx_check_config(c);
-        if (rc) return rc;
-        if (n_weights != weights_count(c))
-            return cbas_fail(CBAS_EINVAL, "weights blob has %lld floats, config needs %lld", (long long)n_weights,
-                             (long long)weights_count(c));
-        HIP_TRY(hipSetDevice(device_id));
-        cbas_enc* h = new (std::nothrow) cbas_enc();
-        if (!h) return cbas_fail(CBAS_ENOMEM, "out of host memory");
-        h->cfg = c; h->device = device_id;
-        h->D = c.hidden_size;
-        rc = CBAS_OK;
-        if (hipStreamCreateWithFlags(&h->compute, hipStreamNonBlocking) != hipSuccess ||
-            hipStreamCreateWithFlags(&h->copy, hipStreamNonBlocking) != hipSuccess ||
-            hipStreamCreateWithFlags(&h->aux, hipStreamNonBlocking) != hipSuccess)
-            rc = cbas_fail(CBAS_EHIP, "stream creation failed");
-        if (!rc) rc = cnx_build(h, weights_host);
-        if (rc) {
-            const int code = rc;
-            char msg[sizeof(g_cbas_err)];
-            memcpy(msg, g_cbas_err, sizeof(msg));
-            cbas_enc_destroy(h);
-            memcpy(g_cbas_err, msg, sizeof(msg));
-            return code;
-        }
-        *out = h;
-        return CBAS_OK;
-    }
+int vit_check_config(const cbas_enc_config& c) {
     if (c.family != 0) return cbas_fail(CBAS_EINVAL, "family=%d: 0 (ViT) or 1 (DINOv3 ConvNeXt)", c.family);
     if (c.hidden_size <= 0 || c.hidden_size % 128 || c.num_heads * 64 != c.hidden_size)
         return cbas_fail(CBAS_EINVAL, "hidden_size=%d must be a multiple of 128 with head_dim 64 (num_heads=%d)",
@@ -1156,69 +1115,52 @@ extern "C" int cbas_enc_create_mlp(const cbas_enc_config* cfg, int32_t mlp, cons
         return cbas_fail(CBAS_EINVAL, "exactly one of use_rope / pos_embed_grid must be set");
     if (c.num_layers <= 0 || c.num_register_tokens < 0 || c.max_batch <= 0 || c.max_height < c.patch_size || c.max_width < c.patch_size)
         return cbas_fail(CBAS_EINVAL, "bad layer/register/batch/frame-size field");
-    if (n_weights != weights_count(c, mlp))
-        return cbas_fail(CBAS_EINVAL, "weights blob has %lld floats, config needs %lld", (long long)n_weights,
-                         (long long)weights_count(c, mlp));
-    HIP_TRY(hipSetDevice(device_id));
+    return CBAS_OK;
+}
 
-    cbas_enc* h = new (std::nothrow) cbas_enc();
-    if (!h) return cbas_fail(CBAS_ENOMEM, "out of host memory");
-    h->cfg = c; h->device = device_id; h->mlp = mlp;
-    h->D = c.hidden_size; h->F = c.intermediate_size; h->L = c.num_layers; h->NH = c.num_heads;
+// ViT weights: the blob on the device as it is, and every GEMM weight once more in the format the handle's precision
+// multiplies in (packing kernels on the compute stream)
+int vit_build(cbas_enc* h, const float* weights_host, int64_t n_weights) {
+    const cbas_enc_config& c = h->cfg;
+    h->F = c.intermediate_size; h->L = c.num_layers; h->NH = c.num_heads;
     h->R = c.num_register_tokens; h->NP = 1 + h->R;
     const int64_t D = h->D, F = h->F;
-
-#define CREATE_TRY(expr)                                                                                  \
-    do {                                                                                                  \
-        hipError_t _e = (expr);                                                                           \
-        if (_e != hipSuccess) {                                                                           \
-            cbas_fail(CBAS_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-            cbas_enc_destroy(h);                                                                          \
-            return _e == hipErrorOutOfMemory ? CBAS_ENOMEM : CBAS_EHIP;                                   \
-        }                                                                                                 \
-    } while (0)
-
-    CREATE_TRY(hipStreamCreateWithFlags(&h->compute, hipStreamNonBlocking));
-    CREATE_TRY(hipStreamCreateWithFlags(&h->copy, hipStreamNonBlocking));
-    CREATE_TRY(hipStreamCreateWithFlags(&h->aux, hipStreamNonBlocking));
-    CREATE_TRY(hipMalloc(&h->blob, n_weights * sizeof(float)));
-    CREATE_TRY(hipMemcpy(h->blob, weights_host, n_weights * sizeof(float), hipMemcpyHostToDevice));
+    ALLOC_TRY(hipMalloc(&h->blob, n_weights * sizeof(float)));
+    ALLOC_TRY(hipMemcpy(h->blob, weights_host, n_weights * sizeof(float), hipMemcpyHostToDevice));
 
     // fp16 weight arena: patch (D*256 + D*512) + per layer (3DD + DD + FD + DF); a gated MLP's gate | up weight is 2FD
-    const bool gated = mlp == CBAS_MLP_SWIGLU;
+    const bool gated = h->mlp == CBAS_MLP_SWIGLU;
     const int64_t FU = gated ? 2 * F : F;      // rows of the up GEMM's weight
     const int64_t n16 = D * 256 + D * 512 + (int64_t)h->L * (4 * D * D + FU * D + F * D);
     const bool p3 = c.precision >= 3;         // fp32 end to end (3: fp32 MFMA; 4: three-term fp16 split of the same operands): no fp16 copies, every workspace 4 bytes per element
-    if (!p3) CREATE_TRY(hipMalloc(&h->w16, n16 * sizeof(f16)));
-    if (c.precision == 1) CREATE_TRY(hipMalloc(&h->w16_lo, n16 * sizeof(f16)));
+    if (!p3) ALLOC_TRY(hipMalloc(&h->w16, n16 * sizeof(f16)));
+    if (c.precision == 1) ALLOC_TRY(hipMalloc(&h->w16_lo, n16 * sizeof(f16)));
     float* w32p = nullptr;
     if (c.precision == 4) {
         // every weight once more in the split hi | lo format (same byte size as fp32) + a scratch patch weight
-        CREATE_TRY(hipMalloc(&h->w32, (2 * D * 256 + (int64_t)h->L * (4 * D * D + FU * D + F * D)) * sizeof(float)));
+        ALLOC_TRY(hipMalloc(&h->w32, (2 * D * 256 + (int64_t)h->L * (4 * D * D + FU * D + F * D)) * sizeof(float)));
         w32p = h->w32;
     } else if (p3) {
         // (gated: + the interleaved gate | up weight of every layer, which precision 3 reads as it is)
-        CREATE_TRY(hipMalloc(&h->w32, (D * 256 + (int64_t)h->L * (3 * D * D + (gated ? FU * D : 0))) * sizeof(float)));
+        ALLOC_TRY(hipMalloc(&h->w32, (D * 256 + (int64_t)h->L * (3 * D * D + (gated ? FU * D : 0))) * sizeof(float)));
         w32p = h->w32;
     }
     uint8_t* w8p = nullptr;
     uint32_t* s8p = nullptr;
     if (c.precision == 2) {
         const int64_t n8 = (int64_t)h->L * (4 * D * D + 2 * F * D);
-        CREATE_TRY(hipMalloc(&h->w8, n8));
-        CREATE_TRY(hipMalloc(&h->w8_sc, n8 / 32));              // one E8M0 byte per 32 elements
+        ALLOC_TRY(hipMalloc(&h->w8, n8));
+        ALLOC_TRY(hipMalloc(&h->w8_sc, n8 / 32));              // one E8M0 byte per 32 elements
         w8p = h->w8; s8p = h->w8_sc;
     }
-    CREATE_TRY(hipMalloc(&h->nonfinite_dev, sizeof(unsigned)));
-    CREATE_TRY(hipMemsetAsync(h->nonfinite_dev, 0, sizeof(unsigned), h->compute));
-    CREATE_TRY(hipMalloc(&h->qkv_bias_all, (int64_t)h->L * 3 * D * sizeof(float)));
+    ALLOC_TRY(hipMalloc(&h->qkv_bias_all, (int64_t)h->L * 3 * D * sizeof(float)));
     // on the stream the packing kernels and copies below run on: a null-stream hipMemset may still be in flight when work on a
     // NON-BLOCKING stream (every stream of this library) touches the buffer - found by running training beside the encoder (r5)
-    CREATE_TRY(hipMemsetAsync(h->qkv_bias_all, 0, (int64_t)h->L * 3 * D * sizeof(float), h->compute));
+    ALLOC_TRY(hipMemsetAsync(h->qkv_bias_all, 0, (int64_t)h->L * 3 * D * sizeof(float), h->compute));
 
     if (gated) {
-        CREATE_TRY(hipMalloc(&h->gu_bias_all, (int64_t)h->L * FU * sizeof(float)));
-        if (c.precision != 3) CREATE_TRY(hipMalloc(&h->gu_scratch, FU * D * sizeof(float)));
+        ALLOC_TRY(hipMalloc(&h->gu_bias_all, (int64_t)h->L * FU * sizeof(float)));
+        if (c.precision != 3) ALLOC_TRY(hipMalloc(&h->gu_scratch, FU * D * sizeof(float)));
     }
 
     // LayerNorm fold: folded copies of the q|k|v and up_proj weights (+ column sums and biases), fp16 path only; not for a
@@ -1227,8 +1169,8 @@ extern "C" int cbas_enc_create_mlp(const cbas_enc_config* cfg, int32_t mlp, cons
     f16* wf = nullptr;
     float* fv = nullptr;
     if (h->fold_ok) {
-        CREATE_TRY(hipMalloc(&h->w16_fold, (int64_t)h->L * (3 * D * D + F * D) * sizeof(f16)));
-        CREATE_TRY(hipMalloc(&h->fold_vec, (int64_t)h->L * 2 * (3 * D + F) * sizeof(float)));
+        ALLOC_TRY(hipMalloc(&h->w16_fold, (int64_t)h->L * (3 * D * D + F * D) * sizeof(f16)));
+        ALLOC_TRY(hipMalloc(&h->fold_vec, (int64_t)h->L * 2 * (3 * D + F) * sizeof(float)));
         wf = h->w16_fold; fv = h->fold_vec;
     }
 
@@ -1247,8 +1189,8 @@ extern "C" int cbas_enc_create_mlp(const cbas_enc_config* cfg, int32_t mlp, cons
             h->pos_host.assign(pos, pos + (1 + G * G) * D);
             for (int64_t d = 0; d < D; ++d) pre[d] += pos[d];
         }
-        CREATE_TRY(hipMalloc(&h->prefix_dev, pre.size() * sizeof(float)));
-        CREATE_TRY(hipMemcpy(h->prefix_dev, pre.data(), pre.size() * sizeof(float), hipMemcpyHostToDevice));
+        ALLOC_TRY(hipMalloc(&h->prefix_dev, pre.size() * sizeof(float)));
+        ALLOC_TRY(hipMemcpy(h->prefix_dev, pre.data(), pre.size() * sizeof(float), hipMemcpyHostToDevice));
         h->prefix = h->prefix_dev;
         p += (1 + h->R) * D + (G > 0 ? (1 + G * G) * D : 0);
     }
@@ -1343,9 +1285,9 @@ extern "C" int cbas_enc_create_mlp(const cbas_enc_config* cfg, int32_t mlp, cons
             lw.wdown32 = w32p; w32p += D * F;
         } else if (p3) {
             // q, k, v sit in the blob with their biases between them: one packed [3D][D] copy; the rest is used in place
-            CREATE_TRY(hipMemcpyAsync(w32p, qw, D * D * sizeof(float), hipMemcpyDeviceToDevice, st));
-            CREATE_TRY(hipMemcpyAsync(w32p + D * D, kw, D * D * sizeof(float), hipMemcpyDeviceToDevice, st));
-            CREATE_TRY(hipMemcpyAsync(w32p + 2 * D * D, vw, D * D * sizeof(float), hipMemcpyDeviceToDevice, st));
+            ALLOC_TRY(hipMemcpyAsync(w32p, qw, D * D * sizeof(float), hipMemcpyDeviceToDevice, st));
+            ALLOC_TRY(hipMemcpyAsync(w32p + D * D, kw, D * D * sizeof(float), hipMemcpyDeviceToDevice, st));
+            ALLOC_TRY(hipMemcpyAsync(w32p + 2 * D * D, vw, D * D * sizeof(float), hipMemcpyDeviceToDevice, st));
             lw.wqkv32 = w32p; w32p += 3 * D * D;
             lw.wo32 = ow; lw.wup32 = uw; lw.wdown32 = dw;
             if (gated) {
@@ -1390,101 +1332,107 @@ extern "C" int cbas_enc_create_mlp(const cbas_enc_config* cfg, int32_t mlp, cons
             rc |= launch_interleave_gate_up(gb, lw.up_b, gub, F, 1, st);
             lw.up_b = gub;
         }
-        CREATE_TRY(hipMemcpyAsync(lw.qkv_b, qb, D * sizeof(float), hipMemcpyDeviceToDevice, st));
-        CREATE_TRY(hipMemcpyAsync(lw.qkv_b + D, kb, D * sizeof(float), hipMemcpyDeviceToDevice, st));
-        CREATE_TRY(hipMemcpyAsync(lw.qkv_b + 2 * D, vb, D * sizeof(float), hipMemcpyDeviceToDevice, st));
+        ALLOC_TRY(hipMemcpyAsync(lw.qkv_b, qb, D * sizeof(float), hipMemcpyDeviceToDevice, st));
+        ALLOC_TRY(hipMemcpyAsync(lw.qkv_b + D, kb, D * sizeof(float), hipMemcpyDeviceToDevice, st));
+        ALLOC_TRY(hipMemcpyAsync(lw.qkv_b + 2 * D, vb, D * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
     h->norm_w = p; p += D;
     h->norm_b = p; p += D;
-    if (rc || (p - h->blob) != n_weights) {
-        cbas_fail(CBAS_EHIP, "weight packing failed (rc=%d, consumed %lld of %lld)", rc, (long long)(p - h->blob),
-                  (long long)n_weights);
-        cbas_enc_destroy(h);
-        return CBAS_EHIP;
-    }
+    if (rc || (p - h->blob) != n_weights)
+        return cbas_fail(CBAS_EHIP, "weight packing failed (rc=%d, consumed %lld of %lld)", rc, (long long)(p - h->blob),
+                         (long long)n_weights);
+    return CBAS_OK;
+}
 
-    // workspaces
+// rows a ViT lane holds (kept for check_frame and the scale / statistics strides) and the bytes of its buffers
+LaneBytes vit_lane_bytes(cbas_enc* h) {
+    const cbas_enc_config& c = h->cfg;
+    const int64_t D = h->D, F = h->F;
     const int64_t Pmax = (int64_t)(c.max_height / c.patch_size) * (c.max_width / c.patch_size);
     const int64_t Tmax = Pmax + h->NP;
     h->rows_cap = round_up((int64_t)c.max_batch * Tmax, 128);
     h->prow_cap = round_up((int64_t)c.max_batch * Pmax, 128);
     h->rope_cap = (int)Pmax;
     h->pos_tables.reserve(cbas_enc::POS_TABLES_MAX);     // entries are handed out by pointer: never reallocate
-    const size_t esz = p3 ? sizeof(float) : sizeof(f16);      // activation element size (A_patch is 512 f16 = 256 f32 per row)
-    CREATE_TRY(hipMalloc(&h->A_patch, h->prow_cap * 512 * sizeof(f16)));
-    CREATE_TRY(hipMalloc(&h->x, h->rows_cap * D * sizeof(float)));
-    CREATE_TRY(hipMalloc(&h->h16, h->rows_cap * D * esz));
-    CREATE_TRY(hipMalloc(&h->qkv16, h->rows_cap * 3 * D * esz));
-    CREATE_TRY(hipMalloc(&h->u16, h->rows_cap * F * esz));
-    const int64_t sch_elems = (D / 128) * h->rows_cap, scu_elems = (F / 128) * h->rows_cap;    // dwords
+    const size_t esz = c.precision >= 3 ? sizeof(float) : sizeof(f16);      // activation element size (A_patch is 512 f16 = 256 f32 per row)
+    LaneBytes sz;
+    sz.A_patch = h->prow_cap * 512 * sizeof(f16);
+    sz.x = h->rows_cap * D * sizeof(float);
+    sz.h16 = h->rows_cap * D * esz;
+    sz.qkv16 = h->rows_cap * 3 * D * esz;
+    sz.u16 = h->rows_cap * F * esz;
+    sz.cls16 = round_up(c.max_batch, 128) * (3 * D + F) * esz;
     if (c.precision == 2) {
-        CREATE_TRY(hipMalloc(&h->sc_h, sch_elems * 4));
-        CREATE_TRY(hipMalloc(&h->sc_u, scu_elems * 4));
-        CREATE_TRY(hipMemsetAsync(h->sc_h, 0, sch_elems * 4, st));
-        CREATE_TRY(hipMemsetAsync(h->sc_u, 0, scu_elems * 4, st));
+        sz.sc_h = (D / 128) * h->rows_cap * 4;      // dwords
+        sz.sc_u = (F / 128) * h->rows_cap * 4;
     }
     if (h->fold_ok) {
-        CREATE_TRY(hipMalloc(&h->x16, h->rows_cap * D * sizeof(f16)));
-        CREATE_TRY(hipMalloc(&h->lnst, 4 * h->rows_cap * sizeof(float2)));
-        CREATE_TRY(hipMemsetAsync(h->x16, 0, h->rows_cap * D * sizeof(f16), st));
-        CREATE_TRY(hipMemsetAsync(h->lnst, 0, 4 * h->rows_cap * sizeof(float2), st));
+        sz.x16 = h->rows_cap * D * sizeof(f16);
+        sz.lnst = 4 * h->rows_cap * sizeof(float2);
     }
-    const int64_t cls_elems = round_up(c.max_batch, 128) * (3 * D + F);
-    CREATE_TRY(hipMalloc(&h->cls16, cls_elems * esz));
-    CREATE_TRY(hipMemsetAsync(h->cls16, 0, cls_elems * esz, st));
-    CREATE_TRY(hipMemsetAsync(h->A_patch, 0, h->prow_cap * 512 * sizeof(f16), st));
-    CREATE_TRY(hipMemsetAsync(h->x, 0, h->rows_cap * D * sizeof(float), st));
-    CREATE_TRY(hipMemsetAsync(h->h16, 0, h->rows_cap * D * esz, st));
-    CREATE_TRY(hipMemsetAsync(h->qkv16, 0, h->rows_cap * 3 * D * esz, st));
-    CREATE_TRY(hipMemsetAsync(h->u16, 0, h->rows_cap * F * esz, st));
-    // second compute lane (see cbas_enc::Lane); CBAS_LANES=1 (read here, once per handle) keeps a single lane
-    {
-        const char* e = getenv("CBAS_LANES");
-        h->n_lanes = (e && atoi(e) == 1) ? 1 : 2;
-        cbas_enc::Lane& L0 = h->lanes[0];
-        L0.A_patch = h->A_patch; L0.x = h->x; L0.h16 = h->h16; L0.qkv16 = h->qkv16; L0.u16 = h->u16; L0.cls16 = h->cls16; L0.sc_h = h->sc_h; L0.sc_u = h->sc_u; L0.stream = h->compute;
-        L0.x16 = h->x16; L0.lnst = h->lnst;
-        if (h->n_lanes == 2) {
-            cbas_enc::Lane& L1 = h->lanes[1];
-            CREATE_TRY(hipMalloc(&L1.A_patch, h->prow_cap * 512 * sizeof(f16)));
-            CREATE_TRY(hipMalloc(&L1.x, h->rows_cap * D * sizeof(float)));
-            CREATE_TRY(hipMalloc(&L1.h16, h->rows_cap * D * esz));
-            CREATE_TRY(hipMalloc(&L1.qkv16, h->rows_cap * 3 * D * esz));
-            CREATE_TRY(hipMalloc(&L1.u16, h->rows_cap * F * esz));
-            if (c.precision == 2) {
-                CREATE_TRY(hipMalloc(&L1.sc_h, sch_elems * 4));
-                CREATE_TRY(hipMalloc(&L1.sc_u, scu_elems * 4));
-                CREATE_TRY(hipMemsetAsync(L1.sc_h, 0, sch_elems * 4, st));
-                CREATE_TRY(hipMemsetAsync(L1.sc_u, 0, scu_elems * 4, st));
-            }
-            if (h->fold_ok) {
-                CREATE_TRY(hipMalloc(&L1.x16, h->rows_cap * D * sizeof(f16)));
-                CREATE_TRY(hipMalloc(&L1.lnst, 4 * h->rows_cap * sizeof(float2)));
-                CREATE_TRY(hipMemsetAsync(L1.x16, 0, h->rows_cap * D * sizeof(f16), st));
-                CREATE_TRY(hipMemsetAsync(L1.lnst, 0, 4 * h->rows_cap * sizeof(float2), st));
-            }
-            CREATE_TRY(hipMalloc(&L1.cls16, cls_elems * esz));
-            CREATE_TRY(hipMemsetAsync(L1.cls16, 0, cls_elems * esz, st));
-            CREATE_TRY(hipMemsetAsync(L1.A_patch, 0, h->prow_cap * 512 * sizeof(f16), st));
-            CREATE_TRY(hipMemsetAsync(L1.x, 0, h->rows_cap * D * sizeof(float), st));
-            CREATE_TRY(hipMemsetAsync(L1.h16, 0, h->rows_cap * D * esz, st));
-            CREATE_TRY(hipMemsetAsync(L1.qkv16, 0, h->rows_cap * 3 * D * esz, st));
-            CREATE_TRY(hipMemsetAsync(L1.u16, 0, h->rows_cap * F * esz, st));
-            CREATE_TRY(hipStreamCreateWithFlags(&L1.stream, hipStreamNonBlocking));
-        }
-        CREATE_TRY(hipEventCreateWithFlags(&h->lane0_async_done, hipEventDisableTiming));
-        CREATE_TRY(hipEventCreateWithFlags(&h->sync_done, hipEventDisableTiming));
-    }
+    return sz;
+}
 
-    // host-streaming slots
+// Everything cbas_enc_create_mlp puts on the device; on a non-zero return the caller destroys the handle.
+int enc_init(cbas_enc* h, const float* weights_host, int64_t n_weights) {
+    const bool cnx = h->cfg.family == 1;
+    ALLOC_TRY(hipStreamCreateWithFlags(&h->compute, hipStreamNonBlocking));
+    ALLOC_TRY(hipStreamCreateWithFlags(&h->copy, hipStreamNonBlocking));
+    ALLOC_TRY(hipStreamCreateWithFlags(&h->aux, hipStreamNonBlocking));
+    hipStream_t st = h->compute;
+    ALLOC_TRY(hipMalloc(&h->nonfinite_dev, sizeof(unsigned)));
+    ALLOC_TRY(hipMemsetAsync(h->nonfinite_dev, 0, sizeof(unsigned), st));
+
+    int rc = cnx ? cnx_build(h, weights_host) : vit_build(h, weights_host, n_weights);
+    if (rc) return rc;
+
+    // compute lanes (see cbas_enc::lanes); CBAS_LANES=1 (read here, once per handle) keeps a single lane
+    const LaneBytes sz = cnx ? cnx_lane_bytes(h) : vit_lane_bytes(h);
+    const char* e = getenv("CBAS_LANES");
+    h->n_lanes = (e && atoi(e) == 1) ? 1 : 2;
+    for (int l = 0; l < h->n_lanes; ++l) {
+        rc = alloc_lane(h, l, sz, st);
+        if (rc) return rc;
+        if (l == 0) h->lanes[l].stream = h->compute;
+        else ALLOC_TRY(hipStreamCreateWithFlags(&h->lanes[l].stream, hipStreamNonBlocking));
+    }
+    ALLOC_TRY(hipEventCreateWithFlags(&h->lane0_async_done, hipEventDisableTiming));
+    ALLOC_TRY(hipEventCreateWithFlags(&h->sync_done, hipEventDisableTiming));
     rc = create_slots(h);
+    if (rc) return rc;
+    ALLOC_TRY(hipStreamSynchronize(st));
+    if (h->gu_scratch) { (void)hipFree(h->gu_scratch); h->gu_scratch = nullptr; }
+    return CBAS_OK;
+}
+
+}  // namespace
+
+extern "C" int cbas_enc_create(const cbas_enc_config* cfg, const float* weights_host, int64_t n_weights,
+                               int device_id, cbas_enc** out) {
+    return cbas_enc_create_mlp(cfg, CBAS_MLP_GELU, weights_host, n_weights, device_id, out);
+}
+
+extern "C" int cbas_enc_create_mlp(const cbas_enc_config* cfg, int32_t mlp, const float* weights_host, int64_t n_weights,
+                                   int device_id, cbas_enc** out) {
+    if (!cfg || !weights_host || !out) return cbas_fail(CBAS_EINVAL, "null argument");
+    *out = nullptr;
+    const cbas_enc_config& c = *cfg;
+    if (const char* why = mlp_refusal(c, mlp)) return cbas_fail(CBAS_EINVAL, "%s", why);
+    int rc = c.family == 1 ? cnx_check_config(c) : vit_check_config(c);
+    if (rc) return rc;
+    if (n_weights != weights_count(c, mlp))
+        return cbas_fail(CBAS_EINVAL, "weights blob has %lld floats, config needs %lld", (long long)n_weights,
+                         (long long)weights_count(c, mlp));
+    HIP_TRY(hipSetDevice(device_id));
+    cbas_enc* h = new (std::nothrow) cbas_enc();
+    if (!h) return cbas_fail(CBAS_ENOMEM, "out of host memory");
+    h->cfg = c; h->device = device_id; h->mlp = mlp;
+    h->D = c.hidden_size;
+    rc = enc_init(h, weights_host, n_weights);
     if (rc) {
-        cbas_enc_destroy(h);
+        cbas_enc_destroy(h);      // never touches the error text: the failing step's message stands
         return rc;
     }
-    CREATE_TRY(hipStreamSynchronize(st));
-    if (h->gu_scratch) { (void)hipFree(h->gu_scratch); h->gu_scratch = nullptr; }
-#undef CREATE_TRY
     *out = h;
     return CBAS_OK;
 }
@@ -1518,7 +1466,7 @@ extern "C" int cbas_enc_forward_u8(cbas_enc* h, const uint8_t* frames_dev, int n
     hipStream_t st = (hipStream_t)stream;
     int rc = sync_enter(h, st);
     if (rc) return rc;
-    rc = forward_u8(h, frames_dev, n, height, width, frame_stride, row_stride, pixel_stride, cls_f32_dev,
+    rc = forward_u8(h, h->lanes[0], frames_dev, n, height, width, frame_stride, row_stride, pixel_stride, cls_f32_dev,
                     (f16*)cls_f16_dev, st, -1, -1);
     if (rc) return rc;
     return sync_leave(h, st);
@@ -1535,18 +1483,19 @@ extern "C" int cbas_enc_forward_f32(cbas_enc* h, const float* x_dev, int n, int 
     const int T = ps > 0 ? (height / ps) * (width / ps) + h->NP : 0;
     rc = sync_enter(h, st);
     if (rc) return rc;
+    const Lane& ws = h->lanes[0];
     if (h->cfg.family == 1) {
-        LAUNCH_TRY(launch_cnx_stem_im2col_f32(x_dev, n, height, width, reinterpret_cast<float*>(h->h16), h->cfg.precision == 4, st));
-        rc = run_cnx(h, n, height, width, cls_f32_dev, (f16*)cls_f16_dev, st, -1);
+        LAUNCH_TRY(launch_cnx_stem_im2col_f32(x_dev, n, height, width, reinterpret_cast<float*>(ws.h16), h->cfg.precision == 4, st));
+        rc = run_cnx(h, ws, n, height, width, cls_f32_dev, (f16*)cls_f16_dev, st, -1);
         if (rc) return rc;
         return sync_leave(h, st);
     }
     if (h->cfg.precision >= 3)
-        LAUNCH_TRY(launch_im2col_f32_f32(x_dev, n, height, width, reinterpret_cast<float*>(h->A_patch), h->x, h->prefix, h->NP, h->D, T, ps,
+        LAUNCH_TRY(launch_im2col_f32_f32(x_dev, n, height, width, reinterpret_cast<float*>(ws.A_patch), ws.x, h->prefix, h->NP, h->D, T, ps,
                                          h->cfg.precision == 4, st));
     else
-        LAUNCH_TRY(launch_im2col_f32(x_dev, n, height, width, h->A_patch, h->x, h->prefix, h->NP, h->D, T, ps, st));
-    rc = run_blocks(h, n, height, width, 512, 1.0f, cls_f32_dev, (f16*)cls_f16_dev, st, -1, -1);
+        LAUNCH_TRY(launch_im2col_f32(x_dev, n, height, width, ws.A_patch, ws.x, h->prefix, h->NP, h->D, T, ps, st));
+    rc = run_blocks(h, ws, n, height, width, 512, 1.0f, cls_f32_dev, (f16*)cls_f16_dev, st, -1, -1);
     if (rc) return rc;
     return sync_leave(h, st);
 }
@@ -1556,7 +1505,7 @@ extern "C" int cbas_enc_debug_forward_u8(cbas_enc* h, const uint8_t* frames_dev,
                                          int64_t frame_stride, int64_t row_stride, int64_t pixel_stride,
                                          int stop_layer, int stop_stage) {
     if (!h) return cbas_fail(CBAS_EINVAL, "null encoder handle");
-    int rc = forward_u8(h, frames_dev, n, height, width, frame_stride, row_stride, pixel_stride, nullptr, nullptr,
+    int rc = forward_u8(h, h->lanes[0], frames_dev, n, height, width, frame_stride, row_stride, pixel_stride, nullptr, nullptr,
                         h->compute, stop_layer, stop_stage);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(h->compute));
@@ -1567,6 +1516,7 @@ extern "C" int cbas_enc_debug_read(cbas_enc* h, int which, void* host_out, int64
     if (!h || !host_out) return cbas_fail(CBAS_EINVAL, "null argument");
     const void* src = nullptr;
     int64_t cap = 0;
+    const Lane& ws = h->lanes[0];      // the taps run there (cbas_enc_debug_forward_u8)
     if (h->cfg.family == 1) {
         // the tensor the last tapped pass stopped at: rows of C floats out of the residual stream's Cp-float rows
         if (which < 4 || which > 8) return cbas_fail(CBAS_EINVAL, "ConvNeXt taps are which = 4 (stem) .. 8 (stage 3); got %d", which);
@@ -1576,16 +1526,16 @@ extern "C" int cbas_enc_debug_read(cbas_enc* h, int which, void* host_out, int64
         if (n_bytes != need) return cbas_fail(CBAS_EINVAL, "tap %d holds %lld bytes, asked for %lld", which, (long long)need, (long long)n_bytes);
         HIP_TRY(hipSetDevice(h->device));
         HIP_TRY(hipStreamSynchronize(h->compute));
-        HIP_TRY(hipMemcpy2D(host_out, (size_t)S.C * 4, h->x, (size_t)S.Cp * 4, (size_t)S.C * 4, (size_t)h->cnx_tap_rows,
+        HIP_TRY(hipMemcpy2D(host_out, (size_t)S.C * 4, ws.x, (size_t)S.Cp * 4, (size_t)S.C * 4, (size_t)h->cnx_tap_rows,
                             hipMemcpyDeviceToHost));
         return CBAS_OK;
     }
     switch (which) {
-        case 0: src = h->x; cap = h->rows_cap * h->D * 4; break;
+        case 0: src = ws.x; cap = h->rows_cap * h->D * 4; break;
         // precision 3 keeps these as fp32 (4 bytes per element)
-        case 1: src = h->h16; cap = h->rows_cap * h->D * (h->cfg.precision >= 3 ? 4 : 2); break;
-        case 2: src = h->qkv16; cap = h->rows_cap * 3 * h->D * (h->cfg.precision >= 3 ? 4 : 2); break;
-        case 3: src = h->u16; cap = h->rows_cap * h->F * (h->cfg.precision >= 3 ? 4 : 2); break;
+        case 1: src = ws.h16; cap = h->rows_cap * h->D * (h->cfg.precision >= 3 ? 4 : 2); break;
+        case 2: src = ws.qkv16; cap = h->rows_cap * 3 * h->D * (h->cfg.precision >= 3 ? 4 : 2); break;
+        case 3: src = ws.u16; cap = h->rows_cap * h->F * (h->cfg.precision >= 3 ? 4 : 2); break;
         default: return cbas_fail(CBAS_EINVAL, "unknown buffer %d", which);
     }
     if (n_bytes < 0 || n_bytes > cap) return cbas_fail(CBAS_EINVAL, "read of %lld bytes exceeds buffer (%lld)", (long long)n_bytes, (long long)cap);
@@ -1654,14 +1604,13 @@ static int submit_u8_host_impl(cbas_enc* h, int slot, const uint8_t* frames_host
     HIP_TRY(hipMemcpyAsync(s.in_dev, src_host, bytes, hipMemcpyHostToDevice, h->copy));
     HIP_TRY(hipEventRecord(s.ev_copied, h->copy));
     const int lane = (int)(h->submit_count++ % (uint64_t)h->n_lanes);
-    hipStream_t ls = h->lanes[lane].stream;
+    const Lane& ws = h->lanes[lane];
+    hipStream_t ls = ws.stream;
     HIP_TRY(hipStreamWaitEvent(ls, s.ev_copied, 0));
     rc = async_enter(h, lane, ls);
     if (rc) return rc;
-    use_lane(h, lane);
-    rc = forward_u8(h, s.in_dev, n, height, width, dev_frame_stride, dev_row_stride, dev_pixel_stride,
+    rc = forward_u8(h, ws, s.in_dev, n, height, width, dev_frame_stride, dev_row_stride, dev_pixel_stride,
                     to_device ? cls_f32_dev : s.out32_dev, to_device ? cls_f16_dev : s.out16_dev, ls, -1, -1);
-    use_lane(h, 0);
     if (rc) return rc;
     rc = async_leave(h, lane, ls);
     if (rc) return rc;
@@ -1718,15 +1667,14 @@ extern "C" int cbas_enc_submit_u8(cbas_enc* h, int slot, const uint8_t* frames_d
     if (s.busy) return cbas_fail(CBAS_ESTATE, "slot %d is busy; call cbas_enc_wait_stream first", slot);
     HIP_TRY(hipSetDevice(h->device));
     const int lane = (int)(h->submit_count++ % (uint64_t)h->n_lanes);
-    hipStream_t ls = h->lanes[lane].stream;
+    const Lane& ws = h->lanes[lane];
+    hipStream_t ls = ws.stream;
     HIP_TRY(hipEventRecord(s.ev_in, (hipStream_t)after_stream));      // the frames (and the output rows) are ready
     HIP_TRY(hipStreamWaitEvent(ls, s.ev_in, 0));
     rc = async_enter(h, lane, ls);
     if (rc) return rc;
-    use_lane(h, lane);
-    rc = forward_u8(h, frames_dev, n, height, width, frame_stride, row_stride, pixel_stride, cls_f32_dev,
+    rc = forward_u8(h, ws, frames_dev, n, height, width, frame_stride, row_stride, pixel_stride, cls_f32_dev,
                     (f16*)cls_f16_dev, ls, -1, -1);
-    use_lane(h, 0);
     if (rc) return rc;
     rc = async_leave(h, lane, ls);
     if (rc) return rc;

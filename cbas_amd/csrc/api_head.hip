@@ -333,24 +333,21 @@ extern "C" int cbas_head_create(const cbas_head_config* cfg, const float* weight
     h->att_temp = (att_temp_raw > 20.f ? att_temp_raw : (float)log1p(exp((double)att_temp_raw))) + 1e-3f;
     h->b_att = att_b;
 
-#define CREATE_TRY(expr)                                                                                  \
-    do {                                                                                                  \
-        hipError_t _e = (expr);                                                                           \
-        if (_e != hipSuccess) {                                                                           \
-            cbas_fail(CBAS_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-            cbas_head_destroy(h);                                                                         \
-            return _e == hipErrorOutOfMemory ? CBAS_ENOMEM : CBAS_EHIP;                                   \
-        }                                                                                                 \
-    } while (0)
-    CREATE_TRY(hipMalloc(&h->wbuf, arena.size() * sizeof(float)));
-    CREATE_TRY(hipMemcpy(h->wbuf, arena.data(), arena.size() * sizeof(float), hipMemcpyHostToDevice));
+    auto upload = [&]() -> int {
+        ALLOC_TRY(hipMalloc(&h->wbuf, arena.size() * sizeof(float)));
+        ALLOC_TRY(hipMemcpy(h->wbuf, arena.data(), arena.size() * sizeof(float), hipMemcpyHostToDevice));
+        return CBAS_OK;
+    };
+    if (const int rc = upload()) {
+        cbas_head_destroy(h);       // never touches the error text
+        return rc;
+    }
     h->w_proj = h->wbuf + o_proj; h->b_bott = h->wbuf + o_bbott; h->ln_w = h->wbuf + o_lnw; h->ln_b = h->wbuf + o_lnb;
     h->b_lin1 = h->wbuf + o_blin1; h->w_lin0 = h->wbuf + o_wlin0; h->b_lin0 = h->wbuf + o_blin0;
     for (int l = 0; l < NL; ++l) { h->w_ih[l] = h->wbuf + o_wih[l]; h->b_gate[l] = h->wbuf + o_bgate[l]; h->w_hh[l] = h->wbuf + o_whh[l]; }
     h->w_att = h->wbuf + o_watt; h->w_lin2 = h->wbuf + o_wlin2; h->b_lin2 = h->wbuf + o_blin2;
 
     // activations are allocated on demand (ensure_workspace): nothing here
-#undef CREATE_TRY
     *out = h;
     return CBAS_OK;
 }

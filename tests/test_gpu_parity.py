@@ -470,6 +470,53 @@ def test_async_lanes_match_synchronous_forward():
     enc.close()
 
 
+def _lane_kind(kind):
+    """(config, weights, precision, LayerNorm fold on) of the handle kinds whose per-lane buffers differ."""
+    if kind == "convnext_p4":
+        return C.CONVNEXT_TINY, W.synth_convnext_weights(C.CONVNEXT_TINY, 1234), 4, False
+    cfg, precision = {"vit_p4": (C.VIT_TINY, 4), "vit_p3": (C.VIT_TINY, 3), "gated_p0": (C.VIT_TINY_GATED, 0),
+                      "ln_fold_p0": (C.ViTConfig(hidden_size=768, intermediate_size=3072, num_hidden_layers=2,
+                                                 num_attention_heads=12, image_size=64), 0)}[kind]
+    return cfg, W.synth_encoder_weights(cfg, 1234), precision, kind == "ln_fold_p0"
+
+
+@pytest.mark.parametrize("kind", ["vit_p4", "vit_p3", "gated_p0", "ln_fold_p0", "convnext_p4"])
+def test_every_kind_of_lane_workspace_matches_the_synchronous_forward(kind):
+    """Each lane owns a whole workspace of the buffers its handle's mode needs (fp32 activations, a gated MLP's, the LayerNorm
+    fold's fp16 residual copy and row statistics, ConvNeXt's three): batches alternating over both lanes, with lane 0 reused,
+    give the rows of one synchronous encode_u8 bit for bit, with 2 lanes and with 1."""
+    from cbas_amd import _lib as L
+    from cbas_amd.encoder import DinoEncoder
+    cfg, w, precision, fold = _lane_kind(kind)
+    enc = DinoEncoder.from_weights(cfg, w, "cuda", max_batch=8, max_frame=(64, 64), precision=precision)
+    try:
+        if fold:
+            enc.debug_option("ln_fold", 1)
+        sizes = [8, 3, 8, 1]
+        frames = torch.from_numpy(synth.cage_frames(17, sum(sizes), 64, 64)).cuda()
+        ref16, ref32 = enc.encode_u8(frames)
+        torch.cuda.synchronize()
+        for lanes in (2, 1):
+            enc.set_lanes(lanes)
+            out16, out32 = torch.zeros_like(ref16), torch.zeros_like(ref32)
+            busy, o = [], 0
+            for i, n in enumerate(sizes):
+                slot = i % L.ENC_SLOTS
+                if slot in busy:
+                    enc.wait_stream(slot)
+                    busy.remove(slot)
+                enc.submit_dev(slot, frames[o:o + n], out16[o:o + n], out32[o:o + n])
+                busy.append(slot)
+                o += n
+            for slot in busy:
+                enc.wait_stream(slot)
+            torch.cuda.synchronize()
+            assert torch.equal(out16, ref16) and torch.equal(out32, ref32), lanes
+        enc.check_finite()
+    finally:
+        enc.close()
+
+
 def test_mixing_sync_and_async_calls_on_one_handle():
     """A synchronous forward issued while asynchronous batches are queued on lane 0 (and the reverse) is ordered
     by the library: both forms use lane 0's workspace, neither corrupts the other."""
