@@ -68,7 +68,7 @@ struct Lane {
     f16 *A_patch = nullptr, *h16 = nullptr, *qkv16 = nullptr, *u16 = nullptr;
     float* x = nullptr;
     // compact per-frame rows of the pruned last layer (only the CLS row is consumed: [tf]:540-541, cbas.py:677):
-    // cls16 = [q | ctx | LN2 | (pad)] x [max_batch][D] fp16, then GELU(up) [max_batch][F]
+    // cls16 = [q | ctx | LN2 | (pad)] x [max_batch][D] fp16, then GELU(up) [max_batch][F]: cls_rows()
     f16* cls16 = nullptr;
     uint32_t *sc_h = nullptr, *sc_u = nullptr; // precision 2: block scales of the fp8 activations in h16 / u16 ([K/128][rows_cap])
     f16* x16 = nullptr;                // LayerNorm fold: [rows_cap][D] fp16 copy of the residual stream (the folded GEMMs' A operand)
@@ -384,8 +384,9 @@ int ensure_rope(cbas_enc* h, int nh, int nw) {
     return CBAS_OK;
 }
 
-// RoPE tables of the grid ensure_rope() selected, into the q|k|v GEMM's parameters
-void set_rope(const cbas_enc* h, GemmParams& p) {
+// RoPE tables of the grid ensure_rope() selected, into a q|k|v GEMM's parameters (GemmParams or Gemm32VitParams)
+template <typename Params>
+void set_rope(const cbas_enc* h, Params& p) {
     if (!h->cfg.use_rope) return;
     p.rope_cos = h->rope_cos; p.rope_sin = h->rope_sin;
     p.rope_fac = h->rope_in_lds ? h->rope_fac : nullptr; p.rope_nh = h->rope_nh; p.rope_nw = h->rope_nw;
@@ -446,176 +447,232 @@ struct ProfScope {
 #define PROF(cat, flops) ProfScope _prof_scope_##cat(h, st, cat, flops)
 
 
-// Last transformer layer when only the CLS rows are consumed.  K and V are still projected for every row
-// (the CLS query attends to all tokens); the query, attention, o_proj, LayerNorm 2 and the MLP run on the n CLS
-// rows, read and written in place in the residual stream with a row stride of T*D.
-int run_last_layer_cls(cbas_enc* h, const Lane& ws, const LayerW& w, int n, int T, hipStream_t st, bool fold) {
-    const int D = h->D, F = h->F, M = n * T, M_pad = (int)round_up(M, 128);
-    const int NU = h->mlp ? 2 * F : F;      // columns of the up GEMM: gate | up interleaved for a gated MLP
+// The ViT forward: the patch GEMM, then per layer ([tf]:404-445)
+//     LayerNorm 1 -> q|k|v -> attention -> o_proj -> LayerNorm 2 -> up -> down
+// (debug taps stop after stage 1..7 of a layer, in that order; layer 0, stage 0: after the patch GEMM), then the final norm of the
+// CLS rows.  Written once per operand family: run_blocks on GemmParams / launch_gemm (precisions 0, 1, 2), run_blocks_f32 on
+// Gemm32VitParams / launch_gemm_f32_vit (precisions 3, 4); in each, the row-wise part from o_proj on is vit_tail* on a RowView.
+// The last layer feeds only the final norm of the CLS rows, so it is pruned unless a debug tap runs: K and V are still projected
+// for every row (the CLS query attends to all tokens); the query, attention and the row-wise part run on the n CLS rows, read
+// and written in place in the residual stream with a row stride of T*D (rows are independent: bit-identical CLS).
+struct VitShape {
+    int ps, nh, nw, P, T;      // patch size, patch grid, patches and tokens per frame
+    int M, M_pad;              // token rows of the batch; rounded up to the GEMMs' 128-row tile
+    int D, F, NU;              // NU = columns of the up GEMM: gate | up interleaved for a gated MLP
+    GemmEpilogue EU;           // the up GEMM's epilogue
+    bool prune;                // the last layer runs pruned
+};
+
+// the shape of this forward, and the position tables of its patch grid selected
+int vit_begin(cbas_enc* h, int n, int height, int width, bool want_cls, int stop_layer, VitShape& s) {
+    s.ps = h->cfg.patch_size; s.nh = height / s.ps; s.nw = width / s.ps; s.P = s.nh * s.nw; s.T = s.P + h->NP;
+    s.M = n * s.T; s.M_pad = (int)round_up(s.M, 128);
+    s.D = h->D; s.F = h->F; s.NU = h->mlp ? 2 * s.F : s.F;
+    s.EU = h->mlp ? EPI_SWIGLU : EPI_GELU;
+    s.prune = h->prune_last && stop_layer < 0 && want_cls;
+    h->last_rows = s.M;
+    return ensure_rope(h, s.nh, s.nw);
+}
+
+// The rows the row-wise part of a layer works on, E = f16 or float by family: every token row, or the CLS rows of the pruned last
+// layer.  The CLS rows' operands are fp16 (+ lo halves) / fp32 (split) whatever the handle's mode: never MX-fp8, never folded.
+template <typename E>
+struct RowView {
+    int M, M_pad;
+    int64_t ldx;               // row stride of these rows in the residual stream
+    E *ln, *ctx, *u;           // LayerNorm output, attention context, MLP activation (GELU(up) / silu(gate) * up)
+    E* q;                      // CLS rows: their queries (bias added, scaled by 1/8; no RoPE on prefix rows); nullptr: every row
+};
+
+template <typename E>
+RowView<E> cls_rows(const cbas_enc* h, const VitShape& s, const Lane& ws, int n) {
     const int64_t cap = round_up(h->cfg.max_batch, 128);
-    f16* qc = ws.cls16;                     // [n][D] CLS queries (bias added, scaled by 1/8; no RoPE on prefix rows)
-    f16* cc = qc + cap * D;                 // [n][D] attention context of the CLS rows
-    f16* hc = cc + cap * D;                 // [n][D] LayerNorm 2 of the CLS rows
-    f16* uc = hc + cap * D;                 // [n][F] GELU(up_proj) / silu(gate_proj) * up_proj
-    // precision 2: the k | v projection of all rows follows the plan's q|k|v bit; the CLS tail is fp16 in every plan
-    const bool split = h->cfg.precision == 1, f8 = h->cfg.precision == 2 && (h->fp8_plan & CBAS_FP8_PLAN_QKV);
-    const int sc_ld = (int)h->rows_cap;
-    GemmParams kv{};                        // k | v sections of the fused QKV weight, all rows
-    if (f8) {
-        { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f8(ws.x, D, w.ln1_w, w.ln1_b, (uint8_t*)ws.h16, ws.sc_h, sc_ld, M, D, h->cfg.layer_norm_eps, st)); }
-        // the CLS tail of this layer stays fp16 (fp16 weights, n rows): its LayerNorm 1 rows go to the LN2 slot for now
-        { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f16(ws.x, (int64_t)T * D, w.ln1_w, w.ln1_b, hc, n, D, h->cfg.layer_norm_eps, st)); }
-        kv.A8 = (const uint8_t*)ws.h16; kv.A_sc = ws.sc_h; kv.sc_lda = sc_ld;
-        kv.W8 = w.wqkv8 + (size_t)D * D; kv.W_sc = w.sqkv + D; kv.sc_ldw = 3 * D;
-    } else if (fold) {
-        // LayerNorm fold: the k | v rows of the folded weight on the raw fp16 residual stream; the n CLS rows' LayerNorm 1
-        // (for the query) is computed on its own, into the LN2 slot for now
-        { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f16(ws.x, (int64_t)T * D, w.ln1_w, w.ln1_b, hc, n, D, h->cfg.layer_norm_eps, st)); }
-        kv.A = ws.x16; kv.W = w.wqkv_f + (size_t)D * D;
-        kv.tile = (long)((M + 255) / 256) * (2 * D / 256) >= 120 ? GEMM_TILE_PP_AUTO : GEMM_TILE_PP_128x256;
-        kv.ln_in = ws.lnst; kv.ln_colsum = w.qkv_cs + D; kv.ln_parts = D / 256; kv.ln_ld = (int)h->rows_cap; kv.ln_eps = h->cfg.layer_norm_eps;
+    E* const q = reinterpret_cast<E*>(ws.cls16);
+    return {n, n, (int64_t)s.T * s.D, q + 2 * cap * s.D, q + cap * s.D, q + 3 * cap * s.D, q};
+}
+
+// ---- half family: fp16 operands, fp32 residual stream ----
+// The operand format of each GEMM of a layer; all false = fp16.
+struct HalfFormats {
+    bool split;                                // precision 1: weights as fp16 hi + lo
+    // precision 2: the GEMMs with MX-fp8 operands (cbas_enc_set_fp8_plan).  An activation is stored in the format of the GEMM
+    // that consumes it: LayerNorm 1 -> q|k|v, attention context -> o_proj, LayerNorm 2 -> up, MLP activation -> down; fp8
+    // activations live in the fp16 buffers' memory.
+    bool f8_qkv, f8_proj, f8_up, f8_down;
+    // LayerNorm fold.  LN(x) W^T + b = rstd (x (gamma o W)^T - mean colsum(gamma o W)) + (beta W^T + b): the two GEMMs that
+    // consume a LayerNorm output (q|k|v, up) run on the raw fp16 residual stream with gamma folded into their weights and apply
+    // mean / rstd in their epilogues; the two that produce the residual stream (o_proj, down) write that fp16 copy and the row
+    // statistics in theirs, as launch_ln_stats_x16 does once for layer 0.  The fold lives in the ping-pong kernel only, so all
+    // four GEMMs run there at EVERY batch size: a frame's CLS row must not depend on how many frames shared its batch.
+    bool fold;
+};
+
+// ping-pong tile of a folded handle's GEMMs: 128-row tiles for small problems, as precision 2 does
+int pp_tile(int M, int N) { return (long)((M + 255) / 256) * (N / 256) >= 120 ? GEMM_TILE_PP_AUTO : GEMM_TILE_PP_128x256; }
+
+// A and W of a GEMM as MX-fp8 bytes + block scales, or as fp16 (+ the weight's lo half under precision 1)
+void set_operands(const cbas_enc* h, GemmParams& g, bool f8, bool split, const f16* A, const uint32_t* A_sc, const f16* W,
+                  const f16* W_lo, const uint8_t* W8, const uint32_t* W_sc) {
+    if (f8) { g.A8 = reinterpret_cast<const uint8_t*>(A); g.A_sc = A_sc; g.sc_lda = (int)h->rows_cap; g.W8 = W8; g.W_sc = W_sc; }
+    else { g.A = A; g.W = W; g.W_lo = split ? W_lo : nullptr; }
+}
+
+// LayerNorm fold: the operands and statistics of a consumer GEMM, the extra outputs of a producer GEMM
+void fold_consumer(const cbas_enc* h, const Lane& ws, GemmParams& g, const f16* W_folded, const float* colsum) {
+    g.A = ws.x16; g.W = W_folded;
+    g.ln_in = ws.lnst; g.ln_colsum = colsum; g.ln_parts = h->D / 256; g.ln_ld = (int)h->rows_cap; g.ln_eps = h->cfg.layer_norm_eps;
+}
+void fold_producer(const cbas_enc* h, const Lane& ws, GemmParams& g) { g.x16_out = ws.x16; g.ln_out = ws.lnst; g.ln_ld = (int)h->rows_cap; }
+
+// q|k|v of every token row, from section sec0 of the fused weight on: 0 = q | k | v, 1 = k | v (the pruned last layer)
+int vit_qkv(cbas_enc* h, const Lane& ws, const LayerW& w, const VitShape& s, const HalfFormats& f, int sec0, hipStream_t st) {
+    const int D = s.D, M = s.M, N = (3 - sec0) * D;
+    const size_t w0 = (size_t)sec0 * D * D;
+    GemmParams q{};
+    if (f.fold) {
+        fold_consumer(h, ws, q, w.wqkv_f + w0, w.qkv_cs + sec0 * D);
+        q.tile = pp_tile(M, N);
+    } else if (f.f8_qkv) {
+        q.A8 = reinterpret_cast<const uint8_t*>(ws.h16); q.A_sc = ws.sc_h; q.sc_lda = (int)h->rows_cap;
+        q.W8 = w.wqkv8 + w0; q.W_sc = w.sqkv + sec0 * D;
+        if (sec0) q.sc_ldw = 3 * D;
     } else {
-        { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f16(ws.x, D, w.ln1_w, w.ln1_b, ws.h16, M, D, h->cfg.layer_norm_eps, st)); }
-        kv.A = ws.h16; kv.W = w.wqkv + (size_t)D * D; kv.W_lo = split ? w.wqkv_lo + (size_t)D * D : nullptr;
+        q.A = ws.h16; q.W = w.wqkv + w0; q.W_lo = f.split ? w.wqkv_lo + w0 : nullptr;
     }
-    kv.M = M; kv.M_pad = M_pad; kv.N = 2 * D; kv.K = D; kv.bias = (fold ? w.qkv_bf : w.qkv_b) + D; kv.out_f16 = ws.qkv16 + D; kv.ldo = 3 * D;
-    kv.tokens_per_frame = T; kv.n_prefix = h->NP; kv.D = D; kv.sec0 = 1;
-    set_rope(h, kv);
-    { PROF(CBAS_PROF_QKV, 2.0 * M * 2.0 * D * D); LAUNCH_TRY(launch_gemm(fold ? EPI_QKV_LN : EPI_QKV, kv, st)); }
-    const bool compact_q = f8 || fold;      // the CLS rows' LayerNorm 1 sits in hc
-    GemmParams q{};                         // q section, CLS rows only (row b*T of h16; the compact fp16 rows when f8 / folded)
-    q.A = compact_q ? hc : ws.h16; q.lda = compact_q ? D : T * D; q.W = w.wqkv; q.W_lo = split ? w.wqkv_lo : nullptr;
-    q.M = n; q.M_pad = n; q.N = D; q.K = D; q.bias = w.qkv_b; q.out_f16 = qc; q.ldo = D;
-    q.tokens_per_frame = 1; q.n_prefix = 1; q.D = D; q.sec0 = 0;      // every row is token 0: no RoPE
-    { PROF(CBAS_PROF_QKV, 2.0 * n * (double)D * D); LAUNCH_TRY(launch_gemm(EPI_QKV, q, st)); }
-    { PROF(CBAS_PROF_ATTENTION, 4.0 * n * (double)T * D); LAUNCH_TRY(launch_attention(ws.qkv16, qc, cc, nullptr, 0, n, T, D, h->NH, st)); }
-    GemmParams o{};
-    o.A = cc; o.W = w.wo; o.W_lo = split ? w.wo_lo : nullptr;
-    o.M = n; o.M_pad = n; o.N = D; o.K = D; o.bias = w.o_b; o.lambda = w.ls1; o.out_f32 = ws.x; o.ldo = T * D;
-    { PROF(CBAS_PROF_OPROJ, 2.0 * n * (double)D * D); LAUNCH_TRY(launch_gemm(EPI_RESID, o, st)); }
-    { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f16(ws.x, (int64_t)T * D, w.ln2_w, w.ln2_b, hc, n, D, h->cfg.layer_norm_eps, st)); }
-    GemmParams u{};
-    u.A = hc; u.W = w.wup; u.W_lo = split ? w.wup_lo : nullptr;
-    u.M = n; u.M_pad = n; u.N = NU; u.K = D; u.bias = w.up_b; u.out_f16 = uc; u.ldo = F;
-    { PROF(CBAS_PROF_UP, 2.0 * n * (double)NU * D); LAUNCH_TRY(launch_gemm(h->mlp ? EPI_SWIGLU : EPI_GELU, u, st)); }
-    GemmParams d{};
-    d.A = uc; d.W = w.wdown; d.W_lo = split ? w.wdown_lo : nullptr;
-    d.M = n; d.M_pad = n; d.N = D; d.K = F; d.bias = w.down_b; d.lambda = w.ls2; d.out_f32 = ws.x; d.ldo = T * D;
-    { PROF(CBAS_PROF_DOWN, 2.0 * n * (double)F * D); LAUNCH_TRY(launch_gemm(EPI_RESID, d, st)); }
+    q.M = M; q.M_pad = s.M_pad; q.N = N; q.K = D; q.bias = (f.fold ? w.qkv_bf : w.qkv_b) + sec0 * D;
+    q.out_f16 = ws.qkv16 + sec0 * D; q.ldo = 3 * D;
+    q.tokens_per_frame = s.T; q.n_prefix = h->NP; q.D = D; q.sec0 = sec0;
+    set_rope(h, q);
+    PROF(CBAS_PROF_QKV, 2.0 * M * (3.0 - sec0) * D * D);
+    LAUNCH_TRY(launch_gemm(f.fold ? EPI_QKV_LN : EPI_QKV, q, st));
     return CBAS_OK;
 }
 
-// precision 3: the same schedule with every buffer and every contraction in fp32 (vit_f32.hip).  The workspace pointers
-// (A_patch, h16, qkv16, u16, cls16) are allocated at 4 bytes per element in this mode and hold floats.
+// o_proj -> LayerNorm 2 -> up -> down on the rows of v; returns after stage `stop` (4..7) when a debug tap asks for one.
+// more = a layer follows this one.
+int vit_tail(cbas_enc* h, const Lane& ws, const LayerW& w, const VitShape& s, const HalfFormats& all, const RowView<f16>& v,
+             bool more, int stop, hipStream_t st) {
+    const HalfFormats f = v.q ? HalfFormats{all.split} : all;
+    const int D = s.D, F = s.F, NU = s.NU, M = v.M, sc_ld = (int)h->rows_cap;
+    const float eps = h->cfg.layer_norm_eps;
+    GemmParams o{};
+    set_operands(h, o, f.f8_proj, f.split, v.ctx, ws.sc_h, w.wo, w.wo_lo, w.wo8, w.so);
+    o.M = M; o.M_pad = v.M_pad; o.N = D; o.K = D; o.bias = w.o_b; o.lambda = w.ls1; o.out_f32 = ws.x; o.ldo = (int)v.ldx;
+    if (f.fold) { o.tile = pp_tile(M, D); fold_producer(h, ws, o); }
+    { PROF(CBAS_PROF_OPROJ, 2.0 * M * (double)D * D); LAUNCH_TRY(launch_gemm(f.fold ? EPI_RESID_LN : EPI_RESID, o, st)); }
+    if (stop == 4) return CBAS_OK;
+
+    if (f.f8_up) { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f8(ws.x, v.ldx, w.ln2_w, w.ln2_b, reinterpret_cast<uint8_t*>(v.ln), ws.sc_h, sc_ld, M, D, eps, st)); }
+    else if (!f.fold) { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f16(ws.x, v.ldx, w.ln2_w, w.ln2_b, v.ln, M, D, eps, st)); }
+    if (stop == 5) return CBAS_OK;
+
+    GemmParams u{};                         // operands in the format of `up`, the result in the format `down` consumes
+    if (f.fold) { fold_consumer(h, ws, u, w.wup_f, w.up_cs); u.tile = pp_tile(M, NU); }
+    else set_operands(h, u, f.f8_up, f.split, v.ln, ws.sc_h, w.wup, w.wup_lo, w.wup8, w.sup);
+    if (f.f8_down) { u.out_f8 = reinterpret_cast<uint8_t*>(v.u); u.out_sc = ws.sc_u; u.sc_ldo = sc_ld; }
+    else u.out_f16 = v.u;
+    u.M = M; u.M_pad = v.M_pad; u.N = NU; u.K = D; u.bias = f.fold ? w.up_bf : w.up_b; u.ldo = F;
+    const GemmEpilogue eu = f.fold ? EPI_GELU_LN : f.f8_down && s.EU == EPI_GELU ? EPI_GELU_F8 : s.EU;
+    { PROF(CBAS_PROF_UP, 2.0 * M * (double)NU * D); LAUNCH_TRY(launch_gemm(eu, u, st)); }
+    if (stop == 6) return CBAS_OK;
+
+    GemmParams d{};
+    set_operands(h, d, f.f8_down, f.split, v.u, ws.sc_u, w.wdown, w.wdown_lo, w.wdown8, w.sdown);
+    d.M = M; d.M_pad = v.M_pad; d.N = D; d.K = F; d.bias = w.down_b; d.lambda = w.ls2; d.out_f32 = ws.x; d.ldo = (int)v.ldx;
+    const bool stats = f.fold && more;      // the last layer's down_proj feeds the final norm only
+    if (f.fold) { d.tile = pp_tile(M, D); if (stats) fold_producer(h, ws, d); }
+    { PROF(CBAS_PROF_DOWN, 2.0 * M * (double)F * D); LAUNCH_TRY(launch_gemm(stats ? EPI_RESID_LN : EPI_RESID, d, st)); }
+    return CBAS_OK;
+}
+
+// ---- fp32 family (vit_f32.hip): every buffer and every contraction in fp32; the workspace pointers (A_patch, h16, qkv16, u16,
+// cls16) are allocated at 4 bytes per element and hold floats.  Precision 4: every GEMM's products on the fp16 pipe as
+// three-term splits of scaled operands: LayerNorm rows and pixels as they are, weights by their per-tensor power of two, the
+// attention context and the MLP activation by these (typical magnitudes ~0.05 / ~0.3: keeps their low halves out of fp16's
+// subnormal range) ----
+constexpr float P4_CTX_SCALE = 16.f, P4_ACT_SCALE = 4.f;
+
+void set_split(const cbas_enc* h, Gemm32VitParams& g, float a_scale, float w_scale) { g.split = h->cfg.precision == 4; g.a_scale = a_scale; g.w_scale = w_scale; }
+
+// o_proj -> LayerNorm 2 -> up -> down on the rows of v (see vit_tail)
+int vit_tail_f32(cbas_enc* h, const Lane& ws, const LayerW& w, const VitShape& s, const RowView<float>& v, int stop, hipStream_t st) {
+    const int D = s.D, F = s.F, NU = s.NU, M = v.M;
+    Gemm32VitParams o{};
+    set_split(h, o, P4_CTX_SCALE, w.sc_o);
+    o.A = v.ctx; o.lda = D; o.W = w.wo32; o.M = M; o.N = D; o.K = D; o.bias = w.o_b; o.lambda = w.ls1; o.out = ws.x; o.ldo = v.ldx;
+    { PROF(CBAS_PROF_OPROJ, 2.0 * M * (double)D * D); LAUNCH_TRY(launch_gemm_f32_vit(EPI_RESID, o, st)); }
+    if (stop == 4) return CBAS_OK;
+
+    { PROF(CBAS_PROF_LAYERNORM, 0.0);
+      LAUNCH_TRY(launch_layernorm_f32(ws.x, v.ldx, w.ln2_w, w.ln2_b, v.ln, M, D, h->cfg.layer_norm_eps, h->cfg.precision == 4, st)); }
+    if (stop == 5) return CBAS_OK;
+
+    Gemm32VitParams u{};
+    set_split(h, u, 1.f, w.sc_up);
+    u.out_scale = P4_ACT_SCALE;
+    u.A = v.ln; u.lda = D; u.W = w.wup32; u.M = M; u.N = NU; u.K = D; u.bias = w.up_b; u.out = v.u; u.ldo = F;
+    { PROF(CBAS_PROF_UP, 2.0 * M * (double)NU * D); LAUNCH_TRY(launch_gemm_f32_vit(s.EU, u, st)); }
+    if (stop == 6) return CBAS_OK;
+
+    Gemm32VitParams d{};
+    set_split(h, d, P4_ACT_SCALE, w.sc_down);
+    d.A = v.u; d.lda = F; d.W = w.wdown32; d.M = M; d.N = D; d.K = F; d.bias = w.down_b; d.lambda = w.ls2; d.out = ws.x; d.ldo = v.ldx;
+    { PROF(CBAS_PROF_DOWN, 2.0 * M * (double)F * D); LAUNCH_TRY(launch_gemm_f32_vit(EPI_RESID, d, st)); }
+    return CBAS_OK;
+}
+
 int run_blocks_f32(cbas_enc* h, const Lane& ws, int n, int height, int width, float* cls_f32, f16* cls_f16, hipStream_t st,
                    int stop_layer, int stop_stage) {
-    const int ps = h->cfg.patch_size;
-    const int nh = height / ps, nw = width / ps, P = nh * nw, T = P + h->NP;
-    const int D = h->D, F = h->F;
-    const int NU = h->mlp ? 2 * F : F;      // columns of the up GEMM: gate | up interleaved for a gated MLP
-    const GemmEpilogue EU = h->mlp ? EPI_SWIGLU : EPI_GELU;
-    const int M = n * T;
-    h->last_rows = M;
-    int rc = ensure_rope(h, nh, nw);
+    VitShape s{};
+    int rc = vit_begin(h, n, height, width, cls_f32 || cls_f16, stop_layer, s);
     if (rc) return rc;
-    float* const A32 = reinterpret_cast<float*>(ws.A_patch);
+    const int D = s.D, T = s.T, M = s.M;
     float* const h32 = reinterpret_cast<float*>(ws.h16);
     float* const qkv32 = reinterpret_cast<float*>(ws.qkv16);
-    float* const u32 = reinterpret_cast<float*>(ws.u16);
     const float eps = h->cfg.layer_norm_eps;
-
-    // precision 4: the same schedule with every GEMM's products on the fp16 pipe as three-term splits; operand scales:
-    // LayerNorm rows and pixels as they are, attention context x 16, GELU / gated-MLP output x 4 (typical magnitudes ~0.05 / ~0.3:
-    // keeps their low halves out of fp16's subnormal range), weights by their per-tensor power of two
     const int split = h->cfg.precision == 4;
-    auto sp = [&](Gemm32VitParams& q, float a_scale, float w_scale) { q.split = split; q.a_scale = a_scale; q.w_scale = w_scale; };
+
     Gemm32VitParams g{};
-    sp(g, 1.f, h->sc_patch);
-    g.A = A32; g.lda = 256; g.W = h->wpatch32; g.M = n * P; g.N = D; g.K = 256; g.bias = h->patch_b; g.out = ws.x; g.ldo = D;
-    g.patches_per_frame = P; g.tokens_per_frame = T; g.n_prefix = h->NP; g.pos = h->cfg.use_rope ? nullptr : h->pos_tab;
+    set_split(h, g, 1.f, h->sc_patch);
+    g.A = reinterpret_cast<float*>(ws.A_patch); g.lda = 256; g.W = h->wpatch32; g.M = n * s.P; g.N = D; g.K = 256;
+    g.bias = h->patch_b; g.out = ws.x; g.ldo = D;
+    g.patches_per_frame = s.P; g.tokens_per_frame = T; g.n_prefix = h->NP; g.pos = h->cfg.use_rope ? nullptr : h->pos_tab;
     { PROF(CBAS_PROF_PATCH, 2.0 * g.M * g.N * g.K); LAUNCH_TRY(launch_gemm_f32_vit(EPI_PATCH, g, st)); }
     if (stop_layer == 0 && stop_stage == 0) return CBAS_OK;
 
-    const bool prune = h->prune_last && stop_layer < 0 && (cls_f32 || cls_f16);
-    auto qkv_params = [&](const LayerW& w, Gemm32VitParams& q) {
-        q.K = D; q.D = D; q.tokens_per_frame = T; q.n_prefix = h->NP;
-        if (h->cfg.use_rope) {
-            q.rope_cos = h->rope_cos; q.rope_sin = h->rope_sin;
-            if (h->rope_in_lds) {
-                q.rope_fac = h->rope_fac; q.rope_nh = h->rope_nh; q.rope_nw = h->rope_nw;
-                q.rope_magic = (unsigned)((1ull << 32) / (unsigned)h->rope_nw) + 1u;
-            }
-        }
-    };
+    const RowView<float> all{M, s.M_pad, D, h32, h32, reinterpret_cast<float*>(ws.u16), nullptr}, cls = cls_rows<float>(h, s, ws, n);
     for (int l = 0; l < h->L; ++l) {
         const LayerW& w = h->layers[l];
-        auto stop = [&](int stage) { return stop_layer == l && stop_stage == stage; };
-        if (prune && l == h->L - 1) {
-            // the last layer feeds only the final norm of the CLS rows (see run_last_layer_cls): K | V for every row,
-            // everything else for the n CLS rows, read and written in place with a row stride of T*D
-            const int64_t cap = round_up(h->cfg.max_batch, 128);
-            float* qc = reinterpret_cast<float*>(ws.cls16);      // [n][D] CLS queries
-            float* cc = qc + cap * D;                            // [n][D] attention context
-            float* hc = cc + cap * D;                            // [n][D] LayerNorm rows
-            float* uc = hc + cap * D;                            // [n][F] GELU(up_proj)
-            { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f32(ws.x, D, w.ln1_w, w.ln1_b, h32, M, D, eps, split, st)); }
-            Gemm32VitParams kv{};
-            qkv_params(w, kv);
-            sp(kv, 1.f, w.sc_qkv);
-            kv.A = h32; kv.lda = D; kv.W = w.wqkv32 + (size_t)D * D; kv.M = M; kv.N = 2 * D; kv.bias = w.qkv_b + D;
-            kv.out = qkv32 + D; kv.ldo = 3 * D; kv.sec0 = 1;
-            { PROF(CBAS_PROF_QKV, 2.0 * M * 2.0 * D * D); LAUNCH_TRY(launch_gemm_f32_vit(EPI_QKV, kv, st)); }
-            Gemm32VitParams q{};
-            qkv_params(w, q);
-            sp(q, 1.f, w.sc_qkv);
-            q.A = h32; q.lda = (int64_t)T * D; q.W = w.wqkv32; q.M = n; q.N = D; q.bias = w.qkv_b; q.out = qc; q.ldo = D;
-            q.tokens_per_frame = 1; q.n_prefix = 1; q.sec0 = 0;       // every row is token 0: no RoPE
-            { PROF(CBAS_PROF_QKV, 2.0 * n * (double)D * D); LAUNCH_TRY(launch_gemm_f32_vit(EPI_QKV, q, st)); }
-            { PROF(CBAS_PROF_ATTENTION, 4.0 * n * (double)T * D); LAUNCH_TRY(launch_attention_f32(qkv32, qc, cc, n, T, D, h->NH, split ? 16.f : 0.f, st)); }
-            Gemm32VitParams o{};
-            sp(o, 16.f, w.sc_o);
-            o.A = cc; o.lda = D; o.W = w.wo32; o.M = n; o.N = D; o.K = D; o.bias = w.o_b; o.lambda = w.ls1; o.out = ws.x; o.ldo = (int64_t)T * D;
-            { PROF(CBAS_PROF_OPROJ, 2.0 * n * (double)D * D); LAUNCH_TRY(launch_gemm_f32_vit(EPI_RESID, o, st)); }
-            { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f32(ws.x, (int64_t)T * D, w.ln2_w, w.ln2_b, hc, n, D, eps, split, st)); }
-            Gemm32VitParams u{};
-            sp(u, 1.f, w.sc_up);
-            u.out_scale = 4.f;
-            u.A = hc; u.lda = D; u.W = w.wup32; u.M = n; u.N = NU; u.K = D; u.bias = w.up_b; u.out = uc; u.ldo = F;
-            { PROF(CBAS_PROF_UP, 2.0 * n * (double)NU * D); LAUNCH_TRY(launch_gemm_f32_vit(EU, u, st)); }
-            Gemm32VitParams d{};
-            sp(d, 4.f, w.sc_down);
-            d.A = uc; d.lda = F; d.W = w.wdown32; d.M = n; d.N = D; d.K = F; d.bias = w.down_b; d.lambda = w.ls2; d.out = ws.x; d.ldo = (int64_t)T * D;
-            { PROF(CBAS_PROF_DOWN, 2.0 * n * (double)F * D); LAUNCH_TRY(launch_gemm_f32_vit(EPI_RESID, d, st)); }
-            break;
-        }
+        const int stop = stop_layer == l ? stop_stage : -1;
+        const bool cls_only = s.prune && l == h->L - 1;
+        const RowView<float>& v = cls_only ? cls : all;
         { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f32(ws.x, D, w.ln1_w, w.ln1_b, h32, M, D, eps, split, st)); }
-        if (stop(1)) return CBAS_OK;
-        Gemm32VitParams q{};
-        qkv_params(w, q);
-        sp(q, 1.f, w.sc_qkv);
-        q.A = h32; q.lda = D; q.W = w.wqkv32; q.M = M; q.N = 3 * D; q.bias = w.qkv_b; q.out = qkv32; q.ldo = 3 * D;
-        { PROF(CBAS_PROF_QKV, 2.0 * M * 3.0 * D * D); LAUNCH_TRY(launch_gemm_f32_vit(EPI_QKV, q, st)); }
-        if (stop(2)) return CBAS_OK;
-        { PROF(CBAS_PROF_ATTENTION, 4.0 * n * (double)T * T * D); LAUNCH_TRY(launch_attention_f32(qkv32, nullptr, h32, n, T, D, h->NH, split ? 16.f : 0.f, st)); }
-        if (stop(3)) return CBAS_OK;
-        Gemm32VitParams o{};
-        sp(o, 16.f, w.sc_o);
-        o.A = h32; o.lda = D; o.W = w.wo32; o.M = M; o.N = D; o.K = D; o.bias = w.o_b; o.lambda = w.ls1; o.out = ws.x; o.ldo = D;
-        { PROF(CBAS_PROF_OPROJ, 2.0 * M * (double)D * D); LAUNCH_TRY(launch_gemm_f32_vit(EPI_RESID, o, st)); }
-        if (stop(4)) return CBAS_OK;
-        { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f32(ws.x, D, w.ln2_w, w.ln2_b, h32, M, D, eps, split, st)); }
-        if (stop(5)) return CBAS_OK;
-        Gemm32VitParams u{};
-        sp(u, 1.f, w.sc_up);
-        u.out_scale = 4.f;
-        u.A = h32; u.lda = D; u.W = w.wup32; u.M = M; u.N = NU; u.K = D; u.bias = w.up_b; u.out = u32; u.ldo = F;
-        { PROF(CBAS_PROF_UP, 2.0 * M * (double)NU * D); LAUNCH_TRY(launch_gemm_f32_vit(EU, u, st)); }
-        if (stop(6)) return CBAS_OK;
-        Gemm32VitParams d{};
-        sp(d, 4.f, w.sc_down);
-        d.A = u32; d.lda = F; d.W = w.wdown32; d.M = M; d.N = D; d.K = F; d.bias = w.down_b; d.lambda = w.ls2; d.out = ws.x; d.ldo = D;
-        { PROF(CBAS_PROF_DOWN, 2.0 * M * (double)F * D); LAUNCH_TRY(launch_gemm_f32_vit(EPI_RESID, d, st)); }
-        if (stop(7)) return CBAS_OK;
+        if (stop == 1) return CBAS_OK;
+
+        const int sec0 = cls_only ? 1 : 0;  // q|k|v of every token row from this section of the packed weight on (see vit_qkv)
+        Gemm32VitParams qkv{};
+        set_split(h, qkv, 1.f, w.sc_qkv);
+        qkv.A = h32; qkv.lda = D; qkv.W = w.wqkv32 + (size_t)sec0 * D * D; qkv.M = M; qkv.N = (3 - sec0) * D; qkv.K = D;
+        qkv.bias = w.qkv_b + sec0 * D; qkv.out = qkv32 + sec0 * D; qkv.ldo = 3 * D;
+        qkv.tokens_per_frame = T; qkv.n_prefix = h->NP; qkv.D = D; qkv.sec0 = sec0;
+        set_rope(h, qkv);
+        { PROF(CBAS_PROF_QKV, 2.0 * M * (3.0 - sec0) * D * D); LAUNCH_TRY(launch_gemm_f32_vit(EPI_QKV, qkv, st)); }
+        if (stop == 2) return CBAS_OK;
+
+        if (cls_only) {
+            Gemm32VitParams q{};            // q section, CLS rows only (row b*T of h32)
+            set_split(h, q, 1.f, w.sc_qkv);
+            q.A = h32; q.lda = (int64_t)T * D; q.W = w.wqkv32; q.M = n; q.N = D; q.K = D; q.bias = w.qkv_b; q.out = cls.q; q.ldo = D;
+            q.tokens_per_frame = 1; q.n_prefix = 1; q.D = D; q.sec0 = 0;      // every row is token 0: no RoPE
+            set_rope(h, q);
+            { PROF(CBAS_PROF_QKV, 2.0 * n * (double)D * D); LAUNCH_TRY(launch_gemm_f32_vit(EPI_QKV, q, st)); }
+        }
+        { PROF(CBAS_PROF_ATTENTION, 4.0 * n * (double)T * (cls_only ? 1 : T) * D);      // the view's queries against every key
+          LAUNCH_TRY(launch_attention_f32(qkv32, v.q, v.ctx, n, T, D, h->NH, split ? P4_CTX_SCALE : 0.f, st)); }
+        if (stop == 3) return CBAS_OK;
+
+        rc = vit_tail_f32(h, ws, w, s, v, stop, st);
+        if (rc || (stop >= 4 && stop <= 7)) return rc;
     }
     if (cls_f32 || cls_f16)
         LAUNCH_TRY(launch_final_norm_cls(ws.x, h->norm_w, h->norm_b, cls_f32, cls_f16, n, T, D, eps, st, h->nonfinite_dev));
@@ -626,137 +683,66 @@ int run_blocks_f32(cbas_enc* h, const Lane& ws, int n, int height, int width, fl
 int run_blocks(cbas_enc* h, const Lane& ws, int n, int height, int width, int patch_k, float in_scale, float* cls_f32,
                f16* cls_f16, hipStream_t st, int stop_layer, int stop_stage) {
     if (h->cfg.precision >= 3) return run_blocks_f32(h, ws, n, height, width, cls_f32, cls_f16, st, stop_layer, stop_stage);
-    const int ps = h->cfg.patch_size;
-    const int nh = height / ps, nw = width / ps, P = nh * nw, T = P + h->NP;
-    const int D = h->D, F = h->F;
-    const int M = n * T, M_pad = (int)round_up(M, 128);
-    h->last_rows = M;
-    int rc = ensure_rope(h, nh, nw);
+    VitShape s{};
+    int rc = vit_begin(h, n, height, width, cls_f32 || cls_f16, stop_layer, s);
     if (rc) return rc;
+    const int D = s.D, T = s.T, M = s.M;
+    const float eps = h->cfg.layer_norm_eps;
+    const int sc_ld = (int)h->rows_cap;
 
     GemmParams g{};
     g.A = ws.A_patch;
     g.W = patch_k == 256 ? h->wpatch : h->wpatch2;
     g.W_lo = h->cfg.precision == 1 ? (patch_k == 256 ? h->wpatch_lo : h->wpatch2_lo) : nullptr;
-    g.M = n * P; g.M_pad = (int)round_up(n * P, 128); g.N = D; g.K = patch_k;
+    g.M = n * s.P; g.M_pad = (int)round_up(n * s.P, 128); g.N = D; g.K = patch_k;
     g.bias = h->patch_b; g.out_f32 = ws.x; g.ldo = D;
-    g.patches_per_frame = P; g.tokens_per_frame = T; g.n_prefix = h->NP; g.in_scale = in_scale;
+    g.patches_per_frame = s.P; g.tokens_per_frame = T; g.n_prefix = h->NP; g.in_scale = in_scale;
     g.pos = h->cfg.use_rope ? nullptr : h->pos_tab;
     { PROF(CBAS_PROF_PATCH, 2.0 * g.M * g.N * g.K); LAUNCH_TRY(launch_gemm(EPI_PATCH, g, st)); }
     if (stop_layer == 0 && stop_stage == 0) return CBAS_OK;
 
-    // The last layer feeds only the final norm of the CLS rows, so everything after its K/V projection is
-    // done for n rows instead of n*T (rows are independent: bit-identical CLS).  Debug taps run it in full.
-    const bool prune = h->prune_last && stop_layer < 0 && (cls_f32 || cls_f16);
-    const bool split = h->cfg.precision == 1, f8 = h->cfg.precision == 2;
-    // precision 2: the GEMMs with MX-fp8 operands (cbas_enc_set_fp8_plan).  An activation is stored in the format of the GEMM
-    // that consumes it: LayerNorm 1 -> q|k|v, attention context -> o_proj, LayerNorm 2 -> up, GELU output -> down.
-    const int plan = f8 ? h->fp8_plan : 0;
-    const bool f8_qkv = plan & CBAS_FP8_PLAN_QKV, f8_proj = plan & CBAS_FP8_PLAN_PROJ, f8_up = plan & CBAS_FP8_PLAN_UP,
-               f8_down = plan & CBAS_FP8_PLAN_DOWN;
+    const int plan = h->cfg.precision == 2 ? h->fp8_plan : 0;
+    const HalfFormats f{h->cfg.precision == 1, bool(plan & CBAS_FP8_PLAN_QKV), bool(plan & CBAS_FP8_PLAN_PROJ), bool(plan & CBAS_FP8_PLAN_UP),
+                        bool(plan & CBAS_FP8_PLAN_DOWN), h->ln_fold && h->fold_ok && stop_layer < 0};      // debug taps keep the LayerNorm kernels
     h->vit_forward_seen = true;
-    // LayerNorm fold.  LN(x) W^T + b = rstd (x (gamma o W)^T - mean colsum(gamma o W)) + (beta W^T + b): the two GEMMs that
-    // consume a LayerNorm output ([tf]:404-445: q|k|v after norm1, up_proj after norm2) run on the raw fp16 residual stream
-    // with gamma folded into their weights and apply mean / rstd in their epilogues; the two GEMMs that produce the residual
-    // stream (o_proj, down_proj) write that fp16 copy and the row statistics in theirs.  22 of the 24 LayerNorm launches
-    // of a ViT-B step and their 114 MB per layer of traffic disappear.  The fold lives in the ping-pong kernel only, so in this
-    // mode all four GEMMs run there at EVERY batch size (128-row tiles for small problems, as precision 2 does): a frame's
-    // CLS row must not depend on how many frames shared its batch.  Debug taps and precision 1 / 2 keep the LayerNorm kernels.
-    const bool fold = h->ln_fold && h->fold_ok && stop_layer < 0;
-    const int ln_ld = (int)h->rows_cap;
-    auto pp_tile = [&](int N) { return (long)((M + 255) / 256) * (N / 256) >= 120 ? GEMM_TILE_PP_AUTO : GEMM_TILE_PP_128x256; };
-    if (fold) { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_ln_stats_x16(ws.x, ws.x16, ws.lnst, ln_ld, M, D, st)); }
-    if (f8 && stop_layer >= 0) return cbas_fail(CBAS_EINVAL, "debug taps read fp16 buffers; not available with precision 2");
-    const int sc_ld = (int)h->rows_cap;
-    uint8_t* const h8 = reinterpret_cast<uint8_t*>(ws.h16);      // fp8 activations live in the fp16 buffers' memory
-    uint8_t* const u8 = reinterpret_cast<uint8_t*>(ws.u16);
+    if (f.fold) { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_ln_stats_x16(ws.x, ws.x16, ws.lnst, sc_ld, M, D, st)); }
+    if (h->cfg.precision == 2 && stop_layer >= 0)
+        return cbas_fail(CBAS_EINVAL, "debug taps read fp16 buffers; not available with precision 2");
+
+    const RowView<f16> all{M, s.M_pad, D, ws.h16, ws.h16, ws.u16, nullptr}, cls = cls_rows<f16>(h, s, ws, n);
     for (int l = 0; l < h->L; ++l) {
         const LayerW& w = h->layers[l];
-        auto stop = [&](int stage) { return stop_layer == l && stop_stage == stage; };
-        if (prune && l == h->L - 1) {
-            rc = run_last_layer_cls(h, ws, w, n, T, st, fold);
-            if (rc) return rc;
-            break;
+        const int stop = stop_layer == l ? stop_stage : -1;
+        const bool cls_only = s.prune && l == h->L - 1;
+        const RowView<f16>& v = cls_only ? cls : all;
+        if (f.f8_qkv) { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f8(ws.x, D, w.ln1_w, w.ln1_b, reinterpret_cast<uint8_t*>(ws.h16), ws.sc_h, sc_ld, M, D, eps, st)); }
+        else if (!f.fold) { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f16(ws.x, D, w.ln1_w, w.ln1_b, ws.h16, M, D, eps, st)); }
+        if (stop == 1) return CBAS_OK;
+
+        // the CLS query is an fp16 GEMM on the unfolded weight in every mode: where LayerNorm 1 of every row is MX-fp8 or folded
+        // away, the n CLS rows get one of their own (in the view's LayerNorm 2 rows for now)
+        const bool compact_q = cls_only && (f.f8_qkv || f.fold);
+        if (compact_q) { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f16(ws.x, cls.ldx, w.ln1_w, w.ln1_b, cls.ln, n, D, eps, st)); }
+        rc = vit_qkv(h, ws, w, s, f, cls_only ? 1 : 0, st);
+        if (rc) return rc;
+        if (stop == 2) return CBAS_OK;
+
+        if (cls_only) {
+            GemmParams q{};                 // q section, CLS rows only (row b*T of h16, or the compact rows)
+            q.A = compact_q ? cls.ln : ws.h16; q.lda = compact_q ? D : T * D; q.W = w.wqkv; q.W_lo = f.split ? w.wqkv_lo : nullptr;
+            q.M = n; q.M_pad = n; q.N = D; q.K = D; q.bias = w.qkv_b; q.out_f16 = cls.q; q.ldo = D;
+            q.tokens_per_frame = 1; q.n_prefix = 1; q.D = D; q.sec0 = 0;      // every row is token 0: no RoPE
+            { PROF(CBAS_PROF_QKV, 2.0 * n * (double)D * D); LAUNCH_TRY(launch_gemm(EPI_QKV, q, st)); }
         }
-        if (fold) {
-            auto ln_consumer = [&](GemmParams& g, const float* colsum) {
-                g.ln_in = ws.lnst; g.ln_colsum = colsum; g.ln_parts = D / 256; g.ln_ld = ln_ld; g.ln_eps = h->cfg.layer_norm_eps;
-            };
-            auto ln_producer = [&](GemmParams& g) { g.x16_out = ws.x16; g.ln_out = ws.lnst; g.ln_ld = ln_ld; };
-            const bool more = l + 1 < h->L;             // the last layer's down_proj feeds the final norm only
-            GemmParams q{};
-            q.tile = pp_tile(3 * D);
-            q.A = ws.x16; q.W = w.wqkv_f; q.M = M; q.M_pad = M_pad; q.N = 3 * D; q.K = D; q.bias = w.qkv_bf; q.out_f16 = ws.qkv16; q.ldo = 3 * D;
-            q.tokens_per_frame = T; q.n_prefix = h->NP; q.D = D;
-            ln_consumer(q, w.qkv_cs);
-            set_rope(h, q);
-            { PROF(CBAS_PROF_QKV, 2.0 * M * 3.0 * D * D); LAUNCH_TRY(launch_gemm(EPI_QKV_LN, q, st)); }
-            { PROF(CBAS_PROF_ATTENTION, 4.0 * n * (double)T * T * D);
-              LAUNCH_TRY(launch_attention(ws.qkv16, nullptr, ws.h16, nullptr, sc_ld, n, T, D, h->NH, st)); }
-            GemmParams o{};
-            o.tile = pp_tile(D);
-            o.A = ws.h16; o.W = w.wo; o.M = M; o.M_pad = M_pad; o.N = D; o.K = D; o.bias = w.o_b; o.lambda = w.ls1; o.out_f32 = ws.x; o.ldo = D;
-            ln_producer(o);
-            { PROF(CBAS_PROF_OPROJ, 2.0 * M * (double)D * D); LAUNCH_TRY(launch_gemm(EPI_RESID_LN, o, st)); }
-            GemmParams u{};
-            u.tile = pp_tile(F);
-            u.A = ws.x16; u.W = w.wup_f; u.out_f16 = ws.u16; u.M = M; u.M_pad = M_pad; u.N = F; u.K = D; u.bias = w.up_bf; u.ldo = F;
-            ln_consumer(u, w.up_cs);
-            { PROF(CBAS_PROF_UP, 2.0 * M * (double)F * D); LAUNCH_TRY(launch_gemm(EPI_GELU_LN, u, st)); }
-            GemmParams d{};
-            d.tile = pp_tile(D);
-            d.A = ws.u16; d.W = w.wdown; d.M = M; d.M_pad = M_pad; d.N = D; d.K = F; d.bias = w.down_b; d.lambda = w.ls2; d.out_f32 = ws.x; d.ldo = D;
-            if (more) ln_producer(d);
-            { PROF(CBAS_PROF_DOWN, 2.0 * M * (double)F * D); LAUNCH_TRY(launch_gemm(more ? EPI_RESID_LN : EPI_RESID, d, st)); }
-            continue;
-        }
-        if (f8_qkv) { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f8(ws.x, D, w.ln1_w, w.ln1_b, h8, ws.sc_h, sc_ld, M, D, h->cfg.layer_norm_eps, st)); }
-        else { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f16(ws.x, D, w.ln1_w, w.ln1_b, ws.h16, M, D, h->cfg.layer_norm_eps, st)); }
-        if (stop(1)) return CBAS_OK;
+        { PROF(CBAS_PROF_ATTENTION, 4.0 * n * (double)T * (cls_only ? 1 : T) * D);      // the view's queries against every key
+          LAUNCH_TRY(launch_attention(ws.qkv16, v.q, v.ctx, f.f8_proj && !cls_only ? ws.sc_h : nullptr, cls_only ? 0 : sc_ld, n, T, D, h->NH, st)); }
+        if (stop == 3) return CBAS_OK;
 
-        GemmParams q{};
-        if (f8_qkv) { q.A8 = h8; q.A_sc = ws.sc_h; q.sc_lda = sc_ld; q.W8 = w.wqkv8; q.W_sc = w.sqkv; }
-        else { q.A = ws.h16; q.W = w.wqkv; q.W_lo = split ? w.wqkv_lo : nullptr; }
-        q.M = M; q.M_pad = M_pad; q.N = 3 * D; q.K = D; q.bias = w.qkv_b; q.out_f16 = ws.qkv16; q.ldo = 3 * D;
-        q.tokens_per_frame = T; q.n_prefix = h->NP; q.D = D;
-        set_rope(h, q);
-        { PROF(CBAS_PROF_QKV, 2.0 * M * 3.0 * D * D); LAUNCH_TRY(launch_gemm(EPI_QKV, q, st)); }
-        if (stop(2)) return CBAS_OK;
-
-        { PROF(CBAS_PROF_ATTENTION, 4.0 * n * (double)T * T * D);
-          LAUNCH_TRY(launch_attention(ws.qkv16, nullptr, ws.h16, f8_proj ? ws.sc_h : nullptr, sc_ld, n, T, D, h->NH, st)); }
-        if (stop(3)) return CBAS_OK;
-
-        GemmParams o{};
-        if (f8_proj) { o.A8 = h8; o.A_sc = ws.sc_h; o.sc_lda = sc_ld; o.W8 = w.wo8; o.W_sc = w.so; }
-        else { o.A = ws.h16; o.W = w.wo; o.W_lo = split ? w.wo_lo : nullptr; }
-        o.M = M; o.M_pad = M_pad; o.N = D; o.K = D; o.bias = w.o_b; o.lambda = w.ls1; o.out_f32 = ws.x; o.ldo = D;
-        { PROF(CBAS_PROF_OPROJ, 2.0 * M * (double)D * D); LAUNCH_TRY(launch_gemm(EPI_RESID, o, st)); }
-        if (stop(4)) return CBAS_OK;
-
-        if (f8_up) { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f8(ws.x, D, w.ln2_w, w.ln2_b, h8, ws.sc_h, sc_ld, M, D, h->cfg.layer_norm_eps, st)); }
-        else { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_layernorm_f16(ws.x, D, w.ln2_w, w.ln2_b, ws.h16, M, D, h->cfg.layer_norm_eps, st)); }
-        if (stop(5)) return CBAS_OK;
-
-        GemmParams u{};                     // operands by the plan's `up` bit, result in the format `down` consumes
-        if (f8_up) { u.A8 = h8; u.A_sc = ws.sc_h; u.sc_lda = sc_ld; u.W8 = w.wup8; u.W_sc = w.sup; }
-        else { u.A = ws.h16; u.W = w.wup; u.W_lo = split ? w.wup_lo : nullptr; }
-        if (f8_down) { u.out_f8 = u8; u.out_sc = ws.sc_u; u.sc_ldo = sc_ld; }
-        else u.out_f16 = ws.u16;
-        u.M = M; u.M_pad = M_pad; u.N = h->mlp ? 2 * F : F; u.K = D; u.bias = w.up_b; u.ldo = F;      // gated: gate | up interleaved
-        { PROF(CBAS_PROF_UP, 2.0 * M * (double)u.N * D); LAUNCH_TRY(launch_gemm(h->mlp ? EPI_SWIGLU : f8_down ? EPI_GELU_F8 : EPI_GELU, u, st)); }
-        if (stop(6)) return CBAS_OK;
-
-        GemmParams d{};
-        if (f8_down) { d.A8 = u8; d.A_sc = ws.sc_u; d.sc_lda = sc_ld; d.W8 = w.wdown8; d.W_sc = w.sdown; }
-        else { d.A = ws.u16; d.W = w.wdown; d.W_lo = split ? w.wdown_lo : nullptr; }
-        d.M = M; d.M_pad = M_pad; d.N = D; d.K = F; d.bias = w.down_b; d.lambda = w.ls2; d.out_f32 = ws.x; d.ldo = D;
-        { PROF(CBAS_PROF_DOWN, 2.0 * M * (double)F * D); LAUNCH_TRY(launch_gemm(EPI_RESID, d, st)); }
-        if (stop(7)) return CBAS_OK;
+        rc = vit_tail(h, ws, w, s, f, v, l + 1 < h->L, stop, st);
+        if (rc || (stop >= 4 && stop <= 7)) return rc;
     }
     if (cls_f32 || cls_f16)
-        LAUNCH_TRY(launch_final_norm_cls(ws.x, h->norm_w, h->norm_b, cls_f32, cls_f16, n, T, D,
-                                         h->cfg.layer_norm_eps, st, h->nonfinite_dev));
+        LAUNCH_TRY(launch_final_norm_cls(ws.x, h->norm_w, h->norm_b, cls_f32, cls_f16, n, T, D, eps, st, h->nonfinite_dev));
     return CBAS_OK;
 }
 
@@ -802,9 +788,9 @@ int run_cnx(cbas_enc* h, const Lane& ws, int n, int height, int width, float* cl
             { PROF(CBAS_PROF_LAYERNORM, 0.0);
               LAUNCH_TRY(launch_cnx_dwconv_ln(ws.x, S.Cp, n, hh, ww, b.dw_t, b.dw_b, b.ln_w, b.ln_b, C, eps, A32, split, st)); }
             Gemm32VitParams u = gemm(A32, C, b.pw1_w, M, 4 * C, C, b.pw1_b, u32, 4 * C, 1.f, b.sc1);
-            u.out_scale = 4.f;                                        // the GELU output as pointwise_conv2's split A operand
+            u.out_scale = P4_ACT_SCALE;                               // the GELU output as pointwise_conv2's split A operand
             { PROF(CBAS_PROF_UP, 2.0 * M * 4.0 * C * C); LAUNCH_TRY(launch_gemm_f32_vit(EPI_GELU, u, st)); }
-            Gemm32VitParams d = gemm(u32, 4 * C, b.pw2_w, M, S.Cp, 4 * C, b.pw2_b, ws.x, S.Cp, 4.f, b.sc2);
+            Gemm32VitParams d = gemm(u32, 4 * C, b.pw2_w, M, S.Cp, 4 * C, b.pw2_b, ws.x, S.Cp, P4_ACT_SCALE, b.sc2);
             d.lambda = b.gamma;                                       // x += (pointwise_conv2 + b) * gamma
             { PROF(CBAS_PROF_DOWN, 2.0 * M * 4.0 * C * C); LAUNCH_TRY(launch_gemm_f32_vit(EPI_RESID, d, st)); }
         }
