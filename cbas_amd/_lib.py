@@ -106,6 +106,10 @@ SIGNATURES = {
     "cbas_probs_top1": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cbas_disagreement_runs": (c_int64, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                          c_void_p, c_int32, c_void_p, c_int64, C.POINTER(c_int64), c_void_p]),
+    "cbas_labels_median": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "cbas_label_runs": (c_int64, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, C.c_double, c_void_p, c_int64,
+                                  C.POINTER(c_int64), c_void_p]),
+    "cbas_activity_bins": (c_int, [c_void_p, c_int64, c_int32, c_int32, C.c_double, c_int64, c_void_p, c_int64, c_void_p]),
     "cbas_head_train_read": (c_int, [c_void_p, c_int32, c_void_p, c_int64]),
     "cbas_head_train_last_outputs": (c_int, [c_void_p, c_void_p, c_void_p, c_int32]),
     "cbas_csv_format_f32": (c_int64, [c_void_p, c_int64, c_int32, c_void_p, c_int64]),

@@ -532,6 +532,98 @@ extern "C" int64_t cbas_disagreement_runs(const int32_t* pred_dev, const float* 
     return total;
 }
 
+static_assert(sizeof(cbas_label_run) == sizeof(LabelRunRecord) && sizeof(LabelRunRecord) == 24 &&
+              offsetof(cbas_label_run, confidence) == offsetof(LabelRunRecord, confidence) &&
+              offsetof(cbas_label_run, label) == offsetof(LabelRunRecord, label),
+              "cbas_label_run is the record the kernels write");
+
+extern "C" int cbas_labels_median(const int32_t* pred_dev, int64_t n_frames_total, const int64_t* clip_table_dev, int32_t n_clips,
+                                  int32_t n_classes, int32_t kernel_size, int32_t* out_dev, void* stream) {
+    if (!pred_dev || !clip_table_dev || !out_dev) return cbas_fail(CBAS_EINVAL, "cbas_labels_median: pred_dev / clip_table_dev / out_dev NULL");
+    if (out_dev == pred_dev) return cbas_fail(CBAS_EINVAL, "cbas_labels_median: out_dev must not be pred_dev (a window reads its neighbours)");
+    if (n_frames_total < 0 || n_clips < 1 || n_classes < 1 || n_classes > HEAD_SCORE_MAX_CLASSES)
+        return cbas_fail(CBAS_EINVAL, "cbas_labels_median: n_frames_total=%lld, n_clips=%d, n_classes=%d: n_frames_total >= 0, n_clips >= 1 "
+                         "and 1 <= n_classes <= %d", (long long)n_frames_total, n_clips, n_classes, HEAD_SCORE_MAX_CLASSES);
+    if (kernel_size < 1 || !(kernel_size & 1))
+        return cbas_fail(CBAS_EINVAL, "cbas_labels_median: kernel_size=%d must be odd and >= 1", kernel_size);
+    hipPointerAttribute_t attr;
+    HIP_TRY(hipPointerGetAttributes(&attr, pred_dev));
+    HIP_TRY(hipSetDevice(attr.device));
+    hipStream_t st = (hipStream_t)stream;
+    RunsScratch scratch;                                       // the flags: a 16-byte block
+    HIP_TRY(hipMalloc(&scratch.p, 16));
+    unsigned* flags = reinterpret_cast<unsigned*>(scratch.p);
+    HIP_TRY(hipMemsetAsync(flags, 0, 16, st));
+    LAUNCH_TRY(launch_labels_median(pred_dev, n_frames_total, clip_table_dev, n_clips, n_classes, kernel_size, out_dev, flags, st));
+    unsigned bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, flags, sizeof(bad), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (bad & POST_FLAG_TABLE)
+        return cbas_fail(CBAS_EINVAL, "cbas_labels_median: a clip table entry reaches outside the %lld frames of pred", (long long)n_frames_total);
+    if (bad & POST_FLAG_VALUE) return cbas_fail(CBAS_EINVAL, "cbas_labels_median: a value lies outside [-1, %d)", n_classes);
+    return CBAS_OK;
+}
+
+extern "C" int64_t cbas_label_runs(const int32_t* key_dev, const float* conf_dev, int64_t n_frames_total, const int64_t* clip_table_dev,
+                                   int32_t n_clips, int32_t n_classes, int32_t use_threshold, double threshold,
+                                   cbas_label_run* records_dev, int64_t capacity, int64_t* needed_host, void* stream) {
+    if (needed_host) *needed_host = 0;
+    if (!key_dev || !conf_dev || !clip_table_dev) return cbas_fail(CBAS_EINVAL, "cbas_label_runs: key_dev / conf_dev / clip_table_dev NULL");
+    if (n_frames_total < 0 || n_clips < 1 || n_classes < 1 || n_classes > HEAD_SCORE_MAX_CLASSES)
+        return cbas_fail(CBAS_EINVAL, "cbas_label_runs: n_frames_total=%lld, n_clips=%d, n_classes=%d: n_frames_total >= 0, n_clips >= 1 "
+                         "and 1 <= n_classes <= %d", (long long)n_frames_total, n_clips, n_classes, HEAD_SCORE_MAX_CLASSES);
+    if (use_threshold && threshold != threshold) return cbas_fail(CBAS_EINVAL, "cbas_label_runs: the threshold is NaN");
+    if (capacity < 0 || (capacity > 0 && !records_dev)) return cbas_fail(CBAS_EINVAL, "cbas_label_runs: capacity=%lld with records_dev %s",
+                                                                         (long long)capacity, records_dev ? "set" : "NULL");
+    hipPointerAttribute_t attr;
+    HIP_TRY(hipPointerGetAttributes(&attr, key_dev));
+    HIP_TRY(hipSetDevice(attr.device));
+    hipStream_t st = (hipStream_t)stream;
+    // scratch: [flags: 16 bytes][offsets: n_clips + 1 int64][counts: n_clips int32]
+    RunsScratch scratch;
+    const size_t off_bytes = ((size_t)n_clips + 1) * sizeof(long long);
+    HIP_TRY(hipMalloc(&scratch.p, 16 + off_bytes + (size_t)n_clips * sizeof(int)));
+    unsigned* flags = reinterpret_cast<unsigned*>(scratch.p);
+    long long* offsets = reinterpret_cast<long long*>(reinterpret_cast<char*>(scratch.p) + 16);
+    int* counts = reinterpret_cast<int*>(reinterpret_cast<char*>(scratch.p) + 16 + off_bytes);
+    HIP_TRY(hipMemsetAsync(flags, 0, 16, st));
+    const LabelRunsParams p{key_dev, conf_dev, n_frames_total, clip_table_dev, n_clips, n_classes, use_threshold ? 1 : 0, threshold};
+    LAUNCH_TRY(launch_label_runs_count(p, counts, offsets, flags, st));
+    // the emit passes read the total on the device and write at most `capacity` records, so the call waits for the stream once
+    if (capacity > 0) LAUNCH_TRY(launch_label_runs_emit(p, offsets, reinterpret_cast<LabelRunRecord*>(records_dev), capacity, flags, st));
+    unsigned bad = 0;
+    long long total = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, flags, sizeof(bad), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&total, offsets + n_clips, sizeof(total), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));                         // the scratch is freed on return
+    if (bad & POST_FLAG_TABLE)
+        return cbas_fail(CBAS_EINVAL, "cbas_label_runs: a clip table entry reaches outside the %lld frames of key / conf", (long long)n_frames_total);
+    if (bad & POST_FLAG_VALUE) return cbas_fail(CBAS_EINVAL, "cbas_label_runs: a key lies outside [-1, %d)", n_classes);
+    if (needed_host) *needed_host = total;
+    if (total > capacity)
+        return cbas_fail(CBAS_EINVAL, "cbas_label_runs: %lld records, the buffer holds %lld", total, (long long)capacity);
+    return total;
+}
+
+extern "C" int cbas_activity_bins(const float* probs_dev, int64_t n_total, int32_t n_classes, int32_t behavior, double threshold,
+                                  int64_t bin_frames, int64_t* bins_dev, int64_t n_bins, void* stream) {
+    if (!probs_dev || !bins_dev) return cbas_fail(CBAS_EINVAL, "cbas_activity_bins: probs_dev / bins_dev NULL");
+    if (n_total < 1 || n_classes < 1 || n_classes > HEAD_SCORE_MAX_CLASSES || behavior < 0 || behavior >= n_classes)
+        return cbas_fail(CBAS_EINVAL, "cbas_activity_bins: n_total=%lld, n_classes=%d, behavior=%d: n_total >= 1, 1 <= n_classes <= %d and "
+                         "0 <= behavior < n_classes", (long long)n_total, n_classes, behavior, HEAD_SCORE_MAX_CLASSES);
+    if (bin_frames < 1 || n_bins != (n_total - 1) / bin_frames + 1)
+        return cbas_fail(CBAS_EINVAL, "cbas_activity_bins: bin_frames=%lld, n_bins=%lld: bin_frames >= 1 and n_bins = ceil(n_total / bin_frames)",
+                         (long long)bin_frames, (long long)n_bins);
+    hipPointerAttribute_t attr;
+    HIP_TRY(hipPointerGetAttributes(&attr, probs_dev));
+    HIP_TRY(hipSetDevice(attr.device));
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(bins_dev, 0, (size_t)n_bins * sizeof(int64_t), st));
+    LAUNCH_TRY(launch_activity_bins(probs_dev, n_total, n_classes, behavior, threshold, bin_frames,
+                                    reinterpret_cast<unsigned long long*>(bins_dev), n_bins, st));
+    return CBAS_OK;
+}
+
 // rows: the clip's CLS rows as IEEE half (what _cls.h5 holds) or float32 (a foreign `cls` dataset, which the reference
 // reads with .float(): backend/cbas.py:507-508)
 static int infer_range(cbas_head* h, const void* cls_dev, bool half_rows, int64_t n_frames, int64_t first, int64_t count,

@@ -22,6 +22,7 @@
 // probabilities (>= 1 / C >= 2^-6, <= 1) every partial sum of up to 2^22 float32 confidences is exact in float64, so the sum equals
 // the one taken in ascending frame order bit for bit; for other values it is a float64 sum in the fixed order above.
 #include "kernels.h"
+#include "run_sum.h"
 
 namespace {
 
@@ -180,7 +181,7 @@ __global__ void __launch_bounds__(RUNS_BLOCK) runs_reduce_kernel(RunsParams p, R
     hist[wave][lane] = 0;
     __syncthreads();
     int first = 0, last = -1;
-    double sum = 0.0;
+    int64_t run_base = 0;
     if (live) {
         const RunRecord rec = records[k];
         // the launcher filled the records with -1 before the mark pass: a record that pass did not complete (the predictions
@@ -192,8 +193,8 @@ __global__ void __launch_bounds__(RUNS_BLOCK) runs_reduce_kernel(RunsParams p, R
                 if (base >= 0 && n >= 0 && base <= p.n_frames_total && n <= p.n_frames_total - base && rec.end_frame < n) {
                     first = rec.start_frame;
                     last = rec.end_frame;
+                    run_base = base;
                     for (int64_t f = (int64_t)first + lane; f <= last; f += 64) {
-                        sum += (double)p.conf[base + f];
                         const int cls = p.pred[base + f];
                         if (cls >= 0 && cls < p.n_classes) atomicAdd(&hist[wave][cls], 1);
                     }
@@ -201,7 +202,7 @@ __global__ void __launch_bounds__(RUNS_BLOCK) runs_reduce_kernel(RunsParams p, R
             }
         }
     }
-    for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d);         // a + b == b + a: every lane holds the same bits
+    const double sum = run_conf_sum(p.conf + run_base, first, last, lane);      // run_sum.h: shared with cbas_label_runs
     __syncthreads();
     // lane c speaks for class c: the largest count wins, then the smallest name rank; a run without a countable prediction
     // (every frame's row held a NaN) reports -1
@@ -233,12 +234,17 @@ static bool runs_params_ok(const RunsParams& p) {
            p.n_frames_total >= 0 && p.n_clips >= 1 && p.n_instances >= 1 && p.n_classes >= 1 && p.n_classes <= HEAD_SCORE_MAX_CLASSES;
 }
 
+int launch_runs_scan(const int* counts, int n, long long* offsets, hipStream_t st) {
+    if (!counts || !offsets || n < 1) return -1;
+    hipLaunchKernelGGL(runs_scan_kernel, dim3(1), dim3(RUNS_BLOCK), 0, st, counts, n, offsets);
+    return CHECK_LAUNCH();
+}
+
 int launch_runs_count(const RunsParams& p, int* counts, long long* offsets, unsigned* flags, hipStream_t st) {
     if (!runs_params_ok(p) || !counts || !offsets || !flags) return -1;
     hipLaunchKernelGGL(runs_count_kernel, dim3((unsigned)p.n_instances), dim3(RUNS_BLOCK), 0, st, p, counts, flags);
     if (CHECK_LAUNCH()) return -2;
-    hipLaunchKernelGGL(runs_scan_kernel, dim3(1), dim3(RUNS_BLOCK), 0, st, counts, p.n_instances, offsets);
-    return CHECK_LAUNCH();
+    return launch_runs_scan(counts, p.n_instances, offsets, st);
 }
 
 int launch_runs_emit(const RunsParams& p, const long long* offsets, RunRecord* records, long long n_records, unsigned* flags,

@@ -422,3 +422,34 @@ constexpr unsigned RUNS_FLAG_PRED = 16u;    // a prediction outside [-1, C)
 int launch_runs_count(const RunsParams& p, int* counts, long long* offsets, unsigned* flags, hipStream_t st);
 int launch_runs_emit(const RunsParams& p, const long long* offsets, RunRecord* records, long long n_records, unsigned* flags,
                      hipStream_t st);
+// launch_runs_scan: offsets[i] = counts[0] + ... + counts[i - 1] for i in [0, n], by one workgroup (the scan both record
+// writers share).
+int launch_runs_scan(const int* counts, int n, long long* offsets, hipStream_t st);
+
+// head_post_kernels.hip: what CBAS does with a clip's probabilities after inference (backend/cbas.py:903-1000), on the device.
+// All clips lie back to back in the per-frame arrays; clip_table is (n_clips, 2) = (first frame, frames), as above.
+constexpr unsigned POST_FLAG_TABLE = 1u;    // a table entry outside the n_frames_total frames
+constexpr unsigned POST_FLAG_VALUE = 2u;    // a label outside [-1, C)
+// launch_labels_median: out = scipy.signal.medfilt(pred, kernel_size) per clip (zero padding at both ends of every clip).
+int launch_labels_median(const int* pred, int64_t n_frames_total, const int64_t* clip_table, int n_clips, int C, int kernel_size,
+                         int* out, unsigned* flags, hipStream_t st);
+struct LabelRunsParams {
+    const int* key;
+    const float* conf;
+    int64_t n_frames_total;
+    const int64_t* clip_table;
+    int n_clips, n_classes, use_threshold;
+    double threshold;
+};
+struct LabelRunRecord {     // = cbas_label_run of include/cbas_mi355x.h
+    int clip, start_frame, end_frame, label;
+    double confidence;
+};
+// launch_label_runs_count: counts[c] = runs of clip c, offsets = their exclusive scan and the total; *flags |= POST_FLAG_*.
+// launch_label_runs_emit: the first min(offsets[n_clips], capacity) records ordered by (clip, start); reads the total on the device.
+int launch_label_runs_count(const LabelRunsParams& p, int* counts, long long* offsets, unsigned* flags, hipStream_t st);
+int launch_label_runs_emit(const LabelRunsParams& p, const long long* offsets, LabelRunRecord* records, long long capacity,
+                           unsigned* flags, hipStream_t st);
+// launch_activity_bins: bins[j] += frames f of bin j with (double)p[f][b] * is_max(f) >= threshold; the caller zeroes bins.
+int launch_activity_bins(const float* probs, int64_t n, int C, int behavior, double threshold, int64_t bin_frames,
+                         unsigned long long* bins, int64_t n_bins, hipStream_t st);

@@ -1149,6 +1149,54 @@ def write_probs_csv(path: str, probs: np.ndarray, behaviors: List[str], threads:
                                       probs.shape[0], probs.shape[1], int(threads)), "cbas_csv_write_f32")
 
 
+def read_outputs_csv(path: str):
+    """``(column names, float64 values (n, C), float32 values or None)`` of an ``_outputs.csv``: the one reader of these files
+    (the disagreement report, the events / pre-labels and the actogram parse through it).  An empty field is NaN; a file
+    without a header line gives ``([], empty, None)``; a field that is no number raises ValueError.  The third entry is the
+    rows as float32 when the file's text is, byte for byte, what ``write_probs_csv`` writes for them - each field the
+    shortest decimal of a float32 (backend/cbas.py:565) - so that the float32 values ARE the file; for any other file it is None
+    and the float64 values are all there is."""
+    import csv
+    import warnings
+    with open(path, "rb") as fb:
+        raw = fb.read()
+    head, _, body = raw.partition(b"\n")
+    header = next(csv.reader([head.decode("utf-8").rstrip("\r")]), None) if head.strip() else None
+    if not header:
+        return [], np.empty((0, 0), np.float64), None
+    values = None
+    try:
+        import io
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", UserWarning)       # "input contained no data": a header-only file
+            values = np.loadtxt(io.BytesIO(body), delimiter=",", dtype=np.float64, ndmin=2)
+    except ValueError:
+        pass                                                   # an empty or quoted field: the slow reader below
+    if values is None:
+        rows = csv.reader(body.decode("utf-8").splitlines())
+        values = np.array([[float(x) if x != "" else np.nan for x in r] for r in rows if r], np.float64)
+    values = values.reshape(-1, len(header))
+    exact = None
+    if values.shape[0]:
+        with np.errstate(over="ignore", invalid="ignore"):
+            f = np.ascontiguousarray(values.astype(np.float32))
+        import ctypes
+        lib = _lib.load()
+        at, piece, same = 0, 1 << 16, True                     # formatted and compared 65 536 rows at a time
+        for a in range(0, f.shape[0], piece):
+            part = f[a:a + piece]
+            cap = int(lib.cbas_csv_format_f32(part.ctypes.data, part.shape[0], part.shape[1], None, 0))
+            buf = ctypes.create_string_buffer(cap)
+            n = int(lib.cbas_csv_format_f32(part.ctypes.data, part.shape[0], part.shape[1], buf, cap))
+            same = n > 0 and buf.raw[:n] == body[at:at + n]
+            at += n
+            if not same:
+                break
+        if same and at == len(body):
+            exact = f
+    return list(header), values, exact
+
+
 _head_cache = {}       # single entry: id(module) -> (weakref to the module, parameter versions, device head)
 
 

@@ -33,7 +33,6 @@ from __future__ import annotations
 
 import contextlib
 import copy
-import csv
 import ctypes as C
 import os
 import queue
@@ -1132,21 +1131,12 @@ def disagreement_runs(pred: torch.Tensor, conf: torch.Tensor, clip_table, clip, 
 def _read_outputs_csv(path: str, behaviors: Sequence[str]) -> np.ndarray:
     """The behaviour columns of an ``_outputs.csv`` as float64 (n, C), selected by name as ``pred_df[task.behaviors]`` does
     (workthreads.py:761-763); an empty field is NaN.  Raises when a column is missing or a field is no number."""
-    with open(path, newline="", encoding="utf-8") as f:
-        header = next(csv.reader(f), None)
-        if header is None:
-            raise ValueError("empty file")
-        cols = [header.index(b) for b in behaviors]                   # ValueError: a behaviour without a column
-        try:
-            values = np.loadtxt(f, delimiter=",", dtype=np.float64, ndmin=2, usecols=cols)
-        except ValueError:
-            values = None                                             # an empty or quoted field: the slow reader below
-    if values is None:
-        with open(path, newline="", encoding="utf-8") as f:
-            rows = csv.reader(f)
-            next(rows)
-            values = np.array([[float(r[c]) if r[c] != "" else np.nan for c in cols] for r in rows if r], np.float64)
-    return values.reshape(-1, len(behaviors))
+    from .pipeline import read_outputs_csv
+    header, values, _ = read_outputs_csv(path)
+    if not header:
+        raise ValueError("empty file")
+    cols = [header.index(b) for b in behaviors]                       # ValueError: a behaviour without a column
+    return np.ascontiguousarray(values[:, cols])
 
 
 class _CsvWriter:
@@ -1197,7 +1187,7 @@ def _kept_rows_of(path: str, dim: int, device):
         return store, held
 
 
-def _clip_rows(path: str, dim: int, device, log):
+def _clip_rows(path: str, dim: int, device, log, what: str = "disagreement report"):
     """The half-precision rows of one ``_cls.h5`` on ``device``: a view of the kept store, or the file uploaded once.  None
     (with the reason logged) when the file is not what the device path takes: the caller hands the clip to ``infer_file``."""
     kept = _kept_rows_of(path, dim, device)
@@ -1210,7 +1200,7 @@ def _clip_rows(path: str, dim: int, device, log):
             if len(shape) != 2 or shape[1] != dim or not half or shape[0] == 0:
                 return None
             if shape[0] * dim * 2 > _resident_budget(device):
-                log(f"disagreement report: {path} does not fit in device memory, classified through infer_file")
+                log(f"{what}: {path} does not fit in device memory, classified through infer_file")
                 return None
             rows = torch.empty((shape[0], dim), dtype=torch.float16, device=device)
             for a in range(0, shape[0], ResidentRows.READ_ROWS):

@@ -53,8 +53,9 @@ extern "C" {
 #define CBAS_ERANGE       -5   /* a frame's CLS row came out NaN / infinite: an activation left the arithmetic mode's range */
 
 /* Still 11 with cbas_rows_gather_windows / cbas_head_train_step_rows, with cbas_head_score_rows / cbas_logits_nll, with
- * cbas_enc_set_pos_interp, with cbas_enc_set_fp8_plan and with cbas_probs_top1 / cbas_disagreement_runs: they are additions.  No structure and no existing signature changed, so a caller built against the earlier version 11 header
- * runs unchanged. */
+ * cbas_enc_set_pos_interp, with cbas_enc_set_fp8_plan, with cbas_probs_top1 / cbas_disagreement_runs and with
+ * cbas_labels_median / cbas_label_runs / cbas_activity_bins: they are additions.  No structure and no existing signature
+ * changed, so a caller built against the earlier version 11 header runs unchanged. */
 #define CBAS_ABI_VERSION   11
 
 typedef struct cbas_enc  cbas_enc;
@@ -550,6 +551,65 @@ int64_t cbas_disagreement_runs(const int32_t* pred_dev, const float* conf_dev, i
                                const int32_t* inst_start_dev, const int32_t* inst_end_dev, const int32_t* inst_label_dev,
                                int32_t n_instances, const int32_t* name_rank_dev, int32_t n_classes,
                                cbas_disagreement_run* records_dev, int64_t capacity, int64_t* needed_host, void* stream);
+
+/* What CBAS does with a clip's probabilities after inference - events, guided-labelling pre-labels, actogram bins
+ * (backend/cbas.py:903-1000) - from per-frame values that are on the device, instead of reading `_outputs.csv` back with
+ * pandas and walking it in Python.  The per-frame arrays hold the frames of all clips back to back (n_frames_total of them);
+ * clip_table_dev (n_clips, 2) int64 gives each clip's (first frame, frames); clips must not overlap.  Every table entry and
+ * label is checked on the device before anything is indexed with it.
+ *
+ * cbas_labels_median replaces :939, `medfilt(df['predicted_index'], kernel_size=smoothing_window)`, per clip: out_dev[f] is
+ * the median of the kernel_size values around frame f of its clip.  As scipy does, every clip is padded with
+ * kernel_size // 2 ZEROS at both ends, so the first and last frames of a clip are pulled towards class 0; windows never cross
+ * clips.  Values lie in [-1, n_classes): -1 is the reference's `fillna(-1)` (:938) and takes part as -1.  kernel_size is
+ * odd, >= 1 (1 copies) and may exceed a clip's length.  The result is an integer: the smallest value whose count in the
+ * window, cumulated from -1 upwards with the padding zeros added to value 0, reaches (kernel_size + 1) / 2.
+ * out_dev and pred_dev must not overlap at all (a window reads its neighbours; only out_dev == pred_dev is detected).
+ * CBAS_EINVAL: a NULL pointer, out_dev == pred_dev, n_frames_total < 0, n_clips < 1, n_classes outside [1, 64], an even or
+ * non-positive kernel_size, a table entry that reaches outside the n_frames_total frames, a value outside [-1, n_classes).
+ * The call synchronises `stream` (it reads the refusals back). */
+int cbas_labels_median(const int32_t* pred_dev, int64_t n_frames_total, const int64_t* clip_table_dev, int32_t n_clips,
+                       int32_t n_classes, int32_t kernel_size, int32_t* out_dev, void* stream);
+/* cbas_label_runs replaces the `df.iterrows()` state machine of Dataset.predictions_to_instances (:910-925) and the block
+ * scan of Dataset.predictions_to_instances_with_confidence (:944-955).  key_dev is a label per frame (cbas_probs_top1's pred,
+ * or cbas_labels_median's output), conf_dev the top-1 probability.  With use_threshold != 0 a frame's key counts as -1
+ * unless (double)conf >= threshold (`row['max_prob'] >= threshold`, :912; a NaN is not).  One record per maximal run of
+ * consecutive frames of ONE clip with equal key != -1, ordered by (clip, start_frame) whatever the order of execution (count,
+ * exclusive scan, emit; nothing is appended with an atomic):
+ *   with the threshold     the events of :910-925 - a run ends where the label changes or the probability drops below the
+ *                          threshold, and a new one starts on the same frame when only the label changed;
+ *   without                the blocks of :944-955; a block whose label is NaN there (key -1) is skipped, as at :950.
+ *   confidence             the mean of conf over the run in float64 (:951), summed in the fixed order of
+ *                          cbas_disagreement_runs' model_confidence (the same device function).
+ * Returns the number of records (>= 0) or a negative CBAS_E* code; *needed_host (may be NULL) receives the number of records
+ * whenever the arguments were accepted.  records_dev holds `capacity` records; with fewer than needed the call returns
+ * CBAS_EINVAL and the buffer's contents are unspecified (capacity 0 with records_dev NULL asks for the count).  CBAS_EINVAL
+ * also for: a NULL pointer, n_frames_total < 0, n_clips < 1, n_classes outside [1, 64], a NaN threshold, a table entry that
+ * reaches outside the n_frames_total frames, a key outside [-1, n_classes).  The call synchronises `stream` once. */
+typedef struct cbas_label_run {
+    int32_t clip;              /* row of clip_table_dev */
+    int32_t start_frame;       /* first and last frame of the run, in frames of the clip */
+    int32_t end_frame;
+    int32_t label;
+    double  confidence;
+} cbas_label_run;
+int64_t cbas_label_runs(const int32_t* key_dev, const float* conf_dev, int64_t n_frames_total, const int64_t* clip_table_dev,
+                        int32_t n_clips, int32_t n_classes, int32_t use_threshold, double threshold,
+                        cbas_label_run* records_dev, int64_t capacity, int64_t* needed_host, void* stream);
+/* cbas_activity_bins replaces :977-979 / :991-993 and :999 of Actogram.__init__.  probs_dev (n_total, n_classes) float32
+ * holds the rows of all `_outputs.csv` files of a recording back to back, in the caller's order.  bins_dev[j] (int64,
+ * n_bins = ceil(n_total / bin_frames) of them, zeroed by the call) counts the frames f of [j * bin_frames, (j + 1) *
+ * bin_frames) with
+ *   (double)p[f][behavior] * (is_max ? 1.0 : 0.0) >= threshold,      is_max = (max of the OTHER columns) < p[f][behavior].
+ * The comparison is strict, so a tie is no maximum; the maximum skips NaN as pandas' does and over no value (n_classes == 1,
+ * or every other column NaN) it is NaN, so is_max is false.  A threshold <= 0 therefore counts every frame whose own
+ * probability is a number; a NaN probability counts nothing.  Bins run across file boundaries, as the reference's
+ * concatenated list does.  Integer atomics only: equal inputs give equal bins.  Runs on the device probs_dev lives on,
+ * asynchronously on `stream`.
+ * CBAS_EINVAL: a NULL pointer, n_total < 1, n_classes outside [1, 64], behavior outside [0, n_classes), bin_frames < 1,
+ * n_bins != ceil(n_total / bin_frames). */
+int cbas_activity_bins(const float* probs_dev, int64_t n_total, int32_t n_classes, int32_t behavior, double threshold,
+                       int64_t bin_frames, int64_t* bins_dev, int64_t n_bins, void* stream);
 
 /* Copy the current parameters (what = 0), the gradients of the last step (what = 1) or Adam's first / second moment
  * (what = 2 / 3) to the host, in the blob order of cbas_head_create (n = cbas_head_weights_count).  Synchronises the device. */
