@@ -147,6 +147,70 @@ void build_temporal(int T, double alpha, int lo, int hi, std::vector<float>& tma
     }
 }
 
+// Device side of cbas_head_train_create: every buffer of the handle, zero-filled, and the parameters in the train layout.
+// On a non-zero return the caller destroys the handle, which frees what t->allocs holds by then.
+int trainer_init(cbas_head_trainer* t, const float* weights_host, const float* class_weights_host) {
+    auto dalloc = [&](float** p, int64_t n) -> hipError_t {
+        hipError_t e = hipMalloc((void**)p, (size_t)(n > 0 ? n : 1) * sizeof(float));
+        if (e == hipSuccess) { t->allocs.push_back(*p); e = hipMemset(*p, 0, (size_t)(n > 0 ? n : 1) * sizeof(float)); }
+        return e;
+    };
+    const int T = t->T;
+    const int64_t B = t->tcfg.max_batch, R = B * T, Rp = round_up(R, K_PAD), Bp = round_up(B, 32);
+    t->Bcap = B; t->Rcap = R; t->Rp = Rp; t->Bp = Bp;
+    const int64_t I = t->I, C = t->C, F = t->F, L0 = t->L0, h = t->h, H2 = t->H2, NP = t->NPROJ, nc = t->hi - t->lo;
+    ALLOC_TRY(dalloc(&t->P, t->n_train)); ALLOC_TRY(dalloc(&t->G, t->n_train)); ALLOC_TRY(dalloc(&t->M, t->n_train)); ALLOC_TRY(dalloc(&t->V, t->n_train));
+    {   // parameters: blob -> train layout
+        std::vector<float> host((size_t)t->n_train, 0.f);
+        for (const MapEntry& e : t->map) memcpy(host.data() + e.train_off, weights_host + e.blob_off, (size_t)e.n * sizeof(float));
+        ALLOC_TRY(hipMemcpy(t->P, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    if (class_weights_host) {
+        ALLOC_TRY(dalloc(&t->cw, C));
+        ALLOC_TRY(hipMemcpy(t->cw, class_weights_host, (size_t)C * sizeof(float), hipMemcpyHostToDevice));
+    }
+    {
+        std::vector<float> tm, lv;
+        build_temporal(T, (double)t->cfg.ema_alpha, t->lo, t->hi, tm, lv);
+        ALLOC_TRY(dalloc(&t->tmat, (int64_t)tm.size())); ALLOC_TRY(dalloc(&t->lin_vec, T));
+        ALLOC_TRY(hipMemcpy(t->tmat, tm.data(), tm.size() * sizeof(float), hipMemcpyHostToDevice));
+        ALLOC_TRY(hipMemcpy(t->lin_vec, lv.data(), lv.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    ALLOC_TRY(dalloc(&t->proj, R * NP)); ALLOC_TRY(dalloc(&t->Y, R * F)); ALLOC_TRY(dalloc(&t->aug, R * F));
+    ALLOC_TRY(dalloc(&t->Z, R * L0)); ALLOC_TRY(dalloc(&t->xl, R * L0)); ALLOC_TRY(dalloc(&t->gin, R * 8 * h));
+    for (int l = 0; l < t->NL; ++l) {
+        ALLOC_TRY(dalloc(&t->act[l], R * 8 * h)); ALLOC_TRY(dalloc(&t->cst[l], R * H2)); ALLOC_TRY(dalloc(&t->hout[l], R * H2));
+    }
+    ALLOC_TRY(dalloc(&t->attw, B * nc)); ALLOC_TRY(dalloc(&t->scores, B * nc)); ALLOC_TRY(dalloc(&t->latent, B * H2));
+    ALLOC_TRY(dalloc(&t->lstm_logits, B * C)); ALLOC_TRY(dalloc(&t->final_logits, B * C)); ALLOC_TRY(dalloc(&t->lin_logits, B * C));
+    ALLOC_TRY(dalloc(&t->b_gate, 8 * h));
+    ALLOC_TRY(dalloc(&t->terms, B * 2)); ALLOC_TRY(dalloc(&t->sums, 8)); ALLOC_TRY(dalloc(&t->dfinal, B * C)); ALLOC_TRY(dalloc(&t->dlstm, B * C));
+    ALLOC_TRY(dalloc(&t->dlin, B * C)); ALLOC_TRY(dalloc(&t->part_pool, B * (H2 + 12))); ALLOC_TRY(dalloc(&t->part_exp, B * 3 * F));
+    const int64_t max_cols = 8 * h > 3 * F ? 8 * h : 3 * F;
+    ALLOC_TRY(dalloc(&t->cs_tmp, COLSUM_CHUNKS * max_cols));
+    ALLOC_TRY(dalloc(&t->dhA, R * H2)); ALLOC_TRY(dalloc(&t->dhB, R * H2)); ALLOC_TRY(dalloc(&t->dgin, R * 8 * h)); ALLOC_TRY(dalloc(&t->hprev, R * H2));
+    ALLOC_TRY(dalloc(&t->dxl, R * L0)); ALLOC_TRY(dalloc(&t->daug, R * F)); ALLOC_TRY(dalloc(&t->dproj, R * NP));
+    ALLOC_TRY(dalloc(&t->XT, I * Rp)); ALLOC_TRY(dalloc(&t->dprojT, NP * Rp)); ALLOC_TRY(dalloc(&t->augT, F * Rp)); ALLOC_TRY(dalloc(&t->dZT, L0 * Rp));
+    ALLOC_TRY(dalloc(&t->dginT, 8 * h * Rp)); ALLOC_TRY(dalloc(&t->xinT, (L0 > H2 ? L0 : H2) * Rp)); ALLOC_TRY(dalloc(&t->hprevT, H2 * Rp));
+    ALLOC_TRY(dalloc(&t->latentT, H2 * Bp)); ALLOC_TRY(dalloc(&t->dlogT, pad4(C) * Bp)); ALLOC_TRY(dalloc(&t->Rc, B * H2)); ALLOC_TRY(dalloc(&t->RcT, H2 * Bp));
+    ALLOC_TRY(dalloc(&t->cov, H2 * H2)); ALLOC_TRY(dalloc(&t->Gm, H2 * H2)); ALLOC_TRY(dalloc(&t->sq, H2)); ALLOC_TRY(dalloc(&t->dlat_cov, B * H2));
+    ALLOC_TRY(dalloc(&t->wlin0T, F * L0)); ALLOC_TRY(dalloc(&t->wihT, (L0 > H2 ? L0 : H2) * 8 * h));
+    {
+        int64_t mx = (int64_t)NP * I;
+        if (L0 * F > mx) mx = L0 * F;
+        if (8 * h * (L0 > H2 ? L0 : H2) > mx) mx = 8 * h * (L0 > H2 ? L0 : H2);
+        ALLOC_TRY(dalloc(&t->skbuf, 16 * mx));
+    }
+    ALLOC_TRY(dalloc(&t->xg, R * I));    // filled below like every other buffer: ordered before the handle is handed out
+    // dalloc zero-fills with hipMemset on the NULL stream, which may return before the fill has run, and the training step is
+    // queued on the caller's stream - in CBAS a torch stream, NON-BLOCKING, hence not ordered after the null stream: beside a
+    // busy encoder the fills of G / M / V landed after the first steps had written them (r5: 114 of 125 forty-step runs
+    // beside encoder passes ended with other weights than the idle-device run; scripts/train_beside_encoder.py).  The handle
+    // is only handed out once every fill has completed.
+    ALLOC_TRY(hipStreamSynchronize(nullptr));
+    return CBAS_OK;
+}
+
 }  // namespace
 
 extern "C" void cbas_head_train_destroy(cbas_head_trainer* t) {
@@ -198,73 +262,11 @@ extern "C" int cbas_head_train_create(const cbas_head_config* cfg, const cbas_tr
         return cbas_fail(CBAS_EINVAL, "seq_len=%d too long for the training kernels (window does not fit the 160 KiB LDS)", T);
     }
 
-#define TRY_HIP(expr)                                                                                     \
-    do {                                                                                                  \
-        hipError_t _e = (expr);                                                                           \
-        if (_e != hipSuccess) {                                                                           \
-            cbas_fail(CBAS_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-            cbas_head_train_destroy(t);                                                                   \
-            return _e == hipErrorOutOfMemory ? CBAS_ENOMEM : CBAS_EHIP;                                   \
-        }                                                                                                 \
-    } while (0)
-    auto dalloc = [&](float** p, int64_t n) -> hipError_t {
-        hipError_t e = hipMalloc((void**)p, (size_t)(n > 0 ? n : 1) * sizeof(float));
-        if (e == hipSuccess) { t->allocs.push_back(*p); e = hipMemset(*p, 0, (size_t)(n > 0 ? n : 1) * sizeof(float)); }
-        return e;
-    };
-    const int64_t B = tcfg->max_batch, R = B * T, Rp = round_up(R, K_PAD), Bp = round_up(B, 32);
-    t->Bcap = B; t->Rcap = R; t->Rp = Rp; t->Bp = Bp;
-    const int64_t I = t->I, C = t->C, F = t->F, L0 = t->L0, h = t->h, H2 = t->H2, NP = t->NPROJ, nc = hi - lo;
-    TRY_HIP(dalloc(&t->P, t->n_train)); TRY_HIP(dalloc(&t->G, t->n_train)); TRY_HIP(dalloc(&t->M, t->n_train)); TRY_HIP(dalloc(&t->V, t->n_train));
-    {   // parameters: blob -> train layout
-        std::vector<float> host((size_t)t->n_train, 0.f);
-        for (const MapEntry& e : t->map) memcpy(host.data() + e.train_off, weights_host + e.blob_off, (size_t)e.n * sizeof(float));
-        TRY_HIP(hipMemcpy(t->P, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
+    const int rc = trainer_init(t, weights_host, class_weights_host);
+    if (rc != CBAS_OK) {
+        cbas_head_train_destroy(t);      // never touches the error text: the failing call's message stands
+        return rc;
     }
-    if (class_weights_host) {
-        TRY_HIP(dalloc(&t->cw, C));
-        TRY_HIP(hipMemcpy(t->cw, class_weights_host, (size_t)C * sizeof(float), hipMemcpyHostToDevice));
-    }
-    {
-        std::vector<float> tm, lv;
-        build_temporal(T, (double)c.ema_alpha, lo, hi, tm, lv);
-        TRY_HIP(dalloc(&t->tmat, (int64_t)tm.size())); TRY_HIP(dalloc(&t->lin_vec, T));
-        TRY_HIP(hipMemcpy(t->tmat, tm.data(), tm.size() * sizeof(float), hipMemcpyHostToDevice));
-        TRY_HIP(hipMemcpy(t->lin_vec, lv.data(), lv.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-    TRY_HIP(dalloc(&t->proj, R * NP)); TRY_HIP(dalloc(&t->Y, R * F)); TRY_HIP(dalloc(&t->aug, R * F));
-    TRY_HIP(dalloc(&t->Z, R * L0)); TRY_HIP(dalloc(&t->xl, R * L0)); TRY_HIP(dalloc(&t->gin, R * 8 * h));
-    for (int l = 0; l < t->NL; ++l) {
-        TRY_HIP(dalloc(&t->act[l], R * 8 * h)); TRY_HIP(dalloc(&t->cst[l], R * H2)); TRY_HIP(dalloc(&t->hout[l], R * H2));
-    }
-    TRY_HIP(dalloc(&t->attw, B * nc)); TRY_HIP(dalloc(&t->scores, B * nc)); TRY_HIP(dalloc(&t->latent, B * H2));
-    TRY_HIP(dalloc(&t->lstm_logits, B * C)); TRY_HIP(dalloc(&t->final_logits, B * C)); TRY_HIP(dalloc(&t->lin_logits, B * C));
-    TRY_HIP(dalloc(&t->b_gate, 8 * h));
-    TRY_HIP(dalloc(&t->terms, B * 2)); TRY_HIP(dalloc(&t->sums, 8)); TRY_HIP(dalloc(&t->dfinal, B * C)); TRY_HIP(dalloc(&t->dlstm, B * C));
-    TRY_HIP(dalloc(&t->dlin, B * C)); TRY_HIP(dalloc(&t->part_pool, B * (H2 + 12))); TRY_HIP(dalloc(&t->part_exp, B * 3 * F));
-    const int64_t max_cols = 8 * h > 3 * F ? 8 * h : 3 * F;
-    TRY_HIP(dalloc(&t->cs_tmp, COLSUM_CHUNKS * max_cols));
-    TRY_HIP(dalloc(&t->dhA, R * H2)); TRY_HIP(dalloc(&t->dhB, R * H2)); TRY_HIP(dalloc(&t->dgin, R * 8 * h)); TRY_HIP(dalloc(&t->hprev, R * H2));
-    TRY_HIP(dalloc(&t->dxl, R * L0)); TRY_HIP(dalloc(&t->daug, R * F)); TRY_HIP(dalloc(&t->dproj, R * NP));
-    TRY_HIP(dalloc(&t->XT, I * Rp)); TRY_HIP(dalloc(&t->dprojT, NP * Rp)); TRY_HIP(dalloc(&t->augT, F * Rp)); TRY_HIP(dalloc(&t->dZT, L0 * Rp));
-    TRY_HIP(dalloc(&t->dginT, 8 * h * Rp)); TRY_HIP(dalloc(&t->xinT, (L0 > H2 ? L0 : H2) * Rp)); TRY_HIP(dalloc(&t->hprevT, H2 * Rp));
-    TRY_HIP(dalloc(&t->latentT, H2 * Bp)); TRY_HIP(dalloc(&t->dlogT, pad4(C) * Bp)); TRY_HIP(dalloc(&t->Rc, B * H2)); TRY_HIP(dalloc(&t->RcT, H2 * Bp));
-    TRY_HIP(dalloc(&t->cov, H2 * H2)); TRY_HIP(dalloc(&t->Gm, H2 * H2)); TRY_HIP(dalloc(&t->sq, H2)); TRY_HIP(dalloc(&t->dlat_cov, B * H2));
-    TRY_HIP(dalloc(&t->wlin0T, F * L0)); TRY_HIP(dalloc(&t->wihT, (L0 > H2 ? L0 : H2) * 8 * h));
-    {
-        int64_t mx = (int64_t)NP * I;
-        if (L0 * F > mx) mx = L0 * F;
-        if (8 * h * (L0 > H2 ? L0 : H2) > mx) mx = 8 * h * (L0 > H2 ? L0 : H2);
-        TRY_HIP(dalloc(&t->skbuf, 16 * mx));
-    }
-    TRY_HIP(dalloc(&t->xg, R * I));      // filled below like every other buffer: ordered before the handle is handed out
-    // dalloc zero-fills with hipMemset on the NULL stream, which may return before the fill has run, and the training step is
-    // queued on the caller's stream - in CBAS a torch stream, NON-BLOCKING, hence not ordered after the null stream: beside a
-    // busy encoder the fills of G / M / V landed after the first steps had written them (r5: 114 of 125 forty-step runs
-    // beside encoder passes ended with other weights than the idle-device run; scripts/train_beside_encoder.py).  The handle
-    // is only handed out once every fill has completed.
-    TRY_HIP(hipStreamSynchronize(nullptr));
-#undef TRY_HIP
     *out = t;
     return CBAS_OK;
 }
@@ -312,198 +314,268 @@ void bind_job(Job& c) {
     c.dh_cur = t->dhA; c.dh_next = t->dhB;
 }
 
-// The step of k trainers that share one head configuration (k = 1: the one trainer of cbas_head_train_step, and exactly its
-// launches in its order).  The LSTM, expand and pool kernels, the transposes and the GEMMs are queued per trainer on
-// jobs[j].st and overlap there.  For k > 1 the small kernels - Adam, the column sums, the cross-entropy pair, cov_offdiag,
-// add / copy, GELU + dropout - go out as ONE trial-batched launch for all k on the leading stream jobs[0].st: `join` orders
-// that stream behind every trainer's with one event each, `fork` orders every trainer's stream behind it again.  Batched
-// launches that follow each other need neither.  The call returns forked, so each stream alone orders the next step.
-int step_jobs(Job* jobs, const int k, const int update) {
-    const cbas_head_trainer* cfg = jobs[0].t;
-    const int I = cfg->I, C = cfg->C, T = cfg->T, L0 = cfg->L0, h = cfg->h, F = cfg->F, H2 = cfg->H2, NP = cfg->NPROJ, NL = cfg->NL;
-    const hipStream_t lead = jobs[0].st;
+// The k jobs of one step and the two ways their launches are queued.  The LSTM, expand and pool kernels, the transposes and
+// the GEMMs go out per trainer on jobs[j].st and overlap there (`each`).  The small kernels - Adam, the column sums, the
+// cross-entropy pair, cov_offdiag, add / copy, GELU + dropout - go out as ONE launch for all k on the leading stream
+// jobs[0].st, with trainer j's operands in entry j of the kernel's table (`batched`).  `join` orders the leading stream
+// behind every trainer's with one event each, `fork` orders every trainer's stream behind it again; launches of one kind
+// that follow each other need neither, and for k = 1 both do nothing: everything is queued on the one stream.
+// A table of one goes out through the single-trial launcher of head_train_kernels.hip, whose kernel takes the operands as
+// plain arguments: measured 0.012 ms per solo step (0.75 %) faster than the table form at k = 1, same bytes.
+// Every call returns the step's status and queues nothing once that is not CBAS_OK: a step is a list of calls.
+struct Step {
+    Job* jobs;
+    int k;
+    int rc = CBAS_OK;
     bool joined = false;
-    auto join = [&]() -> int {
+    hipStream_t lead() const { return jobs[0].st; }
+
+    int join() {
         if (joined || k == 1) return CBAS_OK;
         for (int j = 1; j < k; ++j) {
             HIP_TRY(hipEventRecord(jobs[j].t->ev, jobs[j].st));
-            HIP_TRY(hipStreamWaitEvent(lead, jobs[j].t->ev, 0));
+            HIP_TRY(hipStreamWaitEvent(lead(), jobs[j].t->ev, 0));
         }
         joined = true;
         return CBAS_OK;
-    };
-    auto fork = [&]() -> int {
+    }
+    int fork() {
         if (!joined) return CBAS_OK;
-        HIP_TRY(hipEventRecord(jobs[0].t->ev, lead));
+        HIP_TRY(hipEventRecord(jobs[0].t->ev, lead()));
         for (int j = 1; j < k; ++j) HIP_TRY(hipStreamWaitEvent(jobs[j].st, jobs[0].t->ev, 0));
         joined = false;
         return CBAS_OK;
-    };
-#define TRY_RC(expr)                       \
-    do {                                   \
-        const int rc_ = (expr);            \
-        if (rc_ != CBAS_OK) return rc_;    \
-    } while (0)
-// the statements once per trainer j, with c / t / P / G / st naming that trainer's job, handle, parameters, gradients, stream
-#define PER_JOB(...)                                                                                       \
-    for (int j = 0; j < k; ++j) {                                                                          \
-        Job& c = jobs[j];                                                                                  \
-        cbas_head_trainer* const t = c.t;                                                                  \
-        float* const P = t->P;                                                                             \
-        float* const G = t->G;                                                                             \
-        const hipStream_t st = c.st;                                                                       \
-        (void)P; (void)G; (void)st;                                                                        \
-        __VA_ARGS__;                                                                                       \
     }
-#define EACH(...)       do { TRY_RC(fork()); PER_JOB(__VA_ARGS__) } while (0)      /* queued on every trainer's own stream */
-#define FILL(...)       do { TRY_RC(join()); PER_JOB(__VA_ARGS__) } while (0)      /* entry j of a table for the leading stream */
-// the small kernels: the single-trial launcher for k = 1, else one batched launch; ON: does trainer j take part
-#define COLSUM(ON, SRC, ROWS, COLS, DST)                                                                                        \
-    do {                                                                                                                        \
-        if (k == 1) { EACH(if (ON) LAUNCH_TRY(launch_colsum(SRC, ROWS, COLS, COLS, 1.0f, t->cs_tmp, DST, st))); }               \
-        else {                                                                                                                  \
-            ColsumBatch b_{};                                                                                                   \
-            FILL(if (ON) { b_.src[j] = SRC; b_.rows[j] = ROWS; b_.cols[j] = COLS; b_.ld[j] = COLS; b_.tmp[j] = t->cs_tmp; b_.dst[j] = DST; }); \
-            LAUNCH_TRY(launch_colsum_multi(b_, k, lead));                                                                       \
-        }                                                                                                                       \
-    } while (0)
-#define ADD_VEC(A, B_, OUT, N)                                                                                                  \
-    do {                                                                                                                        \
-        if (k == 1) { EACH(LAUNCH_TRY(launch_add_vec(A, B_, OUT, N, st))); }                                                    \
-        else {                                                                                                                  \
-            VecBatch b_{};                                                                                                      \
-            FILL(b_.a[j] = A; b_.b[j] = B_; b_.out[j] = OUT; b_.n[j] = N);                                                      \
-            LAUNCH_TRY(launch_add_vec_multi(b_, k, lead));                                                                      \
-        }                                                                                                                       \
-    } while (0)
-#define GELU_DROPOUT(Z_, IO, BACKWARD)                                                                                          \
-    do {                                                                                                                        \
-        if (k == 1) { EACH(LAUNCH_TRY(launch_gelu_dropout(Z_, IO, c.R * L0, c.key[3], c.thr_l, c.sc_l, BACKWARD, st))); }       \
-        else {                                                                                                                  \
-            GeluBatch b_{};                                                                                                     \
-            FILL(b_.Z[j] = Z_; b_.io[j] = IO; b_.n[j] = c.R * L0; b_.key[j] = c.key[3]; b_.thr[j] = c.thr_l; b_.scale[j] = c.sc_l); \
-            LAUNCH_TRY(launch_gelu_dropout_multi(b_, k, BACKWARD, lead));                                                       \
-        }                                                                                                                       \
-    } while (0)
+    // launches(job, job.t), once per trainer, queue on job.st
+    template <class Launches>
+    int each(Launches launches) {
+        if (rc == CBAS_OK) rc = fork();
+        for (int j = 0; j < k && rc == CBAS_OK; ++j) rc = launches(jobs[j], jobs[j].t);
+        return rc;
+    }
+    // fill(j, job) writes entry j of a table (an entry left alone has the count 0 and takes no part); launch() queues the
+    // table's kernel on the leading stream
+    template <class Fill, class Launch>
+    int batched(Fill fill, Launch launch) {
+        if (rc == CBAS_OK) rc = join();
+        if (rc != CBAS_OK) return rc;
+        for (int j = 0; j < k; ++j) fill(j, jobs[j]);
+        return rc = launch();
+    }
+};
+
+// ---- the small kernels of a step: one table per launch, the operands spelled once ----
+int gelu_dropout(Step& s, int backward) {        // lin0's activation: xl = dropout(gelu(Z)); backward: dxl becomes dZ in place
+    GeluBatch b{};
+    return s.batched(
+        [&](int j, Job& c) {
+            b.Z[j] = c.t->Z; b.io[j] = backward ? c.t->dxl : c.t->xl; b.n[j] = c.R * c.t->L0;
+            b.key[j] = c.key[3]; b.thr[j] = c.thr_l; b.scale[j] = c.sc_l;
+        },
+        [&]() -> int {
+            if (s.k > 1) LAUNCH_TRY(launch_gelu_dropout_multi(b, s.k, backward, s.lead()));
+            else LAUNCH_TRY(launch_gelu_dropout(b.Z[0], b.io[0], b.n[0], b.key[0], b.thr[0], b.scale[0], backward, s.lead()));
+            return CBAS_OK;
+        });
+}
+
+int cross_entropy(Step& s, int grad) {           // final_logits -> terms; grad: final_logits, sums[0..1] -> dfinal
+    CeBatch b{};
+    return s.batched(
+        [&](int j, Job& c) {
+            b.logits[j] = c.t->final_logits; b.labels[j] = c.labels; b.cw[j] = c.t->cw; b.sums[j] = c.t->sums; b.n[j] = c.B;
+            b.C[j] = c.t->C; b.eps[j] = c.t->tcfg.label_smoothing; b.out[j] = grad ? c.t->dfinal : c.t->terms;
+        },
+        [&]() -> int {
+            if (s.k > 1) LAUNCH_TRY(launch_ce_multi(b, s.k, grad, s.lead()));
+            else if (grad) LAUNCH_TRY(launch_ce_grad(b.logits[0], b.labels[0], b.cw[0], b.sums[0], b.n[0], b.C[0], b.eps[0], b.out[0], s.lead()));
+            else LAUNCH_TRY(launch_ce_terms(b.logits[0], b.labels[0], b.cw[0], b.n[0], b.C[0], b.eps[0], b.out[0], s.lead()));
+            return CBAS_OK;
+        });
+}
+
+int cov_offdiag(Step& s) {                       // cov -> Gm, sq; only the trainers with a covariance penalty
+    CovBatch b{};
+    return s.batched(
+        [&](int j, Job& c) {
+            if (!c.use_cov) return;
+            b.cov[j] = c.t->cov; b.n[j] = c.t->H2; b.cscale[j] = c.cov_inv; b.gscale[j] = 4.0f * c.cov_inv; b.G[j] = c.t->Gm;
+            b.sq[j] = c.t->sq;
+        },
+        [&]() -> int {
+            if (s.k > 1) LAUNCH_TRY(launch_cov_offdiag_multi(b, s.k, s.lead()));
+            else if (b.n[0]) LAUNCH_TRY(launch_cov_offdiag(b.cov[0], b.n[0], b.cscale[0], b.gscale[0], b.G[0], b.sq[0], s.lead()));
+            return CBAS_OK;
+        });
+}
+
+struct Cols { const float* src; int64_t rows; int cols; float* dst; };      // cols = 0: the trainer takes no part
+template <class Of>
+int colsum(Step& s, Of of) {                     // of(job, job.t): that trainer's column sum, dst [cols] = sum_r src [r][cols]
+    ColsumBatch b{};
+    return s.batched(
+        [&](int j, Job& c) {
+            const Cols o = of(c, c.t);
+            if (!o.cols) return;
+            b.src[j] = o.src; b.rows[j] = o.rows; b.cols[j] = o.cols; b.ld[j] = o.cols; b.tmp[j] = c.t->cs_tmp; b.dst[j] = o.dst;
+        },
+        [&]() -> int {
+            if (s.k > 1) LAUNCH_TRY(launch_colsum_multi(b, s.k, s.lead()));
+            else if (b.cols[0]) LAUNCH_TRY(launch_colsum(b.src[0], b.rows[0], b.cols[0], b.ld[0], 1.0f, b.tmp[0], b.dst[0], s.lead()));
+            return CBAS_OK;
+        });
+}
+
+int add_lstm_biases(Step& s, int l, int backward) {   // b_gate = b_ih + b_hh; backward: d b_hh = d b_ih
+    VecBatch b{};
+    return s.batched(
+        [&](int j, Job& c) {
+            cbas_head_trainer* t = c.t;
+            b.a[j] = (backward ? t->G : t->P) + t->o_bih[l]; b.b[j] = backward ? nullptr : t->P + t->o_bhh[l];
+            b.out[j] = backward ? t->G + t->o_bhh[l] : t->b_gate; b.n[j] = 8 * t->h;
+        },
+        [&]() -> int {
+            if (s.k > 1) LAUNCH_TRY(launch_add_vec_multi(b, s.k, s.lead()));
+            else LAUNCH_TRY(launch_add_vec(b.a[0], b.b[0], b.out[0], b.n[0], s.lead()));
+            return CBAS_OK;
+        });
+}
+
+int adam(Step& s) {
+    AdamBatch b{};
+    b.wd_special = 1e-3f;                                                                       // cbas.py:1307
+    return s.batched(
+        [&](int j, Job& c) {
+            cbas_head_trainer* t = c.t;
+            b.p[j] = t->P; b.g[j] = t->G; b.m[j] = t->M; b.v[j] = t->V; b.n[j] = t->n_train; b.wd[j] = t->tcfg.weight_decay;
+            b.wd_lo[j] = t->o_gate; b.wd_hi[j] = t->o_gate + 1;
+            adam_bias_corrections(t->tcfg.lr, t->step + 1, &b.lr_c1[j], &b.inv_sqrt_c2[j]);
+        },
+        [&]() -> int {
+            const cbas_head_trainer* t = s.jobs[0].t;
+            if (s.k > 1) LAUNCH_TRY(launch_adam_step_multi(b, s.k, s.lead()));
+            else LAUNCH_TRY(launch_adam_step(b.p[0], b.g[0], b.m[0], b.v[0], b.n[0], t->tcfg.lr, b.wd[0], b.wd_lo[0], b.wd_hi[0], b.wd_special,
+                                             t->step + 1, s.lead()));
+            return CBAS_OK;
+        });
+}
+
+// The step of k trainers that share one head configuration (k = 1: the one trainer of cbas_head_train_step, on the caller's
+// stream).  The call returns forked, so each stream alone orders the next step.
+int step_jobs(Job* jobs, const int k, const int update) {
+    const cbas_head_trainer* cfg = jobs[0].t;
+    const int I = cfg->I, C = cfg->C, T = cfg->T, L0 = cfg->L0, h = cfg->h, F = cfg->F, H2 = cfg->H2, NP = cfg->NPROJ, NL = cfg->NL;
+    Step s{jobs, k};
 
     // ---------------- forward ----------------
-    EACH(LAUNCH_TRY(gemm_nt(c.x, I, P + t->o_wproj, NP, nullptr, t->proj, NP, c.R, NP, I, st));
-         LAUNCH_TRY(launch_train_expand_fwd(c.ep, c.B, t->Y, t->aug, t->lin_logits, st));
-         LAUNCH_TRY(gemm_nt(t->aug, F, P + t->o_wlin0, L0, P + t->o_blin0, t->Z, L0, c.R, L0, F, st)));
-    GELU_DROPOUT(t->Z, t->xl, 0);
-    EACH(LAUNCH_TRY(launch_head_centre(t->xl, c.B, T, L0, st)));
+    s.each([&](Job& c, cbas_head_trainer* t) -> int {
+        LAUNCH_TRY(gemm_nt(c.x, I, t->P + t->o_wproj, NP, nullptr, t->proj, NP, c.R, NP, I, c.st));
+        LAUNCH_TRY(launch_train_expand_fwd(c.ep, c.B, t->Y, t->aug, t->lin_logits, c.st));
+        LAUNCH_TRY(gemm_nt(t->aug, F, t->P + t->o_wlin0, L0, t->P + t->o_blin0, t->Z, L0, c.R, L0, F, c.st));
+        return CBAS_OK;
+    });
+    gelu_dropout(s, 0);
+    s.each([&](Job& c, cbas_head_trainer* t) -> int { LAUNCH_TRY(launch_head_centre(t->xl, c.B, T, L0, c.st)); return CBAS_OK; });
     for (int l = 0; l < NL; ++l) {
         const int in = l == 0 ? L0 : H2;
-        ADD_VEC(P + t->o_bih[l], P + t->o_bhh[l], t->b_gate, 8 * h);
-        EACH(LAUNCH_TRY(gemm_nt(l == 0 ? t->xl : t->hout[l - 1], in, P + t->o_wih[l], 8 * h, t->b_gate, t->gin, 8 * h, c.R, 8 * h, in, st));
-             LAUNCH_TRY(launch_lstm_train_fwd(t->gin, P + t->o_whh[l], h, T, c.B, t->act[l], t->cst[l], t->hout[l], st)));
+        add_lstm_biases(s, l, 0);
+        s.each([&](Job& c, cbas_head_trainer* t) -> int {
+            LAUNCH_TRY(gemm_nt(l == 0 ? t->xl : t->hout[l - 1], in, t->P + t->o_wih[l], 8 * h, t->b_gate, t->gin, 8 * h, c.R, 8 * h, in, c.st));
+            LAUNCH_TRY(launch_lstm_train_fwd(t->gin, t->P + t->o_whh[l], h, T, c.B, t->act[l], t->cst[l], t->hout[l], c.st));
+            return CBAS_OK;
+        });
     }
-    EACH(LAUNCH_TRY(launch_pool_train_fwd(c.pp, c.B, t->attw, t->scores, t->latent, t->lstm_logits, t->final_logits, st)));
+    s.each([&](Job& c, cbas_head_trainer* t) -> int {
+        LAUNCH_TRY(launch_pool_train_fwd(c.pp, c.B, t->attw, t->scores, t->latent, t->lstm_logits, t->final_logits, c.st));
+        return CBAS_OK;
+    });
 
     // ---------------- loss ----------------
-    if (k == 1) {
-        EACH(LAUNCH_TRY(launch_ce_terms(t->final_logits, c.labels, t->cw, c.B, C, t->tcfg.label_smoothing, t->terms, st)));
-    } else {
-        CeBatch b{};
-        FILL(b.logits[j] = t->final_logits; b.labels[j] = c.labels; b.cw[j] = t->cw; b.n[j] = c.B; b.C[j] = C;
-             b.eps[j] = t->tcfg.label_smoothing; b.out[j] = t->terms);
-        LAUNCH_TRY(launch_ce_multi(b, k, 0, lead));
-    }
-    COLSUM(true, t->terms, c.B, 2, t->sums);                                                    // sums[0..1]
-    if (k == 1) {
-        EACH(LAUNCH_TRY(launch_ce_grad(t->final_logits, c.labels, t->cw, t->sums, c.B, C, t->tcfg.label_smoothing, t->dfinal, st)));
-    } else {
-        CeBatch b{};
-        FILL(b.logits[j] = t->final_logits; b.labels[j] = c.labels; b.cw[j] = t->cw; b.sums[j] = t->sums; b.n[j] = c.B; b.C[j] = C;
-             b.eps[j] = t->tcfg.label_smoothing; b.out[j] = t->dfinal);
-        LAUNCH_TRY(launch_ce_multi(b, k, 1, lead));
-    }
-    COLSUM(c.use_cov, t->latent, c.B, H2, t->sq);                                               // column sums (sq as scratch)
-    EACH(if (c.use_cov) {
-        LAUNCH_TRY(launch_sub_colmean(t->latent, t->sq, c.B, H2, t->Rc, st));
-        LAUNCH_TRY(launch_transpose_pad(t->Rc, c.B, H2, H2, t->RcT, c.Bp, st));
-        LAUNCH_TRY(gemm_nt(t->RcT, c.Bp, t->RcT, H2, nullptr, t->cov, H2, H2, H2, (int)c.Bp, st));
+    cross_entropy(s, 0);
+    colsum(s, [&](Job& c, cbas_head_trainer* t) { return Cols{t->terms, c.B, 2, t->sums}; });                  // sums[0..1]
+    cross_entropy(s, 1);
+    colsum(s, [&](Job& c, cbas_head_trainer* t) { return c.use_cov ? Cols{t->latent, c.B, H2, t->sq} : Cols{}; });     // column sums (sq as scratch)
+    s.each([&](Job& c, cbas_head_trainer* t) -> int {
+        if (!c.use_cov) return CBAS_OK;
+        LAUNCH_TRY(launch_sub_colmean(t->latent, t->sq, c.B, H2, t->Rc, c.st));
+        LAUNCH_TRY(launch_transpose_pad(t->Rc, c.B, H2, H2, t->RcT, c.Bp, c.st));
+        LAUNCH_TRY(gemm_nt(t->RcT, c.Bp, t->RcT, H2, nullptr, t->cov, H2, H2, H2, (int)c.Bp, c.st));
+        return CBAS_OK;
     });
-    if (k == 1) {
-        EACH(if (c.use_cov) LAUNCH_TRY(launch_cov_offdiag(t->cov, H2, c.cov_inv, 4.0f * c.cov_inv, t->Gm, t->sq, st)));
-    } else {
-        CovBatch b{};
-        FILL(if (c.use_cov) {
-            b.cov[j] = t->cov; b.n[j] = H2; b.cscale[j] = c.cov_inv; b.gscale[j] = 4.0f * c.cov_inv; b.G[j] = t->Gm; b.sq[j] = t->sq;
-        });
-        LAUNCH_TRY(launch_cov_offdiag_multi(b, k, lead));
-    }
-    COLSUM(c.use_cov, t->sq, H2, 1, t->sums + 2);                                               // sums[2] = covariance penalty
-    EACH(if (c.use_cov) LAUNCH_TRY(gemm_nt(t->Rc, H2, t->Gm, H2, nullptr, t->dlat_cov, H2, c.B, H2, H2, st));
-         else HIP_TRY(hipMemsetAsync(t->sums + 2, 0, sizeof(float), st)));
+    cov_offdiag(s);
+    colsum(s, [&](Job& c, cbas_head_trainer* t) { return c.use_cov ? Cols{t->sq, H2, 1, t->sums + 2} : Cols{}; });     // sums[2] = covariance penalty
+    s.each([&](Job& c, cbas_head_trainer* t) -> int {
+        if (c.use_cov) LAUNCH_TRY(gemm_nt(t->Rc, H2, t->Gm, H2, nullptr, t->dlat_cov, H2, c.B, H2, H2, c.st));
+        else HIP_TRY(hipMemsetAsync(t->sums + 2, 0, sizeof(float), c.st));
+        return CBAS_OK;
+    });
 
     // ---------------- backward ----------------
-    EACH(LAUNCH_TRY(launch_pool_train_bwd(c.pp, c.B, t->attw, t->scores, t->lstm_logits, t->dfinal, c.use_cov ? t->dlat_cov : nullptr,
-                                          t->dhA, t->dlstm, t->dlin, t->part_pool, st)));
+    s.each([&](Job& c, cbas_head_trainer* t) -> int {
+        LAUNCH_TRY(launch_pool_train_bwd(c.pp, c.B, t->attw, t->scores, t->lstm_logits, t->dfinal, c.use_cov ? t->dlat_cov : nullptr,
+                                         t->dhA, t->dlstm, t->dlin, t->part_pool, c.st));
+        return CBAS_OK;
+    });
     // w_att | b_att | gate | att_temp are contiguous in the layout and in part_pool's row
-    COLSUM(true, t->part_pool, c.B, H2 + 12, G + t->o_watt);
-    COLSUM(true, t->dlstm, c.B, C, G + t->o_blin2);
-    COLSUM(true, t->dlin, c.B, C, G + t->o_blin1);
-    EACH(LAUNCH_TRY(launch_transpose_pad(t->dlstm, c.B, C, C, t->dlogT, c.Bp, st));
-         LAUNCH_TRY(launch_transpose_pad(t->latent, c.B, H2, H2, t->latentT, c.Bp, st));
-         LAUNCH_TRY(gemm_nt(t->dlogT, c.Bp, t->latentT, H2, nullptr, G + t->o_wlin2, H2, C, H2, (int)c.Bp, st)));
+    colsum(s, [&](Job& c, cbas_head_trainer* t) { return Cols{t->part_pool, c.B, H2 + 12, t->G + t->o_watt}; });
+    colsum(s, [&](Job& c, cbas_head_trainer* t) { return Cols{t->dlstm, c.B, C, t->G + t->o_blin2}; });
+    colsum(s, [&](Job& c, cbas_head_trainer* t) { return Cols{t->dlin, c.B, C, t->G + t->o_blin1}; });
+    s.each([&](Job& c, cbas_head_trainer* t) -> int {
+        LAUNCH_TRY(launch_transpose_pad(t->dlstm, c.B, C, C, t->dlogT, c.Bp, c.st));
+        LAUNCH_TRY(launch_transpose_pad(t->latent, c.B, H2, H2, t->latentT, c.Bp, c.st));
+        LAUNCH_TRY(gemm_nt(t->dlogT, c.Bp, t->latentT, H2, nullptr, t->G + t->o_wlin2, H2, C, H2, (int)c.Bp, c.st));
+        return CBAS_OK;
+    });
 
     for (int l = NL - 1; l >= 0; --l) {
         const int in = l == 0 ? L0 : H2;
-        EACH(LAUNCH_TRY(launch_lstm_train_bwd(c.dh_cur, t->act[l], t->cst[l], t->hout[l], P + t->o_whh[l], h, T, c.B, t->dgin, t->hprev, st)));
-        COLSUM(true, t->dgin, c.R, 8 * h, G + t->o_bih[l]);
-        ADD_VEC(G + t->o_bih[l], nullptr, G + t->o_bhh[l], 8 * h);
-        EACH(const float* xin = l == 0 ? t->xl : t->hout[l - 1];
-             LAUNCH_TRY(launch_transpose_pad(t->dgin, c.R, 8 * h, 8 * h, t->dginT, c.Rp, st));
-             LAUNCH_TRY(launch_transpose_pad(t->hprev, c.R, H2, H2, t->hprevT, c.Rp, st));
-             LAUNCH_TRY(launch_transpose_pad(xin, c.R, in, in, t->xinT, c.Rp, st));
-             for (int dir = 0; dir < 2; ++dir)
-                 LAUNCH_TRY(gemm_nt_longk(t->dginT + (int64_t)dir * 4 * h * c.Rp, t->hprevT + (int64_t)dir * h * c.Rp, h,
-                                          G + t->o_whh[l] + (int64_t)dir * 4 * h * h, 4 * h, h, c.Rp, t->skbuf, st));
-             LAUNCH_TRY(gemm_nt_longk(t->dginT, t->xinT, in, G + t->o_wih[l], 8 * h, in, c.Rp, t->skbuf, st));
-             LAUNCH_TRY(launch_transpose_pad(P + t->o_wih[l], 8 * h, in, in, t->wihT, 8 * h, st));   /* [in][8h] */
-             LAUNCH_TRY(gemm_nt(t->dgin, 8 * h, t->wihT, in, nullptr, l == 0 ? t->dxl : c.dh_next, in, c.R, in, 8 * h, st));
-             float* tmp = c.dh_cur; c.dh_cur = c.dh_next; c.dh_next = tmp);
+        s.each([&](Job& c, cbas_head_trainer* t) -> int {
+            LAUNCH_TRY(launch_lstm_train_bwd(c.dh_cur, t->act[l], t->cst[l], t->hout[l], t->P + t->o_whh[l], h, T, c.B, t->dgin, t->hprev, c.st));
+            return CBAS_OK;
+        });
+        colsum(s, [&](Job& c, cbas_head_trainer* t) { return Cols{t->dgin, c.R, 8 * h, t->G + t->o_bih[l]}; });
+        add_lstm_biases(s, l, 1);
+        s.each([&](Job& c, cbas_head_trainer* t) -> int {
+            const float* xin = l == 0 ? t->xl : t->hout[l - 1];
+            LAUNCH_TRY(launch_transpose_pad(t->dgin, c.R, 8 * h, 8 * h, t->dginT, c.Rp, c.st));
+            LAUNCH_TRY(launch_transpose_pad(t->hprev, c.R, H2, H2, t->hprevT, c.Rp, c.st));
+            LAUNCH_TRY(launch_transpose_pad(xin, c.R, in, in, t->xinT, c.Rp, c.st));
+            for (int dir = 0; dir < 2; ++dir)
+                LAUNCH_TRY(gemm_nt_longk(t->dginT + (int64_t)dir * 4 * h * c.Rp, t->hprevT + (int64_t)dir * h * c.Rp, h,
+                                         t->G + t->o_whh[l] + (int64_t)dir * 4 * h * h, 4 * h, h, c.Rp, t->skbuf, c.st));
+            LAUNCH_TRY(gemm_nt_longk(t->dginT, t->xinT, in, t->G + t->o_wih[l], 8 * h, in, c.Rp, t->skbuf, c.st));
+            LAUNCH_TRY(launch_transpose_pad(t->P + t->o_wih[l], 8 * h, in, in, t->wihT, 8 * h, c.st));      // [in][8h]
+            LAUNCH_TRY(gemm_nt(t->dgin, 8 * h, t->wihT, in, nullptr, l == 0 ? t->dxl : c.dh_next, in, c.R, in, 8 * h, c.st));
+            float* tmp = c.dh_cur; c.dh_cur = c.dh_next; c.dh_next = tmp;
+            return CBAS_OK;
+        });
     }
     // centring (classifier_head.py:166-167) is its own adjoint: d x = d xc - mean_t(d xc)
-    EACH(LAUNCH_TRY(launch_head_centre(t->dxl, c.B, T, L0, st)));
-    GELU_DROPOUT(t->Z, t->dxl, 1);                                                              // dxl is now dZ
-    COLSUM(true, t->dxl, c.R, L0, G + t->o_blin0);
-    EACH(LAUNCH_TRY(launch_transpose_pad(t->dxl, c.R, L0, L0, t->dZT, c.Rp, st));
-         LAUNCH_TRY(launch_transpose_pad(t->aug, c.R, F, F, t->augT, c.Rp, st));
-         LAUNCH_TRY(gemm_nt_longk(t->dZT, t->augT, F, G + t->o_wlin0, L0, F, c.Rp, t->skbuf, st));
-         LAUNCH_TRY(launch_transpose_pad(P + t->o_wlin0, L0, F, F, t->wlin0T, L0, st));         /* [F][L0] */
-         LAUNCH_TRY(gemm_nt(t->dxl, L0, t->wlin0T, F, nullptr, t->daug, F, c.R, F, L0, st));
-         LAUNCH_TRY(launch_train_expand_bwd(c.ep, c.B, t->Y, t->daug, t->dlin, t->dproj, t->part_exp, st)));
+    s.each([&](Job& c, cbas_head_trainer* t) -> int { LAUNCH_TRY(launch_head_centre(t->dxl, c.B, T, L0, c.st)); return CBAS_OK; });
+    gelu_dropout(s, 1);                                                                         // dxl is now dZ
+    colsum(s, [&](Job& c, cbas_head_trainer* t) { return Cols{t->dxl, c.R, L0, t->G + t->o_blin0}; });
+    s.each([&](Job& c, cbas_head_trainer* t) -> int {
+        LAUNCH_TRY(launch_transpose_pad(t->dxl, c.R, L0, L0, t->dZT, c.Rp, c.st));
+        LAUNCH_TRY(launch_transpose_pad(t->aug, c.R, F, F, t->augT, c.Rp, c.st));
+        LAUNCH_TRY(gemm_nt_longk(t->dZT, t->augT, F, t->G + t->o_wlin0, L0, F, c.Rp, t->skbuf, c.st));
+        LAUNCH_TRY(launch_transpose_pad(t->P + t->o_wlin0, L0, F, F, t->wlin0T, L0, c.st));      // [F][L0]
+        LAUNCH_TRY(gemm_nt(t->dxl, L0, t->wlin0T, F, nullptr, t->daug, F, c.R, F, L0, c.st));
+        LAUNCH_TRY(launch_train_expand_bwd(c.ep, c.B, t->Y, t->daug, t->dlin, t->dproj, t->part_exp, c.st));
+        return CBAS_OK;
+    });
     // b_bott | ln_w | ln_b are contiguous in the layout and in part_exp's row
-    COLSUM(true, t->part_exp, c.B, 3 * F, G + t->o_bbott);
-    EACH(LAUNCH_TRY(launch_transpose_pad(t->dproj, c.R, NP, NP, t->dprojT, c.Rp, st));
-         LAUNCH_TRY(launch_transpose_pad(c.x, c.R, I, I, t->XT, c.Rp, st));
-         LAUNCH_TRY(gemm_nt_longk(t->dprojT, t->XT, I, G + t->o_wproj, NP, I, c.Rp, t->skbuf, st)));
+    colsum(s, [&](Job& c, cbas_head_trainer* t) { return Cols{t->part_exp, c.B, 3 * F, t->G + t->o_bbott}; });
+    s.each([&](Job& c, cbas_head_trainer* t) -> int {
+        LAUNCH_TRY(launch_transpose_pad(t->dproj, c.R, NP, NP, t->dprojT, c.Rp, c.st));
+        LAUNCH_TRY(launch_transpose_pad(c.x, c.R, I, I, t->XT, c.Rp, c.st));
+        LAUNCH_TRY(gemm_nt_longk(t->dprojT, t->XT, I, t->G + t->o_wproj, NP, I, c.Rp, t->skbuf, c.st));
+        return CBAS_OK;
+    });
 
-    if (update) {
-        if (k == 1) {
-            EACH(LAUNCH_TRY(launch_adam_step(P, G, t->M, t->V, t->n_train, t->tcfg.lr, t->tcfg.weight_decay, t->o_gate, t->o_gate + 1,
-                                             1e-3f /* cbas.py:1307 */, t->step + 1, st)));
-        } else {
-            AdamBatch b{};
-            b.wd_special = 1e-3f;                                                               // cbas.py:1307
-            FILL(b.p[j] = P; b.g[j] = G; b.m[j] = t->M; b.v[j] = t->V; b.n[j] = t->n_train; b.wd[j] = t->tcfg.weight_decay;
-                 b.wd_lo[j] = t->o_gate; b.wd_hi[j] = t->o_gate + 1;
-                 adam_bias_corrections(t->tcfg.lr, t->step + 1, &b.lr_c1[j], &b.inv_sqrt_c2[j]));
-            LAUNCH_TRY(launch_adam_step_multi(b, k, lead));
-        }
+    if (update && adam(s) == CBAS_OK)
         for (int j = 0; j < k; ++j) jobs[j].t->step += 1;
-    }
-    TRY_RC(fork());
-    return CBAS_OK;
-#undef GELU_DROPOUT
-#undef ADD_VEC
-#undef COLSUM
-#undef FILL
-#undef EACH
-#undef PER_JOB
-#undef TRY_RC
+    if (s.rc == CBAS_OK) s.rc = s.fork();
+    return s.rc;
 }
 
 void read_loss(const float* s, float* loss_host) {

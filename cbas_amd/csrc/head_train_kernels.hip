@@ -816,8 +816,8 @@ T max_of(const T* v, int k) {
 }  // namespace
 
 int launch_gelu_dropout_multi(const GeluBatch& b, int k, int backward, hipStream_t st) {
-    const int64_t n = max_of(b.n, k);
     if (k < 1 || k > TRAIN_MULTI_MAX) return -1;
+    const int64_t n = max_of(b.n, k);
     if (n == 0) return 0;
     const dim3 grid((unsigned)((n + 255) / 256), (unsigned)k);
     if (backward) hipLaunchKernelGGL(gelu_dropout_bwd_multi_kernel, grid, dim3(256), 0, st, b);
@@ -825,8 +825,8 @@ int launch_gelu_dropout_multi(const GeluBatch& b, int k, int backward, hipStream
     return CHECK_LAUNCH();
 }
 int launch_ce_multi(const CeBatch& b, int k, int grad, hipStream_t st) {
-    const int64_t n = max_of(b.n, k);
     if (k < 1 || k > TRAIN_MULTI_MAX) return -1;
+    const int64_t n = max_of(b.n, k);
     if (n == 0) return 0;
     const dim3 grid((unsigned)((n + 127) / 128), (unsigned)k);
     if (grad) hipLaunchKernelGGL(ce_grad_multi_kernel, grid, dim3(128), 0, st, b);
@@ -834,15 +834,15 @@ int launch_ce_multi(const CeBatch& b, int k, int grad, hipStream_t st) {
     return CHECK_LAUNCH();
 }
 int launch_cov_offdiag_multi(const CovBatch& b, int k, hipStream_t st) {
-    const int n = max_of(b.n, k);
     if (k < 1 || k > TRAIN_MULTI_MAX) return -1;
+    const int n = max_of(b.n, k);
     if (n == 0) return 0;
     hipLaunchKernelGGL(cov_offdiag_multi_kernel, dim3((unsigned)n, (unsigned)k), dim3(64), 0, st, b);
     return CHECK_LAUNCH();
 }
 int launch_colsum_multi(const ColsumBatch& b, int k, hipStream_t st) {
-    const int cols = max_of(b.cols, k);
     if (k < 1 || k > TRAIN_MULTI_MAX) return -1;
+    const int cols = max_of(b.cols, k);
     if (cols == 0) return 0;
     const int chunks = COLSUM_CHUNKS;
     hipLaunchKernelGGL(colsum_stage1_multi_kernel, dim3((cols + 63) / 64, chunks, (unsigned)k), dim3(64), 0, st, b, chunks);
@@ -850,15 +850,15 @@ int launch_colsum_multi(const ColsumBatch& b, int k, hipStream_t st) {
     return CHECK_LAUNCH();
 }
 int launch_add_vec_multi(const VecBatch& v, int k, hipStream_t st) {
-    const int n = max_of(v.n, k);
     if (k < 1 || k > TRAIN_MULTI_MAX) return -1;
+    const int n = max_of(v.n, k);
     if (n == 0) return 0;
     hipLaunchKernelGGL(add_vec_multi_kernel, dim3((n + 255) / 256, (unsigned)k), dim3(256), 0, st, v);
     return CHECK_LAUNCH();
 }
 int launch_adam_step_multi(const AdamBatch& a, int k, hipStream_t st) {
-    const int64_t n = max_of(a.n, k);
     if (k < 1 || k > TRAIN_MULTI_MAX) return -1;
+    const int64_t n = max_of(a.n, k);
     if (n == 0) return 0;
     hipLaunchKernelGGL(adam_step_multi_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)k), dim3(256), 0, st, a, 0.9f, 0.999f,
                        1e-8f);

@@ -8,9 +8,10 @@ measured on (4 files x 5 031 rows of width 768, seq_len 31, batch 512, every fra
 Alternated a b a b ..., REPEATS pairs after one warm-up pair, in one process; medians, every sample and the spread
 (max - min) are reported.  The weights of (b) are compared with those of (a), bit for bit.
 
-The time of the trial-batched small kernels against their single-trial forms comes from one kernel trace of its own, without
-counters: this script starts `rocprofv3 --kernel-trace` over `--steps`, a child that takes STEPS solo steps with each of 4
-trainers and then STEPS steps of the 4 together, and sums the kernels' durations by name.
+The time of the small kernels, launched per trainer against once for all four, comes from two kernel traces of their own,
+without counters: this script starts `rocprofv3 --kernel-trace` over `--steps solo`, a child that takes STEPS solo steps with
+each of 4 trainers, and over `--steps together`, a child that takes STEPS steps of the 4 together, and sums the kernels'
+durations by base name.  The phase, not the kernel's name, tells the launches apart.
 
     python scripts/train_trials_rate.py [--out profiles/train_trials.json] [--no-trace]
 """
@@ -51,54 +52,54 @@ def summary(samples):
     return {"median_s": statistics.median(samples), "spread_s": max(samples) - min(samples), "samples_s": samples}
 
 
-def steps_only():
-    """The traced child: STEPS steps of 4 trainers one after another, then STEPS steps of the 4 together."""
+def steps_only(phase):
+    """The traced child: STEPS steps of 4 trainers one after another ("solo") or STEPS steps of the 4 together."""
     hcfg = C.HeadConfig(in_features=DIM, out_features=CLASSES, seq_len=SEQ)
     rows = torch.from_numpy(synth.cls_walk(3, FILES * ROWS, DIM)).cuda()
     rng = np.random.default_rng(1)
     batches = [(torch.from_numpy(rng.integers(0, FILES * ROWS - SEQ, BATCH)), torch.from_numpy(rng.integers(0, CLASSES, BATCH)))
                for _ in range(TRIALS)]
-    solo = [T.HeadTrainer(hcfg, W.synth_head_weights(hcfg, s), "cuda", max_batch=BATCH, seed=s) for s in range(TRIALS)]
-    multi = [T.HeadTrainer(hcfg, W.synth_head_weights(hcfg, s), "cuda", max_batch=BATCH, seed=s) for s in range(TRIALS)]
+    trainers = [T.HeadTrainer(hcfg, W.synth_head_weights(hcfg, s), "cuda", max_batch=BATCH, seed=s) for s in range(TRIALS)]
     for _ in range(STEPS):
-        for t, (f, y) in zip(solo, batches):
-            t.step_rows(rows, f, y, want_loss=False)
+        if phase == "solo":
+            for t, (f, y) in zip(trainers, batches):
+                t.step_rows(rows, f, y, want_loss=False)
+        else:
+            T.step_rows_multi(rows, [(t, f, y) for t, (f, y) in zip(trainers, batches)], want_loss=False)
     torch.cuda.synchronize()
-    for _ in range(STEPS):
-        T.step_rows_multi(rows, [(t, f, y) for t, (f, y) in zip(multi, batches)], want_loss=False)
-    torch.cuda.synchronize()
-    for t in solo + multi:
+    for t in trainers:
         t.close()
 
 
 def kernel_trace():
-    """{"single": {kernel: [launches, total us]}, "batched": {...}} of the small kernels, from one rocprofv3 kernel trace."""
-    with tempfile.TemporaryDirectory() as td:
-        cmd = ["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", td, "--", sys.executable, os.path.abspath(__file__), "--steps"]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        files = glob.glob(os.path.join(td, "**", "*kernel_trace.csv"), recursive=True)
-        if r.returncode != 0 or not files:
-            return {"error": f"rocprofv3 ended with {r.returncode} and {len(files)} trace file(s)", "stderr_tail": r.stderr[-400:]}
-        out = {"single": {}, "batched": {}}
-        for path in files:
-            with open(path, newline="") as f:
-                for row in csv.DictReader(f):
-                    name = row.get("Kernel_Name", "")
-                    base = next((s for s in SMALL if s + "_kernel" in name or s + "_multi_kernel" in name), None)
-                    if base is None:
-                        continue
-                    kind = "batched" if "_multi_kernel" in name else "single"
-                    n, us = out[kind].get(base, [0, 0.0])
-                    out[kind][base] = [n + 1, us + (int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e3]
-        out["single_total_us_per_step_of_4"] = sum(v[1] for v in out["single"].values()) / STEPS
-        out["batched_total_us_per_step_of_4"] = sum(v[1] for v in out["batched"].values()) / STEPS
-        out["steps"] = STEPS
-        return out
+    """{"solo": {kernel: [launches, total us]}, "together": {...}} of the small kernels, from one rocprofv3 kernel trace per phase."""
+    out = {}
+    for phase in ("solo", "together"):
+        out[phase] = {}
+        with tempfile.TemporaryDirectory() as td:
+            cmd = ["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", td, "--", sys.executable, os.path.abspath(__file__),
+                   "--steps", phase]
+            r = subprocess.run(cmd, capture_output=True, text=True)
+            files = glob.glob(os.path.join(td, "**", "*kernel_trace.csv"), recursive=True)
+            if r.returncode != 0 or not files:
+                return {"error": f"rocprofv3 ({phase}) ended with {r.returncode} and {len(files)} trace file(s)", "stderr_tail": r.stderr[-400:]}
+            for path in files:
+                with open(path, newline="") as f:
+                    for row in csv.DictReader(f):
+                        name = row.get("Kernel_Name", "")
+                        base = next((s for s in SMALL if s + "_kernel" in name or s + "_multi_kernel" in name), None)
+                        if base is None:
+                            continue
+                        n, us = out[phase].get(base, [0, 0.0])
+                        out[phase][base] = [n + 1, us + (int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e3]
+        out[f"{phase}_total_us_per_step_of_4"] = sum(v[1] for v in out[phase].values()) / STEPS
+    out["steps"] = STEPS
+    return out
 
 
 def main():
     if "--steps" in sys.argv:
-        return steps_only()
+        return steps_only(sys.argv[sys.argv.index("--steps") + 1])
     out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None
     dev = torch.device("cuda")
     res = {"shape": {"files": FILES, "rows_per_file": ROWS, "dim": DIM, "seq_len": SEQ, "classes": CLASSES, "batch": BATCH,

@@ -1,8 +1,9 @@
 """The trials of a run trained beside each other (train_lstm_trials, cbas_head_train_step_rows_multi): every trial ends bit
 for bit where the same seed ends alone - through the public function on manifest datasets (all slots busy, a slot reused
 mid-epoch, a two-layer head, early stopping) and through the entry point itself (k = 1, uneven batches with every option of
-the loss and of Adam switched on, a neighbour with huge rows, refusals).  The trial-batched small kernels have no tolerance
-to meet: the reference for each is the single-trial kernel, and equality is exact."""
+the loss and of Adam switched on, the smallest trainer leading, a neighbour with huge rows, refusals).  The trial-batched
+small kernels have no tolerance to meet: the reference is the same trainer stepped alone, through the single-trial kernels,
+and equality is exact.  The arithmetic itself is held to the float64 oracle and the reference fixtures by tests/test_gpu_train.py."""
 import ctypes as C
 import threading
 
@@ -191,6 +192,25 @@ def test_uneven_trainers_in_one_call_equal_their_own_steps():
     assert step_rows_multi(rows, [(t, f, y) for t, (f, y) in zip(together, batches)], want_loss=False) is None
     for j in range(3):
         assert_same_state(state_of(together[j]), state_of(alone[j]))
+    for t in alone + together:
+        t.close()
+
+
+def test_the_smallest_trainer_leads_and_the_larger_ones_are_masked():
+    """1, 37 and 64 windows in that order: every table's grid is sized by the last entry and must mask the others, and
+    trainer 0 - the leading stream - is the one without the covariance penalty, so its entries in the `cov_offdiag` table and
+    in two of the column-sum tables have the count 0."""
+    from cbas_amd.train import step_rows_multi
+    hcfg = CFG.HeadConfig(in_features=768, out_features=5, lstm_hidden_size=32, lstm_layers=2, use_acceleration=False)
+    opts = dict(lr=1e-3, weight_decay=1e-2, label_smoothing=0.1, class_weights=[0.5, 1.0, 2.0, 1.5, 0.25])
+    rows, batches = store_and_batches([1, 37, 64])
+    alone, together = [make_trainer(hcfg, s, **opts) for s in (1, 2, 3)], [make_trainer(hcfg, s, **opts) for s in (1, 2, 3)]
+    want = [[t.step_rows(rows, f, y) for _ in range(2)] for t, (f, y) in zip(alone, batches)]
+    got = [step_rows_multi(rows, [(t, f, y) for t, (f, y) in zip(together, batches)]) for _ in range(2)]
+    for j in range(3):
+        assert [got[0][j], got[1][j]] == want[j], j
+        assert_same_state(state_of(together[j]), state_of(alone[j]))
+    assert want[0][0][2] == 0.0 and want[2][0][2] > 0.0 and all(np.isfinite(l[0]) for w in want for l in w)
     for t in alone + together:
         t.close()
 
