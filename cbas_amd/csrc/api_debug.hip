@@ -901,3 +901,218 @@ extern "C" int cbas_debug_rows_run(const cbas_debug_rows_args* a) {
     if (counter) HIP_TRY(hipMemcpy(a->counter, counter, 4, hipMemcpyDeviceToHost));
     return CBAS_OK;
 }
+
+// ---- tests: one launch of a classifier-head kernel (the exact-fp32 GEMM, the small training kernels) on host operands ----
+namespace {
+struct HeadNeed { int64_t in[4] = {0, 0, 0, 0}, out[3] = {0, 0, 0}; bool in_opt[4] = {false, false, false, false}; };
+
+// bytes entry e's launch reads (in) and writes (out); returns a message for a shape the launcher would mis-handle
+const char* head_entry_need(int op, bool multi, const cbas_debug_head_entry& e, HeadNeed* nd) {
+    const int64_t n = e.n;
+    if (n < (multi ? 0 : 1)) return "n below 1 (a trial-batched entry: below 0)";
+    if (n > 0x7fffffff) return "n beyond 2^31 - 1";
+    switch (op) {
+        case CBAS_DEBUG_HEAD_TRANSPOSE_PAD:
+            if (e.cols < 1 || e.ld < e.cols || e.rows_pad < n) return "transpose_pad: cols >= 1, ld >= cols, rows_pad >= rows";
+            nd->in[0] = ((n - 1) * e.ld + e.cols) * 4;
+            nd->out[0] = (int64_t)e.cols * e.rows_pad * 4;
+            break;
+        case CBAS_DEBUG_HEAD_GELU_DROPOUT_FWD:
+        case CBAS_DEBUG_HEAD_GELU_DROPOUT_BWD:
+            if (e.thr > (1u << 24)) return "thr beyond 2^24";
+            nd->in[0] = n * 4; nd->out[0] = n * 4;
+            break;
+        case CBAS_DEBUG_HEAD_CE_TERMS:
+        case CBAS_DEBUG_HEAD_CE_GRAD:
+            if (e.C < 1 || e.C > 64) return "C outside 1 .. 64";
+            nd->in[0] = n * e.C * 4; nd->in[1] = n * 4; nd->in[2] = (int64_t)e.C * 4; nd->in_opt[2] = true;
+            if (op == CBAS_DEBUG_HEAD_CE_GRAD) { nd->in[3] = 8; nd->out[0] = n * e.C * 4; }
+            else nd->out[0] = n * 8;
+            break;
+        case CBAS_DEBUG_HEAD_COV_OFFDIAG:
+            if (n > 4096) return "cov_offdiag: n beyond 4096";
+            nd->in[0] = n * n * 4; nd->out[0] = n * n * 4; nd->out[1] = n * 4;
+            break;
+        case CBAS_DEBUG_HEAD_SUB_COLMEAN:
+            if (e.cols < 1) return "sub_colmean: cols >= 1";
+            nd->in[0] = n * e.cols * 4; nd->in[1] = (int64_t)e.cols * 4; nd->out[0] = n * e.cols * 4;
+            break;
+        case CBAS_DEBUG_HEAD_COLSUM:
+            if (e.cols < (multi ? 0 : 1) || e.ld < e.cols) return "colsum: cols >= 1 (trial-batched: >= 0), ld >= cols";
+            if (multi && e.scale != 1.0f) return "the trial-batched column sum has no scale";
+            if (multi && e.cols > 0 && n < 1) return "colsum: rows >= 1";
+            nd->in[0] = n > 0 && e.cols > 0 ? ((n - 1) * e.ld + e.cols) * 4 : 0;
+            nd->out[0] = (int64_t)COLSUM_CHUNKS * e.cols * 4; nd->out[1] = (int64_t)e.cols * 4;
+            break;
+        case CBAS_DEBUG_HEAD_ADD_VEC:
+            nd->in[0] = n * 4; nd->in[1] = n * 4; nd->in_opt[1] = true; nd->out[0] = n * 4;
+            break;
+        case CBAS_DEBUG_HEAD_ADAM:
+            if (e.step < 1) return "adam: step >= 1";
+            nd->in[0] = n * 4; nd->out[0] = nd->out[1] = nd->out[2] = n * 4;
+            break;
+        default: return "op";
+    }
+    return nullptr;
+}
+}  // namespace
+
+extern "C" int cbas_debug_head_run(const cbas_debug_head_args* a) {
+    if (!a || a->struct_bytes != (int64_t)sizeof(cbas_debug_head_args) || a->entry_bytes != (int64_t)sizeof(cbas_debug_head_entry))
+        return cbas_fail(CBAS_EINVAL, "cbas_debug_head_args: struct_bytes %lld / entry_bytes %lld, library expects %lld / %lld",
+                         a ? (long long)a->struct_bytes : -1ll, a ? (long long)a->entry_bytes : -1ll, (long long)sizeof(cbas_debug_head_args),
+                         (long long)sizeof(cbas_debug_head_entry));
+    const int op = a->op, k = a->k;
+    const bool multi = a->multi != 0;
+    if (op < CBAS_DEBUG_HEAD_GEMM || op > CBAS_DEBUG_HEAD_ADAM) return cbas_fail(CBAS_EINVAL, "op %d", op);
+    if (k < 1 || k > TRAIN_MULTI_MAX || !a->entries) return cbas_fail(CBAS_EINVAL, "k = %d: 1 .. %d entries", k, TRAIN_MULTI_MAX);
+    if (multi && (op == CBAS_DEBUG_HEAD_GEMM || op == CBAS_DEBUG_HEAD_TRANSPOSE_PAD || op == CBAS_DEBUG_HEAD_SUB_COLMEAN))
+        return cbas_fail(CBAS_EINVAL, "op %d has no trial-batched launcher", op);
+    const int ne = multi ? k : 1;
+    const cbas_debug_head_entry* E = a->entries;
+    HeadNeed need[TRAIN_MULTI_MAX];
+    Gemm32Params g{};
+    const bool gemm = op == CBAS_DEBUG_HEAD_GEMM;
+    const int splits = a->splits > 1 ? a->splits : 1;
+    if (gemm) {
+        const int64_t ldw = a->ldw ? a->ldw : a->K, Kt = (int64_t)a->K * splits;
+        g.lda = a->lda; g.ldo = a->ldo; g.M = a->M; g.N = a->N; g.N_alloc = a->N_alloc; g.K = a->K; g.ldw = a->ldw;
+        g.splits = a->splits; g.split_stride = a->split_stride;
+        // launch_gemm_f32's own refusals, before anything is allocated, and what it does not check
+        if (a->M <= 0 || a->M > (1 << 24) || a->N <= 0 || a->N % 4 || a->K < 32 || a->K % 32 || a->N_alloc < a->N || a->lda % 4 || a->ldo % 4 || a->ldw % 4 ||
+            a->splits < 0 || a->splits > 64 || (a->gelu != 0 && a->gelu != 1))
+            return cbas_fail(CBAS_EINVAL, "GEMM: M > 0, N %% 4, K a positive multiple of 32, N_alloc >= N, lda / ldo / ldw %% 4, splits 0 .. 64, gelu 0 / 1");
+        if (a->lda < Kt || ldw < Kt || a->ldo < a->N) return cbas_fail(CBAS_EINVAL, "GEMM: lda / ldw below the k range read, or ldo < N");
+        if (splits > 1 && (E[0].in[2] || a->gelu || a->split_stride % 4 || a->ldo != a->N || a->split_stride < a->M * a->N))
+            return cbas_fail(CBAS_EINVAL, "split-K: no bias, no GELU, ldo = N, split_stride %% 4 == 0 and >= M N");
+        need[0].in[0] = ((a->M - 1) * a->lda + Kt) * 4;
+        need[0].in[1] = ((int64_t)(a->N_alloc - 1) * ldw + Kt) * 4;
+        need[0].in[2] = (int64_t)a->N * 4; need[0].in_opt[2] = true;
+        need[0].out[0] = ((a->M - 1) * a->ldo + a->N) * 4;
+        if (splits > 1) need[0].out[1] = ((splits - 1) * a->split_stride + a->M * a->N) * 4;
+    } else {
+        for (int j = 0; j < ne; ++j) {
+            const char* msg = head_entry_need(op, multi, E[j], &need[j]);
+            if (msg) return cbas_fail(CBAS_EINVAL, "op %d entry %d: %s", op, j, msg);
+            if (op == CBAS_DEBUG_HEAD_ADAM && E[j].wd_special != E[0].wd_special) return cbas_fail(CBAS_EINVAL, "adam: one wd_special per launch");
+        }
+    }
+    for (int j = 0; j < ne; ++j) {
+        for (int i = 0; i < 4; ++i) {
+            const bool absent = !E[j].in[i];
+            if (need[j].in[i] && !(absent && need[j].in_opt[i]) && (absent || E[j].in_bytes[i] < need[j].in[i]))
+                return cbas_fail(CBAS_EINVAL, "op %d entry %d: in[%d] is missing or too small (%lld of %lld bytes)", op, j, i,
+                                 (long long)E[j].in_bytes[i], (long long)need[j].in[i]);
+        }
+        for (int i = 0; i < 3; ++i)
+            if (need[j].out[i] && (!E[j].out[i] || E[j].out_bytes[i] < need[j].out[i]))
+                return cbas_fail(CBAS_EINVAL, "op %d entry %d: out[%d] is missing or too small (%lld of %lld bytes)", op, j, i,
+                                 (long long)E[j].out_bytes[i], (long long)need[j].out[i]);
+    }
+    // labels are indices into cw: checked on the host images before anything is launched
+    if (op == CBAS_DEBUG_HEAD_CE_TERMS || op == CBAS_DEBUG_HEAD_CE_GRAD)
+        for (int j = 0; j < ne; ++j) {
+            const int* lab = static_cast<const int*>(E[j].in[1]);
+            for (int64_t w = 0; w < E[j].n; ++w)
+                if (lab[w] < 0 || lab[w] >= E[j].C) return cbas_fail(CBAS_EINVAL, "ce entry %d: label %d of window %lld outside [0, %d)", j, lab[w], (long long)w, E[j].C);
+        }
+    DevBufs B;
+    char* din[TRAIN_MULTI_MAX][4] = {};
+    char* dout[TRAIN_MULTI_MAX][3] = {};
+    for (int j = 0; j < ne; ++j) {
+        for (int i = 0; i < 4; ++i)
+            if (E[j].in[i] && (need[j].in[i] || need[j].in_opt[i])) {
+                HIP_TRY(B.alloc(&din[j][i], (size_t)E[j].in_bytes[i]));
+                if (E[j].in_bytes[i] > 0) HIP_TRY(hipMemcpy(din[j][i], E[j].in[i], (size_t)E[j].in_bytes[i], hipMemcpyHostToDevice));
+            }
+        for (int i = 0; i < 3; ++i)
+            if (E[j].out[i] && E[j].out_bytes[i] > 0) {
+                HIP_TRY(B.alloc(&dout[j][i], (size_t)E[j].out_bytes[i]));
+                HIP_TRY(hipMemcpy(dout[j][i], E[j].out[i], (size_t)E[j].out_bytes[i], hipMemcpyHostToDevice));
+            }
+    }
+    const auto fin = [&](int j, int i) { return reinterpret_cast<const float*>(din[j][i]); };
+    const auto fout = [&](int j, int i) { return reinterpret_cast<float*>(dout[j][i]); };
+    const cbas_debug_head_entry& e0 = E[0];
+    int rc = -1;
+    if (gemm) {
+        g.A = fin(0, 0); g.W = fin(0, 1); g.bias = fin(0, 2);
+        g.out = splits > 1 ? fout(0, 1) : fout(0, 0);
+        rc = launch_gemm_f32(g, a->gelu, 0);
+        if (!rc && splits > 1) rc = launch_splitk_reduce(fout(0, 1), splits, a->split_stride, a->M * a->N, fout(0, 0), 0);
+    } else if (!multi) {
+        switch (op) {
+            case CBAS_DEBUG_HEAD_TRANSPOSE_PAD: rc = launch_transpose_pad(fin(0, 0), e0.n, e0.cols, e0.ld, fout(0, 0), e0.rows_pad, 0); break;
+            case CBAS_DEBUG_HEAD_GELU_DROPOUT_FWD: rc = launch_gelu_dropout(fin(0, 0), fout(0, 0), e0.n, e0.key, e0.thr, e0.scale, 0, 0); break;
+            case CBAS_DEBUG_HEAD_GELU_DROPOUT_BWD: rc = launch_gelu_dropout(fin(0, 0), fout(0, 0), e0.n, e0.key, e0.thr, e0.scale, 1, 0); break;
+            case CBAS_DEBUG_HEAD_CE_TERMS:
+                rc = launch_ce_terms(fin(0, 0), reinterpret_cast<const int*>(din[0][1]), fin(0, 2), e0.n, e0.C, e0.eps, fout(0, 0), 0);
+                break;
+            case CBAS_DEBUG_HEAD_CE_GRAD:
+                rc = launch_ce_grad(fin(0, 0), reinterpret_cast<const int*>(din[0][1]), fin(0, 2), fin(0, 3), e0.n, e0.C, e0.eps, fout(0, 0), 0);
+                break;
+            case CBAS_DEBUG_HEAD_COV_OFFDIAG: rc = launch_cov_offdiag(fin(0, 0), (int)e0.n, e0.cscale, e0.gscale, fout(0, 0), fout(0, 1), 0); break;
+            case CBAS_DEBUG_HEAD_SUB_COLMEAN: rc = launch_sub_colmean(fin(0, 0), fin(0, 1), e0.n, e0.cols, fout(0, 0), 0); break;
+            case CBAS_DEBUG_HEAD_COLSUM: rc = launch_colsum(fin(0, 0), e0.n, e0.cols, e0.ld, e0.scale, fout(0, 0), fout(0, 1), 0); break;
+            case CBAS_DEBUG_HEAD_ADD_VEC: rc = launch_add_vec(fin(0, 0), fin(0, 1), fout(0, 0), (int)e0.n, 0); break;
+            case CBAS_DEBUG_HEAD_ADAM:
+                rc = launch_adam_step(fout(0, 0), fin(0, 0), fout(0, 1), fout(0, 2), e0.n, e0.lr, e0.wd, e0.wd_lo, e0.wd_hi, e0.wd_special, e0.step, 0);
+                break;
+        }
+    } else {
+        switch (op) {
+            case CBAS_DEBUG_HEAD_GELU_DROPOUT_FWD:
+            case CBAS_DEBUG_HEAD_GELU_DROPOUT_BWD: {
+                GeluBatch b{};
+                for (int j = 0; j < k; ++j) { b.Z[j] = fin(j, 0); b.io[j] = fout(j, 0); b.n[j] = E[j].n; b.key[j] = E[j].key; b.thr[j] = E[j].thr; b.scale[j] = E[j].scale; }
+                rc = launch_gelu_dropout_multi(b, k, op == CBAS_DEBUG_HEAD_GELU_DROPOUT_BWD, 0);
+                break;
+            }
+            case CBAS_DEBUG_HEAD_CE_TERMS:
+            case CBAS_DEBUG_HEAD_CE_GRAD: {
+                CeBatch b{};
+                for (int j = 0; j < k; ++j) {
+                    b.logits[j] = fin(j, 0); b.labels[j] = reinterpret_cast<const int*>(din[j][1]); b.cw[j] = fin(j, 2); b.sums[j] = fin(j, 3);
+                    b.out[j] = fout(j, 0); b.n[j] = E[j].n; b.C[j] = E[j].C; b.eps[j] = E[j].eps;
+                }
+                rc = launch_ce_multi(b, k, op == CBAS_DEBUG_HEAD_CE_GRAD, 0);
+                break;
+            }
+            case CBAS_DEBUG_HEAD_COV_OFFDIAG: {
+                CovBatch b{};
+                for (int j = 0; j < k; ++j) { b.cov[j] = fin(j, 0); b.G[j] = fout(j, 0); b.sq[j] = fout(j, 1); b.n[j] = (int)E[j].n; b.cscale[j] = E[j].cscale; b.gscale[j] = E[j].gscale; }
+                rc = launch_cov_offdiag_multi(b, k, 0);
+                break;
+            }
+            case CBAS_DEBUG_HEAD_COLSUM: {
+                ColsumBatch b{};
+                for (int j = 0; j < k; ++j) { b.src[j] = fin(j, 0); b.tmp[j] = fout(j, 0); b.dst[j] = fout(j, 1); b.rows[j] = E[j].n; b.ld[j] = E[j].ld; b.cols[j] = E[j].cols; }
+                rc = launch_colsum_multi(b, k, 0);
+                break;
+            }
+            case CBAS_DEBUG_HEAD_ADD_VEC: {
+                VecBatch b{};
+                for (int j = 0; j < k; ++j) { b.a[j] = fin(j, 0); b.b[j] = fin(j, 1); b.out[j] = fout(j, 0); b.n[j] = (int)E[j].n; }
+                rc = launch_add_vec_multi(b, k, 0);
+                break;
+            }
+            case CBAS_DEBUG_HEAD_ADAM: {
+                AdamBatch b{};
+                for (int j = 0; j < k; ++j) {
+                    b.p[j] = fout(j, 0); b.g[j] = fin(j, 0); b.m[j] = fout(j, 1); b.v[j] = fout(j, 2); b.n[j] = E[j].n; b.wd_lo[j] = E[j].wd_lo; b.wd_hi[j] = E[j].wd_hi;
+                    adam_bias_corrections(E[j].lr, E[j].step, &b.lr_c1[j], &b.inv_sqrt_c2[j]);
+                    b.wd[j] = E[j].wd;
+                }
+                b.wd_special = e0.wd_special;
+                rc = launch_adam_step_multi(b, k, 0);
+                break;
+            }
+        }
+    }
+    if (rc) return cbas_fail(CBAS_EINVAL, "head kernel launch failed (op %d, multi %d: rc=%d)", op, (int)multi, rc);
+    HIP_TRY(hipDeviceSynchronize());
+    for (int j = 0; j < ne; ++j)
+        for (int i = 0; i < 3; ++i)
+            if (E[j].out[i] && E[j].out_bytes[i] > 0 && dout[j][i]) HIP_TRY(hipMemcpy(E[j].out[i], dout[j][i], (size_t)E[j].out_bytes[i], hipMemcpyDeviceToHost));
+    return CBAS_OK;
+}

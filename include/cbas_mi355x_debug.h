@@ -200,6 +200,65 @@ typedef struct cbas_debug_rows_args {
 } cbas_debug_rows_args;
 int cbas_debug_rows_run(const cbas_debug_rows_args* a);
 
+/* Tests: ONE launch of a classifier-head kernel with an exact or tightly derivable reference on host operands
+ * (tests/test_gpu_head_kernels_reference.py compares it with the references of oracle/kernel_ref.py): the exact-fp32 GEMM of
+ * gemm_f32.hip (plain, fused GELU, split-K + its reduction) and the element-wise, reduction and optimiser kernels of
+ * head_train_kernels.hip, single-trial or trial-batched (`_multi`).  The harness uploads every in[] image and the caller's
+ * pre-filled out[] images (whole, out_bytes each: what the launch does not own is the caller's canary), runs exactly one
+ * launcher on the default stream (GEMM with splits > 1: launch_gemm_f32 into the partial image, then launch_splitk_reduce),
+ * synchronises and copies the out[] images back.  It refuses (CBAS_EINVAL, nothing launched): whatever launch_gemm_f32 rejects,
+ * K < 32, lda / ldw below the k range read, ldo < N, split-K with ldo != N or split_stride < M N; k outside 1 ..
+ * TRAIN_MULTI_MAX (8); multi = 1 for an op without a `_multi` launcher; a size below 1 (multi = 1: below 0); C outside 1 .. 64;
+ * a label outside [0, C); rows_pad < rows; ld < cols; a trial-batched column sum with scale != 1; trial-batched Adam entries
+ * whose wd_special differ; step < 1; and any image that is missing or smaller than what the launch reads or writes.
+ *   op                launcher (multi = 1)                          in[0..3]                                   out[0..2]
+ *   GEMM              launch_gemm_f32 (+ launch_splitk_reduce)      A [M][lda], W [N_alloc][ldw], bias [N] / -  result [M][ldo], partial (splits > 1)
+ *   TRANSPOSE_PAD     launch_transpose_pad                          src [n][ld]                                dst [cols][rows_pad]
+ *   GELU_DROPOUT_FWD  launch_gelu_dropout (.._multi) backward 0     Z [n]                                      io [n]
+ *   GELU_DROPOUT_BWD  ... backward 1                                Z [n]                                      io [n] (d in, d out)
+ *   CE_TERMS          launch_ce_terms (launch_ce_multi grad 0)      logits [n][C], labels [n] int32, cw [C] / - terms [n][2]
+ *   CE_GRAD           launch_ce_grad (launch_ce_multi grad 1)       ..., in[3] sums [2]                        dlogits [n][C]
+ *   COV_OFFDIAG       launch_cov_offdiag (.._multi)                 cov [n][n]                                 G [n][n], sq [n]
+ *   SUB_COLMEAN       launch_sub_colmean                            src [n][cols], colsum [cols]               dst [n][cols]
+ *   COLSUM            launch_colsum (.._multi: scale 1)             src [n][ld]                                tmp [64][cols], dst [cols]
+ *   ADD_VEC           launch_add_vec (.._multi)                     a [n], b [n] / - (copy)                    out [n]
+ *   ADAM              launch_adam_step (.._multi)                   g [n]                                      p [n], m [n], v [n]
+ * n is the entry's element / window / row count.  multi = 0 runs the single-trial launcher on entry 0; multi = 1 runs the
+ * `_multi` launcher on all k entries, which may differ in size (0 included: such an entry takes no part, its images may be
+ * absent, and an absent image reaches the launcher's table as a null pointer - the kernels touch no entry past its count). */
+enum {
+    CBAS_DEBUG_HEAD_GEMM = 0, CBAS_DEBUG_HEAD_TRANSPOSE_PAD = 1, CBAS_DEBUG_HEAD_GELU_DROPOUT_FWD = 2,
+    CBAS_DEBUG_HEAD_GELU_DROPOUT_BWD = 3, CBAS_DEBUG_HEAD_CE_TERMS = 4, CBAS_DEBUG_HEAD_CE_GRAD = 5,
+    CBAS_DEBUG_HEAD_COV_OFFDIAG = 6, CBAS_DEBUG_HEAD_SUB_COLMEAN = 7, CBAS_DEBUG_HEAD_COLSUM = 8, CBAS_DEBUG_HEAD_ADD_VEC = 9,
+    CBAS_DEBUG_HEAD_ADAM = 10
+};
+typedef struct cbas_debug_head_entry {
+    int64_t n;                   /* elements / windows / rows (see the table) */
+    int64_t rows_pad, ld;        /* TRANSPOSE_PAD; row stride of src (TRANSPOSE_PAD, COLSUM) */
+    int64_t wd_lo, wd_hi;        /* ADAM: [wd_lo, wd_hi) decays with wd_special */
+    uint64_t key;                /* GELU_DROPOUT_*: the dropout stream's key */
+    int cols, C, step;
+    uint32_t thr;                /* GELU_DROPOUT_*: keep <=> top 24 hash bits >= thr */
+    float eps;                   /* CE_*: label smoothing */
+    float scale;                 /* GELU_DROPOUT_*: 1 / (1 - p); COLSUM: the factor on the sums */
+    float cscale, gscale;        /* COV_OFFDIAG */
+    float lr, wd, wd_special;    /* ADAM */
+    const void* in[4];
+    int64_t in_bytes[4];
+    void* out[3];                /* in / out */
+    int64_t out_bytes[3];
+} cbas_debug_head_entry;
+typedef struct cbas_debug_head_args {
+    int64_t struct_bytes;        /* sizeof(cbas_debug_head_args): a mismatch is rejected */
+    int64_t entry_bytes;         /* sizeof(cbas_debug_head_entry): likewise */
+    int op, multi, k;            /* k entries (GEMM, TRANSPOSE_PAD, SUB_COLMEAN: entry 0 holds the images) */
+    int gelu, splits;            /* GEMM */
+    int N, N_alloc, K;           /* GEMM (K: the k range of ONE split) */
+    int64_t M, lda, ldw, ldo, split_stride;
+    const cbas_debug_head_entry* entries;
+} cbas_debug_head_args;
+int cbas_debug_head_run(const cbas_debug_head_args* a);
+
 /* Root-cause probe (round 5): run a kernel from a separately built code object IN PLACE of the library's head_expand_kernel
  * on this handle (same grid, block, dynamic LDS and arguments: scripts/probes/expand_r4/expand_r4.hip has the signature).
  * hsaco_path = NULL restores the library's kernel.  scripts/expand_rootcause.py builds instruction-level variants of the

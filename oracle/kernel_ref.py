@@ -3,12 +3,14 @@ exact precision-3 accumulator, the row-wise kernels between the GEMMs (LayerNorm
 producers), and element-wise error bounds derived from where each kernel rounds.
 
 Used by tests/test_gpu_kernel_reference.py (the kernels through cbas_debug_gemm_run / cbas_debug_attention_run),
-tests/test_gpu_rows_reference.py (cbas_debug_rows_run) and tests/test_kernel_reference_bounds.py (the references and
-bounds themselves, on the CPU).
+tests/test_gpu_rows_reference.py (cbas_debug_rows_run), tests/test_gpu_head_kernels_reference.py (the classifier head's
+exact-fp32 GEMM and small training kernels through cbas_debug_head_run) and tests/test_kernel_reference_bounds.py (the
+references and bounds themselves, on the CPU).
 
 Units: u32 = 2^-24 (fp32 unit roundoff), u16 = 2^-11 (fp16).  A bound is a float64 array shaped like the output; a kernel
 output y passes when |y - ref| <= bound everywhere (non-finite y never passes).  Every bound is a sum of the terms its
-docstring names; no term is fitted to measured errors.
+docstring names; no term is fitted to measured errors, except the device math library's budgets in the classifier-head
+section, which are measured as their comment describes.
 """
 from __future__ import annotations
 
@@ -466,6 +468,418 @@ def pool_order_f32(x32: np.ndarray) -> np.ndarray:
     for p in range(hw):
         part[p % 4] = part[p % 4] + x32[:, p]
     return (((part[0] + part[1]) + part[2]) + part[3]) / np.float32(hw)
+
+
+# ---- classifier head: the exact-fp32 GEMM (gemm_f32.hip) and the small training kernels (head_train_kernels.hip) -------
+# Used by tests/test_gpu_head_kernels_reference.py through cbas_debug_head_run.  gemm_f32_kernel issues its MFMAs in the order
+# of vit_f32.hip's kernel (both read fragment chunk kk * 4 + (lane >> 4) of gemm_f32_tile.h's rows and loop kt, kk, e):
+# f32_mfma_k_order is its k order too.
+COLSUM_CHUNKS = 64            # kernels.h
+TRAIN_MULTI_MAX = 8
+ERF_BF_U = 4.0                # common.h erf_bf inside gelu_erf: the arith-3 budget of the encoder's GELU epilogue, u32 (|v| + |y|)
+# Device math library (expf, logf, erff of head_train_kernels.hip).  The ROCm installation's documentation states no ulp
+# figures for them, so each budget comes from a measurement on an MI355X against the float64 reference over the inputs of
+# tests/test_gpu_head_kernels_reference.py, which prints the figure beside the budget.  A figure is what the library adds
+# BEYOND the kernel's own fp32 roundings: from each stored value's error the roundings its bound itemises are taken off first
+# (so nothing is budgeted twice), and the rest is divided by the unit the budget multiplies.  The budget is twice the figure,
+# rounded up to a whole unit, and never below 1: no fp32 function returns better than half an ulp (1 u32 of its result).
+#   GELU_LIB_U   erff and the three roundings inside gelu_erf_lib (x c, 1 + erf, the product); unit u32 (|z| + |gelu z|) scale;
+#                itemised and taken off: the product with scale, u32 |ref|.                          measured 0.74 -> 2
+#   GELU_GRAD_U  erff, expf and the roundings inside gelu_erf_grad; unit u32 |d| scale (1 + |gelu' z|); taken off: the two
+#                products d scale gelu', 2 u32 |ref|.                                                measured 0.75 -> 2
+#   CE_LSE_U     expf and logf in lse = mx + logf(sum expf(z - mx)); unit u32 (1 + |log den|); measured on fl(lse - z_y) (cw
+#                NULL, eps 0); taken off: u32 (|lse| + |lse - z_y| + C).                              measured 0.00 -> 1
+#   CE_P_U       expf in p = expf(z - mx) / den; unit u32 p; measured on p of the classes c != y (cw NULL, eps 0, sums[1] = 1)
+#                against the fp32 argument z - mx; taken off: u32 p (C + 2) (the sum, the division).  measured 0.00 -> 1
+# The two cross-entropy figures are zero because the itemised terms are worst cases (a sum of C terms seldom rounds C times
+# the same way) and cover the library's share as well on these inputs; the budgets are the floor.
+GELU_LIB_U = 2.0
+GELU_GRAD_U = 2.0
+CE_LSE_U = 1.0
+CE_P_U = 1.0
+
+
+def head_gemm_exact(A, W, bias, K: int, splits: int = 1):
+    """launch_gemm_f32 without GELU, bit for bit: per split z the fmaf chain over k = z K + f32_mfma_k_order(K) from +0; the
+    result is the fp32 sum of the partials, z ascending (launch_splitk_reduce), then ONE fp32 addition of the bias (plain GEMM
+    only).  A [M][>= splits K], W [N][>= splits K] fp32 (unread columns are cut off here).  Returns (out fp32, [partials])."""
+    A = np.asarray(A, np.float32)
+    W = np.asarray(W, np.float32)
+    order = f32_mfma_k_order(K)
+    parts = [fmaf_chain(A[:, z * K:(z + 1) * K], W[:, z * K:(z + 1) * K], order) for z in range(splits)]
+    out = parts[0]
+    with np.errstate(over="ignore", invalid="ignore"):
+        for z in range(1, splits):
+            out = (out + parts[z]).astype(np.float32)
+        if bias is not None:
+            out = (out + np.asarray(bias, np.float32)[None, :]).astype(np.float32)
+    return out, parts
+
+
+def gelu64(v) -> np.ndarray:
+    v = np.asarray(v, np.float64)
+    return 0.5 * v * (1.0 + _erf64(v / math.sqrt(2.0)))
+
+
+def gelu_grad64(v) -> np.ndarray:
+    """d/dx gelu(x) = Phi(x) + x phi(x)."""
+    v = np.asarray(v, np.float64)
+    return 0.5 * (1.0 + _erf64(v / math.sqrt(2.0))) + v * np.exp(-0.5 * v * v) / math.sqrt(2.0 * math.pi)
+
+
+def head_gemm_gelu_ref(pre32):
+    """The fused GELU on the EXACT fp32 pre-activation (head_gemm_exact's output): float64 gelu and the bound
+    gemm_epilogue_ref + the GPU tests give EPI_GELU of arith 3 with no accumulator error left: the branch-free erf's
+    ERF_BF_U u32 (|v| + |y|) and the stored value's fp32 rounding."""
+    v = np.asarray(pre32, np.float32).astype(np.float64)
+    y = gelu64(v)
+    return y, ERF_BF_U * U32 * (np.abs(v) + np.abs(y)) + out_rounding(y, "f32")
+
+
+def transpose_pad_ref(src, rows: int, cols: int, rows_pad: int) -> np.ndarray:
+    """dst [cols][rows_pad] = src[:rows, :cols]^T, columns rows .. rows_pad exact +0."""
+    out = np.zeros((cols, rows_pad), np.float32)
+    out[:, :rows] = np.asarray(src, np.float32)[:rows, :cols].T
+    return out
+
+
+def colsum_f32(x, scale):
+    """launch_colsum in its own order, float32: COLSUM_CHUNKS contiguous ranges of ceil(rows / 64) rows, each summed in row
+    order from +0 (tmp [64][cols]; a range past the last row holds +0), the chunks added in order from +0, times scale.
+    Returns (tmp, dst)."""
+    x = np.asarray(x, np.float32)
+    rows, cols = x.shape
+    per = -(-rows // COLSUM_CHUNKS)
+    tmp = np.zeros((COLSUM_CHUNKS, cols), np.float32)
+    for ch in range(COLSUM_CHUNKS):
+        for r in range(ch * per, min(ch * per + per, rows)):
+            tmp[ch] = tmp[ch] + x[r]
+    s = np.zeros(cols, np.float32)
+    for ch in range(COLSUM_CHUNKS):
+        s = s + tmp[ch]
+    return tmp, (s * np.float32(scale)).astype(np.float32)
+
+
+def colsum_ref(x, scale):
+    """float64 column sums times scale, and the independent bound (rows + chunks) u32 sum |x| |scale|: no value passes
+    through more than ceil(rows / 64) + 64 additions and one product."""
+    x = np.asarray(x, np.float64)
+    sc = float(np.float32(scale))
+    return x.sum(0) * sc, (x.shape[0] + COLSUM_CHUNKS) * U32 * np.abs(x).sum(0) * abs(sc) + 2.0 ** -149
+
+
+def sub_colmean_f32(src, colsum) -> np.ndarray:
+    """src - colsum[c] / float(rows): one IEEE division and one subtraction per element (no fast-math in the build)."""
+    src = np.asarray(src, np.float32)
+    return (src - (np.asarray(colsum, np.float32) / np.float32(src.shape[0]))[None, :]).astype(np.float32)
+
+
+def cov_offdiag_f32(cov, cscale, gscale) -> np.ndarray:
+    """G = gscale * (cov * cscale) with the diagonal's factor replaced by +0, float32."""
+    v = (np.asarray(cov, np.float32) * np.float32(cscale)).astype(np.float32)
+    np.fill_diagonal(v, np.float32(0.0))
+    return (np.float32(gscale) * v).astype(np.float32)
+
+
+def cov_sq_ref(cov, cscale):
+    """sq[i] = sum_{j != i} (cov[i][j] cscale)^2 in float64.  Kernel: v = fl(cov cscale) (1 u32), v v (1 u32, or fused), lane l
+    adds j = l, l + 64, ... in order (ceil(n / 64) additions), then the 6-level wave_sum: (3 + ceil(n / 64) + 6) u32 sum v^2."""
+    c = np.asarray(cov, np.float64) * float(np.float32(cscale))
+    np.fill_diagonal(c, 0.0)
+    q = (c * c).sum(1)
+    n = c.shape[0]
+    return q, (3 + (n + 63) // 64 + 6) * U32 * q + 2.0 ** -149
+
+
+def cov_sq_f32(cov, cscale) -> np.ndarray:
+    """cov_offdiag_row's sq in its own order, float32 (unfused): per-lane stride-64 sums, then the xor butterfly 32 .. 1."""
+    v = (np.asarray(cov, np.float32) * np.float32(cscale)).astype(np.float32)
+    np.fill_diagonal(v, np.float32(0.0))
+    n = v.shape[0]
+    s = np.zeros((n, 64), np.float32)
+    for j0 in range(0, n, 64):
+        blk = v[:, j0:j0 + 64]
+        s[:, :blk.shape[1]] = s[:, :blk.shape[1]] + blk * blk
+    lanes = np.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        s = s + s[:, lanes ^ o]
+    return s[:, 0]
+
+
+def _ce_parts(logits, cw, eps):
+    z = np.asarray(logits, np.float32).astype(np.float64)
+    C = z.shape[1]
+    w = np.ones(C) if cw is None else np.asarray(cw, np.float32).astype(np.float64)
+    e32 = np.float32(eps)
+    one_m = float(np.float32(1.0) - e32)                      # (1.0f - eps) and eps / (float)C as the kernel forms them
+    e_c = float(e32 / np.float32(C))
+    mx = z.max(1, keepdims=True)
+    ex = np.exp(z - mx)
+    den = ex.sum(1, keepdims=True)
+    return z, C, w, one_m, e_c, mx, ex, den
+
+
+def ce_terms_ref(logits, labels, cw, eps):
+    """nn.CrossEntropyLoss(weight, label_smoothing) per window, float64 (oracle/head_train_oracle.cross_entropy before its
+    sums): terms[w] = [(1 - eps) w[y] (lse - z_y) + eps / C sum_c w[c] (lse - z_c), w[y]].  Bound of the numerator:
+      lse = mx + logf(sum expf(z - mx)): E_lse = C u32 (the sum of C terms <= C; a relative error of den is an absolute one
+            of its log) + u32 |lse| (the addition) + CE_LSE_U u32 (1 + |log den|) (expf, logf);
+      a_c = lse - z_c: E_a = E_lse + u32 |a_c|;   (1 - eps) w[y] a_y: 3 u32 more;   the smoothing sum of C products:
+      w_c (E_a + u32 |a_c|) each + (C + 3) u32 sum |w_c a_c| (sum, eps / C, product);   the last addition u32 |ref|.
+    w[y] is exact.  Returns (terms [n][2], bound [n][2])."""
+    z, C, w, one_m, e_c, mx, ex, den = _ce_parts(logits, cw, eps)
+    y = np.asarray(labels, np.int64)
+    rows = np.arange(len(y))
+    lse = mx + np.log(den)
+    a = lse - z
+    wy = w[y]
+    nll = one_m * wy * a[rows, y]
+    smooth = e_c * (w[None, :] * a).sum(1)
+    ref = nll + smooth
+    E_lse = C * U32 + U32 * np.abs(lse) + CE_LSE_U * U32 * (1.0 + np.abs(np.log(den)))
+    E_a = E_lse + U32 * np.abs(a)
+    Eb = (one_m * wy * (E_a[rows, y] + 3 * U32 * np.abs(a[rows, y]))
+          + e_c * ((w[None, :] * (E_a + U32 * np.abs(a))).sum(1) + (C + 3) * U32 * (w[None, :] * np.abs(a)).sum(1))
+          + U32 * (np.abs(nll) + np.abs(smooth)))
+    return np.stack([ref, wy], 1), np.stack([Eb * (1 + 2.0 ** -10), np.zeros_like(Eb)], 1)
+
+
+def ce_grad_ref(logits, labels, cw, eps, sums):
+    """d loss / d logits given sums = [sum of numerators, sum of w[y]], float64:
+    ((1 - eps) w[y] (p - [c = y]) + eps / C (p sum(w) - w_c)) / sums[1].  Bound: p = expf(z - mx) / den is off by
+    E_p = p u32 (CE_P_U + |z - mx| + C + 2) (expf, its argument's rounding, the sum, the division); the bracket adds
+    3 u32 |(1 - eps) w[y] (p - [c = y])|, (C + 4) u32 (|p wsum| + |w_c|) eps / C and u32 of the sum; 1 / sums[1] and the last
+    product 3 u32 |ref|."""
+    z, C, w, one_m, e_c, mx, ex, den = _ce_parts(logits, cw, eps)
+    y = np.asarray(labels, np.int64)
+    p = ex / den
+    oh = np.zeros_like(p)
+    oh[np.arange(len(y)), y] = 1.0
+    wy = w[y][:, None]
+    wsum = w.sum()
+    inv = 1.0 / float(np.float32(sums[1]))
+    t1 = one_m * wy * (p - oh)
+    t2 = e_c * (p * wsum - w[None, :])
+    ref = (t1 + t2) * inv
+    E_p = p * U32 * (CE_P_U + np.abs(z - mx) + C + 2)
+    Eb = (one_m * wy * E_p + 3 * U32 * np.abs(t1) + e_c * (E_p * wsum + (C + 4) * U32 * (p * wsum + w[None, :]))
+          + U32 * (np.abs(t1) + np.abs(t2))) * abs(inv) + 3 * U32 * np.abs(ref)
+    return ref, Eb * (1 + 2.0 ** -10) + 2.0 ** -149
+
+
+_M64 = (1 << 64) - 1
+
+
+def mix64(z):
+    """head_train_kernels.hip mix64 (the splitmix64 step and finaliser) on uint64 arrays, wrapping arithmetic;
+    tests/test_kernel_reference_bounds.py holds it to oracle/head_train_oracle._mix64."""
+    z = np.asarray(z, np.uint64)
+    with np.errstate(over="ignore"):
+        z = z + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return z ^ (z >> np.uint64(31))
+
+
+def _unxorshift(x: int, s: int) -> int:
+    r = x
+    for _ in range(64 // s + 1):
+        r = x ^ (r >> s)
+    return r
+
+
+def mix64_inverse(h: int) -> int:
+    """The z with mix64(z) = h (every step of the hash is a bijection of 64-bit words)."""
+    z = _unxorshift(h, 31)
+    z = (z * pow(0x94D049BB133111EB, -1, 1 << 64)) & _M64
+    z = _unxorshift(z, 27)
+    z = (z * pow(0xBF58476D1CE4E5B9, -1, 1 << 64)) & _M64
+    z = _unxorshift(z, 30)
+    return (z - 0x9E3779B97F4A7C15) & _M64
+
+
+def dropout_key_hitting(thr: int, i: int, salt: int = 0) -> int:
+    """A stream key whose element i hashes to EXACTLY thr in its top 24 bits (thr < 2^24): the one element at which
+    `>= thr` and `> thr` differ."""
+    h = ((thr & 0xFFFFFF) << 40) | ((0x123456789A + 7919 * salt) & ((1 << 40) - 1))
+    return (mix64_inverse(h) - i) & _M64
+
+
+def dropout_keep_mask(key: int, n: int, thr: int, offset: int = 0) -> np.ndarray:
+    """drop_scale's rule: keep element i <=> mix64(key + i) >> 40 >= thr."""
+    with np.errstate(over="ignore"):
+        idx = (np.uint64(key) + np.arange(offset, n + offset, dtype=np.uint64))
+        return (mix64(idx) >> np.uint64(40)).astype(np.int64) >= int(thr)
+
+
+def gelu_dropout_fwd_ref(z, key, thr, scale):
+    """(kept values gelu(z) scale in float64 with exact zeros elsewhere, bound, keep mask).  gelu_erf_lib: GELU_LIB_U u32
+    (|z| + |gelu z|) scale, then the product with scale: u32 |ref|."""
+    z = np.asarray(z, np.float32).astype(np.float64)
+    sc = float(np.float32(scale))
+    keep = dropout_keep_mask(key, z.size, thr)
+    g = gelu64(z)
+    ref = np.where(keep, g * sc, 0.0)
+    bound = np.where(keep, GELU_LIB_U * U32 * (np.abs(z) + np.abs(g)) * sc + U32 * np.abs(ref) + 2.0 ** -149, 0.0)
+    return ref, bound, keep
+
+
+def gelu_dropout_bwd_ref(z, d, key, thr, scale):
+    """d scale gelu'(z) where kept, exact zero elsewhere: fl(fl(d s) g'), g' off by GELU_GRAD_U u32 (1 + |g'|)."""
+    z = np.asarray(z, np.float32).astype(np.float64)
+    d = np.asarray(d, np.float32).astype(np.float64)
+    sc = float(np.float32(scale))
+    keep = dropout_keep_mask(key, z.size, thr)
+    gp = gelu_grad64(z)
+    ref = np.where(keep, d * sc * gp, 0.0)
+    bound = np.where(keep, GELU_GRAD_U * U32 * np.abs(d) * sc * (1.0 + np.abs(gp)) + 2 * U32 * np.abs(ref) + 2.0 ** -149, 0.0)
+    return ref, bound, keep
+
+
+def adam_corrections(lr, step: int):
+    """adam_bias_corrections: (float32(lr / (1 - 0.9^step)), float32(1 / sqrt(1 - 0.999^step))), formed in double."""
+    return (np.float32(float(np.float32(lr)) / (1.0 - 0.9 ** step)), np.float32(1.0 / math.sqrt(1.0 - 0.999 ** step)))
+
+
+def adam_decay(n: int, wd, wd_lo: int, wd_hi: int, wd_special) -> np.ndarray:
+    """The decay factor of each element: wd_special on [wd_lo, wd_hi), wd elsewhere (the fp32 values, as float64)."""
+    i = np.arange(n)
+    return np.where((i >= wd_lo) & (i < wd_hi), float(np.float32(wd_special)), float(np.float32(wd)))
+
+
+def adam_ref_core(p, g, m, v, lr_c1, c2, wdv):
+    """torch.optim.Adam (betas 0.9 / 0.999, eps 1e-8 as fp32 constants, L2 decay wdv added to the gradient) in float64, given
+    the corrections lr_c1 = lr / (1 - b1^step) and c2 = 1 / sqrt(1 - b2^step) and the per-element decay wdv.  Returns
+    ((p, m, v), (Ep, Em, Ev)); each bound follows adam_element, one u32 per fp32 operation:
+      g' = g + wd p                        Eg = u32 (|wd p| + |g'|)
+      m' = b1 m + (1 - b1) g'              Em = (1 - b1) Eg + u32 (|b1 m| + |(1 - b1) g'| + |m'|)
+      v' = b2 v + ((1 - b2) g') g'         Ev = (1 - b2) Eg (2 |g'| + Eg) + u32 (|b2 v| + 2 (1 - b2) g'^2 + |v'|)
+      den = sqrtf(v') c2 + eps             Ed = c2 (sqrt(v') - sqrt(v' - Ev) + SQRT_U u32 sqrt(v')) + u32 (c2 sqrt(v') + den)
+      upd = (lr_c1 m') / den               Eu = (lr_c1 Em + |upd| Ed) / (den - Ed) + (1 + DIV_U) u32 |upd|
+      p' = p - upd                         Ep = Eu + u32 |p'|"""
+    f = lambda t: np.asarray(t, np.float32).astype(np.float64)      # noqa: E731
+    p, g, m, v = f(p), f(g), f(m), f(v)
+    lr_c1, c2 = float(lr_c1), float(c2)
+    wdv = np.asarray(wdv, np.float64)
+    b1, b2, eps = float(np.float32(0.9)), float(np.float32(0.999)), float(np.float32(1e-8))
+    omb1, omb2 = float(np.float32(1.0) - np.float32(0.9)), float(np.float32(1.0) - np.float32(0.999))
+    gi = g + wdv * p
+    mi = b1 * m + omb1 * gi
+    vi = b2 * v + omb2 * gi * gi
+    s = np.sqrt(vi)
+    den = s * c2 + eps
+    upd = lr_c1 * mi / den
+    pn = p - upd
+    Eg = U32 * (np.abs(wdv * p) + np.abs(gi))
+    Em = omb1 * Eg + U32 * (np.abs(b1 * m) + np.abs(omb1 * gi) + np.abs(mi))
+    Ev = omb2 * Eg * (2 * np.abs(gi) + Eg) + U32 * (np.abs(b2 * v) + 2 * omb2 * gi * gi + np.abs(vi))
+    Ed = c2 * (s - np.sqrt(np.maximum(vi - Ev, 0.0)) + SQRT_U * U32 * s) + U32 * (c2 * s + den)
+    Eu = (lr_c1 * Em + np.abs(upd) * Ed) / (den - Ed) + (1 + DIV_U) * U32 * np.abs(upd)
+    Ep = Eu + U32 * np.abs(pn)
+    k = 1 + 2.0 ** -10
+    return (pn, mi, vi), (Ep * k + 2.0 ** -149, Em * k + 2.0 ** -149, Ev * k + 2.0 ** -149)
+
+
+def adam_ref(p, g, m, v, lr, wd, wd_lo, wd_hi, wd_special, step):
+    """launch_adam_step in float64: adam_ref_core with wd_special on [wd_lo, wd_hi) and the bias corrections
+    adam_bias_corrections hands the kernel (fp32 values)."""
+    lr_c1, c2 = adam_corrections(lr, step)
+    return adam_ref_core(p, g, m, v, lr_c1, c2, adam_decay(np.asarray(p).size, wd, wd_lo, wd_hi, wd_special))
+
+
+def adam_f32(p, g, m, v, lr, wd, wd_lo, wd_hi, wd_special, step):
+    """adam_element in numpy float32, unfused."""
+    f = np.float32
+    p, g, m, v = (np.asarray(t, f) for t in (p, g, m, v))
+    lr_c1, c2 = adam_corrections(lr, step)
+    i = np.arange(p.size)
+    wdv = np.where((i >= wd_lo) & (i < wd_hi), f(wd_special), f(wd)).astype(f)
+    gi = g + wdv * p
+    mi = f(0.9) * m + (f(1.0) - f(0.9)) * gi
+    vi = f(0.999) * v + (f(1.0) - f(0.999)) * gi * gi
+    pn = p - lr_c1 * mi / (np.sqrt(vi) * c2 + f(1e-8))
+    return pn.astype(f), mi.astype(f), vi.astype(f)
+
+
+# Inputs shared by the GPU tests and the CPU validation of the bounds (tests/test_kernel_reference_bounds.py)
+def head_gemm_case(M, N, K, seed, *, N_alloc=None, lda=None, ldw=None, bias=True, nan_row=None):
+    """A [M][lda], W [N_alloc][ldw] with NaN in what a launch must not use (columns K .. of A, weight rows N .. N_alloc - 1 are
+    read into the tile but feed no stored column), bias [N] or None."""
+    rng = np.random.default_rng(seed)
+    N_alloc, lda, ldw = N_alloc or N, lda or K, ldw or K
+    A = np.full((M, lda), np.nan, np.float32)
+    A[:, :K] = rng.standard_normal((M, K)).astype(np.float32)
+    W = np.full((N_alloc, ldw), np.nan, np.float32)
+    W[:N, :K] = (rng.standard_normal((N, K)) / np.sqrt(K)).astype(np.float32)
+    if nan_row is not None:
+        A[nan_row, K // 2] = np.nan
+    b = (0.5 * rng.standard_normal(N)).astype(np.float32) if bias else None
+    return A, W, b
+
+
+def ce_case(n, C, seed, with_cw):
+    """logits [n][C] (row 0: +-80, row 1: every maximum tied, row 2: two tied maxima at 80, row 3: +-100), labels, class
+    weights or None.  expf(80) = 5.5e34 is still an fp32 number, so a kernel that forgot the max subtraction would get rows
+    0 and 2 right; expf(100) overflows, and row 3 is where that defect shows."""
+    rng = np.random.default_rng(seed)
+    z = (3.0 * rng.standard_normal((n, C))).astype(np.float32)
+    z[0] = np.where(np.arange(C) % 2 == 0, 80.0, -80.0)
+    if n > 1:
+        z[1] = np.float32(1.25)
+    if n > 2:
+        z[2, 0] = z[2, C - 1] = np.float32(80.0)
+    if n > 3:
+        z[3] = np.where(np.arange(C) % 2 == 0, -100.0, 100.0)
+    y = rng.integers(0, C, n).astype(np.int32)
+    y[0] = 1                                                         # the -80 logit carries the label
+    cw = (0.25 + 2.0 * rng.random(C)).astype(np.float32) if with_cw else None
+    return z, y, cw
+
+
+def colsum_case(rows, cols, seed):
+    """src [rows][cols + 3] (NaN in the three unread columns), columns of different magnitudes; returns (src, ld)."""
+    rng = np.random.default_rng(seed)
+    ld = cols + 3
+    src = np.full((rows, ld), np.nan, np.float32)
+    src[:, :cols] = (rng.standard_normal((rows, cols)) * rng.uniform(0.1, 10.0, (1, cols)) + 0.5).astype(np.float32)
+    return src, ld
+
+
+def cov_case(n, seed):
+    """A raw Rc^T Rc of n + 5 rows, cscale = 1 / (rows - 1), a gscale that is no power of two."""
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal((n + 5, n)).astype(np.float32)
+    return (x.T @ x).astype(np.float32), np.float32(1.0 / (n + 4)), np.float32(2.0 / 7.0)
+
+
+def gelu_case(n, thr, which):
+    """z spans [-6, 6] (never 0), d is a gradient without zeros; key `which` (0 / 1) puts element n - 1 resp. n // 2 exactly
+    AT thr, the one hash value at which `>= thr` and `> thr` differ.  Returns (z, d, key, scale)."""
+    rng = np.random.default_rng(n + thr % 1000 + which)
+    z = np.linspace(-6.0, 6.0, n) if n > 1 else np.array([0.8])
+    z = (z + rng.uniform(0.001, 0.002, n)).astype(np.float32)
+    d = rng.standard_normal(n).astype(np.float32)
+    d[d == 0] = 1.0
+    key = dropout_key_hitting(thr, (n - 1) if which == 0 else n // 2, salt=which)
+    scale = np.float32(1.0 / (1.0 - thr / 2.0 ** 24)) if thr < 2 ** 23 else np.float32(1.5)
+    return z, d, key, scale
+
+
+def adam_case(n, seed):
+    """Decay is visible: |p| ~ 10, |g| ~ 0.1, m and v as a previous step leaves them (wd p is comparable to g).  Every 7th
+    element is quiet (|p| ~ 1e-2, |g| ~ 1e-5, v ~ 1e-10): there sqrt(v) is comparable to sqrt(eps), so eps's place shows."""
+    rng = np.random.default_rng(seed)
+    sgn = lambda: np.where(rng.random(n) < 0.5, -1.0, 1.0)           # noqa: E731
+    p = sgn() * rng.uniform(5.0, 15.0, n)
+    g = sgn() * rng.uniform(0.05, 0.15, n)
+    m = 0.1 * sgn() * rng.uniform(0.05, 0.15, n)
+    v = 0.001 * rng.uniform(0.05, 0.15, n) ** 2 * 10
+    q = np.arange(n) % 7 == 3
+    p[q] *= 1e-3
+    g[q] *= 1e-4
+    m[q] *= 1e-4
+    v[q] *= 1e-8
+    return tuple(t.astype(np.float32) for t in (p, g, m, v))
 
 
 def ratio(y, ref, bound) -> float:

@@ -470,3 +470,211 @@ def test_stem_reference_gathers_4x4_patches_and_ignores_the_remainder():
     assert np.array_equal(A[m, :16].reshape(4, 4), (f[1, 4:8, 8:12] / 255.0).astype(F32))
     g = rng.standard_normal((2, 9, 14)).astype(F32)
     assert np.array_equal(R.cnx_stem_ref(g, False)[m, :16].reshape(4, 4), g[1, 4:8, 8:12])
+
+
+# ---- classifier head: the exact-fp32 GEMM and the small training kernels (tests/test_gpu_head_kernels_reference.py) ----
+# Same inputs as the GPU tests (the case builders of oracle/kernel_ref.py).  Where the GPU test asks for equal bits, a planted
+# defect must change bits; where it asks for a bound, a float32 simulation in the kernel's order must pass and the defect fail.
+def _f32_gelu(v32):
+    return (F32(0.5) * v32 * (F32(1.0) + R._erf64(v32.astype(np.float64) / np.sqrt(2.0)).astype(F32))).astype(F32)
+
+
+def test_head_gemm_reference_rejects_planted_defects():
+    M, N, K = 129, 132, 96
+    A, W, b = R.head_gemm_case(M, N, K, 1000 * M + 10 * N + K, N_alloc=N + 4, lda=K + 4)
+    A, W = A[:, :K], W[:N, :K]
+    pre, _ = R.head_gemm_exact(A, W, b, K)
+    acc, _ = R.head_gemm_exact(A, W, None, K)
+    y, bound = R.head_gemm_gelu_ref(pre)
+    assert R.ratio(_f32_gelu(pre), y, bound) <= 1.0
+    same = lambda t: np.array_equal(t.view(np.uint32), pre.view(np.uint32))     # noqa: E731
+    assert not same((R.fmaf_chain(A, W) + b[None, :]).astype(F32)), "k order 0 .. K-1 must differ from the MFMA's in some bits"
+    dropped = (R.fmaf_chain(A[:, :K - 32], W[:, :K - 32], R.f32_mfma_k_order(K - 32)) + b[None, :]).astype(F32)
+    shifted = (acc + np.roll(b, 4)[None, :]).astype(F32)
+    before = (_f32_gelu(acc) + b[None, :]).astype(F32)
+    assert not same(dropped) and not same(shifted)
+    for name, out in (("last K-tile dropped", _f32_gelu(dropped)), ("bias shifted by 4 columns", _f32_gelu(shifted)),
+                      ("GELU before the bias", before)):
+        assert R.ratio(out, y, bound) > 1.0, name
+    # split-K: a partial added twice / skipped changes the sum's bits
+    Kt, splits = 1024, 4
+    A, W, _ = R.head_gemm_case(12, 128, Kt, Kt + splits + 12, bias=False)
+    want, parts = R.head_gemm_exact(A, W, None, Kt // splits, splits)
+    twice = ((((parts[0] + parts[1]) + parts[1]) + parts[2]) + parts[3]).astype(F32)
+    skipped = ((parts[0] + parts[1]) + parts[3]).astype(F32)
+    backwards = (((parts[3] + parts[2]) + parts[1]) + parts[0]).astype(F32)
+    for t in (twice, skipped, backwards):
+        assert not np.array_equal(t.view(np.uint32), want.view(np.uint32))
+    # ... and against the float64 product those two are far outside fp32 accumulation's K u32 sum |a w|
+    acc64, E, _ = R.gemm_acc(3, A, W)
+    assert R.ratio(want, acc64, E) <= 1.0 and R.ratio(twice, acc64, E) > 1.0 and R.ratio(skipped, acc64, E) > 1.0
+
+
+@pytest.mark.parametrize("rows", [1, 37, 63, 64, 65, 1000])
+def test_colsum_bound_accepts_the_kernel_order_and_rejects_planted_defects(rows):
+    for cols in (1, 65):
+        src, _ = R.colsum_case(rows, cols, 7 * rows + cols)
+        x = src[:, :cols]
+        for scale in (1.0, 1.0 / 37.0):
+            tmp, dst = R.colsum_f32(x, scale)
+            ref, bound = R.colsum_ref(x, scale)
+            assert R.ratio(dst, ref, bound) <= 1.0
+            per = -(-rows // 64)
+            if rows > 63 * per:                                              # chunk 63 holds rows: drop it
+                assert R.ratio((tmp[:63].sum(0, dtype=F32) * F32(scale)), ref, bound) > 1.0, "last chunk dropped"
+            if rows % 64:                                                    # per = rows / chunks rounded down loses the tail
+                lost = x[:(rows // 64) * 64].sum(0, dtype=F32) * F32(scale)
+                assert R.ratio(lost, ref, bound) > 1.0, "per rounded down"
+            if scale != 1.0:
+                assert R.ratio(R.colsum_f32(x, 1.0)[1], ref, bound) > 1.0, "scale ignored"
+
+
+@pytest.mark.parametrize("n", [32, 100, 256])
+def test_cov_offdiag_reference_rejects_planted_defects(n):
+    cov, cs, gs = R.cov_case(n, n)
+    ref, bound = R.cov_sq_ref(cov, cs)
+    sim = R.cov_sq_f32(cov, cs)
+    assert R.ratio(sim, ref, bound) <= 1.0
+    v = (cov * cs).astype(F32)
+    kept = (sim + np.diagonal(v) ** 2).astype(F32)
+    assert R.ratio(kept, ref, bound) > 1.0, "diagonal kept"
+    assert R.ratio((gs * gs) * sim, ref, bound) > 1.0 and R.ratio(gs * sim, ref, bound) > 1.0, "gscale applied to sq"
+    G = R.cov_offdiag_f32(cov, cs, gs)
+    assert (np.diagonal(G).view(np.uint32) == 0).all() and not np.array_equal(G, (gs * v).astype(F32))
+
+
+def _sim_ce(z, y, cw, eps, sums=None, *, no_max=False, c_minus_1=False, no_w_smooth=False, no_div=False):
+    """ce_terms_window / ce_grad_window in numpy float32 (the kernels' loops, sums in class order), optional planted defects."""
+    n, Cc = z.shape
+    w = np.ones(Cc, F32) if cw is None else cw.astype(F32)
+    ws = np.ones(Cc, F32) if no_w_smooth else w
+    eps = F32(eps)
+    ec = eps / F32(Cc - 1 if c_minus_1 else Cc)
+    rows = np.arange(n)
+    with np.errstate(over="ignore", invalid="ignore"):
+        mx = np.zeros((n, 1), F32) if no_max else z.max(1, keepdims=True)
+        ex = np.exp((z - mx).astype(F32)).astype(F32)
+        den = np.zeros(n, F32)
+        for c in range(Cc):
+            den = den + ex[:, c]
+        wy = w[y]
+        if sums is None:
+            lse = mx[:, 0] + np.log(den).astype(F32)
+            sm = np.zeros(n, F32)
+            for c in range(Cc):
+                sm = sm + ws[c] * (lse - z[:, c])
+            return np.stack([(F32(1.0) - eps) * wy * (lse - z[rows, y]) + ec * sm, wy], 1)
+        wsum = F32(0.0)
+        for c in range(Cc):
+            wsum = wsum + ws[c]
+        p = ex / den[:, None]
+        oh = np.zeros_like(p)
+        oh[rows, y] = 1.0
+        inv = F32(1.0) if no_div else F32(1.0) / F32(sums[1])
+        return (((F32(1.0) - eps) * wy[:, None] * (p - oh) + ec * (p * wsum - ws[None, :])) * inv).astype(F32)
+
+
+@pytest.mark.parametrize("Cc", [2, 9, 12, 64])
+def test_cross_entropy_bounds_accept_the_simulated_kernels_and_reject_planted_defects(Cc):
+    for n in (1, 129):
+        for with_cw in (False, True):
+            for eps in (0.0, 0.1):
+                z, y, cw = R.ce_case(n, Cc, 100 * n + Cc, with_cw)
+                ref, bound = R.ce_terms_ref(z, y, cw, eps)
+                sums = ref.sum(0).astype(F32) * F32(3.0)                      # not 1: the division shows
+                gref, gbound = R.ce_grad_ref(z, y, cw, eps, sums)
+                assert R.ratio(_sim_ce(z, y, cw, eps)[:, 0], ref[:, 0], bound[:, 0]) <= 1.0
+                assert R.ratio(_sim_ce(z, y, cw, eps, sums), gref, gbound) <= 1.0
+                defects = [dict(no_div=True)] + ([dict(no_max=True)] if n > 3 else [])      # row 3 (+-100) shows it: see ce_case
+                if eps:
+                    defects.append(dict(c_minus_1=True))
+                    if with_cw:
+                        defects.append(dict(no_w_smooth=True))
+                for d in defects:
+                    if "no_div" not in d:
+                        assert R.ratio(_sim_ce(z, y, cw, eps, **d)[:, 0], ref[:, 0], bound[:, 0]) > 1.0, ("terms", d)
+                    assert R.ratio(_sim_ce(z, y, cw, eps, sums, **d), gref, gbound) > 1.0, ("grad", d)
+
+
+def _sim_gelu_dropout(z, d, key, thr, scale, *, backward, strict=False, offset=0, no_mask=False):
+    keep = R.dropout_keep_mask(key, z.size, thr + (1 if strict else 0), offset)          # hash > thr <=> hash >= thr + 1
+    ds = np.where(keep | no_mask, F32(scale), F32(0.0)).astype(F32)
+    if backward:
+        return ((d * ds) * R.gelu_grad64(z).astype(F32)).astype(F32)
+    return (_f32_gelu(z) * ds).astype(F32)
+
+
+def _gelu_passes(z, d, key, thr, scale, backward, **kw):
+    out = _sim_gelu_dropout(z, d, key, thr, scale, backward=backward, **kw)
+    ref, bound, keep = (R.gelu_dropout_bwd_ref(z, d, key, thr, scale) if backward else R.gelu_dropout_fwd_ref(z, key, thr, scale))
+    return bool((out[~keep] == 0).all()) and R.ratio(out[keep], ref[keep], bound[keep]) <= 1.0
+
+
+@pytest.mark.parametrize("backward", [False, True], ids=["fwd", "bwd"])
+def test_gelu_dropout_reference_accepts_the_simulated_kernel_and_rejects_planted_defects(backward):
+    for n in (1, 255, 256, 257, 5000):
+        for thr in (0, int(0.1 * 2 ** 24), 2 ** 24 - 1):
+            for which in (0, 1):
+                z, d, key, scale = R.gelu_case(n, thr, which)
+                assert _gelu_passes(z, d, key, thr, scale, backward)
+                assert not _gelu_passes(z, d, key, thr, scale, backward, strict=True), ("> thr", n, thr, which)
+                if n >= 255 and thr == int(0.1 * 2 ** 24):
+                    assert not _gelu_passes(z, d, key, thr, scale, backward, offset=1), ("index + 1", n, which)
+                if backward and not R.dropout_keep_mask(key, n, thr).all():
+                    assert not _gelu_passes(z, d, key, thr, scale, backward, no_mask=True), ("no mask", n, thr, which)
+
+
+def test_mix64_is_the_training_oracles_hash():
+    from oracle.head_train_oracle import _mix64
+    z = np.random.default_rng(0).integers(0, 2 ** 64, 4096, dtype=np.uint64)
+    z[:3] = [0, 1, 2 ** 64 - 1]
+    assert np.array_equal(R.mix64(z), _mix64(z))
+    assert all(int(R.mix64(np.array([R.mix64_inverse(int(h))], np.uint64))[0]) == int(h) for h in z[:64])
+
+
+ADAM_DEFECTS = ["closed range", "open range", "range shifted", "wd swapped", "no decay", "step1 corrections", "eps in sqrt"]
+
+
+def _adam_defect(d, ins, lr, wd, lo, hi, wds, step):
+    """The float64 Adam step with one planted defect: a wrong decay range / factor or stale corrections go in through
+    adam_ref_core's inputs; eps inside the square root is its own arithmetic."""
+    n = ins[0].size
+    dlo, dhi = {"closed range": (lo, hi + 1), "open range": (lo + 1, hi), "range shifted": (lo + 1, hi + 1)}.get(d, (lo, hi))
+    a, b = {"wd swapped": (wds, wd), "no decay": (0.0, 0.0)}.get(d, (wd, wds))
+    wdv = R.adam_decay(n, a, dlo, dhi, b)
+    lr_c1, c2 = R.adam_corrections(lr, 1 if d == "step1 corrections" else step)
+    if d != "eps in sqrt":
+        return R.adam_ref_core(*ins, lr_c1, c2, wdv)[0]
+    p, g, m, v = (t.astype(np.float64) for t in ins)
+    b1, b2, eps = float(F32(0.9)), float(F32(0.999)), float(F32(1e-8))
+    gi = g + wdv * p
+    mi = b1 * m + float(F32(1.0) - F32(0.9)) * gi
+    vi = b2 * v + float(F32(1.0) - F32(0.999)) * gi * gi
+    return p - float(lr_c1) * mi / (np.sqrt(vi + eps) * float(c2)), mi, vi
+
+
+@pytest.mark.parametrize("n", [1, 255, 256, 257, 1000])
+def test_adam_bounds_accept_the_simulated_kernel_and_reject_planted_defects(n):
+    ins = R.adam_case(n, n)
+    caught = set()
+    for step in (1, 2, 1000):
+        for lo, hi in [(0, 0), (0, 1), (255, 257), (n - 1, n)]:
+            for wd in (0.0, 1e-2):
+                args = (1e-3, wd, lo, hi, 1e-3, step)
+                ref, E = R.adam_ref(*ins, *args)
+                sim = R.adam_f32(*ins, *args)
+                assert all(R.ratio(s, r, e) <= 1.0 for s, r, e in zip(sim, ref, E)), (n, step, lo, hi, wd)
+                for d in ADAM_DEFECTS:
+                    bad = _adam_defect(d, ins, *args)
+                    out = max(R.ratio(b, r, e) for b, r, e in zip(bad, ref, E))
+                    # a defect must show wherever it changes the arithmetic at all: which elements decay and by how much,
+                    # the corrections (equal at step 1), eps's place (always)
+                    i = np.arange(n)
+                    dlo, dhi = {"closed range": (lo, hi + 1), "open range": (lo + 1, hi), "range shifted": (lo + 1, hi + 1)}.get(d, (lo, hi))
+                    changes = {"wd swapped": True, "no decay": wd > 0 or lo < min(hi, n), "step1 corrections": step > 1,
+                               "eps in sqrt": n > 3}.get(d,      # the quiet elements (adam_case) show eps's place
+                                                         bool((((i >= lo) & (i < hi)) != ((i >= dlo) & (i < dhi))).any()))
+                    assert (out > 1.0) == changes, (d, n, step, lo, hi, wd, out)
+                    if out > 1.0:
+                        caught.add(d)
+    assert caught == set(ADAM_DEFECTS) - ({"eps in sqrt"} if n <= 3 else set())
