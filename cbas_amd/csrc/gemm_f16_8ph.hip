@@ -11,8 +11,17 @@
 //    then they swap.  A K-tile is four such phases (one C quadrant of the wave each).
 //  * LDS-DMA is never drained inside the loop: each K-tile is staged as four sub-tiles (B-sub0,
 //    A-sub0, B-sub1, A-sub1: the rows the phase-1/2/3 fragment reads touch), three sub-tiles stay
-//    in flight across the barriers (s_waitcnt vmcnt(6), raw s_barrier), and a sub-tile region is
-//    re-staged only after every read of it has been retired (see the table).
+//    in flight across the barriers (counted s_waitcnt vmcnt, raw s_barrier), and a sub-tile region
+//    is re-staged only after every read of it has been retired (see the table).
+//  * A wave issues the same number of LDS-DMAs per sub-tile as every other wave, so one vmcnt
+//    immediate serves all eight: 2 for a B sub-tile (16 pieces of 8 rows), NA(T) = (4 T + 7) / 8
+//    for an A sub-tile of 16 T rows per wave group (4 T pieces: 2, 2, 1 for T = 4, 3, 2), + 1 with
+//    A-sub1 in the MX-fp8 form (the scales).  Only a 12-piece sub-tile (T = 3) stages duplicates:
+//    waves 4-7 re-stage piece 11 as their second one.  vmcnt retires in issue order and a K-tile is
+//    always issued B-sub0, A-sub0, B-sub1, A-sub1: what may stay in flight when K-tile t+1 must
+//    have landed is what was issued after A-sub1(t+1), i.e. B-sub0, A-sub0 and B-sub1 of t+2 -
+//    vmcnt(2 + NA(TA) + 2), the DMAs of a K-tile less those of its A-sub1 (6, 6, 6, 5 for the
+//    256-, 192-, 160- and 128-row tile; the scale DMA is part of A-sub1 and never among them).
 //
 //  phase of K-tile t (buffer b = t&1)   fragment reads             LDS-DMA issued           MFMA quadrant
 //    P1                                 B-sub0 (4), A-sub0 (2*TA)   A-sub1(t+1) -> b^1        (A0,B0)
@@ -23,6 +32,8 @@
 //  of the previous K-tile and first read in P1, i.e. after two further barriers - one more than the
 //  group stagger.  WAR: B-sub0 is re-staged one phase after its reads, which P1 retires with
 //  lgkmcnt(2*TA) before its first barrier (reads issue B first); every other region two phases after.
+//  That lgkmcnt counts fragment reads (2 per 16-row tile of A-sub0, whatever the number of pieces
+//  that staged them; LDS-DMA counts on vmcnt only), so it does not depend on NA.
 //
 // Tail balancing: a launch may carry two kinds of tile.  Blocks [0, main_blocks) cover rows
 // [0, tail_row0) with the main tile, the rest cover [tail_row0, M) with 128x256 tiles; the hardware
@@ -88,6 +99,9 @@ constexpr int pp_lds_kernel() {
     return (TAIL && pp_lds_main<2, 2>() > pp_lds_main<TA, TB>() ? pp_lds_main<2, 2>() : pp_lds_main<TA, TB>()) + (F8 ? 4096 : 0);
 }
 
+// LDS-DMAs a wave issues for an A sub-tile of 16 T rows per wave group: its 4 T pieces of 8 rows over 8 waves
+constexpr int pp_na(int T) { return (4 * T + 7) / 8; }
+
 // Runs the tiles `first, first + stride, ...` (< n_kind) of one kind: tile id -> (tm, tn) through the XCD remap over
 // n_kind ids; rows start at base_row.  Persistent: while a tile's epilogue runs, the LDS-DMA of the NEXT tile's first
 // K-tile is already in flight into buffer 0 (its latency - most of the prologue - hides under the epilogue).
@@ -100,6 +114,10 @@ __device__ __forceinline__ void pp_tiles(const GemmParams& p, char* smem, int fi
     constexpr int BM = 2 * WROWS;
     constexpr int A_BYTES = BM * 128, B_BYTES = BN * 128, BUF_BYTES = A_BYTES + B_BYTES;
     constexpr int TMAX = TA > TB ? TA : TB;
+    // per-wave LDS-DMA counts of the four sub-tiles (file header), and what the counted wait leaves in flight: the
+    // DMAs of a K-tile less those of its A-sub1, the last one issued
+    constexpr int N_B = 2, N_A0 = pp_na(TA), N_A1 = pp_na(TB) + (F8 ? 1 : 0);
+    constexpr int VM_KEEP = (2 * N_B + N_A0 + N_A1) - N_A1;
     int row0 = 0, col0 = 0;
 
     const int tid = threadIdx.x;
@@ -119,11 +137,12 @@ __device__ __forceinline__ void pp_tiles(const GemmParams& p, char* smem, int fi
         const_cast<void*>(F8 || SPLIT ? reinterpret_cast<const void*>(p.W8) : reinterpret_cast<const void*>(p.W)), 0, 0x7fffffff, 0x00020000);
     char* const sc_lds = smem + pp_lds_main<TA, TB>(); // F8: [buf][A rows 256 x 4 B | B rows 256 x 4 B]
 
-    // ---- LDS-DMA source offsets: two 8-row pieces per wave and sub-tile --------------------------
+    // ---- LDS-DMA source offsets: 8-row pieces, two per wave and B sub-tile, pp_na(T) per wave and A sub-tile ----
     // A-sub0 = rows {wr' * WROWS + [0, 16 TA)}, A-sub1 = rows {wr' * WROWS + 16 TA + [0, 16 TB)}, wr' = 0,1;
-    // B-sub h = rows with bit 5 == h.  Piece q of a sub-tile (q = wave, wave + 8); a sub-tile with fewer
-    // than 16 pieces clamps q: the duplicates rewrite identical bytes (keeps the per-wave DMA count, and
-    // so the vmcnt immediates, uniform)
+    // B-sub h = rows with bit 5 == h.  Piece q of a sub-tile (q = wave, wave + 8).  T = 2: 8 pieces, one per wave, slot 1
+    // does not exist.  T = 3: 12 pieces in two slots, q is clamped and waves 4-7 stage piece 11 twice (identical bytes):
+    // predicating those 4 away would leave waves 4-7 with fewer DMAs than waves 0-3 and the counted waits no longer
+    // wave-uniform
     int a_lds[2][2], b_lds[2][2];
     unsigned a_src[2][2], b_src[2][2];
     // F8: block scales of one K-tile.  Waves 0-3 fetch the dwords of A rows row0 + 64*wave + lane, waves 4-7 those of
@@ -156,14 +175,16 @@ __device__ __forceinline__ void pp_tiles(const GemmParams& p, char* smem, int fi
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
                 const int T = h ? TB : TA;
-                int q = wave + 8 * s;
-                q = q < 4 * T ? q : 4 * T - 1;
-                const int ar = (q / (2 * T)) * WROWS + h * (16 * TA) + (q % (2 * T)) * 8;   // first row of the piece
-                a_lds[h][s] = ar * 128;
-                const int r = ar + lrow;
-                int grow = row0 + r;
-                grow = grow < p.M_pad - 1 ? grow : p.M_pad - 1;
-                a_src[h][s] = (unsigned)grow * (unsigned)(p.lda * ESZ) + (((lane & 7) ^ ((r >> 1) & 7)) << 4);     // bytes
+                if (s < pp_na(T)) {
+                    int q = wave + 8 * s;
+                    q = q < 4 * T ? q : 4 * T - 1;
+                    const int ar = (q / (2 * T)) * WROWS + h * (16 * TA) + (q % (2 * T)) * 8;   // first row of the piece
+                    a_lds[h][s] = ar * 128;
+                    const int r = ar + lrow;
+                    int grow = row0 + r;
+                    grow = grow < p.M_pad - 1 ? grow : p.M_pad - 1;
+                    a_src[h][s] = (unsigned)grow * (unsigned)(p.lda * ESZ) + (((lane & 7) ^ ((r >> 1) & 7)) << 4);     // bytes
+                }
                 const int qb = wave + 8 * s;
                 const int br = (((qb >> 2) << 3) | (h << 2) | (qb & 3)) * 8;
                 b_lds[h][s] = A_BYTES + br * 128;
@@ -188,7 +209,8 @@ __device__ __forceinline__ void pp_tiles(const GemmParams& p, char* smem, int fi
         if (which & 1) {
 #pragma unroll
             for (int s = 0; s < 2; ++s)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(Arsrc, LDS_PTR(base + a_lds[h][s]), 16, a_src[h][s], kt * 128, 0, 0);
+                if (s < pp_na(h ? TB : TA))
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(Arsrc, LDS_PTR(base + a_lds[h][s]), 16, a_src[h][s], kt * 128, 0, 0);
             if (F8 && h == 1)        // rides with A-sub1: retired by the same counted vmcnt, two barriers before its first read
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(Srsrc, LDS_PTR(sc_lds + buf * 2048 + sc_dst), 4, sc_src, kt * sc_step, 0, 0);
         } else {
@@ -349,7 +371,7 @@ __device__ __forceinline__ void pp_tiles(const GemmParams& p, char* smem, int fi
         // P4
         if (t + 2 < nk) {
             stage(b, t + 2, 2);
-            asm volatile("s_waitcnt vmcnt(6)" ::: "memory");    // K-tile t+1 has landed; 3 sub-tiles of t+2 in flight
+            asm volatile("s_waitcnt vmcnt(%0)" :: "n"(VM_KEEP) : "memory");    // K-tile t+1 has landed; 3 sub-tiles of t+2 in flight
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
@@ -364,14 +386,14 @@ __device__ __forceinline__ void pp_tiles(const GemmParams& p, char* smem, int fi
         set_tile(id);                                     // same values the K-tile 0 staging used; see `lane` above
         set_frag_offsets();
         // ---- rest of the prologue: K-tile 0 is in flight (issued above, or under the previous tile's epilogue);
-        // three sub-tiles of K-tile 1 follow.  vmcnt counts in issue order, so vmcnt(6) also retires every store of
-        // the previous tile's epilogue.
+        // three sub-tiles of K-tile 1 follow.  vmcnt counts in issue order, so leaving only those VM_KEEP in flight
+        // also retires every store of the previous tile's epilogue.
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
         stage(1, 1, 0); stage(1, 1, 1); stage(1, 1, 2);
-        asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(VM_KEEP) : "memory");
         __builtin_amdgcn_s_barrier();
         if constexpr (LNC) {
             // LayerNorm fold, consumer side: thread r of the first four waves pools the statistics of row row0 + r - one
@@ -554,10 +576,15 @@ int launch_8ph(const GemmParams& p, int main_panels, hipStream_t stream) {
 // Makespan of a launch on `slots` CUs, in units of one 256x256 tile: tiles are handed out in block
 // order to whichever CU frees up first.  Relative tile costs measured with scripts/gemm_stamps.py
 // (the smaller tiles are bound by the ~30 B/cycle/CU L2->LDS rate, not by the MFMA pipe).
+// 160 and 128 re-measured with pp_na(T) DMAs per A sub-tile (`python scripts/gemm_stamps.py 50 12864 13,14,15,16`,
+// two runs, profiles/staging_tile_stamps.txt), each where the planner uses it: 160 = prologue + K loop + epilogue
+// cycles of a workgroup's first tile with the residual epilogue, mean of o_proj (0.82) and down (0.77), 0.84 and
+// 0.80 with two DMAs everywhere; 128 = a steady-state tile of `up` (0.63; 0.67 before).  K loop of 12 K-tiles:
+// 23.3k -> 22.1k cycles at 160 rows, 21.2k -> 19.1k at 128, 30.3k at 256 and 24.8k at 192 as before.
 // The split form's loop is three times as long per staged byte and MFMA-bound at every tile height: cost ~ rows.
 double pp_tile_cost(int bm, bool split = false) {
     if (split) return 0.05 + 0.95 * bm / 256.0;
-    return bm == 256 ? 1.0 : bm == 192 ? 0.86 : bm == 160 ? 0.83 : 0.66;
+    return bm == 256 ? 1.0 : bm == 192 ? 0.86 : bm == 160 ? 0.79 : 0.63;
 }
 
 double pp_makespan(int n_main, double c_main, int n_tail, double c_tail, int slots) {
