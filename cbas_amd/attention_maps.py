@@ -1,0 +1,150 @@
+"""What an encoder looks at: the last layer's attention from the CLS token to the patch tokens, averaged over the heads, for
+frames of a video - the picture the reference's encoder comparison tool draws (compare_encoders.py:36-49, :72-79), computed on
+the device by ``DinoEncoder.cls_attention`` beside the CLS rows.
+
+    python -m cbas_amd.attention_maps --video V --frame N --encoder ID [--encoder ID ...] --out PNG [--precision P]
+
+One deliberate difference from that tool: the map here is the map of what the encoder sees INSIDE CBAS - the green plane / 255
+replicated to three channels at the video's own size, exactly what ``encode_file`` feeds the model (backend/cbas.py:431) - not
+of an RGB picture resized and ImageNet-normalised by the checkpoint's image processor, which no CBAS embedding was made from.
+The patch grid is therefore (H // patch, W // patch) and need not be square.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+from typing import Mapping, Sequence, Tuple, Union
+
+import numpy as np
+
+
+def frame_maps(encoder, path: str, frame_indices: Sequence[int]):
+    """Attention maps of the given frames of a video.  Frames are read through ``pipeline.open_video`` (any source it knows) and
+    encoded in batches of ``encoder.max_batch``.  Returns ``(maps, frames_green)``: float32 (n, nh, nw) and uint8 (n, H, W)
+    numpy arrays, in the order of ``frame_indices``."""
+    import torch
+    from . import pipeline
+    idx = [int(i) for i in frame_indices]
+    if not idx:
+        raise ValueError("no frame index given")
+    src = pipeline.open_video(path)
+    try:
+        n_total = len(src)
+        bad = [i for i in idx if i < 0 or i >= n_total]
+        if bad:
+            raise IndexError(f"frame {bad[0]} is out of range: {os.path.basename(path)} has {n_total} frames")
+        maps, greens = [], []
+        for i in range(0, len(idx), encoder.max_batch):
+            part = idx[i:i + encoder.max_batch]
+            frames = np.asarray(src.get_batch(part) if part == list(range(part[0], part[0] + len(part)))
+                                else np.concatenate([np.asarray(src.get_batch([j])) for j in part]))
+            green = np.ascontiguousarray(frames[:, :, :, 1] if frames.ndim == 4 else frames)      # backend/cbas.py:431
+            dev = torch.from_numpy(green).to(encoder.device)
+            maps.append(encoder.cls_attention(dev)[2].cpu().numpy())
+            greens.append(green)
+        return np.concatenate(maps), np.concatenate(greens)
+    finally:
+        if hasattr(src, "close"):
+            src.close()
+
+
+def render_map(map2d, size: Tuple[int, int]) -> np.ndarray:
+    """One (nh, nw) map as the picture the reference tool shows: stretched to [0, 1] by its own minimum and maximum when they
+    differ (a constant map is left as it is), times 255 truncated to uint8, resized to ``size`` = (width, height) with Pillow's
+    bicubic filter.  Returns a uint8 (height, width) array."""
+    from PIL import Image
+    a = np.asarray(map2d, dtype=np.float32)
+    if a.ndim != 2:
+        raise ValueError(f"render_map takes one 2-D map, got shape {a.shape}")
+    return np.asarray(Image.fromarray(_to_u8(a)).resize((int(size[0]), int(size[1])), Image.BICUBIC))
+
+
+def _to_u8(a: np.ndarray) -> np.ndarray:
+    lo, hi = float(a.min()), float(a.max())
+    if hi > lo:
+        a = (a - lo) / (hi - lo)
+    return (a * 255).astype(np.uint8)
+
+
+def compare_encoders(video: str, frame_idx: int, encoders: Mapping[str, Union[str, object]], out_png: str, precision=None) -> str:
+    """One figure row per encoder: the frame as the encoder receives it (green plane) beside its rendered attention map.
+    ``encoders`` maps a display name to a checkpoint directory, an HF-cache id or a ready ``DinoEncoder``; encoders built here
+    are closed again.  Returns ``out_png``."""
+    if not encoders:
+        raise ValueError("no encoder given")
+    from matplotlib.backends.backend_agg import FigureCanvasAgg      # the Agg backend, without pyplot's global state
+    from matplotlib.figure import Figure
+    from .encoder import DinoEncoder
+    panels = []
+    for name, enc in encoders.items():
+        own = isinstance(enc, str)
+        if own:
+            enc = DinoEncoder(enc, **({} if precision is None else {"precision": int(precision)}))
+        try:
+            maps, green = frame_maps(enc, video, [frame_idx])
+        finally:
+            if own:
+                enc.close()
+        panels.append((name, green[0], maps[0].shape, render_map(maps[0], (green.shape[2], green.shape[1]))))
+    _draw(Figure, FigureCanvasAgg, panels, f"{os.path.basename(video)}, frame {frame_idx}", out_png)
+    return out_png
+
+
+PANEL_HEIGHT_IN = 3.2        # every panel is this tall; its width follows the video's aspect ratio
+LABEL_WIDTH_IN = 0.6         # room at the left for the encoders' names
+
+
+def _draw(Figure, Canvas, panels, caption: str, out_png: str) -> None:
+    """panels: (name, green plane (H, W) uint8, patch grid (nh, nw), rendered map (H, W) uint8) per encoder, top to bottom."""
+    H, W = panels[0][1].shape
+    panel_w = PANEL_HEIGHT_IN * W / H
+    fig = Figure(figsize=(LABEL_WIDTH_IN + 2 * panel_w, PANEL_HEIGHT_IN * len(panels) + 0.5), layout="constrained")
+    Canvas(fig)
+    grid = fig.subplots(len(panels), 2, squeeze=False)
+    for r, (name, green, (nh, nw), pic) in enumerate(panels):
+        left, right = grid[r]
+        left.imshow(green, cmap="gray", vmin=0, vmax=255, interpolation="nearest")
+        right.imshow(pic, cmap="inferno", vmin=0, vmax=255, interpolation="nearest")
+        left.set_ylabel(name, fontsize=10)
+        right.set_xlabel(f"{nh} x {nw} patches, stretched to the map's own range", fontsize=8)
+        for a in (left, right):
+            a.set_xticks([])
+            a.set_yticks([])
+        if r == 0:
+            left.set_title("what the encoder is fed: green / 255", fontsize=10)
+            right.set_title("where its CLS token looks (last layer, mean of heads)", fontsize=10)
+    fig.supxlabel(f"{caption}, {H} x {W} pixels", fontsize=9)
+    fig.savefig(out_png, dpi=110)
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(prog="python -m cbas_amd.attention_maps", description=__doc__.split("\n\n")[0])
+    ap.add_argument("--video", required=True)
+    ap.add_argument("--frame", type=int, required=True)
+    ap.add_argument("--encoder", action="append", default=[], metavar="ID", help="checkpoint directory or HF-cache id; repeatable")
+    ap.add_argument("--out", required=True, metavar="PNG")
+    ap.add_argument("--precision", type=int, default=None)
+    a = ap.parse_args(argv)
+    if not a.encoder:
+        ap.error("at least one --encoder is needed")
+    if not os.path.exists(a.video):
+        ap.error(f"no such video: {a.video}")
+    from . import pipeline
+    src = pipeline.open_video(a.video)          # the frame index is checked before any encoder is loaded
+    try:
+        n = len(src)
+    finally:
+        if hasattr(src, "close"):
+            src.close()
+    if a.frame < 0 or a.frame >= n:
+        ap.error(f"--frame {a.frame} is out of range: {os.path.basename(a.video)} has {n} frames")
+    names = {}
+    for e in a.encoder:
+        names[e if e not in names else f"{e} ({len(names)})"] = e
+    print(compare_encoders(a.video, a.frame, names, a.out, precision=a.precision))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

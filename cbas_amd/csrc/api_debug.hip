@@ -785,6 +785,75 @@ extern "C" int cbas_debug_attention_run(const cbas_debug_attention_args* a) {
     return CBAS_OK;
 }
 
+// ---- tests: one launch of the CLS attention map kernel on host arrays ----
+namespace {
+// the first ncols columns (whole heads of 64) of rows of stride ld -> the head-split image at the same place, values x scale
+__global__ void pack_heads_split_kernel(const float* __restrict__ src, float* __restrict__ dst, int64_t rows, int64_t ld, int ncols, float scale) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;     // one thread = 4 consecutive columns
+    const int per_row = ncols / 4;
+    if (i >= rows * per_row) return;
+    const int64_t r = i / per_row;
+    const int c = (int)(i - r * per_row) * 4;
+    const f32x4 v = *reinterpret_cast<const f32x4*>(src + r * ld + c);
+    f16x4v hi, lo;                                     // store_head_split4's values, each product and difference kept scalar (common.h)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float x = keep_scalar(v[e] * scale);
+        const f16 h = (f16)x;
+        hi[e] = h;
+        lo[e] = (f16)keep_scalar(x - (float)h);
+    }
+    char* const head = reinterpret_cast<char*>(dst + r * ld + (c & ~63));
+    *reinterpret_cast<f16x4v*>(head + (c & 63) * 2) = hi;
+    *reinterpret_cast<f16x4v*>(head + 128 + (c & 63) * 2) = lo;
+}
+}  // namespace
+
+extern "C" int cbas_debug_cls_attention(int arith, const float* q_host, const float* K_host, int n, int T, int NH, int n_prefix,
+                                        int64_t ldq, int64_t ldk, float* heads_host, float* map_host) {
+    if (arith != 0 && arith != 3 && arith != 4) return cbas_fail(CBAS_EINVAL, "arith %d", arith);
+    if (!q_host || !K_host || (!heads_host && !map_host) || n <= 0 || T <= 0 || NH <= 0 || n_prefix <= 0 || n_prefix > T ||
+        ldq < 64 * (int64_t)NH || ldk < 64 * (int64_t)NH || ldq % 8 || ldk % 8 || (int64_t)n * T * ldk > ((int64_t)1 << 30) ||
+        (int64_t)n * ldq > ((int64_t)1 << 30))
+        return cbas_fail(CBAS_EINVAL, "bad CLS attention test shape / pointers");
+    const size_t nq = (size_t)n * ldq, nk = (size_t)n * T * ldk, nh = (size_t)n * NH * T, nm = (size_t)n * (T - n_prefix);
+    DevBufs B;
+    float *q32, *K32, *heads = nullptr, *map = nullptr;
+    HIP_TRY(B.alloc(&q32, nq * 4));
+    HIP_TRY(B.alloc(&K32, nk * 4));
+    HIP_TRY(hipMemcpy(q32, q_host, nq * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(K32, K_host, nk * 4, hipMemcpyHostToDevice));
+    if (heads_host) HIP_TRY(B.alloc(&heads, nh * 4));
+    if (map_host) HIP_TRY(B.alloc(&map, nm * 4));
+    int rc = 0;
+    if (arith == 0) {
+        f16 *q16, *K16;
+        HIP_TRY(B.alloc(&q16, nq * 2));
+        HIP_TRY(B.alloc(&K16, nk * 2));
+        LAUNCH_TRY(launch_convert_f16(q32, q16, nullptr, (int64_t)nq, 0));
+        LAUNCH_TRY(launch_convert_f16(K32, K16, nullptr, (int64_t)nk, 0));
+        rc = launch_cls_attention<f16>(q16, ldq, K16, ldk, n, T, NH, n_prefix, 0, heads, map, 0);
+    } else if (arith == 3) {
+        rc = launch_cls_attention<float>(q32, ldq, K32, ldk, n, T, NH, n_prefix, 0, heads, map, 0);
+    } else {
+        float *qs, *Ks;
+        HIP_TRY(B.alloc(&qs, nq * 4));
+        HIP_TRY(B.alloc(&Ks, nk * 4));
+        HIP_TRY(hipMemset(qs, 0, nq * 4));
+        HIP_TRY(hipMemset(Ks, 0, nk * 4));
+        const int64_t tq = (int64_t)n * NH * 16, tk = (int64_t)n * T * NH * 16;
+        hipLaunchKernelGGL(pack_heads_split_kernel, dim3((unsigned)((tq + 255) / 256)), dim3(256), 0, 0, q32, qs, (int64_t)n, ldq, NH * 64, ATT_QS);
+        hipLaunchKernelGGL(pack_heads_split_kernel, dim3((unsigned)((tk + 255) / 256)), dim3(256), 0, 0, K32, Ks, (int64_t)n * T, ldk, NH * 64, ATT_KS);
+        HIP_TRY(hipGetLastError());
+        rc = launch_cls_attention<float>(qs, ldq, Ks, ldk, n, T, NH, n_prefix, 1, heads, map, 0);
+    }
+    if (rc) return cbas_fail(CBAS_EINVAL, "CLS attention launch failed (arith %d, T %d: rc=%d)", arith, T, rc);
+    HIP_TRY(hipDeviceSynchronize());
+    if (heads_host) HIP_TRY(hipMemcpy(heads_host, heads, nh * 4, hipMemcpyDeviceToHost));
+    if (map_host && nm) HIP_TRY(hipMemcpy(map_host, map, nm * 4, hipMemcpyDeviceToHost));
+    return CBAS_OK;
+}
+
 // ---- tests: one launch of a row-wise kernel (LayerNorm forms, the MX-fp8 row, the ConvNeXt producers) on host operands ----
 extern "C" int cbas_debug_rows_run(const cbas_debug_rows_args* a) {
     if (!a || a->struct_bytes != (int64_t)sizeof(cbas_debug_rows_args))

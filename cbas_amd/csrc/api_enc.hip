@@ -484,6 +484,13 @@ struct RowView {
     E* q;                      // CLS rows: their queries (bias added, scaled by 1/8; no RoPE on prefix rows); nullptr: every row
 };
 
+// Optional extra outputs of a forward (cbas_enc_forward_*_attn): the last layer's CLS attention, per head (n, NH, T) and / or
+// averaged over the heads on the patch tokens (n, P).  Both null: none, the forward queues exactly what it queues without them.
+struct AttnOut {
+    float *heads = nullptr, *map = nullptr;
+    explicit operator bool() const { return heads || map; }
+};
+
 template <typename E>
 RowView<E> cls_rows(const cbas_enc* h, const VitShape& s, const Lane& ws, int n) {
     const int64_t cap = round_up(h->cfg.max_batch, 128);
@@ -622,7 +629,7 @@ int vit_tail_f32(cbas_enc* h, const Lane& ws, const LayerW& w, const VitShape& s
 }
 
 int run_blocks_f32(cbas_enc* h, const Lane& ws, int n, int height, int width, float* cls_f32, f16* cls_f16, hipStream_t st,
-                   int stop_layer, int stop_stage) {
+                   int stop_layer, int stop_stage, const AttnOut& attn = AttnOut{}) {
     VitShape s{};
     int rc = vit_begin(h, n, height, width, cls_f32 || cls_f16, stop_layer, s);
     if (rc) return rc;
@@ -669,6 +676,11 @@ int run_blocks_f32(cbas_enc* h, const Lane& ws, int n, int height, int width, fl
         }
         { PROF(CBAS_PROF_ATTENTION, 4.0 * n * (double)T * (cls_only ? 1 : T) * D);      // the view's queries against every key
           LAUNCH_TRY(launch_attention_f32(qkv32, v.q, v.ctx, n, T, D, h->NH, split ? P4_CTX_SCALE : 0.f, st)); }
+        if (attn && l == h->L - 1) {        // the CLS queries and K are still live: compact rows, or row b*T of q|k|v when nothing is pruned
+            PROF(CBAS_PROF_OTHER, 2.0 * n * (double)T * D);
+            LAUNCH_TRY(launch_cls_attention<float>(cls_only ? cls.q : qkv32, cls_only ? D : (int64_t)T * 3 * D, qkv32 + D, 3 * D, n, T,
+                                                   h->NH, h->NP, split, attn.heads, attn.map, st));
+        }
         if (stop == 3) return CBAS_OK;
 
         rc = vit_tail_f32(h, ws, w, s, v, stop, st);
@@ -681,8 +693,8 @@ int run_blocks_f32(cbas_enc* h, const Lane& ws, int n, int height, int width, fl
 
 // Everything after ingest: patch GEMM, L transformer blocks, final CLS norm.
 int run_blocks(cbas_enc* h, const Lane& ws, int n, int height, int width, int patch_k, float in_scale, float* cls_f32,
-               f16* cls_f16, hipStream_t st, int stop_layer, int stop_stage) {
-    if (h->cfg.precision >= 3) return run_blocks_f32(h, ws, n, height, width, cls_f32, cls_f16, st, stop_layer, stop_stage);
+               f16* cls_f16, hipStream_t st, int stop_layer, int stop_stage, const AttnOut& attn = AttnOut{}) {
+    if (h->cfg.precision >= 3) return run_blocks_f32(h, ws, n, height, width, cls_f32, cls_f16, st, stop_layer, stop_stage, attn);
     VitShape s{};
     int rc = vit_begin(h, n, height, width, cls_f32 || cls_f16, stop_layer, s);
     if (rc) return rc;
@@ -736,6 +748,11 @@ int run_blocks(cbas_enc* h, const Lane& ws, int n, int height, int width, int pa
         }
         { PROF(CBAS_PROF_ATTENTION, 4.0 * n * (double)T * (cls_only ? 1 : T) * D);      // the view's queries against every key
           LAUNCH_TRY(launch_attention(ws.qkv16, v.q, v.ctx, f.f8_proj && !cls_only ? ws.sc_h : nullptr, cls_only ? 0 : sc_ld, n, T, D, h->NH, st)); }
+        if (attn && l == h->L - 1) {        // q and K are fp16 in every mode of this family (see run_blocks_f32 for the two query layouts)
+            PROF(CBAS_PROF_OTHER, 2.0 * n * (double)T * D);
+            LAUNCH_TRY(launch_cls_attention<f16>(cls_only ? cls.q : ws.qkv16, cls_only ? D : (int64_t)T * 3 * D, ws.qkv16 + D, 3 * D, n, T,
+                                                 h->NH, h->NP, 0, attn.heads, attn.map, st));
+        }
         if (stop == 3) return CBAS_OK;
 
         rc = vit_tail(h, ws, w, s, f, v, l + 1 < h->L, stop, st);
@@ -807,7 +824,7 @@ int run_cnx(cbas_enc* h, const Lane& ws, int n, int height, int width, float* cl
 
 int forward_u8_one(cbas_enc* h, const Lane& ws, const uint8_t* frames_dev, int n, int height, int width, int64_t frame_stride,
                    int64_t row_stride, int64_t pixel_stride, float* cls_f32, f16* cls_f16, hipStream_t st,
-                   int stop_layer, int stop_stage) {
+                   int stop_layer, int stop_stage, const AttnOut& attn = AttnOut{}) {
     if (h->cfg.family == 1) {
         LAUNCH_TRY(launch_cnx_stem_im2col_u8(frames_dev, n, height, width, frame_stride, row_stride, pixel_stride,
                                              reinterpret_cast<float*>(ws.h16), h->cfg.precision == 4, st));
@@ -823,18 +840,18 @@ int forward_u8_one(cbas_enc* h, const Lane& ws, const uint8_t* frames_dev, int n
     else
         LAUNCH_TRY(launch_im2col_u8(frames_dev, n, height, width, frame_stride, row_stride, pixel_stride, ws.A_patch,
                                     ws.x, h->prefix, h->NP, h->D, T, ps, st));
-    return run_blocks(h, ws, n, height, width, 256, 1.0f / 255.0f, cls_f32, cls_f16, st, stop_layer, stop_stage);
+    return run_blocks(h, ws, n, height, width, 256, 1.0f / 255.0f, cls_f32, cls_f16, st, stop_layer, stop_stage, attn);
 }
 
 int forward_u8(cbas_enc* h, const Lane& ws, const uint8_t* frames_dev, int n, int height, int width, int64_t frame_stride,
                int64_t row_stride, int64_t pixel_stride, float* cls_f32, f16* cls_f16, hipStream_t st,
-               int stop_layer, int stop_stage) {
+               int stop_layer, int stop_stage, const AttnOut& attn = AttnOut{}) {
     int rc = check_frame(h, n, height, width);
     if (rc) return rc;
     if (!frames_dev) return cbas_fail(CBAS_EINVAL, "frames_dev is NULL");
     HIP_TRY(hipSetDevice(h->device));
     return forward_u8_one(h, ws, frames_dev, n, height, width, frame_stride, row_stride, pixel_stride, cls_f32, cls_f16, st,
-                          stop_layer, stop_stage);
+                          stop_layer, stop_stage, attn);
 }
 
 // The buffers of lanes[lane], each zero-filled whole on `st` (the handle's compute stream: see the note at qkv_bias_all in
@@ -1445,21 +1462,59 @@ static int async_leave(cbas_enc* h, int lane, hipStream_t ls) {
     return CBAS_OK;
 }
 
-extern "C" int cbas_enc_forward_u8(cbas_enc* h, const uint8_t* frames_dev, int n, int height, int width,
-                                   int64_t frame_stride, int64_t row_stride, int64_t pixel_stride,
-                                   float* cls_f32_dev, uint16_t* cls_f16_dev, void* stream) {
+// the two synchronous forwards, with or without the attention outputs
+static int enc_forward_u8(cbas_enc* h, const uint8_t* frames_dev, int n, int height, int width, int64_t frame_stride,
+                          int64_t row_stride, int64_t pixel_stride, float* cls_f32_dev, uint16_t* cls_f16_dev, void* stream,
+                          const AttnOut& attn) {
     if (!h) return cbas_fail(CBAS_EINVAL, "null encoder handle");
     hipStream_t st = (hipStream_t)stream;
     int rc = sync_enter(h, st);
     if (rc) return rc;
     rc = forward_u8(h, h->lanes[0], frames_dev, n, height, width, frame_stride, row_stride, pixel_stride, cls_f32_dev,
-                    (f16*)cls_f16_dev, st, -1, -1);
+                    (f16*)cls_f16_dev, st, -1, -1, attn);
     if (rc) return rc;
     return sync_leave(h, st);
 }
 
-extern "C" int cbas_enc_forward_f32(cbas_enc* h, const float* x_dev, int n, int height, int width,
-                                    float* cls_f32_dev, uint16_t* cls_f16_dev, void* stream) {
+// the refusals of the ..._attn forms
+static int check_attn(const cbas_enc* h, const AttnOut& attn) {
+    if (!h) return cbas_fail(CBAS_EINVAL, "null encoder handle");
+    if (h->cfg.family == 1) return cbas_fail(CBAS_EINVAL, "a ConvNeXt encoder has no attention: CLS attention maps exist for the ViT families only");
+    if (!attn) return cbas_fail(CBAS_EINVAL, "attn_heads_dev and attn_map_dev are both NULL (cbas_enc_forward_u8 / _f32 are the forms without maps)");
+    return CBAS_OK;
+}
+// ... and of a frame whose token row does not fit the map kernel's LDS: refused before anything is queued
+static int check_attn_frame(const cbas_enc* h, int height, int width) {
+    const int ps = h->cfg.patch_size;
+    if (ps <= 0 || height < ps || width < ps) return CBAS_OK;      // check_frame names these
+    const int64_t T = (int64_t)(height / ps) * (width / ps) + h->NP;
+    if ((2 * T - h->NP) * (int64_t)sizeof(float) > CLS_ATTENTION_LDS_BYTES)
+        return cbas_fail(CBAS_EINVAL, "frame %dx%d has %lld tokens: the CLS attention map kernel holds at most %lld", height, width,
+                         (long long)T, (long long)((CLS_ATTENTION_LDS_BYTES / (int64_t)sizeof(float) + h->NP) / 2));
+    return CBAS_OK;
+}
+
+extern "C" int cbas_enc_forward_u8(cbas_enc* h, const uint8_t* frames_dev, int n, int height, int width,
+                                   int64_t frame_stride, int64_t row_stride, int64_t pixel_stride,
+                                   float* cls_f32_dev, uint16_t* cls_f16_dev, void* stream) {
+    return enc_forward_u8(h, frames_dev, n, height, width, frame_stride, row_stride, pixel_stride, cls_f32_dev, cls_f16_dev, stream,
+                          AttnOut{});
+}
+
+extern "C" int cbas_enc_forward_u8_attn(cbas_enc* h, const uint8_t* frames_dev, int n, int height, int width,
+                                        int64_t frame_stride, int64_t row_stride, int64_t pixel_stride,
+                                        float* cls_f32_dev, uint16_t* cls_f16_dev, void* stream, float* attn_heads_dev,
+                                        float* attn_map_dev) {
+    AttnOut attn;
+    attn.heads = attn_heads_dev; attn.map = attn_map_dev;
+    int rc = check_attn(h, attn);
+    if (!rc) rc = check_attn_frame(h, height, width);
+    if (rc) return rc;
+    return enc_forward_u8(h, frames_dev, n, height, width, frame_stride, row_stride, pixel_stride, cls_f32_dev, cls_f16_dev, stream, attn);
+}
+
+static int enc_forward_f32(cbas_enc* h, const float* x_dev, int n, int height, int width, float* cls_f32_dev,
+                           uint16_t* cls_f16_dev, void* stream, const AttnOut& attn) {
     int rc = check_frame(h, n, height, width);
     if (rc) return rc;
     if (!x_dev) return cbas_fail(CBAS_EINVAL, "x_dev is NULL");
@@ -1481,9 +1536,25 @@ extern "C" int cbas_enc_forward_f32(cbas_enc* h, const float* x_dev, int n, int 
                                          h->cfg.precision == 4, st));
     else
         LAUNCH_TRY(launch_im2col_f32(x_dev, n, height, width, ws.A_patch, ws.x, h->prefix, h->NP, h->D, T, ps, st));
-    rc = run_blocks(h, ws, n, height, width, 512, 1.0f, cls_f32_dev, (f16*)cls_f16_dev, st, -1, -1);
+    rc = run_blocks(h, ws, n, height, width, 512, 1.0f, cls_f32_dev, (f16*)cls_f16_dev, st, -1, -1, attn);
     if (rc) return rc;
     return sync_leave(h, st);
+}
+
+extern "C" int cbas_enc_forward_f32(cbas_enc* h, const float* x_dev, int n, int height, int width,
+                                    float* cls_f32_dev, uint16_t* cls_f16_dev, void* stream) {
+    return enc_forward_f32(h, x_dev, n, height, width, cls_f32_dev, cls_f16_dev, stream, AttnOut{});
+}
+
+extern "C" int cbas_enc_forward_f32_attn(cbas_enc* h, const float* x_dev, int n, int height, int width,
+                                         float* cls_f32_dev, uint16_t* cls_f16_dev, void* stream, float* attn_heads_dev,
+                                         float* attn_map_dev) {
+    AttnOut attn;
+    attn.heads = attn_heads_dev; attn.map = attn_map_dev;
+    int rc = check_attn(h, attn);
+    if (!rc) rc = check_attn_frame(h, height, width);
+    if (rc) return rc;
+    return enc_forward_f32(h, x_dev, n, height, width, cls_f32_dev, cls_f16_dev, stream, attn);
 }
 
 #if CBAS_BUILD_DEBUG      // stage taps: debug build only (include/cbas_mi355x_debug.h)

@@ -145,6 +145,17 @@ int launch_final_norm_cls(const float* x, const float* gamma, const float* beta,
 int launch_attention(const f16* qkv, const f16* q_cls, void* out, uint32_t* out_sc, int sc_ld, int n, int T, int D,
                      int n_heads, hipStream_t stream);
 
+// cls_attention.hip: the CLS query's softmax row over every token, per head and head-averaged over the patch tokens
+// (compare_encoders.py:36-49).  E = f16 (precisions 0, 1, 2) or float (3; 4 with split != 0: q and K in the head-split hi | lo
+// form of store_head_split4, scales ATT_QS / ATT_KS).  q [n] rows of stride ldq (bias added, x 1/8), K [n*T] rows of stride ldk,
+// both pointing at head 0's first column; NP prefix tokens.  heads_out (n, NH, T) and map_out (n, T - NP), fp32; either may be
+// nullptr, not both.  One workgroup per frame, fixed summation order, no scratch.  -1: bad argument, or T beyond the 64 KiB of LDS
+// (2 T - NP floats: about 8 000 tokens).
+constexpr int64_t CLS_ATTENTION_LDS_BYTES = 64 * 1024 - 256;      // dynamic LDS of a launch: (2 T - NP) floats must fit
+template <typename E>
+int launch_cls_attention(const E* q, int64_t ldq, const E* K, int64_t ldk, int n, int T, int NH, int NP, int split,
+                         float* heads_out, float* map_out, hipStream_t stream);
+
 // gated MLP, create time: out [2F][K] = rows of gate [F][K] and up [F][K] interleaved in blocks of 32 - out rows [64 b, 64 b + 32)
 // are gate rows [32 b, 32 b + 32), out rows [64 b + 32, 64 b + 64) the up rows of the same outputs (K = 1: the biases); F % 32 == 0
 int launch_interleave_gate_up(const float* gate, const float* up, float* out, int64_t F, int K, hipStream_t stream);

@@ -301,6 +301,57 @@ class DinoEncoder:
                 "cbas_enc_forward_u8")
         return out16, out32
 
+    def cls_attention(self, frames: torch.Tensor, channel: int = 1, per_head: bool = False):
+        """The CLS rows plus the last layer's attention from the CLS token to the patch tokens, averaged over the heads - what
+        ``output_attentions=True`` gives the reference's encoder comparison tool - computed on the device from the query and keys
+        of the forward itself (cbas_enc_forward_u8_attn / cbas_enc_forward_f32_attn).
+
+        frames: the uint8 device tensors ``encode_u8`` takes ((n,H,W,3) with ``channel`` picking green, or (n,H,W)), or the
+        reference-form float32 (B,1,H,W) tensor in [0, 1].  Returns ``(cls_f16, cls_f32, maps)`` with ``maps`` a float32
+        (n, nh, nw) device tensor over the patch grid; with ``per_head=True`` a fourth element, the (n, NH, T) softmax rows
+        over all T tokens (CLS and registers first).  The CLS rows are bit for bit ``encode_u8``'s.  Every ViT precision is served;
+        a precision-2 encoder's map is the map of that MX-fp8 encoder, not of the fp16 one.  ConvNeXt encoders have no attention:
+        ``ValueError``."""
+        if is_convnext(self.config):
+            raise ValueError("a ConvNeXt encoder has no attention: CLS attention maps exist for the ViT families only")
+        assert frames.is_cuda
+        if frames.dtype == torch.uint8:
+            frames = frames.contiguous()
+            if frames.dim() == 4:
+                n, H, W, Cn = frames.shape
+                strides, base_off = (H * W * Cn, W * Cn, Cn), channel
+            else:
+                n, H, W = frames.shape
+                strides, base_off = (H * W, W, 1), 0
+        else:
+            if frames.dtype != torch.float32 or frames.dim() != 4 or frames.shape[1] != 1:
+                raise ValueError("cls_attention takes uint8 (n,H,W,3) / (n,H,W) frames or a float32 (B,1,H,W) tensor")
+            frames = frames.contiguous()
+            n, _, H, W = frames.shape
+            strides = None
+        self._fit_frame(H, W)
+        cfg = self.config
+        D, NH, ps = cfg.hidden_size, cfg.num_attention_heads, cfg.patch_size
+        nh, nw = H // ps, W // ps
+        T = cfg.num_tokens(H, W)
+        out16 = torch.empty((n, D), dtype=torch.float16, device=self.device)
+        out32 = torch.empty((n, D), dtype=torch.float32, device=self.device)
+        maps = torch.empty((n, nh, nw), dtype=torch.float32, device=self.device)
+        heads = torch.empty((n, NH, T), dtype=torch.float32, device=self.device) if per_head else None
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        for i in range(0, n, self.max_batch):
+            m = min(self.max_batch, n - i)
+            hp = heads[i:i + m].data_ptr() if per_head else None
+            if strides is None:
+                _lib.check(self._lib.cbas_enc_forward_f32_attn(self._h, frames[i:i + m].data_ptr(), m, H, W, out32[i:i + m].data_ptr(),
+                                                               out16[i:i + m].data_ptr(), stream, hp, maps[i:i + m].data_ptr()),
+                           "cbas_enc_forward_f32_attn")
+            else:
+                _lib.check(self._lib.cbas_enc_forward_u8_attn(self._h, frames[i:i + m].data_ptr() + base_off, m, H, W, *strides,
+                                                              out32[i:i + m].data_ptr(), out16[i:i + m].data_ptr(), stream, hp,
+                                                              maps[i:i + m].data_ptr()), "cbas_enc_forward_u8_attn")
+        return (out16, out32, maps, heads) if per_head else (out16, out32, maps)
+
     def submit_host(self, slot: int, frames: np.ndarray, channel: int = 1) -> None:
         """Queue one host chunk (uint8 (n,H,W,3) or (n,H,W), C-contiguous) on ``slot``."""
         assert frames.dtype == np.uint8 and frames.flags.c_contiguous

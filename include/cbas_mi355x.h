@@ -12,6 +12,8 @@
  *   cbas_enc_forward_f32                   backend/cbas.py:672-677   DinoEncoder.forward
  *                                          + [tf]:523-548 DINOv3ViTModel.forward (CLS row only)
  *   cbas_enc_forward_u8                    backend/cbas.py:431-436   green/255 preprocessing + encoder call
+ *   cbas_enc_forward_u8_attn / _f32_attn   compare_encoders.py:36-49 the last layer's attention from the CLS token to
+ *                                          the patch tokens, averaged over heads (output_attentions=True), beside the CLS rows
  *   cbas_enc_submit_u8_host / cbas_enc_wait  backend/cbas.py:423-440 one iteration of the chunk loop
  *                                          (H2D copy, encode, D2H copy), made asynchronous
  *   cbas_head_create / cbas_head_destroy   backend/workthreads.py:427-447 ClassifierLSTMDeltas(...)
@@ -53,8 +55,9 @@ extern "C" {
 #define CBAS_ERANGE       -5   /* a frame's CLS row came out NaN / infinite: an activation left the arithmetic mode's range */
 
 /* Still 11 with cbas_rows_gather_windows / cbas_head_train_step_rows, with cbas_head_score_rows / cbas_logits_nll, with
- * cbas_enc_set_pos_interp, with cbas_enc_set_fp8_plan, with cbas_probs_top1 / cbas_disagreement_runs and with
- * cbas_labels_median / cbas_label_runs / cbas_activity_bins: they are additions.  No structure and no existing signature
+ * cbas_enc_set_pos_interp, with cbas_enc_set_fp8_plan, with cbas_probs_top1 / cbas_disagreement_runs, with
+ * cbas_labels_median / cbas_label_runs / cbas_activity_bins and with cbas_enc_forward_u8_attn / cbas_enc_forward_f32_attn: they
+ * are additions.  No structure and no existing signature
  * changed, so a caller built against the earlier version 11 header runs unchanged. */
 #define CBAS_ABI_VERSION   11
 
@@ -183,6 +186,26 @@ int cbas_enc_forward_u8(cbas_enc* h, const uint8_t* frames_dev, int n, int heigh
                         int64_t frame_stride, int64_t row_stride, int64_t pixel_stride,
                         float* cls_f32_dev, uint16_t* cls_f16_dev, void* stream);
 
+/* The same two forwards with the last layer's CLS attention as extra outputs - what the reference's encoder comparison tool
+ * shows (compare_encoders.py:36-49: outputs.attentions[-1][0, :, 0, NP:] averaged over the heads, :72-79 reshaped to the
+ * patch grid).  For frame b, head k and token t < T (T = NP + P: CLS, registers, then the patches in row-major grid order):
+ *     attn_heads_dev (n, NH, T) fp32:  softmax over ALL T tokens of q_cls . k_t / 8 of the last layer (rows sum to 1)
+ *     attn_map_dev   (n, P)     fp32:  the mean over the heads (ascending) of columns NP .. T-1 of the above
+ * Either may be NULL, not both (CBAS_EINVAL; the forms above are the calls without maps).  A ConvNeXt handle is CBAS_EINVAL:
+ * it has no attention.  Every ViT precision is served; the scores are formed in fp32 from the query and keys the forward
+ * itself uses (fp16 in precisions 0 - 2, fp32 in 3, 22-bit fp16 pairs in 4), in a fixed order, so a frame's map depends on
+ * neither n nor its place in the batch.  The CLS rows are bit for bit those of the call without maps, and nothing else the
+ * forward computes changes.  Precision 2 (and the LayerNorm-fold option) give the map of THAT encoder - MX-fp8 layers below
+ * the last one - not of the fp16 one.  T may not exceed about 8 000 tokens (the kernel keeps one head's row in
+ * 64 KiB of LDS); a larger frame is CBAS_EINVAL. */
+int cbas_enc_forward_f32_attn(cbas_enc* h, const float* x_dev, int n, int height, int width,
+                              float* cls_f32_dev, uint16_t* cls_f16_dev, void* stream,
+                              float* attn_heads_dev, float* attn_map_dev);
+int cbas_enc_forward_u8_attn(cbas_enc* h, const uint8_t* frames_dev, int n, int height, int width,
+                             int64_t frame_stride, int64_t row_stride, int64_t pixel_stride,
+                             float* cls_f32_dev, uint16_t* cls_f16_dev, void* stream,
+                             float* attn_heads_dev, float* attn_map_dev);
+
 /* Host-streamed form (one iteration of encode_file's chunk loop).  `slot` in [0, CBAS_ENC_SLOTS):
  * submit copies the pixels host->HBM on the handle's copy stream (from pinned staging), encodes
  * on the compute stream and copies the CLS rows back; wait blocks until that slot is done and
@@ -281,7 +304,9 @@ int cbas_enc_set_fp8_plan(cbas_enc* h, int plan);
  * and sums elapsed milliseconds, launch counts and algorithmic FLOPs per category (arrays of
  * CBAS_PROF_NCAT entries); reset != 0 clears the records. */
 enum { CBAS_PROF_PATCH = 0, CBAS_PROF_LAYERNORM = 1, CBAS_PROF_QKV = 2, CBAS_PROF_ATTENTION = 3,
-       CBAS_PROF_OPROJ = 4, CBAS_PROF_UP = 5, CBAS_PROF_DOWN = 6, CBAS_PROF_NCAT = 8 };
+       CBAS_PROF_OPROJ = 4, CBAS_PROF_UP = 5, CBAS_PROF_DOWN = 6,
+       CBAS_PROF_OTHER = 7,      /* the CLS attention map kernel of the ..._attn forwards */
+       CBAS_PROF_NCAT = 8 };
 int cbas_enc_profile(cbas_enc* h, int enable);
 int cbas_enc_profile_read(cbas_enc* h, double* ms_by_cat, int64_t* launches_by_cat, double* flops_by_cat,
                           int reset);

@@ -149,6 +149,14 @@ typedef struct cbas_debug_attention_args {
 } cbas_debug_attention_args;
 int cbas_debug_attention_run(const cbas_debug_attention_args* a);
 
+/* Tests: ONE launch of the CLS attention map kernel (cls_attention.hip) on host arrays.  arith 0: fp16 operands (the values
+ * are converted, so the caller supplies fp16-representable ones); 3: fp32; 4: the head-split hi | lo operands of precision 4
+ * (q x 16, K x 4, packed as the q|k|v epilogue packs them).  q_host: n rows of stride ldq floats, K_host: n T rows of stride
+ * ldk floats, the NH heads in columns 0 .. 64 NH - 1 of both (q already x 1/8); n_prefix = NP.  heads_host (n, NH, T) and
+ * map_host (n, T - NP) fp32; either may be NULL, not both. */
+int cbas_debug_cls_attention(int arith, const float* q_host, const float* K_host, int n, int T, int NH, int n_prefix,
+                             int64_t ldq, int64_t ldk, float* heads_host, float* map_host);
+
 /* Tests: ONE launch of a row-wise encoder kernel on host operands (tests/test_gpu_rows_reference.py compares it with the float64
  * references of oracle/kernel_ref.py).  The harness uploads x (x_bytes) and the caller's pre-filled output images (out_bytes /
  * out2_bytes / *counter), runs exactly one launcher on the default stream and copies the whole output images back: whatever
