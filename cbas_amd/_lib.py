@@ -54,6 +54,9 @@ SIGNATURES = {
     "cbas_enc_forward_f32_attn": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cbas_enc_forward_u8_attn": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_int64, c_int64,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cbas_enc_forward_f32_tokens": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "cbas_enc_forward_u8_tokens": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_int64, c_int64,
+                                           c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "cbas_enc_submit_u8_host": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int64, c_int64, c_int64]),
     "cbas_enc_wait": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "cbas_enc_submit_u8": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_void_p,
@@ -161,7 +164,7 @@ TRAIN_MULTI_MAX = 8                                   # CBAS_TRAIN_MULTI_MAX of 
 POS_INTERP_BICUBIC_AA, POS_INTERP_BICUBIC = 0, 1      # CBAS_POS_INTERP_* of include/cbas_mi355x.h
 MLP_GELU, MLP_SWIGLU = 0, 1                           # CBAS_MLP_* of include/cbas_mi355x.h
 EXPECTED_ABI = 11         # CBAS_ABI_VERSION of include/cbas_mi355x.h these ctypes structures mirror
-PROF_CATS = ["patch_gemm", "layernorm", "qkv_gemm", "attention", "oproj_gemm", "up_gemm", "down_gemm", "other"]      # other: the CLS attention map kernel
+PROF_CATS = ["patch_gemm", "layernorm", "qkv_gemm", "attention", "oproj_gemm", "up_gemm", "down_gemm", "other"]      # other: the CLS attention map and token similarity kernels
 
 
 def library_path() -> str:

@@ -3,6 +3,11 @@ frames of a video - the picture the reference's encoder comparison tool draws (c
 the device by ``DinoEncoder.cls_attention`` beside the CLS rows.
 
     python -m cbas_amd.attention_maps --video V --frame N --encoder ID [--encoder ID ...] --out PNG [--precision P]
+                                      [--kind attention|similarity] [--query Y,X]
+
+``--kind similarity`` draws the other picture of the same question, from ``DinoEncoder.similarity_map``: the cosine of the CLS
+token's final hidden state (``--query Y,X``: of the patch under that pixel) to every patch token's.  It needs no attention, so it
+is the kind DINOv3 ConvNeXt encoders have (their query row is the pooled one, their grid the last stage's 32 x 32 pixel cells).
 
 One deliberate difference from that tool: the map here is the map of what the encoder sees INSIDE CBAS - the green plane / 255
 replicated to three channels at the video's own size, exactly what ``encode_file`` feeds the model (backend/cbas.py:431) - not
@@ -19,13 +24,30 @@ from typing import Mapping, Sequence, Tuple, Union
 import numpy as np
 
 
-def frame_maps(encoder, path: str, frame_indices: Sequence[int]):
-    """Attention maps of the given frames of a video.  Frames are read through ``pipeline.open_video`` (any source it knows) and
+KINDS = ("attention", "similarity")
+
+
+def refuse_kind(cfg, kind: str):
+    """Why an encoder of config ``cfg`` has no map of ``kind``, or None."""
+    from .config import is_convnext
+    if kind not in KINDS:
+        return f"unknown map kind {kind!r}: one of {', '.join(KINDS)}"
+    if kind == "attention" and is_convnext(cfg):
+        return "a ConvNeXt encoder has no attention: --kind similarity is the map it has"
+    return None
+
+
+def frame_maps(encoder, path: str, frame_indices: Sequence[int], kind: str = "attention", query=None):
+    """Maps of the given frames of a video: ``kind`` "attention" (``cls_attention``) or "similarity" (``similarity_map`` of
+    ``query``: None, or a pixel (y, x)).  Frames are read through ``pipeline.open_video`` (any source it knows) and
     encoded in batches of ``encoder.max_batch``.  Returns ``(maps, frames_green)``: float32 (n, nh, nw) and uint8 (n, H, W)
     numpy arrays, in the order of ``frame_indices``."""
     import torch
     from . import pipeline
     idx = [int(i) for i in frame_indices]
+    why = refuse_kind(encoder.config, kind)
+    if why:
+        raise ValueError(why)
     if not idx:
         raise ValueError("no frame index given")
     src = pipeline.open_video(path)
@@ -41,7 +63,7 @@ def frame_maps(encoder, path: str, frame_indices: Sequence[int]):
                                 else np.concatenate([np.asarray(src.get_batch([j])) for j in part]))
             green = np.ascontiguousarray(frames[:, :, :, 1] if frames.ndim == 4 else frames)      # backend/cbas.py:431
             dev = torch.from_numpy(green).to(encoder.device)
-            maps.append(encoder.cls_attention(dev)[2].cpu().numpy())
+            maps.append((encoder.cls_attention(dev)[2] if kind == "attention" else encoder.similarity_map(dev, query)).cpu().numpy())
             greens.append(green)
         return np.concatenate(maps), np.concatenate(greens)
     finally:
@@ -67,8 +89,10 @@ def _to_u8(a: np.ndarray) -> np.ndarray:
     return (a * 255).astype(np.uint8)
 
 
-def compare_encoders(video: str, frame_idx: int, encoders: Mapping[str, Union[str, object]], out_png: str, precision=None) -> str:
-    """One figure row per encoder: the frame as the encoder receives it (green plane) beside its rendered attention map.
+def compare_encoders(video: str, frame_idx: int, encoders: Mapping[str, Union[str, object]], out_png: str, precision=None,
+                     kind: str = "attention", query=None) -> str:
+    """One figure row per encoder: the frame as the encoder receives it (green plane) beside its rendered map (``kind``, ``query``:
+    see ``frame_maps``).
     ``encoders`` maps a display name to a checkpoint directory, an HF-cache id or a ready ``DinoEncoder``; encoders built here
     are closed again.  Returns ``out_png``."""
     if not encoders:
@@ -82,12 +106,14 @@ def compare_encoders(video: str, frame_idx: int, encoders: Mapping[str, Union[st
         if own:
             enc = DinoEncoder(enc, **({} if precision is None else {"precision": int(precision)}))
         try:
-            maps, green = frame_maps(enc, video, [frame_idx])
+            maps, green = frame_maps(enc, video, [frame_idx], kind, query)
         finally:
             if own:
                 enc.close()
         panels.append((name, green[0], maps[0].shape, render_map(maps[0], (green.shape[2], green.shape[1]))))
-    _draw(Figure, FigureCanvasAgg, panels, f"{os.path.basename(video)}, frame {frame_idx}", out_png)
+    what = ("where its CLS token looks (last layer, mean of heads)" if kind == "attention" else
+            "cosine of the final hidden states: " + ("CLS / pooled row" if query is None else f"patch at pixel {tuple(query)}") + " to each patch")
+    _draw(Figure, FigureCanvasAgg, panels, f"{os.path.basename(video)}, frame {frame_idx}", out_png, what)
     return out_png
 
 
@@ -95,7 +121,7 @@ PANEL_HEIGHT_IN = 3.2        # every panel is this tall; its width follows the v
 LABEL_WIDTH_IN = 0.6         # room at the left for the encoders' names
 
 
-def _draw(Figure, Canvas, panels, caption: str, out_png: str) -> None:
+def _draw(Figure, Canvas, panels, caption: str, out_png: str, what: str) -> None:
     """panels: (name, green plane (H, W) uint8, patch grid (nh, nw), rendered map (H, W) uint8) per encoder, top to bottom."""
     H, W = panels[0][1].shape
     panel_w = PANEL_HEIGHT_IN * W / H
@@ -113,7 +139,7 @@ def _draw(Figure, Canvas, panels, caption: str, out_png: str) -> None:
             a.set_yticks([])
         if r == 0:
             left.set_title("what the encoder is fed: green / 255", fontsize=10)
-            right.set_title("where its CLS token looks (last layer, mean of heads)", fontsize=10)
+            right.set_title(what, fontsize=10)
     fig.supxlabel(f"{caption}, {H} x {W} pixels", fontsize=9)
     fig.savefig(out_png, dpi=110)
 
@@ -125,7 +151,18 @@ def main(argv=None) -> int:
     ap.add_argument("--encoder", action="append", default=[], metavar="ID", help="checkpoint directory or HF-cache id; repeatable")
     ap.add_argument("--out", required=True, metavar="PNG")
     ap.add_argument("--precision", type=int, default=None)
+    ap.add_argument("--kind", choices=KINDS, default="attention", help="similarity: the only kind a ConvNeXt encoder has")
+    ap.add_argument("--query", default=None, metavar="Y,X", help="similarity: the pixel whose patch is the query (default: the CLS / pooled row)")
     a = ap.parse_args(argv)
+    query = None
+    if a.query is not None:
+        if a.kind != "similarity":
+            ap.error("--query goes with --kind similarity")
+        try:
+            y, x = (int(v) for v in a.query.split(","))
+        except ValueError:
+            ap.error(f"--query {a.query!r}: two integers Y,X")
+        query = (y, x)
     if not a.encoder:
         ap.error("at least one --encoder is needed")
     if not os.path.exists(a.video):
@@ -139,10 +176,15 @@ def main(argv=None) -> int:
             src.close()
     if a.frame < 0 or a.frame >= n:
         ap.error(f"--frame {a.frame} is out of range: {os.path.basename(a.video)} has {n} frames")
+    from .config import encoder_config_from_json, find_checkpoint_dir
     names = {}
     for e in a.encoder:
+        # the kind is checked against every checkpoint's config before any is loaded
+        why = refuse_kind(encoder_config_from_json(os.path.join(find_checkpoint_dir(e), "config.json")), a.kind)
+        if why:
+            ap.error(f"--encoder {e}: {why}")
         names[e if e not in names else f"{e} ({len(names)})"] = e
-    print(compare_encoders(a.video, a.frame, names, a.out, precision=a.precision))
+    print(compare_encoders(a.video, a.frame, names, a.out, precision=a.precision, kind=a.kind, query=query))
     return 0
 
 

@@ -27,7 +27,7 @@ LIB_NAME = "libcbas_mi355x.so"
 LIB_PATH = os.path.join(HERE, LIB_NAME)
 DEBUG_LIB_NAME = "libcbas_mi355x_debug.so"
 DEBUG_LIB_PATH = os.path.join(HERE, DEBUG_LIB_NAME)
-SOURCES = ["gemm_f16.hip", "gemm_f16_8ph.hip", "gemm_f16_skinny.hip", "gemm_f32.hip", "vit_f32.hip", "convnext_f32.hip", "vit_kernels.hip", "cls_attention.hip", "head_kernels.hip", "head_train_kernels.hip", "rows_gather.hip", "head_score_kernels.hip", "head_report_kernels.hip", "head_post_kernels.hip",
+SOURCES = ["gemm_f16.hip", "gemm_f16_8ph.hip", "gemm_f16_skinny.hip", "gemm_f32.hip", "vit_f32.hip", "convnext_f32.hip", "vit_kernels.hip", "cls_attention.hip", "tokens_out.hip", "head_kernels.hip", "head_train_kernels.hip", "rows_gather.hip", "head_score_kernels.hip", "head_report_kernels.hip", "head_post_kernels.hip",
            "api_enc.hip", "api_head.hip", "api_head_train.hip", "api_fused.hip", "host_text.cpp", "host_mjpeg.cpp", "host_pixels.cpp"]
 DEBUG_ONLY_SOURCES = ["api_debug.hip"]            # harnesses: never in the product
 # -packed-fp32-ops: no v_pk_*_f32 at all in the head's kernels (VALU-light; nothing to gain from packed math) - the blunt way to

@@ -865,17 +865,34 @@ extern "C" int cbas_debug_rows_run(const cbas_debug_rows_args* a) {
     const bool cls = op == CBAS_DEBUG_ROWS_FINAL_CLS || op == CBAS_DEBUG_ROWS_CNX_POOL_LN;
     const bool stem = op == CBAS_DEBUG_ROWS_CNX_STEM_U8 || op == CBAS_DEBUG_ROWS_CNX_STEM_F32;
     const bool cnx = op >= CBAS_DEBUG_ROWS_CNX_LN_ROWS && op <= CBAS_DEBUG_ROWS_CNX_POOL_LN;
-    if (op < CBAS_DEBUG_ROWS_LN_F16 || op > CBAS_DEBUG_ROWS_CNX_POOL_LN) return cbas_fail(CBAS_EINVAL, "op %d", op);
+    const bool tok_rows = op == CBAS_DEBUG_ROWS_TOKEN_ROWS, tok_cnx = tok_rows && (h || w), tok_sim = op == CBAS_DEBUG_ROWS_TOKEN_SIM;
+    if (op < CBAS_DEBUG_ROWS_LN_F16 || op > CBAS_DEBUG_ROWS_TOKEN_SIM) return cbas_fail(CBAS_EINVAL, "op %d", op);
     // what the launch reads (x_need) and writes (out_need, out2_need), in bytes: the images must hold it
     int64_t x_need = 0, out_need = 0, out2_need = 0;
     if (!stem) {
-        if (D <= 0 || D % 4 || !a->gamma || !a->beta) return cbas_fail(CBAS_EINVAL, "D = %d: a positive multiple of 4; gamma / beta", D);
-        if ((vit_ln || op == CBAS_DEBUG_ROWS_FINAL_CLS) && D > 1280) return cbas_fail(CBAS_EINVAL, "D = %d: the ViT LayerNorms stop at 1280", D);
+        if (D <= 0 || D % 4 || (!tok_sim && (!a->gamma || !a->beta))) return cbas_fail(CBAS_EINVAL, "D = %d: a positive multiple of 4; gamma / beta", D);
+        if ((vit_ln || op == CBAS_DEBUG_ROWS_FINAL_CLS || (tok_rows && !tok_cnx)) && D > 1280) return cbas_fail(CBAS_EINVAL, "D = %d: the ViT LayerNorms stop at 1280", D);
         if (op == CBAS_DEBUG_ROWS_LN_SPLIT && D % 32) return cbas_fail(CBAS_EINVAL, "LN_SPLIT: D %% 32");
         if (op == CBAS_DEBUG_ROWS_LN_F8 && (D % 128 || D < 256 || D > 1024)) return cbas_fail(CBAS_EINVAL, "LN_F8: D = 256 .. 1024 in steps of 128");
-        if (cnx && (D % 32 || D > 1536)) return cbas_fail(CBAS_EINVAL, "ConvNeXt width %d: a multiple of 32 up to 1536", D);
+        if ((cnx || tok_cnx) && (D % 32 || D > 1536)) return cbas_fail(CBAS_EINVAL, "ConvNeXt width %d: a multiple of 32 up to 1536", D);
     }
-    if (vit_ln || op == CBAS_DEBUG_ROWS_CNX_LN_ROWS) {
+    if (tok_rows || tok_sim) {
+        // TOKEN_ROWS: sc_ld = the output images' row stride; TOKEN_SIM: M = the prefix rows P0, wt = int32 query indices or NULL
+        const int64_t rows = tok_sim ? (int64_t)n * a->T : tok_cnx ? (int64_t)n * ((int64_t)h * w + 1) : M;
+        const int64_t rows_in = tok_cnx ? (int64_t)n * h * w : rows;
+        if (ld < D || ld % 4) return cbas_fail(CBAS_EINVAL, "ld = %lld: at least D and a multiple of 4", (long long)ld);
+        if (tok_sim ? (n <= 0 || a->T <= 0 || M < 0 || M >= a->T) : tok_cnx ? (n <= 0 || h <= 0 || w <= 0) : M <= 0)
+            return cbas_fail(CBAS_EINVAL, "token op %d: n = %d, M = %d, T = %d, grid %d x %d", op, n, M, a->T, h, w);
+        x_need = ((rows_in - 1) * ld + D) * 4;
+        if (tok_sim) {
+            out_need = (int64_t)n * (a->T - M) * 4;
+        } else {
+            if (a->sc_ld < D || a->sc_ld % 4) return cbas_fail(CBAS_EINVAL, "sc_ld (output row stride) = %d: at least D and a multiple of 4", a->sc_ld);
+            if (!a->out && !a->out2) return cbas_fail(CBAS_EINVAL, "out (fp32) and out2 (fp16) both NULL");
+            out_need = a->out ? ((rows - 1) * a->sc_ld + D) * 4 : 0;
+            out2_need = a->out2 ? ((rows - 1) * a->sc_ld + D) * 2 : 0;
+        }
+    } else if (vit_ln || op == CBAS_DEBUG_ROWS_CNX_LN_ROWS) {
         if (M <= 0 || ld < D) return cbas_fail(CBAS_EINVAL, "M = %d, ld = %lld: M > 0 and ld >= D", M, (long long)ld);
         const int64_t span = ((int64_t)(M - 1) * ld + D) * 4;
         if (vit_ln) x_need = span; else out_need = span;
@@ -934,15 +951,22 @@ extern "C" int cbas_debug_rows_run(const cbas_debug_rows_args* a) {
     if (x_need) HIP_TRY(upload(&x, a->x, (size_t)a->x_bytes));
     if (out_need) HIP_TRY(upload(&out, a->out, (size_t)a->out_bytes));
     if (out2_need) HIP_TRY(upload(&out2, a->out2, (size_t)a->out2_bytes));
-    if (!stem) {
+    if (!stem && !tok_sim) {
         HIP_TRY(upload(&gamma, a->gamma, (size_t)D * 4));
         HIP_TRY(upload(&beta, a->beta, (size_t)D * 4));
+    }
+    int* query = nullptr;
+    f16* x16 = nullptr;
+    if (tok_sim && a->wt) HIP_TRY(upload(&query, a->wt, (size_t)n * 4));
+    if (tok_sim && a->split) {                                       // the fp16 form reads the same image converted (RNE)
+        HIP_TRY(B.alloc(&x16, (size_t)a->x_bytes / 2));
+        LAUNCH_TRY(launch_convert_f16(reinterpret_cast<const float*>(x), x16, nullptr, a->x_bytes / 4, 0));
     }
     if (op == CBAS_DEBUG_ROWS_CNX_DWCONV_LN) {
         HIP_TRY(upload(&wt, a->wt, (size_t)49 * D * 4));
         HIP_TRY(upload(&bias, a->bias, (size_t)D * 4));
     }
-    if (cls && a->counter) HIP_TRY(upload(&counter, a->counter, 4));
+    if ((cls || tok_rows) && a->counter) HIP_TRY(upload(&counter, a->counter, 4));
     const float* xf = reinterpret_cast<const float*>(x);
     float* of = reinterpret_cast<float*>(out);
     const float eps = a->eps;
@@ -962,6 +986,14 @@ extern "C" int cbas_debug_rows_run(const cbas_debug_rows_args* a) {
         case CBAS_DEBUG_ROWS_CNX_DOWNSAMPLE: rc = launch_cnx_downsample(xf, ld, n, h, w, gamma, beta, D, eps, of, split, 0); break;
         case CBAS_DEBUG_ROWS_CNX_DWCONV_LN: rc = launch_cnx_dwconv_ln(xf, ld, n, h, w, wt, bias, gamma, beta, D, eps, of, split, 0); break;
         case CBAS_DEBUG_ROWS_CNX_POOL_LN: rc = launch_cnx_pool_ln(xf, ld, n, h * w, gamma, beta, D, eps, of, (f16*)out2, counter, 0); break;
+        case CBAS_DEBUG_ROWS_TOKEN_ROWS:
+            rc = tok_cnx ? launch_cnx_token_rows(xf, ld, n, h * w, gamma, beta, D, eps, of, (f16*)out2, a->sc_ld, counter, 0)
+                         : launch_final_norm_rows(xf, ld, gamma, beta, of, (f16*)out2, a->sc_ld, M, D, eps, counter, 0);
+            break;
+        case CBAS_DEBUG_ROWS_TOKEN_SIM:
+            rc = x16 ? launch_token_similarity<f16>(x16, ld, n, a->T, D, M, query, of, 0)
+                     : launch_token_similarity<float>(xf, ld, n, a->T, D, M, query, of, 0);
+            break;
     }
     if (rc) return cbas_fail(CBAS_EINVAL, "row kernel launch failed (op %d, D %d: rc=%d)", op, D, rc);
     HIP_TRY(hipDeviceSynchronize());

@@ -1462,16 +1462,65 @@ static int async_leave(cbas_enc* h, int lane, hipStream_t ls) {
     return CBAS_OK;
 }
 
-// the two synchronous forwards, with or without the attention outputs
+// The all-token outputs of cbas_enc_forward_*_tokens: the final LayerNorm of every row of the residual stream instead of the CLS
+// rows, and optionally the cosine map of one row against the patch rows.  Such a forward runs with null CLS pointers, which
+// leaves the last layer unpruned for that call (vit_begin) and queues no CLS tail; tokens_tail then reads lane 0's stream.
+struct TokOut {
+    float* f32 = nullptr;
+    f16* h16 = nullptr;
+    int64_t ld = 0;               // row stride of both images, elements
+    const int* query = nullptr;   // per-frame token index of the similarity map's query row; NULL: row 0
+    float* sim = nullptr;         // (n, T - prefix rows); NULL: no map
+    explicit operator bool() const { return f32 || h16; }
+};
+
+static int check_tokens(const cbas_enc* h, const TokOut& t) {
+    if (!h) return cbas_fail(CBAS_EINVAL, "null encoder handle");
+    if (h->cfg.family != 1 && h->cfg.precision == 2)
+        return cbas_fail(CBAS_EINVAL, "precision 2 serves CLS rows only: the token rows of its MX-fp8 layers are a different encoder's (use precision 0)");
+    if (!t) return cbas_fail(CBAS_EINVAL, "tokens_f32_dev and tokens_f16_dev are both NULL");
+    const int D = h->cfg.family == 1 ? h->cnx[3].C : h->D;
+    if (t.ld < D || t.ld % 4) return cbas_fail(CBAS_EINVAL, "ld_tokens = %lld: at least the width %d and a multiple of 4", (long long)t.ld, D);
+    if (((uintptr_t)t.f32 | (uintptr_t)t.sim) % 16 || (uintptr_t)t.h16 % 8 || (uintptr_t)t.query % 4)
+        return cbas_fail(CBAS_EINVAL, "token outputs must be 16-byte aligned (fp16: 8)");
+    return CBAS_OK;
+}
+
+// after a forward that kept every row: rows -> t.f32 / t.h16, then the map
+static int tokens_tail(cbas_enc* h, const Lane& ws, int n, int height, int width, const TokOut& t, hipStream_t st) {
+    const float eps = h->cfg.layer_norm_eps;
+    int T, D, P0;
+    if (h->cfg.family == 1) {
+        const int hw = (height / 32) * (width / 32);      // stage 3's grid: the stem's / 4, then three floor halvings
+        T = hw + 1; D = h->cnx[3].C; P0 = 1;
+        PROF(CBAS_PROF_LAYERNORM, 0.0);
+        LAUNCH_TRY(launch_cnx_token_rows(ws.x, h->cnx[3].Cp, n, hw, h->cnx_norm_w, h->cnx_norm_b, D, eps, t.f32, t.h16, t.ld,
+                                         h->nonfinite_dev, st));
+    } else {
+        const int ps = h->cfg.patch_size;
+        T = (height / ps) * (width / ps) + h->NP; D = h->D; P0 = h->NP;
+        PROF(CBAS_PROF_LAYERNORM, 0.0);
+        LAUNCH_TRY(launch_final_norm_rows(ws.x, D, h->norm_w, h->norm_b, t.f32, t.h16, t.ld, (int64_t)n * T, D, eps, h->nonfinite_dev, st));
+    }
+    if (t.sim) {
+        PROF(CBAS_PROF_OTHER, 6.0 * n * (double)(T - P0) * D);
+        if (t.f32) LAUNCH_TRY(launch_token_similarity<float>(t.f32, t.ld, n, T, D, P0, t.query, t.sim, st));
+        else LAUNCH_TRY(launch_token_similarity<f16>(t.h16, t.ld, n, T, D, P0, t.query, t.sim, st));
+    }
+    return CBAS_OK;
+}
+
+// the two synchronous forwards: the CLS rows, with or without the attention outputs, or (tok) every token's row instead
 static int enc_forward_u8(cbas_enc* h, const uint8_t* frames_dev, int n, int height, int width, int64_t frame_stride,
                           int64_t row_stride, int64_t pixel_stride, float* cls_f32_dev, uint16_t* cls_f16_dev, void* stream,
-                          const AttnOut& attn) {
+                          const AttnOut& attn, const TokOut& tok = TokOut{}) {
     if (!h) return cbas_fail(CBAS_EINVAL, "null encoder handle");
     hipStream_t st = (hipStream_t)stream;
     int rc = sync_enter(h, st);
     if (rc) return rc;
     rc = forward_u8(h, h->lanes[0], frames_dev, n, height, width, frame_stride, row_stride, pixel_stride, cls_f32_dev,
                     (f16*)cls_f16_dev, st, -1, -1, attn);
+    if (!rc && tok) rc = tokens_tail(h, h->lanes[0], n, height, width, tok, st);
     if (rc) return rc;
     return sync_leave(h, st);
 }
@@ -1514,7 +1563,7 @@ extern "C" int cbas_enc_forward_u8_attn(cbas_enc* h, const uint8_t* frames_dev, 
 }
 
 static int enc_forward_f32(cbas_enc* h, const float* x_dev, int n, int height, int width, float* cls_f32_dev,
-                           uint16_t* cls_f16_dev, void* stream, const AttnOut& attn) {
+                           uint16_t* cls_f16_dev, void* stream, const AttnOut& attn, const TokOut& tok = TokOut{}) {
     int rc = check_frame(h, n, height, width);
     if (rc) return rc;
     if (!x_dev) return cbas_fail(CBAS_EINVAL, "x_dev is NULL");
@@ -1528,6 +1577,7 @@ static int enc_forward_f32(cbas_enc* h, const float* x_dev, int n, int height, i
     if (h->cfg.family == 1) {
         LAUNCH_TRY(launch_cnx_stem_im2col_f32(x_dev, n, height, width, reinterpret_cast<float*>(ws.h16), h->cfg.precision == 4, st));
         rc = run_cnx(h, ws, n, height, width, cls_f32_dev, (f16*)cls_f16_dev, st, -1);
+        if (!rc && tok) rc = tokens_tail(h, ws, n, height, width, tok, st);
         if (rc) return rc;
         return sync_leave(h, st);
     }
@@ -1537,6 +1587,7 @@ static int enc_forward_f32(cbas_enc* h, const float* x_dev, int n, int height, i
     else
         LAUNCH_TRY(launch_im2col_f32(x_dev, n, height, width, ws.A_patch, ws.x, h->prefix, h->NP, h->D, T, ps, st));
     rc = run_blocks(h, ws, n, height, width, 512, 1.0f, cls_f32_dev, (f16*)cls_f16_dev, st, -1, -1, attn);
+    if (!rc && tok) rc = tokens_tail(h, ws, n, height, width, tok, st);
     if (rc) return rc;
     return sync_leave(h, st);
 }
@@ -1555,6 +1606,27 @@ extern "C" int cbas_enc_forward_f32_attn(cbas_enc* h, const float* x_dev, int n,
     if (!rc) rc = check_attn_frame(h, height, width);
     if (rc) return rc;
     return enc_forward_f32(h, x_dev, n, height, width, cls_f32_dev, cls_f16_dev, stream, attn);
+}
+
+extern "C" int cbas_enc_forward_u8_tokens(cbas_enc* h, const uint8_t* frames_dev, int n, int height, int width,
+                                          int64_t frame_stride, int64_t row_stride, int64_t pixel_stride,
+                                          float* tokens_f32_dev, uint16_t* tokens_f16_dev, int64_t ld_tokens,
+                                          const int32_t* query_idx_dev, float* sim_map_dev, void* stream) {
+    TokOut tok;
+    tok.f32 = tokens_f32_dev; tok.h16 = (f16*)tokens_f16_dev; tok.ld = ld_tokens; tok.query = query_idx_dev; tok.sim = sim_map_dev;
+    const int rc = check_tokens(h, tok);
+    if (rc) return rc;
+    return enc_forward_u8(h, frames_dev, n, height, width, frame_stride, row_stride, pixel_stride, nullptr, nullptr, stream, AttnOut{}, tok);
+}
+
+extern "C" int cbas_enc_forward_f32_tokens(cbas_enc* h, const float* x_dev, int n, int height, int width,
+                                           float* tokens_f32_dev, uint16_t* tokens_f16_dev, int64_t ld_tokens,
+                                           const int32_t* query_idx_dev, float* sim_map_dev, void* stream) {
+    TokOut tok;
+    tok.f32 = tokens_f32_dev; tok.h16 = (f16*)tokens_f16_dev; tok.ld = ld_tokens; tok.query = query_idx_dev; tok.sim = sim_map_dev;
+    const int rc = check_tokens(h, tok);
+    if (rc) return rc;
+    return enc_forward_f32(h, x_dev, n, height, width, nullptr, nullptr, stream, AttnOut{}, tok);
 }
 
 #if CBAS_BUILD_DEBUG      // stage taps: debug build only (include/cbas_mi355x_debug.h)

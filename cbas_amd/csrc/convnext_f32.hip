@@ -20,43 +20,9 @@
 // (vit32_epilogue.h store_split4) at scale 1.
 #include "kernels.h"
 #include "vit32_epilogue.h"
+#include "row_norm.h"
 
 namespace {
-
-// LayerNorm of one row held as NV f32x4 per lane (groups lane + 64 k < C / 4), the reference's two-pass form; returns rstd
-// (0 when the variance overflowed fp32, NaN for a non-finite row)
-template <int NV>
-__device__ __forceinline__ float cnx_ln(f32x4 (&v)[NV], int C, float eps, const float* __restrict__ gamma,
-                                       const float* __restrict__ beta, int lane) {
-    const int nvec = C >> 2;
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < NV; ++k)
-        if (lane + 64 * k < nvec) s += add_np(add_np(v[k][0], v[k][1]), add_np(v[k][2], v[k][3]));
-    const float mean = wave_sum_dpp(s) / (float)C;
-    float q = 0.f;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        if (lane + 64 * k < nvec) {
-#pragma clang fp contract(off)
-            const f32x4 d = v[k] - mean;
-            const f32x4 sq = d * d;
-            q += add_np(add_np(sq[0], sq[1]), add_np(sq[2], sq[3]));
-        }
-    }
-    const float rstd = 1.0f / sqrtf(wave_sum_dpp(q) / (float)C + eps);
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        const int idx = lane + 64 * k;
-        if (idx < nvec) {
-#pragma clang fp contract(off)
-            const f32x4 g = reinterpret_cast<const f32x4*>(gamma)[idx];
-            const f32x4 b = reinterpret_cast<const f32x4*>(beta)[idx];
-            v[k] = (v[k] - mean) * rstd * g + b;
-        }
-    }
-    return rstd;
-}
 
 // one thread = one output pixel of the stem: 16 pixels in, 32 floats out (plain or split)
 template <typename SRC>

@@ -156,6 +156,23 @@ template <typename E>
 int launch_cls_attention(const E* q, int64_t ldq, const E* K, int64_t ldk, int n, int T, int NH, int NP, int split,
                          float* heads_out, float* map_out, hipStream_t stream);
 
+// tokens_out.hip: every token's final hidden state (transformers' last_hidden_state) instead of the CLS row alone, and patch
+// similarity maps.  out_f32 / out_f16: rows of stride ld_out elements (>= the width, a multiple of 4); either may be nullptr, not
+// both.  Rows are normalised by the code of the CLS kernels (row_norm.h): row 0 of a frame has launch_final_norm_cls's /
+// launch_cnx_pool_ln's bits.  `nonfinite` (may be NULL) rises by one per ROW that comes out non-finite.  -1: bad argument.
+//   ViT: out[r] = LayerNorm(x[r]), r < M (= n T); x rows of stride ldx; D % 4 == 0, D <= 1280
+int launch_final_norm_rows(const float* x, int64_t ldx, const float* gamma, const float* beta, float* out_f32, f16* out_f16,
+                           int64_t ld_out, int64_t M, int D, float eps, unsigned* nonfinite, hipStream_t stream);
+//   ConvNeXt: out[b (hw + 1)] = LayerNorm(mean over the hw pixels of frame b), out[b (hw + 1) + 1 + p] = LayerNorm(x[b hw + p]);
+//   x rows of stride ld holding C values (C % 32 == 0, C <= 1536)
+int launch_cnx_token_rows(const float* x, int64_t ld, int n, int hw, const float* gamma, const float* beta, int C, float eps,
+                          float* out_f32, f16* out_f16, int64_t ld_out, unsigned* nonfinite, hipStream_t stream);
+//   map[b][p] = cos(tokens[b][q_b], tokens[b][P0 + p]), p < T - P0: E = float or f16 rows (n, T) of stride ld, sums in fp32 in a
+//   fixed order; q_b = query_idx[b] clamped to [0, T) (NULL: row 0, the CLS / pooled row); a zero-norm row gives 0
+template <typename E>
+int launch_token_similarity(const E* tokens, int64_t ld, int n, int T, int D, int P0, const int* query_idx, float* map,
+                            hipStream_t stream);
+
 // gated MLP, create time: out [2F][K] = rows of gate [F][K] and up [F][K] interleaved in blocks of 32 - out rows [64 b, 64 b + 32)
 // are gate rows [32 b, 32 b + 32), out rows [64 b + 32, 64 b + 64) the up rows of the same outputs (K = 1: the biases); F % 32 == 0
 int launch_interleave_gate_up(const float* gate, const float* up, float* out, int64_t F, int K, hipStream_t stream);

@@ -8,6 +8,7 @@
 //   attention     [tf]:210-234 (softmax(q k^T * 64^-0.5) v), heads split/merge :311-313,:330
 #include <stdlib.h>
 #include "kernels.h"
+#include "row_norm.h"
 
 namespace {
 
@@ -82,45 +83,8 @@ __global__ void write_prefix_kernel(float* __restrict__ x, const float* __restri
 
 // ---------------------------------------------------------------------------------------------
 // LayerNorm: one wave per row, two-pass statistics in registers (matches the reference's
-// mean / biased-variance formulation), fp32 in, fp16 out.
+// mean / biased-variance formulation), fp32 in, fp16 out.  The row itself is ln_row (row_norm.h).
 // ---------------------------------------------------------------------------------------------
-// Returns rstd: 0 when the variance overflowed fp32, NaN when the row holds a NaN / infinity (the range checks below read it).
-template <int NV>
-__device__ __forceinline__ float ln_row(const float* __restrict__ xr, const float* __restrict__ gamma,
-                                       const float* __restrict__ beta, int D, float eps, int lane,
-                                       f32x4 (&y)[NV]) {
-    const int nvec = D >> 2;
-    f32x4 v[NV];
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        const int idx = lane + 64 * k;
-        v[k] = (idx < nvec) ? reinterpret_cast<const f32x4*>(xr)[idx] : f32x4{0.f, 0.f, 0.f, 0.f};
-        s += (v[k][0] + v[k][1]) + (v[k][2] + v[k][3]);
-    }
-    const float mean = wave_sum_dpp(s) / (float)D;
-    float q = 0.f;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        const int idx = lane + 64 * k;
-        if (idx < nvec) {
-            const f32x4 d = v[k] - mean;
-            q += (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
-        }
-    }
-    const float rstd = 1.0f / sqrtf(wave_sum_dpp(q) / (float)D + eps);
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        const int idx = lane + 64 * k;
-        if (idx < nvec) {
-            const f32x4 g = reinterpret_cast<const f32x4*>(gamma)[idx];
-            const f32x4 bb = reinterpret_cast<const f32x4*>(beta)[idx];
-            y[k] = (v[k] - mean) * rstd * g + bb;
-        }
-    }
-    return rstd;
-}
-
 template <int NV>
 __global__ __launch_bounds__(256) void layernorm_f16_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ gamma,
                                                             const float* __restrict__ beta, f16* __restrict__ out,

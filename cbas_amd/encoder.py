@@ -63,6 +63,46 @@ def _device_index(device: torch.device) -> int:
     return device.index if device.index is not None else torch.cuda.current_device()
 
 
+def _frame_args(frames: torch.Tensor, channel: int, what: str):
+    """The two frame forms of the synchronous forwards: uint8 (n,H,W,3) / (n,H,W), or float32 (B,1,H,W).  Returns the contiguous
+    tensor, n, H, W, the uint8 byte strides (None for float32) and the byte offset of ``channel``."""
+    assert frames.is_cuda
+    if frames.dtype == torch.uint8:
+        frames = frames.contiguous()
+        if frames.dim() == 4:
+            n, H, W, Cn = frames.shape
+            return frames, n, H, W, (H * W * Cn, W * Cn, Cn), channel
+        n, H, W = frames.shape
+        return frames, n, H, W, (H * W, W, 1), 0
+    if frames.dtype != torch.float32 or frames.dim() != 4 or frames.shape[1] != 1:
+        raise ValueError(f"{what} takes uint8 (n,H,W,3) / (n,H,W) frames or a float32 (B,1,H,W) tensor")
+    frames = frames.contiguous()
+    n, _, H, W = frames.shape
+    return frames, n, H, W, None, 0
+
+
+def token_grid(cfg, H: int, W: int):
+    """(nh, nw, P0) of ``hidden_state``'s rows for an H x W frame: the patch grid and the rows in front of it (ViT: CLS and
+    registers; ConvNeXt: the pooled row, over the last stage's grid of 32 x 32 pixel cells)."""
+    if is_convnext(cfg):
+        nh, nw = cfg.stage_grids(H, W)[-1]
+        return nh, nw, 1
+    return H // cfg.patch_size, W // cfg.patch_size, cfg.num_prefix_tokens
+
+
+def query_token_index(cfg, H: int, W: int, query) -> int:
+    """The row of ``hidden_state`` under pixel ``query = (y, x)`` of an H x W frame (None: 0, the CLS / pooled row).  Pixels of
+    the margin a grid of whole patches leaves uncovered have no patch: ``ValueError``."""
+    if query is None:
+        return 0
+    nh, nw, P0 = token_grid(cfg, H, W)
+    cell = 32 if is_convnext(cfg) else cfg.patch_size
+    y, x = int(query[0]), int(query[1])
+    if not (0 <= y < nh * cell and 0 <= x < nw * cell):
+        raise ValueError(f"query pixel ({y}, {x}) is outside the {nh * cell} x {nw * cell} pixels the {nh} x {nw} patch grid covers")
+    return P0 + (y // cell) * nw + x // cell
+
+
 # What an encoder built the reference's way - DinoEncoder(model_identifier, device), integration.install(),
 # `python -m cbas_amd.encode_files` - computes in: 4 = fp32 storage / attention / LayerNorm with the GEMM products as three-term
 # fp16 splits: the mode that meets BOTH halves of the path's contract (CLS within 1e-3 - by three orders of magnitude - and
@@ -314,21 +354,7 @@ class DinoEncoder:
         ``ValueError``."""
         if is_convnext(self.config):
             raise ValueError("a ConvNeXt encoder has no attention: CLS attention maps exist for the ViT families only")
-        assert frames.is_cuda
-        if frames.dtype == torch.uint8:
-            frames = frames.contiguous()
-            if frames.dim() == 4:
-                n, H, W, Cn = frames.shape
-                strides, base_off = (H * W * Cn, W * Cn, Cn), channel
-            else:
-                n, H, W = frames.shape
-                strides, base_off = (H * W, W, 1), 0
-        else:
-            if frames.dtype != torch.float32 or frames.dim() != 4 or frames.shape[1] != 1:
-                raise ValueError("cls_attention takes uint8 (n,H,W,3) / (n,H,W) frames or a float32 (B,1,H,W) tensor")
-            frames = frames.contiguous()
-            n, _, H, W = frames.shape
-            strides = None
+        frames, n, H, W, strides, base_off = _frame_args(frames, channel, "cls_attention")
         self._fit_frame(H, W)
         cfg = self.config
         D, NH, ps = cfg.hidden_size, cfg.num_attention_heads, cfg.patch_size
@@ -351,6 +377,56 @@ class DinoEncoder:
                                                               out32[i:i + m].data_ptr(), out16[i:i + m].data_ptr(), stream, hp,
                                                               maps[i:i + m].data_ptr()), "cbas_enc_forward_u8_attn")
         return (out16, out32, maps, heads) if per_head else (out16, out32, maps)
+
+    def _tokens(self, frames, channel, dtype, query=None, want_map=False):
+        """One cbas_enc_forward_*_tokens call: the (n, T, D) image in ``dtype`` and, with ``want_map``, the (n, nh, nw) cosine map."""
+        if dtype not in (torch.float32, torch.float16):
+            raise ValueError("hidden states come as torch.float32 or torch.float16")
+        if not is_convnext(self.config) and self.precision == 2:
+            raise ValueError("precision 2 serves CLS rows only: the token rows of its MX-fp8 layers are a different encoder's "
+                             "(use precision 0)")
+        frames, n, H, W, strides, base_off = _frame_args(frames, channel, "hidden_state")
+        self._fit_frame(H, W)
+        nh, nw, P0 = token_grid(self.config, H, W)
+        D = self.config.hidden_size
+        out = torch.empty((n, P0 + nh * nw, D), dtype=dtype, device=self.device)
+        p32, p16 = (out.data_ptr(), None) if dtype == torch.float32 else (None, out.data_ptr())
+        maps = torch.empty((n, nh, nw), dtype=torch.float32, device=self.device) if want_map else None
+        qidx = None
+        if want_map and query is not None:
+            qidx = torch.full((n,), query_token_index(self.config, H, W, query), dtype=torch.int32, device=self.device)
+        tail = (p32, p16, D, qidx.data_ptr() if qidx is not None else None, maps.data_ptr() if want_map else None,
+                torch.cuda.current_stream(self.device).cuda_stream)
+        if strides is None:
+            _lib.check(self._lib.cbas_enc_forward_f32_tokens(self._h, frames.data_ptr(), n, H, W, *tail), "cbas_enc_forward_f32_tokens")
+        else:
+            _lib.check(self._lib.cbas_enc_forward_u8_tokens(self._h, frames.data_ptr() + base_off, n, H, W, *strides, *tail),
+                       "cbas_enc_forward_u8_tokens")
+        return out, maps, (nh, nw, P0)
+
+    def hidden_state(self, frames: torch.Tensor, channel: int = 1, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+        """What ``transformers`` calls the encoder's output: ``last_hidden_state``, the final-LayerNorm'd row of EVERY token, as an
+        (n, T, D) device tensor in ``dtype`` (float32 or float16) - cbas_enc_forward_u8_tokens / cbas_enc_forward_f32_tokens.
+
+        frames: as ``cls_attention`` takes them.  ViT: T = CLS + registers + patches in row-major grid order.  ConvNeXt:
+        T = 1 + (H // 32) * (W // 32) - the pooled row, then the last stage's grid, as ``DINOv3ConvNextModel`` returns them.  Row 0
+        is the CLS row of this encoder with an unpruned last layer.  The call runs the last layer on every row for itself only;
+        ``encode_u8`` before and after it gives the same bits.  One library call: n may not exceed ``max_batch``.  Precision 2
+        is refused (its MX-fp8 layers serve the CLS row; their token rows are a different encoder's)."""
+        return self._tokens(frames, channel, dtype)[0]
+
+    def patch_tokens(self, frames: torch.Tensor, channel: int = 1, dtype: torch.dtype = torch.float32):
+        """``hidden_state`` split the way dense-feature users want it: ``(patches, prefix)`` with ``patches`` (n, nh, nw, D) over the
+        patch grid and ``prefix`` (n, P0, D) the rows in front of them (CLS and registers; ConvNeXt: the pooled row).  Both are views
+        of one tensor."""
+        out, _, (nh, nw, P0) = self._tokens(frames, channel, dtype)
+        return out[:, P0:].reshape(out.shape[0], nh, nw, out.shape[2]), out[:, :P0]
+
+    def similarity_map(self, frames: torch.Tensor, query=None, channel: int = 1) -> torch.Tensor:
+        """Cosine similarity of one token's final hidden state to every patch token's, as a float32 (n, nh, nw) device tensor: the
+        picture of what an encoder looks at that ConvNeXt encoders can give too.  ``query=None``: the CLS row (ConvNeXt: the
+        pooled row); ``query=(y, x)`` in pixels: the patch under that pixel.  Computed on the device from the fp32 rows."""
+        return self._tokens(frames, channel, torch.float32, query, True)[1]
 
     def submit_host(self, slot: int, frames: np.ndarray, channel: int = 1) -> None:
         """Queue one host chunk (uint8 (n,H,W,3) or (n,H,W), C-contiguous) on ``slot``."""

@@ -14,6 +14,8 @@
  *   cbas_enc_forward_u8                    backend/cbas.py:431-436   green/255 preprocessing + encoder call
  *   cbas_enc_forward_u8_attn / _f32_attn   compare_encoders.py:36-49 the last layer's attention from the CLS token to
  *                                          the patch tokens, averaged over heads (output_attentions=True), beside the CLS rows
+ *   cbas_enc_forward_u8_tokens / _f32_tokens   compare_encoders.py:36 / the golden scripts' model(pixel_values=x): the whole
+ *                                          last_hidden_state (n, T, D) instead of row 0, and cosine maps over the patch rows
  *   cbas_enc_submit_u8_host / cbas_enc_wait  backend/cbas.py:423-440 one iteration of the chunk loop
  *                                          (H2D copy, encode, D2H copy), made asynchronous
  *   cbas_head_create / cbas_head_destroy   backend/workthreads.py:427-447 ClassifierLSTMDeltas(...)
@@ -56,8 +58,8 @@ extern "C" {
 
 /* Still 11 with cbas_rows_gather_windows / cbas_head_train_step_rows, with cbas_head_score_rows / cbas_logits_nll, with
  * cbas_enc_set_pos_interp, with cbas_enc_set_fp8_plan, with cbas_probs_top1 / cbas_disagreement_runs, with
- * cbas_labels_median / cbas_label_runs / cbas_activity_bins and with cbas_enc_forward_u8_attn / cbas_enc_forward_f32_attn: they
- * are additions.  No structure and no existing signature
+ * cbas_labels_median / cbas_label_runs / cbas_activity_bins, with cbas_enc_forward_u8_attn / cbas_enc_forward_f32_attn and with
+ * cbas_enc_forward_u8_tokens / cbas_enc_forward_f32_tokens: they are additions.  No structure and no existing signature
  * changed, so a caller built against the earlier version 11 header runs unchanged. */
 #define CBAS_ABI_VERSION   11
 
@@ -206,6 +208,28 @@ int cbas_enc_forward_u8_attn(cbas_enc* h, const uint8_t* frames_dev, int n, int 
                              float* cls_f32_dev, uint16_t* cls_f16_dev, void* stream,
                              float* attn_heads_dev, float* attn_map_dev);
 
+/* The same two forwards returning what transformers calls the encoder's output: last_hidden_state, the final-LayerNorm'd row of
+ * EVERY token, instead of the CLS rows.  For frame b and token t < T:
+ *     tokens_f32_dev / tokens_f16_dev   row b T + t of an image of ld_tokens elements per row (ld_tokens >= D, a multiple of 4;
+ *                                       columns D .. ld_tokens - 1 are not touched); either may be NULL, not both
+ *   ViT:      T = NP + P - CLS, the registers, then the patches in row-major grid order
+ *   ConvNeXt: T = 1 + (height / 32) (width / 32) - row 0 = LayerNorm(mean over the last stage's grid), row 1 + p = LayerNorm of
+ *             grid pixel p (DINOv3ConvNextModel.forward: pool, concatenate, one LayerNorm)
+ * Row 0 of each frame is bit for bit the fp32 / fp16 CLS row of cbas_enc_forward_u8 run with an unpruned last layer (ConvNeXt: of
+ * any cbas_enc_forward_u8).  The call runs the last layer on every row FOR THIS CALL ONLY - cbas_enc_set_prune_last_layer's
+ * setting and every other call's results are untouched.  sim_map_dev (optional) receives (n, T - NP) cosines of row
+ * query_idx_dev[b] (a token index in [0, T), clamped; NULL: row 0) against each patch row, summed in fp32 from the fp32 image (the
+ * fp16 one where only that is asked for); a row of norm 0 gives 0.  ViT handles of precision 0, 1, 3, 4 and ConvNeXt handles
+ * (3, 4) are served; precision 2 is CBAS_EINVAL (its MX-fp8 layers serve the CLS row; their token rows are a different
+ * encoder's).  The range guard counts every non-finite ROW here (cbas_enc_check_finite: CBAS_ERANGE). */
+int cbas_enc_forward_f32_tokens(cbas_enc* h, const float* x_dev, int n, int height, int width,
+                                float* tokens_f32_dev, uint16_t* tokens_f16_dev, int64_t ld_tokens,
+                                const int32_t* query_idx_dev, float* sim_map_dev, void* stream);
+int cbas_enc_forward_u8_tokens(cbas_enc* h, const uint8_t* frames_dev, int n, int height, int width,
+                               int64_t frame_stride, int64_t row_stride, int64_t pixel_stride,
+                               float* tokens_f32_dev, uint16_t* tokens_f16_dev, int64_t ld_tokens,
+                               const int32_t* query_idx_dev, float* sim_map_dev, void* stream);
+
 /* Host-streamed form (one iteration of encode_file's chunk loop).  `slot` in [0, CBAS_ENC_SLOTS):
  * submit copies the pixels host->HBM on the handle's copy stream (from pinned staging), encodes
  * on the compute stream and copies the CLS rows back; wait blocks until that slot is done and
@@ -305,7 +329,7 @@ int cbas_enc_set_fp8_plan(cbas_enc* h, int plan);
  * CBAS_PROF_NCAT entries); reset != 0 clears the records. */
 enum { CBAS_PROF_PATCH = 0, CBAS_PROF_LAYERNORM = 1, CBAS_PROF_QKV = 2, CBAS_PROF_ATTENTION = 3,
        CBAS_PROF_OPROJ = 4, CBAS_PROF_UP = 5, CBAS_PROF_DOWN = 6,
-       CBAS_PROF_OTHER = 7,      /* the CLS attention map kernel of the ..._attn forwards */
+       CBAS_PROF_OTHER = 7,      /* the CLS attention map kernel of the ..._attn forwards, the similarity map of ..._tokens */
        CBAS_PROF_NCAT = 8 };
 int cbas_enc_profile(cbas_enc* h, int enable);
 int cbas_enc_profile_read(cbas_enc* h, double* ms_by_cat, int64_t* launches_by_cat, double* flops_by_cat,

@@ -175,12 +175,18 @@ int cbas_debug_cls_attention(int arith, const float* q_host, const float* K_host
  *   CNX_DOWNSAMPLE    launch_cnx_downsample (split)         [n][h][w][ld] f32          A [n (h/2) (w/2)][4 D]
  *   CNX_DWCONV_LN     launch_cnx_dwconv_ln (split)          [n][h][w][ld] f32          A [n h w][D]; wt [49][D], bias [D]
  *   CNX_POOL_LN       launch_cnx_pool_ln                    [n][h w][ld] f32           as FINAL_CLS
- * counter (FINAL_CLS / CNX_POOL_LN): the non-finite counter, in / out; NULL hands the launcher nonfinite = NULL. */
+ *   TOKEN_ROWS        h = w = 0: launch_final_norm_rows     [M][ld] f32                f32 rows [M][sc_ld] (out2: fp16 rows [M][sc_ld])
+ *                     else: launch_cnx_token_rows           [n][h w][ld] f32           rows [n (h w + 1)][sc_ld], both forms; either may be NULL
+ *   TOKEN_SIM         launch_token_similarity               [n][T][ld] f32             map [n][T - M] f32
+ * TOKEN_ROWS reads the output images' row stride from sc_ld (>= D, % 4; ld likewise).  TOKEN_SIM reads the prefix rows P0 from M
+ * (0 <= M < T) and the per-frame query indices, n int32, from wt (NULL: row 0); split = 1 runs the fp16 form on the image
+ * converted to fp16 (round to nearest even).
+ * counter (FINAL_CLS / CNX_POOL_LN / TOKEN_ROWS): the non-finite counter, in / out; NULL hands the launcher nonfinite = NULL. */
 enum {
     CBAS_DEBUG_ROWS_LN_F16 = 0, CBAS_DEBUG_ROWS_LN_F32 = 1, CBAS_DEBUG_ROWS_LN_SPLIT = 2, CBAS_DEBUG_ROWS_LN_F8 = 3,
     CBAS_DEBUG_ROWS_FINAL_CLS = 4, CBAS_DEBUG_ROWS_CNX_STEM_U8 = 5, CBAS_DEBUG_ROWS_CNX_STEM_F32 = 6,
     CBAS_DEBUG_ROWS_CNX_LN_ROWS = 7, CBAS_DEBUG_ROWS_CNX_DOWNSAMPLE = 8, CBAS_DEBUG_ROWS_CNX_DWCONV_LN = 9,
-    CBAS_DEBUG_ROWS_CNX_POOL_LN = 10
+    CBAS_DEBUG_ROWS_CNX_POOL_LN = 10, CBAS_DEBUG_ROWS_TOKEN_ROWS = 11, CBAS_DEBUG_ROWS_TOKEN_SIM = 12
 };
 typedef struct cbas_debug_rows_args {
     int64_t struct_bytes;        /* sizeof(cbas_debug_rows_args): a mismatch is rejected */
