@@ -57,6 +57,10 @@ SIGNATURES = {
     "cbas_enc_forward_f32_tokens": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "cbas_enc_forward_u8_tokens": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_int64, c_int64,
                                            c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "cbas_patch_pca_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "cbas_patch_pca_fit": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_int64, c_void_p]),
+    "cbas_patch_pca_project": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cbas_enc_submit_u8_host": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int64, c_int64, c_int64]),
     "cbas_enc_wait": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "cbas_enc_submit_u8": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_void_p,
@@ -163,6 +167,8 @@ ENC_SLOTS = 3
 TRAIN_MULTI_MAX = 8                                   # CBAS_TRAIN_MULTI_MAX of include/cbas_mi355x.h
 POS_INTERP_BICUBIC_AA, POS_INTERP_BICUBIC = 0, 1      # CBAS_POS_INTERP_* of include/cbas_mi355x.h
 MLP_GELU, MLP_SWIGLU = 0, 1                           # CBAS_MLP_* of include/cbas_mi355x.h
+PCA_FRAME, PCA_BATCH = 0, 1                           # CBAS_PCA_* of include/cbas_mi355x.h
+PCA_CHUNK, PCA_MEAN_CHUNK, PCA_MAX_K, PCA_MAX_D = 1024, 64, 8, 1536      # csrc/kernels.h: the fixed row chunks and limits of cbas_patch_pca_*
 EXPECTED_ABI = 11         # CBAS_ABI_VERSION of include/cbas_mi355x.h these ctypes structures mirror
 PROF_CATS = ["patch_gemm", "layernorm", "qkv_gemm", "attention", "oproj_gemm", "up_gemm", "down_gemm", "other"]      # other: the CLS attention map and token similarity kernels
 

@@ -3,11 +3,16 @@ frames of a video - the picture the reference's encoder comparison tool draws (c
 the device by ``DinoEncoder.cls_attention`` beside the CLS rows.
 
     python -m cbas_amd.attention_maps --video V --frame N --encoder ID [--encoder ID ...] --out PNG [--precision P]
-                                      [--kind attention|similarity] [--query Y,X]
+                                      [--kind attention|similarity|pca] [--query Y,X] [--pca-scope frame|batch]
 
 ``--kind similarity`` draws the other picture of the same question, from ``DinoEncoder.similarity_map``: the cosine of the CLS
 token's final hidden state (``--query Y,X``: of the patch under that pixel) to every patch token's.  It needs no attention, so it
 is the kind DINOv3 ConvNeXt encoders have (their query row is the pooled one, their grid the last stage's 32 x 32 pixel cells).
+
+``--kind pca`` draws the third picture, from ``DinoEncoder.patch_pca``: the patch rows' coordinates along their first three
+principal components, each stretched to [0, 1] over the picture, as red, green and blue - what the encoder separates, with no
+query and no attention, so every family has it and the pictures of two families can be compared.  ``--pca-scope batch`` fits one
+basis for all frames asked for (the same colours mean the same directions in each), ``frame`` (the default) one per frame.
 
 One deliberate difference from that tool: the map here is the map of what the encoder sees INSIDE CBAS - the green plane / 255
 replicated to three channels at the video's own size, exactly what ``encode_file`` feeds the model (backend/cbas.py:431) - not
@@ -24,7 +29,8 @@ from typing import Mapping, Sequence, Tuple, Union
 import numpy as np
 
 
-KINDS = ("attention", "similarity")
+KINDS = ("attention", "similarity", "pca")
+PCA_SCOPES = ("frame", "batch")
 
 
 def refuse_kind(cfg, kind: str):
@@ -33,15 +39,17 @@ def refuse_kind(cfg, kind: str):
     if kind not in KINDS:
         return f"unknown map kind {kind!r}: one of {', '.join(KINDS)}"
     if kind == "attention" and is_convnext(cfg):
-        return "a ConvNeXt encoder has no attention: --kind similarity is the map it has"
+        return "a ConvNeXt encoder has no attention: --kind similarity and --kind pca are the maps it has"
     return None
 
 
-def frame_maps(encoder, path: str, frame_indices: Sequence[int], kind: str = "attention", query=None):
-    """Maps of the given frames of a video: ``kind`` "attention" (``cls_attention``) or "similarity" (``similarity_map`` of
-    ``query``: None, or a pixel (y, x)).  Frames are read through ``pipeline.open_video`` (any source it knows) and
-    encoded in batches of ``encoder.max_batch``.  Returns ``(maps, frames_green)``: float32 (n, nh, nw) and uint8 (n, H, W)
-    numpy arrays, in the order of ``frame_indices``."""
+def frame_maps(encoder, path: str, frame_indices: Sequence[int], kind: str = "attention", query=None, pca_scope: str = "frame"):
+    """Maps of the given frames of a video: ``kind`` "attention" (``cls_attention``), "similarity" (``similarity_map`` of
+    ``query``: None, or a pixel (y, x)) or "pca" (``patch_pca``, three components).  Frames are read through
+    ``pipeline.open_video`` (any source it knows) and encoded in batches of ``encoder.max_batch``.  Returns ``(maps, frames_green)``:
+    float32 (n, nh, nw) and uint8 (n, H, W) numpy arrays, in the order of ``frame_indices``.  For "pca" ``maps`` is the finished
+    picture instead, float32 (n, H, W, 3) in [0, 1] (``render_pca`` of each frame's scores); with ``pca_scope="batch"`` the basis
+    fitted on the first batch of frames colours all of them."""
     import torch
     from . import pipeline
     idx = [int(i) for i in frame_indices]
@@ -50,6 +58,9 @@ def frame_maps(encoder, path: str, frame_indices: Sequence[int], kind: str = "at
         raise ValueError(why)
     if not idx:
         raise ValueError("no frame index given")
+    if kind == "pca" and pca_scope not in PCA_SCOPES:
+        raise ValueError(f"unknown PCA scope {pca_scope!r}: one of {', '.join(PCA_SCOPES)}")
+    basis = None
     src = pipeline.open_video(path)
     try:
         n_total = len(src)
@@ -63,7 +74,13 @@ def frame_maps(encoder, path: str, frame_indices: Sequence[int], kind: str = "at
                                 else np.concatenate([np.asarray(src.get_batch([j])) for j in part]))
             green = np.ascontiguousarray(frames[:, :, :, 1] if frames.ndim == 4 else frames)      # backend/cbas.py:431
             dev = torch.from_numpy(green).to(encoder.device)
-            maps.append((encoder.cls_attention(dev)[2] if kind == "attention" else encoder.similarity_map(dev, query)).cpu().numpy())
+            if kind == "pca":
+                scores, fitted = encoder.patch_pca(dev, 3, pca_scope, basis)
+                basis = fitted if pca_scope == "batch" else None
+                size = (green.shape[2], green.shape[1])
+                maps.append(np.stack([render_pca(sc, size) for sc in scores.cpu().numpy()]))
+            else:
+                maps.append((encoder.cls_attention(dev)[2] if kind == "attention" else encoder.similarity_map(dev, query)).cpu().numpy())
             greens.append(green)
         return np.concatenate(maps), np.concatenate(greens)
     finally:
@@ -82,6 +99,23 @@ def render_map(map2d, size: Tuple[int, int]) -> np.ndarray:
     return np.asarray(Image.fromarray(_to_u8(a)).resize((int(size[0]), int(size[1])), Image.BICUBIC))
 
 
+def render_pca(scores, size: Tuple[int, int]) -> np.ndarray:
+    """One frame's (nh, nw, k >= 3) PCA scores as a picture: components 0, 1, 2 each stretched to [0, 1] by their own minimum and
+    maximum over the frame (a constant one is 0), resized to ``size`` = (width, height) with Pillow's bicubic filter - the filter
+    ``render_map`` uses - and clipped to [0, 1] (bicubic overshoots).  Returns a float32 (height, width, 3) array: R, G, B."""
+    from PIL import Image
+    a = np.asarray(scores, dtype=np.float32)
+    if a.ndim != 3 or a.shape[2] < 3:
+        raise ValueError(f"render_pca takes one frame's (nh, nw, k >= 3) scores, got shape {a.shape}")
+    out = np.empty((int(size[1]), int(size[0]), 3), np.float32)
+    for c in range(3):
+        ch = a[:, :, c]
+        lo, hi = float(ch.min()), float(ch.max())
+        ch = (ch - lo) / (hi - lo) if hi > lo else np.zeros_like(ch)
+        out[:, :, c] = np.clip(np.asarray(Image.fromarray(ch, mode="F").resize((int(size[0]), int(size[1])), Image.BICUBIC)), 0.0, 1.0)
+    return out
+
+
 def _to_u8(a: np.ndarray) -> np.ndarray:
     lo, hi = float(a.min()), float(a.max())
     if hi > lo:
@@ -90,7 +124,7 @@ def _to_u8(a: np.ndarray) -> np.ndarray:
 
 
 def compare_encoders(video: str, frame_idx: int, encoders: Mapping[str, Union[str, object]], out_png: str, precision=None,
-                     kind: str = "attention", query=None) -> str:
+                     kind: str = "attention", query=None, pca_scope: str = "frame") -> str:
     """One figure row per encoder: the frame as the encoder receives it (green plane) beside its rendered map (``kind``, ``query``:
     see ``frame_maps``).
     ``encoders`` maps a display name to a checkpoint directory, an HF-cache id or a ready ``DinoEncoder``; encoders built here
@@ -99,19 +133,22 @@ def compare_encoders(video: str, frame_idx: int, encoders: Mapping[str, Union[st
         raise ValueError("no encoder given")
     from matplotlib.backends.backend_agg import FigureCanvasAgg      # the Agg backend, without pyplot's global state
     from matplotlib.figure import Figure
-    from .encoder import DinoEncoder
+    from .encoder import DinoEncoder, token_grid
     panels = []
     for name, enc in encoders.items():
         own = isinstance(enc, str)
         if own:
             enc = DinoEncoder(enc, **({} if precision is None else {"precision": int(precision)}))
         try:
-            maps, green = frame_maps(enc, video, [frame_idx], kind, query)
+            maps, green = frame_maps(enc, video, [frame_idx], kind, query, pca_scope)
+            grid = token_grid(enc.config, green.shape[1], green.shape[2])[:2]
         finally:
             if own:
                 enc.close()
-        panels.append((name, green[0], maps[0].shape, render_map(maps[0], (green.shape[2], green.shape[1]))))
+        pic = (maps[0] * 255).astype(np.uint8) if kind == "pca" else render_map(maps[0], (green.shape[2], green.shape[1]))
+        panels.append((name, green[0], grid, pic))
     what = ("where its CLS token looks (last layer, mean of heads)" if kind == "attention" else
+            "patch features along their first three principal components (R, G, B)" if kind == "pca" else
             "cosine of the final hidden states: " + ("CLS / pooled row" if query is None else f"patch at pixel {tuple(query)}") + " to each patch")
     _draw(Figure, FigureCanvasAgg, panels, f"{os.path.basename(video)}, frame {frame_idx}", out_png, what)
     return out_png
@@ -122,7 +159,8 @@ LABEL_WIDTH_IN = 0.6         # room at the left for the encoders' names
 
 
 def _draw(Figure, Canvas, panels, caption: str, out_png: str, what: str) -> None:
-    """panels: (name, green plane (H, W) uint8, patch grid (nh, nw), rendered map (H, W) uint8) per encoder, top to bottom."""
+    """panels: (name, green plane (H, W) uint8, patch grid (nh, nw), picture) per encoder, top to bottom.  The picture is a rendered
+    map, (H, W) uint8, drawn through the inferno colour map - or, for the pca kind, (H, W, 3) uint8 drawn as the RGB it is."""
     H, W = panels[0][1].shape
     panel_w = PANEL_HEIGHT_IN * W / H
     fig = Figure(figsize=(LABEL_WIDTH_IN + 2 * panel_w, PANEL_HEIGHT_IN * len(panels) + 0.5), layout="constrained")
@@ -131,9 +169,11 @@ def _draw(Figure, Canvas, panels, caption: str, out_png: str, what: str) -> None
     for r, (name, green, (nh, nw), pic) in enumerate(panels):
         left, right = grid[r]
         left.imshow(green, cmap="gray", vmin=0, vmax=255, interpolation="nearest")
-        right.imshow(pic, cmap="inferno", vmin=0, vmax=255, interpolation="nearest")
+        rgb = pic.ndim == 3
+        right.imshow(pic, interpolation="nearest", **({} if rgb else {"cmap": "inferno", "vmin": 0, "vmax": 255}))
         left.set_ylabel(name, fontsize=10)
-        right.set_xlabel(f"{nh} x {nw} patches, stretched to the map's own range", fontsize=8)
+        right.set_xlabel(f"{nh} x {nw} patches, " + ("each component stretched to its own range over the frame" if rgb else
+                                                    "stretched to the map's own range"), fontsize=8)
         for a in (left, right):
             a.set_xticks([])
             a.set_yticks([])
@@ -151,7 +191,8 @@ def main(argv=None) -> int:
     ap.add_argument("--encoder", action="append", default=[], metavar="ID", help="checkpoint directory or HF-cache id; repeatable")
     ap.add_argument("--out", required=True, metavar="PNG")
     ap.add_argument("--precision", type=int, default=None)
-    ap.add_argument("--kind", choices=KINDS, default="attention", help="similarity: the only kind a ConvNeXt encoder has")
+    ap.add_argument("--kind", choices=KINDS, default="attention", help="similarity and pca: the kinds a ConvNeXt encoder has")
+    ap.add_argument("--pca-scope", choices=PCA_SCOPES, default=None, help="pca: one basis per frame (default) or one for all frames")
     ap.add_argument("--query", default=None, metavar="Y,X", help="similarity: the pixel whose patch is the query (default: the CLS / pooled row)")
     a = ap.parse_args(argv)
     query = None
@@ -163,6 +204,8 @@ def main(argv=None) -> int:
         except ValueError:
             ap.error(f"--query {a.query!r}: two integers Y,X")
         query = (y, x)
+    if a.pca_scope is not None and a.kind != "pca":
+        ap.error("--pca-scope goes with --kind pca")
     if not a.encoder:
         ap.error("at least one --encoder is needed")
     if not os.path.exists(a.video):
@@ -184,7 +227,8 @@ def main(argv=None) -> int:
         if why:
             ap.error(f"--encoder {e}: {why}")
         names[e if e not in names else f"{e} ({len(names)})"] = e
-    print(compare_encoders(a.video, a.frame, names, a.out, precision=a.precision, kind=a.kind, query=query))
+    print(compare_encoders(a.video, a.frame, names, a.out, precision=a.precision, kind=a.kind, query=query,
+                           pca_scope=a.pca_scope or "frame"))
     return 0
 
 

@@ -481,3 +481,31 @@ int launch_label_runs_emit(const LabelRunsParams& p, const long long* offsets, L
 // launch_activity_bins: bins[j] += frames f of bin j with (double)p[f][b] * is_max(f) >= threshold; the caller zeroes bins.
 int launch_activity_bins(const float* probs, int64_t n, int C, int behavior, double threshold, int64_t bin_frames,
                          unsigned long long* bins, int64_t n_bins, hipStream_t st);
+
+// patch_pca.hip: PCA of patch features.  Rows as cbas_enc_forward_*_tokens lays them out; a problem is one
+// covariance: row m of problem b is patch row m % P of frame b * frames_per_problem + m / P (FRAME scope: frames_per_problem = 1,
+// M = P; BATCH scope: one problem, frames_per_problem = n, M = n P).
+constexpr int PCA_CHUNK = 1024;          // rows per partial covariance: fixed, whatever n and the device
+constexpr int PCA_MEAN_CHUNK = 64;       // rows per partial column sum
+constexpr int PCA_MAX_K = 8, PCA_MAX_D = 1536;
+struct PcaRows {
+    const float* x;
+    int64_t ld;
+    int T, n_prefix, P;
+    int64_t M;
+    int frames_per_problem;
+};
+int64_t pca_cov_chunks(int64_t M);       // partial covariances per problem
+int64_t pca_mean_chunks(int64_t M);      // partial column sums per problem
+// mean [nprob][D]; tmp: nprob * pca_mean_chunks(M) * D floats
+int launch_pca_mean(const PcaRows& r, int nprob, int D, float* tmp, float* mean, hipStream_t st);
+// part: nprob * pca_cov_chunks(M) * D * D floats; on return problem b's D x D covariance (exactly symmetric) starts at
+// part + b * pca_cov_chunks(M) * D * D
+int launch_pca_cov(const PcaRows& r, int nprob, int D, const float* mean, float* part, hipStream_t st);
+// the k leading eigenpairs of nprob symmetric D x D matrices (problem b at C + b * c_stride) by `iters` rounds of subspace
+// iteration and a Rayleigh-Ritz step: comp [nprob][k][D], eig [nprob][k] descending, total_var [nprob] = trace; Z: nprob * k * D floats
+int launch_pca_eig(const float* C, int64_t c_stride, int nprob, int D, int k, int iters, float* Z, float* comp, float* eig,
+                   float* total_var, hipStream_t st);
+// scores [n][P][k] = (x - mean_b) . comp_b[j]; basis b of frame f is f * basis_step (0: one basis for every frame, 1: one per frame)
+int launch_pca_project(const float* x, int64_t ld, int n, int T, int n_prefix, int D, int k, int basis_step, const float* mean,
+                       const float* comp, float* scores, hipStream_t st);

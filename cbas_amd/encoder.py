@@ -7,7 +7,8 @@ through the C ABI (``cbas_enc_*``).  torch tensors are only containers for devic
 
 Extras beyond the reference interface (used by ``encode_file`` and the benchmarks):
 ``encode_u8`` takes uint8 frames already in HBM, ``submit_host``/``wait`` stream host chunks
-through pinned staging with copy/compute overlap.
+through pinned staging with copy/compute overlap.  ``cls_attention``, ``hidden_state`` / ``patch_tokens`` /
+``similarity_map`` and ``patch_pca`` are the three ways to look at what the encoder sees.
 """
 from __future__ import annotations
 
@@ -101,6 +102,51 @@ def query_token_index(cfg, H: int, W: int, query) -> int:
     if not (0 <= y < nh * cell and 0 <= x < nw * cell):
         raise ValueError(f"query pixel ({y}, {x}) is outside the {nh * cell} x {nw * cell} pixels the {nh} x {nw} patch grid covers")
     return P0 + (y // cell) * nw + x // cell
+
+
+PCA_DEFAULT_ITERS = 64      # rounds of subspace iteration in ``patch_pca``: chosen on the host by tests/test_patch_pca_host.py
+
+
+class PatchPCABasis:
+    """What ``DinoEncoder.patch_pca`` fitted: ``mean`` (b, D), ``components`` (b, k, D) with unit rows ordered by ``eigenvalues``
+    (b, k) descending, ``total_variance`` (b,) - float32 tensors, b = 1 for scope "batch" and one per frame for scope "frame" - and
+    ``stamp``, the fitting encoder's (``DinoEncoder.stamp``).  A basis colours only rows of the encoder it was fitted on: ``check``
+    refuses another width or stamp.  The stamp is a name, not a digest of the weights: it catches another checkpoint or
+    precision, not two sets of weights loaded under one name (``from_weights`` encoders all share ``<in-memory>``)."""
+
+    def __init__(self, mean, components, eigenvalues, total_variance, scope: str, stamp: str):
+        if scope not in ("frame", "batch"):
+            raise ValueError(f"scope {scope!r}: 'frame' or 'batch'")
+        if components.dim() != 3 or mean.dim() != 2 or tuple(mean.shape) != (components.shape[0], components.shape[2]) \
+                or tuple(eigenvalues.shape) != tuple(components.shape[:2]) or tuple(total_variance.shape) != (components.shape[0],):
+            raise ValueError("a basis is mean (b, D), components (b, k, D), eigenvalues (b, k), total_variance (b,)")
+        if scope == "batch" and components.shape[0] != 1:
+            raise ValueError("a batch-scope basis is one basis")
+        self.mean, self.components, self.eigenvalues, self.total_variance = mean, components, eigenvalues, total_variance
+        self.scope, self.stamp = scope, str(stamp)
+
+    @property
+    def n_bases(self) -> int:
+        return int(self.components.shape[0])
+
+    @property
+    def n_components(self) -> int:
+        return int(self.components.shape[1])
+
+    @property
+    def dim(self) -> int:
+        return int(self.components.shape[2])
+
+    @property
+    def explained_variance_ratio(self):
+        """eigenvalues / total_variance, (b, k): the share of the patch rows' variance each component carries."""
+        return self.eigenvalues / self.total_variance[:, None]
+
+    def check(self, dim: int, stamp: str) -> None:
+        if self.dim != int(dim):
+            raise ValueError(f"this basis was fitted on rows of width {self.dim}; the encoder's rows are {int(dim)} wide")
+        if self.stamp != str(stamp):
+            raise ValueError(f"this basis was fitted on encoder {self.stamp!r}, not on {str(stamp)!r}: its directions mean nothing here")
 
 
 # What an encoder built the reference's way - DinoEncoder(model_identifier, device), integration.install(),
@@ -427,6 +473,63 @@ class DinoEncoder:
         picture of what an encoder looks at that ConvNeXt encoders can give too.  ``query=None``: the CLS row (ConvNeXt: the
         pooled row); ``query=(y, x)`` in pixels: the patch under that pixel.  Computed on the device from the fp32 rows."""
         return self._tokens(frames, channel, torch.float32, query, True)[1]
+
+    @property
+    def stamp(self) -> str:
+        """The encoder stamp of this encoder's files (``encode_files.run_stamp``: the model identifier, tagged for MX-fp8 rows) with
+        the precision: what a ``PatchPCABasis`` remembers of the encoder it was fitted on.  It names the checkpoint, as the files'
+        stamp does, not the weights: every encoder built by ``from_weights`` is ``<in-memory>@pN``, so two different in-memory
+        encoders of one width and precision cannot be told apart by it."""
+        from .encode_files import run_stamp
+        return f"{run_stamp(getattr(self, 'model_identifier', '<in-memory>'), self.precision, self.fp8_plan or None)}@p{self.precision}"
+
+    def patch_pca(self, frames: torch.Tensor, n_components: int = 3, scope: str = "frame", basis: Optional[PatchPCABasis] = None,
+                  iters: Optional[int] = None, channel: int = 1):
+        """PCA of the patch rows of ``hidden_state(frames)``, fitted and projected on the device (cbas_patch_pca_fit /
+        cbas_patch_pca_project): the picture of what the encoder separates, and the one every family has.
+
+        Returns ``(scores, basis)``: ``scores`` float32 (n, nh, nw, n_components) on the device, the centred patch rows' coordinates
+        along the leading principal components; ``basis`` a ``PatchPCABasis``.  ``scope="frame"`` fits one basis per frame (a
+        frame's result does not depend on its batch), ``scope="batch"`` one for all frames.  With ``basis=`` given nothing is
+        fitted: the rows are projected on it (one basis for every frame, or one per frame) - a basis fitted on one batch colours a
+        whole clip consistently; its ``n_components`` and ``scope`` are the ones used.  A basis of another width or encoder is refused.
+        ``iters``: rounds of subspace iteration (default ``PCA_DEFAULT_ITERS``).  Frames, families and precisions: as
+        ``hidden_state``; ``encode_u8`` before and after gives the same bits.
+
+        The two entry points read rows, mean and components as 16-byte vectors and have no scalar fallback: pointers must be
+        16-byte aligned and the row stride a multiple of 4 floats, or the call is refused (CBAS_EINVAL).  This method always
+        meets that - it allocates the rows itself and copies a given basis into contiguous tensors - but a caller of
+        ``cbas_patch_pca_fit`` / ``cbas_patch_pca_project`` with rows in a view at an odd offset must copy them first."""
+        if basis is None and scope not in ("frame", "batch"):
+            raise ValueError(f"scope {scope!r}: 'frame' or 'batch'")
+        D = self.config.hidden_size
+        if basis is not None:
+            basis.check(D, self.stamp)
+        tokens, _, (nh, nw, P0) = self._tokens(frames, channel, torch.float32)
+        n, T, _ = tokens.shape
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if basis is None:
+            k = int(n_components)
+            sc = _lib.PCA_BATCH if scope == "batch" else _lib.PCA_FRAME
+            nb = 1 if scope == "batch" else n
+            need = int(self._lib.cbas_patch_pca_workspace_bytes(n, T, P0, D, k, sc))
+            if need < 0:
+                _lib.check(int(need), "cbas_patch_pca_workspace_bytes")
+            ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
+            f32 = dict(dtype=torch.float32, device=self.device)
+            basis = PatchPCABasis(torch.empty((nb, D), **f32), torch.empty((nb, k, D), **f32), torch.empty((nb, k), **f32),
+                                  torch.empty((nb,), **f32), scope, self.stamp)
+            _lib.check(self._lib.cbas_patch_pca_fit(tokens.data_ptr(), n, T, P0, D, D, k, sc, int(PCA_DEFAULT_ITERS if iters is None else iters),
+                                                    basis.mean.data_ptr(), basis.components.data_ptr(), basis.eigenvalues.data_ptr(),
+                                                    basis.total_variance.data_ptr(), ws.data_ptr(), need, stream), "cbas_patch_pca_fit")
+        elif basis.n_bases not in (1, n):
+            raise ValueError(f"a basis of {basis.n_bases} frames cannot colour {n} frames (one basis, or one per frame)")
+        k = basis.n_components
+        mean, comp = (t.to(self.device, torch.float32).contiguous() for t in (basis.mean, basis.components))
+        scores = torch.empty((n, nh, nw, k), dtype=torch.float32, device=self.device)
+        _lib.check(self._lib.cbas_patch_pca_project(tokens.data_ptr(), n, T, P0, D, D, k, basis.n_bases, mean.data_ptr(), comp.data_ptr(),
+                                                    scores.data_ptr(), stream), "cbas_patch_pca_project")
+        return scores, basis
 
     def submit_host(self, slot: int, frames: np.ndarray, channel: int = 1) -> None:
         """Queue one host chunk (uint8 (n,H,W,3) or (n,H,W), C-contiguous) on ``slot``."""

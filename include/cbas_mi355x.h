@@ -16,6 +16,8 @@
  *                                          the patch tokens, averaged over heads (output_attentions=True), beside the CLS rows
  *   cbas_enc_forward_u8_tokens / _f32_tokens   compare_encoders.py:36 / the golden scripts' model(pixel_values=x): the whole
  *                                          last_hidden_state (n, T, D) instead of row 0, and cosine maps over the patch rows
+ *   cbas_patch_pca_*                       (no counterpart: the reference draws attention only) PCA of the patch rows of that
+ *                                          last_hidden_state, fitted and projected on the device
  *   cbas_enc_submit_u8_host / cbas_enc_wait  backend/cbas.py:423-440 one iteration of the chunk loop
  *                                          (H2D copy, encode, D2H copy), made asynchronous
  *   cbas_head_create / cbas_head_destroy   backend/workthreads.py:427-447 ClassifierLSTMDeltas(...)
@@ -58,8 +60,8 @@ extern "C" {
 
 /* Still 11 with cbas_rows_gather_windows / cbas_head_train_step_rows, with cbas_head_score_rows / cbas_logits_nll, with
  * cbas_enc_set_pos_interp, with cbas_enc_set_fp8_plan, with cbas_probs_top1 / cbas_disagreement_runs, with
- * cbas_labels_median / cbas_label_runs / cbas_activity_bins, with cbas_enc_forward_u8_attn / cbas_enc_forward_f32_attn and with
- * cbas_enc_forward_u8_tokens / cbas_enc_forward_f32_tokens: they are additions.  No structure and no existing signature
+ * cbas_labels_median / cbas_label_runs / cbas_activity_bins, with cbas_enc_forward_u8_attn / cbas_enc_forward_f32_attn, with
+ * cbas_enc_forward_u8_tokens / cbas_enc_forward_f32_tokens and with cbas_patch_pca_*: they are additions.  No structure and no existing signature
  * changed, so a caller built against the earlier version 11 header runs unchanged. */
 #define CBAS_ABI_VERSION   11
 
@@ -229,6 +231,34 @@ int cbas_enc_forward_u8_tokens(cbas_enc* h, const uint8_t* frames_dev, int n, in
                                int64_t frame_stride, int64_t row_stride, int64_t pixel_stride,
                                float* tokens_f32_dev, uint16_t* tokens_f16_dev, int64_t ld_tokens,
                                const int32_t* query_idx_dev, float* sim_map_dev, void* stream);
+
+/* PCA of patch features: the picture that shows what an encoder separates (the top components of a frame's, or a batch's, patch
+ * rows as colours), fitted and projected on the device.  The reference has no such tool; the arithmetic is the textbook one.
+ * rows_dev is an image as cbas_enc_forward_*_tokens writes it (tokens_f32_dev): n frames of T rows of D floats, ld floats
+ * apart; the first n_prefix rows of each frame (CLS and registers; ConvNeXt: the pooled row) are skipped, P = T - n_prefix
+ * patch rows per frame take part.  Plain device pointers, no handle: any fp32 rows will do.
+ *     scope CBAS_PCA_FRAME   n independent problems of M = P rows: bases (n, ...), frame b's basis has the bits it has when
+ *                            fitted alone, whatever else shares the call
+ *     scope CBAS_PCA_BATCH   one problem of M = n P rows: one basis
+ * cbas_patch_pca_fit, per problem: mean_dev (D) = the column mean; the covariance C = (X - mean)^T (X - mean) / (M - 1) on the
+ * exact-fp32 matrix pipe in row chunks of 1024 added in order; its k leading eigenvectors by `iters` rounds of subspace
+ * iteration (fixed start, Z = C Q, modified Gram-Schmidt twice) and a Rayleigh-Ritz step: components_dev (k, D) with unit rows,
+ * ordered by eigenvalues_dev (k) descending, each with its entry of largest magnitude positive (ties: the lowest index);
+ * total_variance_dev (1) = trace C.  Every sum has a fixed order: two calls give the same bits.  The workspace
+ * (cbas_patch_pca_workspace_bytes, -1 for a refused shape; 16-byte aligned) holds on return, first, the covariances: problem b's
+ * D x D matrix, exactly symmetric, at float offset b * ceil(M / 1024) * D * D.
+ * cbas_patch_pca_project: scores_dev (n, P, k), scores[b][p][j] = (x - mean) . component j, with frame b's own basis
+ * (n_bases = n) or one basis for every frame (n_bases = 1) - from a fit, or the caller's.
+ * CBAS_EINVAL with a message: D % 32 != 0 or D > 1536, k outside 1 .. 8 or k > min(M - 1, D), M < 2, ld < D, iters < 1, a
+ * workspace too small, a NULL pointer, n outside 1 .. 65535, a pointer not 16-byte aligned or ld % 4 != 0, n_bases not 1 or n. */
+#define CBAS_PCA_FRAME 0
+#define CBAS_PCA_BATCH 1
+int64_t cbas_patch_pca_workspace_bytes(int n, int T, int n_prefix, int D, int k, int scope);
+int cbas_patch_pca_fit(const float* rows_dev, int n, int T, int n_prefix, int D, int64_t ld, int k, int scope, int iters,
+                       float* mean_dev, float* components_dev, float* eigenvalues_dev, float* total_variance_dev,
+                       void* workspace_dev, int64_t workspace_bytes, void* stream);
+int cbas_patch_pca_project(const float* rows_dev, int n, int T, int n_prefix, int D, int64_t ld, int k, int n_bases,
+                           const float* mean_dev, const float* components_dev, float* scores_dev, void* stream);
 
 /* Host-streamed form (one iteration of encode_file's chunk loop).  `slot` in [0, CBAS_ENC_SLOTS):
  * submit copies the pixels host->HBM on the handle's copy stream (from pinned staging), encodes
