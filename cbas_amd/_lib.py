@@ -31,6 +31,15 @@ class EncConfig(C.Structure):
                 ("family", c_int32), ("stage_widths", c_int32 * 4), ("stage_depths", c_int32 * 4)]
 
 
+class LayersArgs(C.Structure):
+    """cbas_enc_layers_args of include/cbas_mi355x.h."""
+    _fields_ = [("struct_bytes", c_int64), ("hidden_layers", c_void_p), ("n_hidden_layers", c_int32), ("hidden_norm", c_int32),
+                ("hidden_f32_dev", c_void_p), ("hidden_f16_dev", c_void_p), ("ld_hidden", c_int64), ("hidden_layer_stride", c_int64),
+                ("attn_layers", c_void_p), ("n_attn_layers", c_int32), ("rollout_start_layer", c_int32),
+                ("attn_heads_dev", c_void_p), ("attn_map_dev", c_void_p), ("rollout_dev", c_void_p), ("rollout_query_dev", c_void_p),
+                ("scratch_dev", c_void_p), ("scratch_bytes", c_int64)]
+
+
 class HeadConfigC(C.Structure):
     _fields_ = [("in_features", c_int32), ("out_features", c_int32), ("seq_len", c_int32),
                 ("bottleneck_dim", c_int32), ("lin0_dim", c_int32), ("lstm_hidden_size", c_int32),
@@ -57,6 +66,9 @@ SIGNATURES = {
     "cbas_enc_forward_f32_tokens": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "cbas_enc_forward_u8_tokens": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_int64, c_int64,
                                            c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "cbas_enc_layers_scratch_bytes": (c_int64, [c_void_p, c_int, c_int, c_int]),
+    "cbas_enc_forward_f32_layers": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "cbas_enc_forward_u8_layers": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
     "cbas_patch_pca_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "cbas_patch_pca_fit": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_int64, c_void_p]),
@@ -156,6 +168,8 @@ DEBUG_SIGNATURES = {
     "cbas_debug_gemm_run": (c_int, [c_void_p]),
     "cbas_debug_attention_run": (c_int, [c_void_p]),
     "cbas_debug_cls_attention": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p]),
+    "cbas_debug_attention_mean": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_int64, c_int, c_void_p]),
+    "cbas_debug_rollout_step": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "cbas_debug_rows_run": (c_int, [c_void_p]),
     "cbas_debug_head_run": (c_int, [c_void_p]),
     "cbas_debug_build": (c_int, []),

@@ -3,7 +3,8 @@ frames of a video - the picture the reference's encoder comparison tool draws (c
 the device by ``DinoEncoder.cls_attention`` beside the CLS rows.
 
     python -m cbas_amd.attention_maps --video V --frame N --encoder ID [--encoder ID ...] --out PNG [--precision P]
-                                      [--kind attention|similarity|pca] [--query Y,X] [--pca-scope frame|batch]
+                                      [--kind attention|similarity|pca|rollout] [--query Y,X] [--pca-scope frame|batch]
+                                      [--layer N|all]
 
 ``--kind similarity`` draws the other picture of the same question, from ``DinoEncoder.similarity_map``: the cosine of the CLS
 token's final hidden state (``--query Y,X``: of the patch under that pixel) to every patch token's.  It needs no attention, so it
@@ -13,6 +14,11 @@ is the kind DINOv3 ConvNeXt encoders have (their query row is the pooled one, th
 principal components, each stretched to [0, 1] over the picture, as red, green and blue - what the encoder separates, with no
 query and no attention, so every family has it and the pictures of two families can be compared.  ``--pca-scope batch`` fits one
 basis for all frames asked for (the same colours mean the same directions in each), ``frame`` (the default) one per frame.
+
+``--kind attention --layer N`` draws layer N's CLS attention instead of the last one's (1 .. L, negative from the end), ``--layer
+all`` one map per layer side by side.  ``--kind rollout`` draws attention rollout (Abnar and Zuidema) from
+``DinoEncoder.attention_rollout``: what the whole network looks at, the CLS row (``--query Y,X``: the row of the patch under that
+pixel) of the product of every layer's head-averaged attention mixed half and half with the identity.
 
 One deliberate difference from that tool: the map here is the map of what the encoder sees INSIDE CBAS - the green plane / 255
 replicated to three channels at the video's own size, exactly what ``encode_file`` feeds the model (backend/cbas.py:431) - not
@@ -29,7 +35,7 @@ from typing import Mapping, Sequence, Tuple, Union
 import numpy as np
 
 
-KINDS = ("attention", "similarity", "pca")
+KINDS = ("attention", "similarity", "pca", "rollout")
 PCA_SCOPES = ("frame", "batch")
 
 
@@ -40,16 +46,29 @@ def refuse_kind(cfg, kind: str):
         return f"unknown map kind {kind!r}: one of {', '.join(KINDS)}"
     if kind == "attention" and is_convnext(cfg):
         return "a ConvNeXt encoder has no attention: --kind similarity and --kind pca are the maps it has"
+    if kind == "rollout" and is_convnext(cfg):
+        return "a ConvNeXt encoder has no attention to roll out: --kind similarity and --kind pca are the maps it has"
     return None
 
 
-def frame_maps(encoder, path: str, frame_indices: Sequence[int], kind: str = "attention", query=None, pca_scope: str = "frame"):
+def parse_layer(text):
+    """``--layer``: None, "all", or an integer (negative: from the end)."""
+    if text is None or text == "all":
+        return text
+    try:
+        return int(text)
+    except ValueError:
+        raise ValueError(f"--layer {text!r}: an integer or 'all'") from None
+
+
+def frame_maps(encoder, path: str, frame_indices: Sequence[int], kind: str = "attention", query=None, pca_scope: str = "frame", layer=None):
     """Maps of the given frames of a video: ``kind`` "attention" (``cls_attention``), "similarity" (``similarity_map`` of
     ``query``: None, or a pixel (y, x)) or "pca" (``patch_pca``, three components).  Frames are read through
     ``pipeline.open_video`` (any source it knows) and encoded in batches of ``encoder.max_batch``.  Returns ``(maps, frames_green)``:
     float32 (n, nh, nw) and uint8 (n, H, W) numpy arrays, in the order of ``frame_indices``.  For "pca" ``maps`` is the finished
     picture instead, float32 (n, H, W, 3) in [0, 1] (``render_pca`` of each frame's scores); with ``pca_scope="batch"`` the basis
-    fitted on the first batch of frames colours all of them."""
+    fitted on the first batch of frames colours all of them.  "rollout": ``attention_rollout`` of ``query``.  ``layer`` ("attention"
+    only): a layer number, or "all" - ``maps`` then is (n, L, nh, nw)."""
     import torch
     from . import pipeline
     idx = [int(i) for i in frame_indices]
@@ -79,8 +98,10 @@ def frame_maps(encoder, path: str, frame_indices: Sequence[int], kind: str = "at
                 basis = fitted if pca_scope == "batch" else None
                 size = (green.shape[2], green.shape[1])
                 maps.append(np.stack([render_pca(sc, size) for sc in scores.cpu().numpy()]))
+            elif kind == "rollout":
+                maps.append(encoder.attention_rollout(dev, query).cpu().numpy())
             else:
-                maps.append((encoder.cls_attention(dev)[2] if kind == "attention" else encoder.similarity_map(dev, query)).cpu().numpy())
+                maps.append((encoder.cls_attention(dev, layer=layer)[2] if kind == "attention" else encoder.similarity_map(dev, query)).cpu().numpy())
             greens.append(green)
         return np.concatenate(maps), np.concatenate(greens)
     finally:
@@ -124,7 +145,7 @@ def _to_u8(a: np.ndarray) -> np.ndarray:
 
 
 def compare_encoders(video: str, frame_idx: int, encoders: Mapping[str, Union[str, object]], out_png: str, precision=None,
-                     kind: str = "attention", query=None, pca_scope: str = "frame") -> str:
+                     kind: str = "attention", query=None, pca_scope: str = "frame", layer=None) -> str:
     """One figure row per encoder: the frame as the encoder receives it (green plane) beside its rendered map (``kind``, ``query``:
     see ``frame_maps``).
     ``encoders`` maps a display name to a checkpoint directory, an HF-cache id or a ready ``DinoEncoder``; encoders built here
@@ -140,14 +161,19 @@ def compare_encoders(video: str, frame_idx: int, encoders: Mapping[str, Union[st
         if own:
             enc = DinoEncoder(enc, **({} if precision is None else {"precision": int(precision)}))
         try:
-            maps, green = frame_maps(enc, video, [frame_idx], kind, query, pca_scope)
+            maps, green = frame_maps(enc, video, [frame_idx], kind, query, pca_scope, layer)
             grid = token_grid(enc.config, green.shape[1], green.shape[2])[:2]
         finally:
             if own:
                 enc.close()
-        pic = (maps[0] * 255).astype(np.uint8) if kind == "pca" else render_map(maps[0], (green.shape[2], green.shape[1]))
+        size = (green.shape[2], green.shape[1])
+        pic = ((maps[0] * 255).astype(np.uint8) if kind == "pca" else
+               np.concatenate([render_map(m, size) for m in maps[0]], axis=1) if maps[0].ndim == 3 else render_map(maps[0], size))
         panels.append((name, green[0], grid, pic))
-    what = ("where its CLS token looks (last layer, mean of heads)" if kind == "attention" else
+    who = "CLS token" if query is None else f"patch at pixel {tuple(query)}"
+    what = ("where its CLS token looks (" + ("last layer" if layer is None else "layers 1 .. L, left to right" if layer == "all" else f"layer {layer}") +
+            ", mean of heads)" if kind == "attention" else
+            f"attention rollout of the {who} over every layer" if kind == "rollout" else
             "patch features along their first three principal components (R, G, B)" if kind == "pca" else
             "cosine of the final hidden states: " + ("CLS / pooled row" if query is None else f"patch at pixel {tuple(query)}") + " to each patch")
     _draw(Figure, FigureCanvasAgg, panels, f"{os.path.basename(video)}, frame {frame_idx}", out_png, what)
@@ -184,7 +210,9 @@ def _draw(Figure, Canvas, panels, caption: str, out_png: str, what: str) -> None
     fig.savefig(out_png, dpi=110)
 
 
-def main(argv=None) -> int:
+def parse_cli(argv=None):
+    """``(parser, namespace)``: the command line with ``query`` a pixel or None and ``layer`` None, "all" or an int; argparse's exit
+    on a combination that means nothing."""
     ap = argparse.ArgumentParser(prog="python -m cbas_amd.attention_maps", description=__doc__.split("\n\n")[0])
     ap.add_argument("--video", required=True)
     ap.add_argument("--frame", type=int, required=True)
@@ -193,21 +221,36 @@ def main(argv=None) -> int:
     ap.add_argument("--precision", type=int, default=None)
     ap.add_argument("--kind", choices=KINDS, default="attention", help="similarity and pca: the kinds a ConvNeXt encoder has")
     ap.add_argument("--pca-scope", choices=PCA_SCOPES, default=None, help="pca: one basis per frame (default) or one for all frames")
-    ap.add_argument("--query", default=None, metavar="Y,X", help="similarity: the pixel whose patch is the query (default: the CLS / pooled row)")
+    ap.add_argument("--query", default=None, metavar="Y,X", help="similarity, rollout: the pixel whose patch is the query (default: the CLS / pooled row)")
+    ap.add_argument("--layer", default=None, metavar="N|all", help="attention: the layer whose CLS attention is drawn (default: the last), or every layer in a row")
     a = ap.parse_args(argv)
     query = None
+    if a.layer is not None:
+        if a.kind != "attention":
+            ap.error("--layer goes with --kind attention")
+        try:
+            a.layer = parse_layer(a.layer)
+        except ValueError as e:
+            ap.error(str(e))
     if a.query is not None:
-        if a.kind != "similarity":
-            ap.error("--query goes with --kind similarity")
+        if a.kind not in ("similarity", "rollout"):
+            ap.error("--query goes with --kind similarity or --kind rollout")
         try:
             y, x = (int(v) for v in a.query.split(","))
         except ValueError:
             ap.error(f"--query {a.query!r}: two integers Y,X")
         query = (y, x)
+    a.query = query
     if a.pca_scope is not None and a.kind != "pca":
         ap.error("--pca-scope goes with --kind pca")
     if not a.encoder:
         ap.error("at least one --encoder is needed")
+    return ap, a
+
+
+def main(argv=None) -> int:
+    ap, a = parse_cli(argv)
+    query = a.query
     if not os.path.exists(a.video):
         ap.error(f"no such video: {a.video}")
     from . import pipeline
@@ -228,7 +271,7 @@ def main(argv=None) -> int:
             ap.error(f"--encoder {e}: {why}")
         names[e if e not in names else f"{e} ({len(names)})"] = e
     print(compare_encoders(a.video, a.frame, names, a.out, precision=a.precision, kind=a.kind, query=query,
-                           pca_scope=a.pca_scope or "frame"))
+                           pca_scope=a.pca_scope or "frame", layer=a.layer))
     return 0
 
 

@@ -854,6 +854,69 @@ extern "C" int cbas_debug_cls_attention(int arith, const float* q_host, const fl
     return CBAS_OK;
 }
 
+// ---- tests: one launch of the head-mean attention kernel / of the rollout chain step (attention_rollout.hip) on host arrays ----
+extern "C" int cbas_debug_attention_mean(int arith, const float* q_host, const float* K_host, int n, int T, int NH, int64_t ldq, int64_t ldk,
+                                         int blend, float* out_host) {
+    if (arith != 0 && arith != 3 && arith != 4) return cbas_fail(CBAS_EINVAL, "arith %d", arith);
+    if (!q_host || !K_host || !out_host || n <= 0 || T <= 0 || NH <= 0 || ldq < 64 * (int64_t)NH || ldk < 64 * (int64_t)NH || ldq % 8 || ldk % 8 ||
+        (int64_t)n * T * ldk > ((int64_t)1 << 30) || (int64_t)n * T * ldq > ((int64_t)1 << 30) || (int64_t)n * T * T > ((int64_t)1 << 30))
+        return cbas_fail(CBAS_EINVAL, "bad attention-mean test shape / pointers");
+    if (!attention_mean_rows_per_block(T))
+        return cbas_fail(CBAS_EINVAL, "T = %d: one query row's scores and sums (64 + 2 T floats) do not fit 64 KiB of LDS", T);
+    const size_t nq = (size_t)n * T * ldq, nk = (size_t)n * T * ldk, no = (size_t)n * T * T;
+    DevBufs B;
+    float *q32, *K32, *out;
+    HIP_TRY(B.alloc(&q32, nq * 4));
+    HIP_TRY(B.alloc(&K32, nk * 4));
+    HIP_TRY(B.alloc(&out, no * 4));
+    HIP_TRY(hipMemcpy(q32, q_host, nq * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(K32, K_host, nk * 4, hipMemcpyHostToDevice));
+    int rc = 0;
+    if (arith == 0) {
+        f16 *q16, *K16;
+        HIP_TRY(B.alloc(&q16, nq * 2));
+        HIP_TRY(B.alloc(&K16, nk * 2));
+        LAUNCH_TRY(launch_convert_f16(q32, q16, nullptr, (int64_t)nq, 0));
+        LAUNCH_TRY(launch_convert_f16(K32, K16, nullptr, (int64_t)nk, 0));
+        rc = launch_attention_mean<f16>(q16, ldq, K16, ldk, n, T, NH, 0, blend, out, 0);
+    } else if (arith == 3) {
+        rc = launch_attention_mean<float>(q32, ldq, K32, ldk, n, T, NH, 0, blend, out, 0);
+    } else {
+        float *qs, *Ks;
+        HIP_TRY(B.alloc(&qs, nq * 4));
+        HIP_TRY(B.alloc(&Ks, nk * 4));
+        HIP_TRY(hipMemset(qs, 0, nq * 4));
+        HIP_TRY(hipMemset(Ks, 0, nk * 4));
+        const int64_t tq = (int64_t)n * T * NH * 16;
+        hipLaunchKernelGGL(pack_heads_split_kernel, dim3((unsigned)((tq + 255) / 256)), dim3(256), 0, 0, q32, qs, (int64_t)n * T, ldq, NH * 64, ATT_QS);
+        hipLaunchKernelGGL(pack_heads_split_kernel, dim3((unsigned)((tq + 255) / 256)), dim3(256), 0, 0, K32, Ks, (int64_t)n * T, ldk, NH * 64, ATT_KS);
+        HIP_TRY(hipGetLastError());
+        rc = launch_attention_mean<float>(qs, ldq, Ks, ldk, n, T, NH, 1, blend, out, 0);
+    }
+    if (rc) return cbas_fail(CBAS_EINVAL, "attention-mean launch failed (arith %d, T %d: rc=%d)", arith, T, rc);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out_host, out, no * 4, hipMemcpyDeviceToHost));
+    return CBAS_OK;
+}
+
+extern "C" int cbas_debug_rollout_step(const float* A_host, const float* R_host, int n, int T, float* out_host) {
+    if (!A_host || !R_host || !out_host || n <= 0 || T <= 0 || (int64_t)n * T * T > ((int64_t)1 << 28))
+        return cbas_fail(CBAS_EINVAL, "bad rollout-step test shape / pointers");
+    const size_t no = (size_t)n * T * T;
+    DevBufs B;
+    float *A, *R, *out;
+    HIP_TRY(B.alloc(&A, no * 4));
+    HIP_TRY(B.alloc(&R, no * 4));
+    HIP_TRY(B.alloc(&out, no * 4));
+    HIP_TRY(hipMemcpy(A, A_host, no * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(R, R_host, no * 4, hipMemcpyHostToDevice));
+    const int rc = launch_rollout_step(A, R, out, n, T, 0);
+    if (rc) return cbas_fail(CBAS_EINVAL, "rollout-step launch failed (T %d: rc=%d)", T, rc);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out_host, out, no * 4, hipMemcpyDeviceToHost));
+    return CBAS_OK;
+}
+
 // ---- tests: one launch of a row-wise kernel (LayerNorm forms, the MX-fp8 row, the ConvNeXt producers) on host operands ----
 extern "C" int cbas_debug_rows_run(const cbas_debug_rows_args* a) {
     if (!a || a->struct_bytes != (int64_t)sizeof(cbas_debug_rows_args))

@@ -491,6 +491,71 @@ struct AttnOut {
     explicit operator bool() const { return heads || map; }
 };
 
+// Per-layer outputs of a forward (cbas_enc_forward_*_layers), filled from the buffers the block loop holds at the right moments:
+// the residual stream of every token after the patch GEMM (index 0) and after block l (index l), the CLS attention of any layer
+// and the attention rollout chain.  Null: the forward queues exactly what it queues without them.
+struct LayersOut {
+    const int32_t* hs_layers = nullptr;   // host: n_hs indices 0 .. L
+    int n_hs = 0, hs_norm = 0;
+    float* hs_f32 = nullptr;
+    f16* hs_f16 = nullptr;
+    int64_t hs_ld = 0, hs_stride = 0;     // elements: row stride, distance between two listed layers' images
+    const int32_t* at_layers = nullptr;   // host: n_at layer numbers 1 .. L
+    int n_at = 0;
+    float *at_heads = nullptr, *at_map = nullptr;      // (n_at, n, NH, T) / (n_at, n, P)
+    float* roll = nullptr;                // (n, P)
+    int roll_start = 1;                   // 1 .. L
+    const int32_t* roll_query = nullptr;  // device: per-frame token index; NULL: row 0
+    float* scratch = nullptr;             // 3 n T T floats: A^ of the current layer and the two products that alternate
+};
+
+// index 0: after the patch GEMM; index l: after block l
+int layers_hidden(cbas_enc* h, const Lane& ws, const VitShape& s, const LayersOut* lo, int index, hipStream_t st) {
+    if (!lo) return CBAS_OK;
+    for (int j = 0; j < lo->n_hs; ++j) {
+        if (lo->hs_layers[j] != index) continue;
+        float* const o32 = lo->hs_f32 ? lo->hs_f32 + j * lo->hs_stride : nullptr;
+        f16* const o16 = lo->hs_f16 ? lo->hs_f16 + j * lo->hs_stride : nullptr;
+        PROF(CBAS_PROF_OTHER, 0.0);
+        if (lo->hs_norm)
+            LAUNCH_TRY(launch_final_norm_rows(ws.x, s.D, h->norm_w, h->norm_b, o32, o16, lo->hs_ld, s.M, s.D, h->cfg.layer_norm_eps, h->nonfinite_dev, st));
+        else
+            LAUNCH_TRY(launch_copy_rows(ws.x, s.D, o32, o16, lo->hs_ld, s.M, s.D, h->nonfinite_dev, st));
+    }
+    return CBAS_OK;
+}
+
+// after layer l's (0-based) attention launch, while q | k | v of every token is still in qkv
+template <typename E>
+int layers_attention(cbas_enc* h, const VitShape& s, const LayersOut* lo, int l, const E* qkv, int split, int n, hipStream_t st) {
+    if (!lo) return CBAS_OK;
+    const int T = s.T, D = s.D, NH = h->NH, NP = h->NP, layer = l + 1;
+    for (int j = 0; j < lo->n_at; ++j) {
+        if (lo->at_layers[j] != layer) continue;
+        PROF(CBAS_PROF_OTHER, 2.0 * n * (double)T * D);
+        LAUNCH_TRY(launch_cls_attention<E>(qkv, (int64_t)T * 3 * D, qkv + D, 3 * D, n, T, NH, NP, split,
+                                           lo->at_heads ? lo->at_heads + (int64_t)j * n * NH * T : nullptr,
+                                           lo->at_map ? lo->at_map + (int64_t)j * n * s.P : nullptr, st));
+    }
+    if (lo->roll && layer >= lo->roll_start) {
+        const int64_t sz = (int64_t)n * T * T;
+        const int k = layer - lo->roll_start;            // products so far: R lives in buffer 1 + (k & 1) ... see below
+        float* const A = lo->scratch;
+        float* const R0 = lo->scratch + sz;
+        float* const R1 = lo->scratch + 2 * sz;
+        // layer roll_start writes A^ straight into R0; step k >= 1 reads R[(k - 1) & 1] and writes R[k & 1]
+        float* const cur = k == 0 ? R0 : ((k & 1) ? R1 : R0);
+        { PROF(CBAS_PROF_OTHER, 2.0 * n * (double)T * T * D);
+          LAUNCH_TRY(launch_attention_mean<E>(qkv, 3 * D, qkv + D, 3 * D, n, T, NH, split, 1, k == 0 ? R0 : A, st)); }
+        if (k > 0) {
+            PROF(CBAS_PROF_OTHER, 2.0 * n * (double)T * T * T);
+            LAUNCH_TRY(launch_rollout_step(A, (k & 1) ? R0 : R1, cur, n, T, st));
+        }
+        if (layer == h->L) LAUNCH_TRY(launch_rollout_row(cur, n, T, NP, lo->roll_query, lo->roll, st));
+    }
+    return CBAS_OK;
+}
+
 template <typename E>
 RowView<E> cls_rows(const cbas_enc* h, const VitShape& s, const Lane& ws, int n) {
     const int64_t cap = round_up(h->cfg.max_batch, 128);
@@ -629,7 +694,7 @@ int vit_tail_f32(cbas_enc* h, const Lane& ws, const LayerW& w, const VitShape& s
 }
 
 int run_blocks_f32(cbas_enc* h, const Lane& ws, int n, int height, int width, float* cls_f32, f16* cls_f16, hipStream_t st,
-                   int stop_layer, int stop_stage, const AttnOut& attn = AttnOut{}) {
+                   int stop_layer, int stop_stage, const AttnOut& attn = AttnOut{}, const LayersOut* lo = nullptr) {
     VitShape s{};
     int rc = vit_begin(h, n, height, width, cls_f32 || cls_f16, stop_layer, s);
     if (rc) return rc;
@@ -646,6 +711,7 @@ int run_blocks_f32(cbas_enc* h, const Lane& ws, int n, int height, int width, fl
     g.patches_per_frame = s.P; g.tokens_per_frame = T; g.n_prefix = h->NP; g.pos = h->cfg.use_rope ? nullptr : h->pos_tab;
     { PROF(CBAS_PROF_PATCH, 2.0 * g.M * g.N * g.K); LAUNCH_TRY(launch_gemm_f32_vit(EPI_PATCH, g, st)); }
     if (stop_layer == 0 && stop_stage == 0) return CBAS_OK;
+    if ((rc = layers_hidden(h, ws, s, lo, 0, st))) return rc;
 
     const RowView<float> all{M, s.M_pad, D, h32, h32, reinterpret_cast<float*>(ws.u16), nullptr}, cls = cls_rows<float>(h, s, ws, n);
     for (int l = 0; l < h->L; ++l) {
@@ -681,10 +747,12 @@ int run_blocks_f32(cbas_enc* h, const Lane& ws, int n, int height, int width, fl
             LAUNCH_TRY(launch_cls_attention<float>(cls_only ? cls.q : qkv32, cls_only ? D : (int64_t)T * 3 * D, qkv32 + D, 3 * D, n, T,
                                                    h->NH, h->NP, split, attn.heads, attn.map, st));
         }
+        if (!cls_only && (rc = layers_attention<float>(h, s, lo, l, qkv32, split, n, st))) return rc;
         if (stop == 3) return CBAS_OK;
 
         rc = vit_tail_f32(h, ws, w, s, v, stop, st);
         if (rc || (stop >= 4 && stop <= 7)) return rc;
+        if ((rc = layers_hidden(h, ws, s, lo, l + 1, st))) return rc;
     }
     if (cls_f32 || cls_f16)
         LAUNCH_TRY(launch_final_norm_cls(ws.x, h->norm_w, h->norm_b, cls_f32, cls_f16, n, T, D, eps, st, h->nonfinite_dev));
@@ -693,8 +761,9 @@ int run_blocks_f32(cbas_enc* h, const Lane& ws, int n, int height, int width, fl
 
 // Everything after ingest: patch GEMM, L transformer blocks, final CLS norm.
 int run_blocks(cbas_enc* h, const Lane& ws, int n, int height, int width, int patch_k, float in_scale, float* cls_f32,
-               f16* cls_f16, hipStream_t st, int stop_layer, int stop_stage, const AttnOut& attn = AttnOut{}) {
-    if (h->cfg.precision >= 3) return run_blocks_f32(h, ws, n, height, width, cls_f32, cls_f16, st, stop_layer, stop_stage, attn);
+               f16* cls_f16, hipStream_t st, int stop_layer, int stop_stage, const AttnOut& attn = AttnOut{},
+               const LayersOut* lo = nullptr) {
+    if (h->cfg.precision >= 3) return run_blocks_f32(h, ws, n, height, width, cls_f32, cls_f16, st, stop_layer, stop_stage, attn, lo);
     VitShape s{};
     int rc = vit_begin(h, n, height, width, cls_f32 || cls_f16, stop_layer, s);
     if (rc) return rc;
@@ -712,10 +781,11 @@ int run_blocks(cbas_enc* h, const Lane& ws, int n, int height, int width, int pa
     g.pos = h->cfg.use_rope ? nullptr : h->pos_tab;
     { PROF(CBAS_PROF_PATCH, 2.0 * g.M * g.N * g.K); LAUNCH_TRY(launch_gemm(EPI_PATCH, g, st)); }
     if (stop_layer == 0 && stop_stage == 0) return CBAS_OK;
+    if ((rc = layers_hidden(h, ws, s, lo, 0, st))) return rc;
 
     const int plan = h->cfg.precision == 2 ? h->fp8_plan : 0;
     const HalfFormats f{h->cfg.precision == 1, bool(plan & CBAS_FP8_PLAN_QKV), bool(plan & CBAS_FP8_PLAN_PROJ), bool(plan & CBAS_FP8_PLAN_UP),
-                        bool(plan & CBAS_FP8_PLAN_DOWN), h->ln_fold && h->fold_ok && stop_layer < 0};      // debug taps keep the LayerNorm kernels
+                        bool(plan & CBAS_FP8_PLAN_DOWN), h->ln_fold && h->fold_ok && stop_layer < 0 && !lo};      // debug taps and the per-layer outputs keep the LayerNorm kernels
     h->vit_forward_seen = true;
     if (f.fold) { PROF(CBAS_PROF_LAYERNORM, 0.0); LAUNCH_TRY(launch_ln_stats_x16(ws.x, ws.x16, ws.lnst, sc_ld, M, D, st)); }
     if (h->cfg.precision == 2 && stop_layer >= 0)
@@ -753,10 +823,12 @@ int run_blocks(cbas_enc* h, const Lane& ws, int n, int height, int width, int pa
             LAUNCH_TRY(launch_cls_attention<f16>(cls_only ? cls.q : ws.qkv16, cls_only ? D : (int64_t)T * 3 * D, ws.qkv16 + D, 3 * D, n, T,
                                                  h->NH, h->NP, 0, attn.heads, attn.map, st));
         }
+        if (!cls_only && (rc = layers_attention<f16>(h, s, lo, l, ws.qkv16, 0, n, st))) return rc;
         if (stop == 3) return CBAS_OK;
 
         rc = vit_tail(h, ws, w, s, f, v, l + 1 < h->L, stop, st);
         if (rc || (stop >= 4 && stop <= 7)) return rc;
+        if ((rc = layers_hidden(h, ws, s, lo, l + 1, st))) return rc;
     }
     if (cls_f32 || cls_f16)
         LAUNCH_TRY(launch_final_norm_cls(ws.x, h->norm_w, h->norm_b, cls_f32, cls_f16, n, T, D, eps, st, h->nonfinite_dev));
@@ -824,7 +896,7 @@ int run_cnx(cbas_enc* h, const Lane& ws, int n, int height, int width, float* cl
 
 int forward_u8_one(cbas_enc* h, const Lane& ws, const uint8_t* frames_dev, int n, int height, int width, int64_t frame_stride,
                    int64_t row_stride, int64_t pixel_stride, float* cls_f32, f16* cls_f16, hipStream_t st,
-                   int stop_layer, int stop_stage, const AttnOut& attn = AttnOut{}) {
+                   int stop_layer, int stop_stage, const AttnOut& attn = AttnOut{}, const LayersOut* lo = nullptr) {
     if (h->cfg.family == 1) {
         LAUNCH_TRY(launch_cnx_stem_im2col_u8(frames_dev, n, height, width, frame_stride, row_stride, pixel_stride,
                                              reinterpret_cast<float*>(ws.h16), h->cfg.precision == 4, st));
@@ -840,18 +912,18 @@ int forward_u8_one(cbas_enc* h, const Lane& ws, const uint8_t* frames_dev, int n
     else
         LAUNCH_TRY(launch_im2col_u8(frames_dev, n, height, width, frame_stride, row_stride, pixel_stride, ws.A_patch,
                                     ws.x, h->prefix, h->NP, h->D, T, ps, st));
-    return run_blocks(h, ws, n, height, width, 256, 1.0f / 255.0f, cls_f32, cls_f16, st, stop_layer, stop_stage, attn);
+    return run_blocks(h, ws, n, height, width, 256, 1.0f / 255.0f, cls_f32, cls_f16, st, stop_layer, stop_stage, attn, lo);
 }
 
 int forward_u8(cbas_enc* h, const Lane& ws, const uint8_t* frames_dev, int n, int height, int width, int64_t frame_stride,
                int64_t row_stride, int64_t pixel_stride, float* cls_f32, f16* cls_f16, hipStream_t st,
-               int stop_layer, int stop_stage, const AttnOut& attn = AttnOut{}) {
+               int stop_layer, int stop_stage, const AttnOut& attn = AttnOut{}, const LayersOut* lo = nullptr) {
     int rc = check_frame(h, n, height, width);
     if (rc) return rc;
     if (!frames_dev) return cbas_fail(CBAS_EINVAL, "frames_dev is NULL");
     HIP_TRY(hipSetDevice(h->device));
     return forward_u8_one(h, ws, frames_dev, n, height, width, frame_stride, row_stride, pixel_stride, cls_f32, cls_f16, st,
-                          stop_layer, stop_stage, attn);
+                          stop_layer, stop_stage, attn, lo);
 }
 
 // The buffers of lanes[lane], each zero-filled whole on `st` (the handle's compute stream: see the note at qkv_bias_all in
@@ -1513,13 +1585,13 @@ static int tokens_tail(cbas_enc* h, const Lane& ws, int n, int height, int width
 // the two synchronous forwards: the CLS rows, with or without the attention outputs, or (tok) every token's row instead
 static int enc_forward_u8(cbas_enc* h, const uint8_t* frames_dev, int n, int height, int width, int64_t frame_stride,
                           int64_t row_stride, int64_t pixel_stride, float* cls_f32_dev, uint16_t* cls_f16_dev, void* stream,
-                          const AttnOut& attn, const TokOut& tok = TokOut{}) {
+                          const AttnOut& attn, const TokOut& tok = TokOut{}, const LayersOut* lo = nullptr) {
     if (!h) return cbas_fail(CBAS_EINVAL, "null encoder handle");
     hipStream_t st = (hipStream_t)stream;
     int rc = sync_enter(h, st);
     if (rc) return rc;
     rc = forward_u8(h, h->lanes[0], frames_dev, n, height, width, frame_stride, row_stride, pixel_stride, cls_f32_dev,
-                    (f16*)cls_f16_dev, st, -1, -1, attn);
+                    (f16*)cls_f16_dev, st, -1, -1, attn, lo);
     if (!rc && tok) rc = tokens_tail(h, h->lanes[0], n, height, width, tok, st);
     if (rc) return rc;
     return sync_leave(h, st);
@@ -1563,7 +1635,8 @@ extern "C" int cbas_enc_forward_u8_attn(cbas_enc* h, const uint8_t* frames_dev, 
 }
 
 static int enc_forward_f32(cbas_enc* h, const float* x_dev, int n, int height, int width, float* cls_f32_dev,
-                           uint16_t* cls_f16_dev, void* stream, const AttnOut& attn, const TokOut& tok = TokOut{}) {
+                           uint16_t* cls_f16_dev, void* stream, const AttnOut& attn, const TokOut& tok = TokOut{},
+                           const LayersOut* lo = nullptr) {
     int rc = check_frame(h, n, height, width);
     if (rc) return rc;
     if (!x_dev) return cbas_fail(CBAS_EINVAL, "x_dev is NULL");
@@ -1586,7 +1659,7 @@ static int enc_forward_f32(cbas_enc* h, const float* x_dev, int n, int height, i
                                          h->cfg.precision == 4, st));
     else
         LAUNCH_TRY(launch_im2col_f32(x_dev, n, height, width, ws.A_patch, ws.x, h->prefix, h->NP, h->D, T, ps, st));
-    rc = run_blocks(h, ws, n, height, width, 512, 1.0f, cls_f32_dev, (f16*)cls_f16_dev, st, -1, -1, attn);
+    rc = run_blocks(h, ws, n, height, width, 512, 1.0f, cls_f32_dev, (f16*)cls_f16_dev, st, -1, -1, attn, lo);
     if (!rc && tok) rc = tokens_tail(h, ws, n, height, width, tok, st);
     if (rc) return rc;
     return sync_leave(h, st);
@@ -1627,6 +1700,95 @@ extern "C" int cbas_enc_forward_f32_tokens(cbas_enc* h, const float* x_dev, int 
     const int rc = check_tokens(h, tok);
     if (rc) return rc;
     return enc_forward_f32(h, x_dev, n, height, width, nullptr, nullptr, stream, AttnOut{}, tok);
+}
+
+// ---- per-layer outputs: cbas_enc_forward_*_layers ----
+extern "C" int64_t cbas_enc_layers_scratch_bytes(const cbas_enc* h, int n, int height, int width) {
+    if (!h) { cbas_fail(CBAS_EINVAL, "null encoder handle"); return -1; }
+    if (h->cfg.family == 1) { cbas_fail(CBAS_EINVAL, "a ConvNeXt encoder has no attention: attention rollout exists for the ViT families only"); return -1; }
+    const int ps = h->cfg.patch_size;
+    if (n <= 0 || height < ps || width < ps) { cbas_fail(CBAS_EINVAL, "n = %d frames of %dx%d", n, height, width); return -1; }
+    const int64_t T = (int64_t)(height / ps) * (width / ps) + h->NP;
+    return 3 * (int64_t)n * T * T * (int64_t)sizeof(float);
+}
+
+// every refusal of the ..._layers forms, before anything is queued
+static int check_layers(const cbas_enc* h, const cbas_enc_layers_args* a, int n, int height, int width, LayersOut& lo) {
+    if (!h) return cbas_fail(CBAS_EINVAL, "null encoder handle");
+    if (!a || a->struct_bytes != (int64_t)sizeof(cbas_enc_layers_args))
+        return cbas_fail(CBAS_EINVAL, "cbas_enc_layers_args: struct_bytes %lld, library expects %lld", a ? (long long)a->struct_bytes : -1ll,
+                         (long long)sizeof(cbas_enc_layers_args));
+    if (h->cfg.family == 1)
+        return cbas_fail(CBAS_EINVAL, "a ConvNeXt encoder has no transformer layers: per-layer hidden states, attention and rollout exist for the ViT families only");
+    if (h->cfg.precision == 2)
+        return cbas_fail(CBAS_EINVAL, "precision 2 serves CLS rows only: the token rows of its MX-fp8 layers are a different encoder's (use precision 0)");
+    const bool want_hs = a->hidden_f32_dev || a->hidden_f16_dev, want_at = a->attn_heads_dev || a->attn_map_dev, want_roll = a->rollout_dev != nullptr;
+    if (!want_hs && !want_at && !want_roll)
+        return cbas_fail(CBAS_EINVAL, "hidden_f32_dev, hidden_f16_dev, attn_heads_dev, attn_map_dev and rollout_dev are all NULL");
+    const int L = h->L, D = h->D;
+    if (want_hs) {
+        if (!a->hidden_layers || a->n_hidden_layers <= 0) return cbas_fail(CBAS_EINVAL, "hidden-state outputs without a list of layers");
+        for (int j = 0; j < a->n_hidden_layers; ++j)
+            if (a->hidden_layers[j] < 0 || a->hidden_layers[j] > L)
+                return cbas_fail(CBAS_EINVAL, "hidden_layers[%d] = %d: hidden states are numbered 0 .. %d", j, a->hidden_layers[j], L);
+        if (a->ld_hidden < D || a->ld_hidden % 4) return cbas_fail(CBAS_EINVAL, "ld_hidden = %lld: at least the width %d and a multiple of 4", (long long)a->ld_hidden, D);
+        if (a->hidden_layer_stride % 4 || (a->n_hidden_layers > 1 && a->hidden_layer_stride < ((int64_t)n * (height / h->cfg.patch_size) * (width / h->cfg.patch_size) + (int64_t)n * h->NP - 1) * a->ld_hidden + D))
+            return cbas_fail(CBAS_EINVAL, "hidden_layer_stride = %lld: a multiple of 4 that holds one layer's image", (long long)a->hidden_layer_stride);
+        if ((uintptr_t)a->hidden_f32_dev % 16 || (uintptr_t)a->hidden_f16_dev % 8)
+            return cbas_fail(CBAS_EINVAL, "hidden-state outputs must be 16-byte aligned (fp16: 8)");
+    }
+    if (want_at) {
+        if (!a->attn_layers || a->n_attn_layers <= 0) return cbas_fail(CBAS_EINVAL, "attention outputs without a list of layers");
+        for (int j = 0; j < a->n_attn_layers; ++j)
+            if (a->attn_layers[j] < 1 || a->attn_layers[j] > L)
+                return cbas_fail(CBAS_EINVAL, "attn_layers[%d] = %d: attention layers are numbered 1 .. %d", j, a->attn_layers[j], L);
+        if (((uintptr_t)a->attn_heads_dev | (uintptr_t)a->attn_map_dev) % 4) return cbas_fail(CBAS_EINVAL, "attention outputs must be 4-byte aligned");
+    }
+    if (want_roll) {
+        if (a->rollout_start_layer < 1 || a->rollout_start_layer > L)
+            return cbas_fail(CBAS_EINVAL, "rollout_start_layer = %d: layers are numbered 1 .. %d", a->rollout_start_layer, L);
+        if (((uintptr_t)a->rollout_dev | (uintptr_t)a->rollout_query_dev) % 4) return cbas_fail(CBAS_EINVAL, "rollout outputs must be 4-byte aligned");
+        if (!a->scratch_dev || (uintptr_t)a->scratch_dev % 16) return cbas_fail(CBAS_EINVAL, "the rollout scratch must be a 16-byte aligned device pointer");
+    }
+    int rc = check_frame(const_cast<cbas_enc*>(h), n, height, width);
+    if (rc) return rc;
+    if (want_at && (rc = check_attn_frame(h, height, width))) return rc;
+    if (want_roll) {
+        const int ps = h->cfg.patch_size;
+        const int64_t T = (int64_t)(height / ps) * (width / ps) + h->NP;
+        if (!attention_mean_rows_per_block(T))
+            return cbas_fail(CBAS_EINVAL, "frame %dx%d has %lld tokens: one row of the attention rollout kernel does not fit 64 KiB of LDS", height, width, (long long)T);
+        const int64_t need = 3 * (int64_t)n * T * T * (int64_t)sizeof(float);
+        if (a->scratch_bytes < need)
+            return cbas_fail(CBAS_EINVAL, "rollout scratch of %lld bytes: %d frames of %lld tokens need %lld (cbas_enc_layers_scratch_bytes)",
+                             (long long)a->scratch_bytes, n, (long long)T, (long long)need);
+    }
+    if (want_hs) {
+        lo.hs_layers = a->hidden_layers; lo.n_hs = a->n_hidden_layers; lo.hs_norm = a->hidden_norm != 0;
+        lo.hs_f32 = a->hidden_f32_dev; lo.hs_f16 = (f16*)a->hidden_f16_dev; lo.hs_ld = a->ld_hidden; lo.hs_stride = a->hidden_layer_stride;
+    }
+    if (want_at) { lo.at_layers = a->attn_layers; lo.n_at = a->n_attn_layers; lo.at_heads = a->attn_heads_dev; lo.at_map = a->attn_map_dev; }
+    if (want_roll) {
+        lo.roll = a->rollout_dev; lo.roll_start = a->rollout_start_layer; lo.roll_query = a->rollout_query_dev; lo.scratch = (float*)a->scratch_dev;
+    }
+    return CBAS_OK;
+}
+
+extern "C" int cbas_enc_forward_u8_layers(cbas_enc* h, const uint8_t* frames_dev, int n, int height, int width,
+                                          int64_t frame_stride, int64_t row_stride, int64_t pixel_stride,
+                                          const cbas_enc_layers_args* args, void* stream) {
+    LayersOut lo;
+    const int rc = check_layers(h, args, n, height, width, lo);
+    if (rc) return rc;
+    return enc_forward_u8(h, frames_dev, n, height, width, frame_stride, row_stride, pixel_stride, nullptr, nullptr, stream, AttnOut{}, TokOut{}, &lo);
+}
+
+extern "C" int cbas_enc_forward_f32_layers(cbas_enc* h, const float* x_dev, int n, int height, int width,
+                                           const cbas_enc_layers_args* args, void* stream) {
+    LayersOut lo;
+    const int rc = check_layers(h, args, n, height, width, lo);
+    if (rc) return rc;
+    return enc_forward_f32(h, x_dev, n, height, width, nullptr, nullptr, stream, AttnOut{}, TokOut{}, &lo);
 }
 
 #if CBAS_BUILD_DEBUG      // stage taps: debug build only (include/cbas_mi355x_debug.h)

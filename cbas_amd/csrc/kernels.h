@@ -156,6 +156,21 @@ template <typename E>
 int launch_cls_attention(const E* q, int64_t ldq, const E* K, int64_t ldk, int n, int T, int NH, int NP, int split,
                          float* heads_out, float* map_out, hipStream_t stream);
 
+// attention_rollout.hip: the head-mean softmax rows of EVERY query of a layer, and the rollout chain over the layers.
+//   launch_attention_mean: out (n, T, T) fp32, out[b][i][t] = (1 / NH) sum_h softmax_t(q[b T + i, h] . K[b T + t, h]); q and K
+//   are [n*T] rows of stride ldq / ldk in the storage forms of launch_cls_attention (E, split), pointing at head 0's first column
+//   (q bias added and x 1/8).  blend != 0 writes 0.5 out + 0.5 I instead.  LDS: QB (64 + 2 T) floats for QB query rows per
+//   workgroup (attention_mean_rows_per_block: 16 down to 1, 0 = T does not fit, about 8 100 tokens).  -1: bad argument or such a T.
+//   launch_rollout_step: out = A R per frame, (n, T, T) each, out distinct from both.  launch_rollout_row: out (n, T - NP) =
+//   columns NP.. of row query_idx[b] (clamped to [0, T); NULL: row 0) of R.  All fp32, fixed summation order, no atomics.
+constexpr int64_t ATTENTION_MEAN_LDS_BYTES = 64 * 1024 - 256;
+int attention_mean_rows_per_block(int64_t T);
+template <typename E>
+int launch_attention_mean(const E* q, int64_t ldq, const E* K, int64_t ldk, int n, int T, int NH, int split, int blend, float* out,
+                          hipStream_t stream);
+int launch_rollout_step(const float* A, const float* R, float* out, int n, int T, hipStream_t stream);
+int launch_rollout_row(const float* R, int n, int T, int NP, const int* query_idx, float* out, hipStream_t stream);
+
 // tokens_out.hip: every token's final hidden state (transformers' last_hidden_state) instead of the CLS row alone, and patch
 // similarity maps.  out_f32 / out_f16: rows of stride ld_out elements (>= the width, a multiple of 4); either may be nullptr, not
 // both.  Rows are normalised by the code of the CLS kernels (row_norm.h): row 0 of a frame has launch_final_norm_cls's /
@@ -163,6 +178,9 @@ int launch_cls_attention(const E* q, int64_t ldq, const E* K, int64_t ldk, int n
 //   ViT: out[r] = LayerNorm(x[r]), r < M (= n T); x rows of stride ldx; D % 4 == 0, D <= 1280
 int launch_final_norm_rows(const float* x, int64_t ldx, const float* gamma, const float* beta, float* out_f32, f16* out_f16,
                            int64_t ld_out, int64_t M, int D, float eps, unsigned* nonfinite, hipStream_t stream);
+//   the raw rows (transformers' hidden_states[l]): out[r] = x[r], r < M, as fp32 and / or fp16 (round to nearest even); D % 4 == 0
+int launch_copy_rows(const float* x, int64_t ldx, float* out_f32, f16* out_f16, int64_t ld_out, int64_t M, int D, unsigned* nonfinite,
+                     hipStream_t stream);
 //   ConvNeXt: out[b (hw + 1)] = LayerNorm(mean over the hw pixels of frame b), out[b (hw + 1) + 1 + p] = LayerNorm(x[b hw + p]);
 //   x rows of stride ld holding C values (C % 32 == 0, C <= 1536)
 int launch_cnx_token_rows(const float* x, int64_t ld, int n, int hw, const float* gamma, const float* beta, int C, float eps,

@@ -3,6 +3,7 @@
 // (final_norm_cls_kernel, cnx_pool_ln_kernel).  These kernels write the whole (n, T, D) image instead:
 //
 //   final_norm_rows_kernel    ViT: out[r] = LayerNorm(x[r]) for all M = n T rows                            [tf]:540
+//   copy_rows_kernel          ViT: out[r] = x[r], the raw rows of any layer (transformers' hidden_states[l])
 //   cnx_token_rows_kernel     ConvNeXt: out[b][0] = LayerNorm(mean over the hw pixels), out[b][1 + p] = LayerNorm(x[b][p])
 //                             (DINOv3ConvNextModel.forward: pool, concatenate, then ONE LayerNorm over every row)
 //   token_similarity_kernel   map[b][p] = cos(out[b][q_b], out[b][P0 + p]) over the patch rows
@@ -58,6 +59,31 @@ __global__ __launch_bounds__(256) void final_norm_rows_kernel(const float* __res
     const float rstd = ln_row<NV>(x + row * ldx, gamma, beta, D, eps, lane, y);
     count_nonfinite<NV>(rstd, y, D >> 2, lane, nonfinite);
     store_row<NV>(y, out_f32 ? out_f32 + row * ld_out : nullptr, out_f16 ? out_f16 + row * ld_out : nullptr, D >> 2, lane);
+}
+
+// The raw rows of the residual stream (transformers' hidden_states[l]: no LayerNorm): one wave per row, 16-byte loads, the same
+// stores and the same range check on the values themselves.
+__global__ __launch_bounds__(256) void copy_rows_kernel(const float* __restrict__ x, int64_t ldx, float* __restrict__ out_f32,
+                                                        f16* __restrict__ out_f16, int64_t ld_out, int64_t M, int D,
+                                                        unsigned* __restrict__ nonfinite) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    const float* xr = x + row * ldx;
+    float* o32 = out_f32 ? out_f32 + row * ld_out : nullptr;
+    f16* o16 = out_f16 ? out_f16 + row * ld_out : nullptr;
+    bool bad = false;
+    for (int idx = lane; idx < (D >> 2); idx += 64) {
+        const f32x4 v = reinterpret_cast<const f32x4*>(xr)[idx];
+        const f32x4 a = __builtin_elementwise_abs(v);
+        bad |= !(a[0] <= 3.0e38f && a[1] <= 3.0e38f && a[2] <= 3.0e38f && a[3] <= 3.0e38f);
+        if (o32) reinterpret_cast<f32x4*>(o32)[idx] = v;
+        if (o16) {
+            f16x4 hv = {(f16)v[0], (f16)v[1], (f16)v[2], (f16)v[3]};      // round-to-nearest-even
+            reinterpret_cast<f16x4*>(o16)[idx] = hv;
+        }
+    }
+    if (nonfinite && __ballot(bad) && lane == 0) atomicAdd(nonfinite, 1u);
 }
 
 // grid (1 + ceil(hw / 4), n).  Block 0 of a frame is cnx_pool_ln_kernel's workgroup (wave w sums pixels w, w + 4, ... in order;
@@ -166,6 +192,15 @@ int launch_final_norm_rows(const float* x, int64_t ldx, const float* gamma, cons
         return -1;
     TOK_NV_SWITCH((D / 4 + 63) / 64, final_norm_rows_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, stream, x, ldx, gamma, beta,
                   out_f32, out_f16, ld_out, M, D, eps, nonfinite);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int launch_copy_rows(const float* x, int64_t ldx, float* out_f32, f16* out_f16, int64_t ld_out, int64_t M, int D, unsigned* nonfinite,
+                     hipStream_t stream) {
+    if (!x || (!out_f32 && !out_f16) || M <= 0 || (M + 3) / 4 > 0x7fffffff || D <= 0 || D % 4 || !rows_ok(x, ldx, D, 4) ||
+        !rows_ok(out_f32, ld_out, D, 4) || !rows_ok(out_f16, ld_out, D, 2))
+        return -1;
+    hipLaunchKernelGGL(copy_rows_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, stream, x, ldx, out_f32, out_f16, ld_out, M, D, nonfinite);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

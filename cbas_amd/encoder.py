@@ -8,7 +8,8 @@ through the C ABI (``cbas_enc_*``).  torch tensors are only containers for devic
 Extras beyond the reference interface (used by ``encode_file`` and the benchmarks):
 ``encode_u8`` takes uint8 frames already in HBM, ``submit_host``/``wait`` stream host chunks
 through pinned staging with copy/compute overlap.  ``cls_attention``, ``hidden_state`` / ``patch_tokens`` /
-``similarity_map`` and ``patch_pca`` are the three ways to look at what the encoder sees.
+``similarity_map`` and ``patch_pca`` are the three ways to look at what the encoder sees; ``hidden_states``, ``cls_attention(layer=)``
+and ``attention_rollout`` look below the last layer.
 """
 from __future__ import annotations
 
@@ -102,6 +103,26 @@ def query_token_index(cfg, H: int, W: int, query) -> int:
     if not (0 <= y < nh * cell and 0 <= x < nw * cell):
         raise ValueError(f"query pixel ({y}, {x}) is outside the {nh * cell} x {nw * cell} pixels the {nh} x {nw} patch grid covers")
     return P0 + (y // cell) * nw + x // cell
+
+
+def normalize_layers(layers, L: int, lo: int = 0, what: str = "hidden-state"):
+    """A list of layer indices in [lo, L] from ``None`` / ``"all"`` (every one), an int or a sequence; negative values count from
+    the end (-1 = L).  Out of range: ``ValueError``."""
+    if layers is None or (isinstance(layers, str) and layers == "all"):
+        return list(range(lo, L + 1))
+    if isinstance(layers, str):
+        raise ValueError(f"{what} layers {layers!r}: a list of indices, or 'all'")
+    seq = [layers] if isinstance(layers, (int, np.integer)) else list(layers)
+    if not seq:
+        raise ValueError(f"an empty list of {what} layers")
+    out = []
+    for v in seq:
+        i = int(v)
+        i = i + L + 1 if i < 0 else i
+        if not lo <= i <= L:
+            raise ValueError(f"{what} layer {int(v)} is outside {lo} .. {L} (negative values count from the end)")
+        out.append(i)
+    return out
 
 
 PCA_DEFAULT_ITERS = 64      # rounds of subspace iteration in ``patch_pca``: chosen on the host by tests/test_patch_pca_host.py (DESIGN.md section 16)
@@ -387,7 +408,7 @@ class DinoEncoder:
                 "cbas_enc_forward_u8")
         return out16, out32
 
-    def cls_attention(self, frames: torch.Tensor, channel: int = 1, per_head: bool = False):
+    def cls_attention(self, frames: torch.Tensor, channel: int = 1, per_head: bool = False, layer=None):
         """The CLS rows plus the last layer's attention from the CLS token to the patch tokens, averaged over the heads - what
         ``output_attentions=True`` gives the reference's encoder comparison tool - computed on the device from the query and keys
         of the forward itself (cbas_enc_forward_u8_attn / cbas_enc_forward_f32_attn).
@@ -397,9 +418,16 @@ class DinoEncoder:
         (n, nh, nw) device tensor over the patch grid; with ``per_head=True`` a fourth element, the (n, NH, T) softmax rows
         over all T tokens (CLS and registers first).  The CLS rows are bit for bit ``encode_u8``'s.  Every ViT precision is served;
         a precision-2 encoder's map is the map of that MX-fp8 encoder, not of the fp16 one.  ConvNeXt encoders have no attention:
-        ``ValueError``."""
+        ``ValueError``.
+
+        ``layer=None`` is the path above, the pruned last layer included.  ``layer=l`` (1 .. L, or negative from the end) gives
+        layer l's map (and rows) instead, ``layer="all"`` every layer's: ``maps`` (n, L, nh, nw) and the rows (n, L, NH, T) - one
+        unpruned forward (cbas_enc_forward_*_layers) beside the ``encode_u8`` forward that gives the CLS rows their bits.
+        Precision 2 is refused there, as for ``hidden_state``; n may not exceed ``max_batch``."""
         if is_convnext(self.config):
             raise ValueError("a ConvNeXt encoder has no attention: CLS attention maps exist for the ViT families only")
+        if layer is not None:
+            return self._cls_attention_layers(frames, channel, per_head, layer)
         frames, n, H, W, strides, base_off = _frame_args(frames, channel, "cls_attention")
         self._fit_frame(H, W)
         cfg = self.config
@@ -423,6 +451,113 @@ class DinoEncoder:
                                                               out32[i:i + m].data_ptr(), out16[i:i + m].data_ptr(), stream, hp,
                                                               maps[i:i + m].data_ptr()), "cbas_enc_forward_u8_attn")
         return (out16, out32, maps, heads) if per_head else (out16, out32, maps)
+
+    # -- per-layer outputs: one cbas_enc_forward_*_layers call ---------------------------------------
+    def _layers_refusals(self, what: str) -> None:
+        if is_convnext(self.config):
+            raise ValueError(f"a ConvNeXt encoder has no transformer layers: {what} exists for the ViT families only "
+                             "(its stage outputs are a different object)")
+        if self.precision == 2:
+            raise ValueError("precision 2 serves CLS rows only: the token rows of its MX-fp8 layers are a different encoder's "
+                             "(use precision 0)")
+
+    def _layers_call(self, frames, channel, what, hidden=None, attn=None, rollout=None):
+        """hidden = (layers, norm, dtype) -> (len, n, T, D); attn = (layers, per_head) -> maps (len, n, P), heads (len, n, NH, T) or
+        None; rollout = (start_layer, query) -> (n, nh, nw) and the scratch.  Returns a dict of what was asked for."""
+        self._layers_refusals(what)
+        frames, n, H, W, strides, base_off = _frame_args(frames, channel, what)
+        if n > self.max_batch:
+            raise ValueError(f"{what} is one library call: {n} frames exceed max_batch = {self.max_batch}")
+        self._fit_frame(H, W)
+        cfg = self.config
+        D, NH, ps = cfg.hidden_size, cfg.num_attention_heads, cfg.patch_size
+        nh, nw = H // ps, W // ps
+        T = cfg.num_tokens(H, W)
+        a = _lib.LayersArgs()
+        a.struct_bytes = C.sizeof(_lib.LayersArgs)
+        out = {"grid": (nh, nw, T - nh * nw)}
+        if hidden is not None:
+            layers, norm, dtype = hidden
+            if dtype not in (torch.float32, torch.float16):
+                raise ValueError("hidden states come as torch.float32 or torch.float16")
+            idx = (C.c_int32 * len(layers))(*layers)
+            hs = torch.empty((len(layers), n, T, D), dtype=dtype, device=self.device)
+            a.hidden_layers, a.n_hidden_layers, a.hidden_norm = C.cast(idx, C.c_void_p), len(layers), int(bool(norm))
+            a.hidden_f32_dev, a.hidden_f16_dev = (hs.data_ptr(), None) if dtype == torch.float32 else (None, hs.data_ptr())
+            a.ld_hidden, a.hidden_layer_stride = D, n * T * D
+            out["hidden"] = hs
+        if attn is not None:
+            layers, per_head = attn
+            idx = (C.c_int32 * len(layers))(*layers)
+            maps = torch.empty((len(layers), n, nh * nw), dtype=torch.float32, device=self.device)
+            heads = torch.empty((len(layers), n, NH, T), dtype=torch.float32, device=self.device) if per_head else None
+            a.attn_layers, a.n_attn_layers = C.cast(idx, C.c_void_p), len(layers)
+            a.attn_map_dev, a.attn_heads_dev = maps.data_ptr(), heads.data_ptr() if per_head else None
+            out["maps"], out["heads"] = maps, heads
+        if rollout is not None:
+            start, query = rollout
+            need = int(self._lib.cbas_enc_layers_scratch_bytes(self._h, n, H, W))
+            if need < 0:
+                _lib.check(need, "cbas_enc_layers_scratch_bytes")
+            scratch = torch.empty((need,), dtype=torch.uint8, device=self.device)
+            roll = torch.empty((n, nh, nw), dtype=torch.float32, device=self.device)
+            qidx = None
+            if query is not None:
+                qidx = torch.full((n,), query_token_index(cfg, H, W, query), dtype=torch.int32, device=self.device)
+            a.rollout_dev, a.rollout_start_layer = roll.data_ptr(), int(start)
+            a.rollout_query_dev = qidx.data_ptr() if qidx is not None else None
+            a.scratch_dev, a.scratch_bytes = scratch.data_ptr(), need
+            out["rollout"], out["scratch"] = roll, scratch
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if strides is None:
+            _lib.check(self._lib.cbas_enc_forward_f32_layers(self._h, frames.data_ptr(), n, H, W, C.byref(a), stream), "cbas_enc_forward_f32_layers")
+        else:
+            _lib.check(self._lib.cbas_enc_forward_u8_layers(self._h, frames.data_ptr() + base_off, n, H, W, *strides, C.byref(a), stream),
+                       "cbas_enc_forward_u8_layers")
+        return out
+
+    def hidden_states(self, frames: torch.Tensor, layers=None, norm: bool = False, channel: int = 1,
+                      dtype: torch.dtype = torch.float32) -> torch.Tensor:
+        """What ``output_hidden_states=True`` returns, as one (len(layers), n, T, D) device tensor in ``dtype`` (float32 or float16):
+        index 0 is the embeddings output (prefix rows and patch embeddings, the residual stream before block 0), index l the
+        stream after block l - transformers' numbering, 0 .. L.  ``layers=None``: all L + 1; negative indices count from the end.
+        ``norm=False``: the raw rows, as transformers returns them; ``norm=True``: each layer's rows through the encoder's final
+        LayerNorm (DINO's ``get_intermediate_layers(norm=True)``) - ``hidden_states(frames, layers=[L], norm=True)[0]`` is
+        ``hidden_state(frames)`` bit for bit.  Frames and refusals as ``hidden_state``; ConvNeXt encoders are refused (their stage
+        outputs are a different object).  One library call: n may not exceed ``max_batch``."""
+        self._layers_refusals("hidden_states")
+        lay = normalize_layers(layers, self.config.num_hidden_layers)
+        return self._layers_call(frames, channel, "hidden_states", hidden=(lay, norm, dtype))["hidden"]
+
+    def _cls_attention_layers(self, frames, channel, per_head, layer):
+        self._layers_refusals("per-layer CLS attention")
+        L = self.config.num_hidden_layers
+        every = isinstance(layer, str) and layer == "all"
+        lay = normalize_layers(layer, L, 1, "attention")
+        if not every and len(lay) != 1:
+            raise ValueError("cls_attention takes one layer, or layer='all'")
+        r = self._layers_call(frames, channel, "cls_attention", attn=(lay, per_head))
+        nh, nw, _ = r["grid"]
+        maps = r["maps"].permute(1, 0, 2).reshape(r["maps"].shape[1], len(lay), nh, nw).contiguous()
+        heads = r["heads"].permute(1, 0, 2, 3).contiguous() if per_head else None
+        if not every:
+            maps, heads = maps[:, 0], heads[:, 0] if per_head else None
+        if frames.dtype == torch.uint8:
+            out16, out32 = self.encode_u8(frames, channel)
+        else:
+            out32 = self.forward(frames.reshape(frames.shape[0], 1, *frames.shape[-2:]))[:, 0]
+            out16 = out32.to(torch.float16)
+        return (out16, out32, maps, heads) if per_head else (out16, out32, maps)
+
+    def attention_rollout(self, frames: torch.Tensor, query=None, start_layer: int = 1, channel: int = 1) -> torch.Tensor:
+        """Attention rollout (Abnar and Zuidema) as a float32 (n, nh, nw) device tensor: with A_l the head mean of layer l's softmax
+        rows (T x T) and A^_l = 0.5 A_l + 0.5 I, the query's row of A^_L A^_(L-1) ... A^_(start_layer) on the patch columns, no
+        renormalisation (every A^_l is row-stochastic).  ``query=None``: the CLS row; ``query=(y, x)`` in pixels: the patch under
+        that pixel, as ``similarity_map`` resolves it.  ``start_layer`` 1 .. L (negative from the end).  Computed on the device
+        from the queries and keys of the forward itself; served and refused as ``hidden_states``."""
+        self._layers_refusals("attention rollout")
+        start = normalize_layers(start_layer, self.config.num_hidden_layers, 1, "rollout start")[0]
+        return self._layers_call(frames, channel, "attention_rollout", rollout=(start, query))["rollout"]
 
     def _tokens(self, frames, channel, dtype, query=None, want_map=False):
         """One cbas_enc_forward_*_tokens call: the (n, T, D) image in ``dtype`` and, with ``want_map``, the (n, nh, nw) cosine map."""
@@ -461,10 +596,24 @@ class DinoEncoder:
         is refused (its MX-fp8 layers serve the CLS row; their token rows are a different encoder's)."""
         return self._tokens(frames, channel, dtype)[0]
 
-    def patch_tokens(self, frames: torch.Tensor, channel: int = 1, dtype: torch.dtype = torch.float32):
+    def patch_tokens(self, frames: torch.Tensor, channel: int = 1, dtype: torch.dtype = torch.float32, layer=None,
+                     norm: Optional[bool] = None):
         """``hidden_state`` split the way dense-feature users want it: ``(patches, prefix)`` with ``patches`` (n, nh, nw, D) over the
         patch grid and ``prefix`` (n, P0, D) the rows in front of them (CLS and registers; ConvNeXt: the pooled row).  Both are views
-        of one tensor."""
+        of one tensor.  ``layer=l`` (0 .. L, negative from the end; ViT only): the same split of ``hidden_states(layers=[l], norm=norm)``,
+        ``norm`` defaulting to False as there.  Without ``layer`` the rows are ``hidden_state``'s, which are normalised: ``norm=False``
+        is refused there rather than ignored (``layer=-1, norm=False`` gives the last layer's raw rows)."""
+        if layer is None and norm is not None and not norm:
+            raise ValueError("patch_tokens without layer= returns hidden_state's rows, which are normalised; "
+                             "pass layer=-1, norm=False for the last layer's raw rows")
+        if layer is not None:
+            self._layers_refusals("patch_tokens(layer=)")
+            lay = normalize_layers(layer, self.config.num_hidden_layers)
+            if len(lay) != 1:
+                raise ValueError("patch_tokens takes one layer")
+            r = self._layers_call(frames, channel, "patch_tokens", hidden=(lay, bool(norm), dtype))
+            out, (nh, nw, P0) = r["hidden"][0], r["grid"]
+            return out[:, P0:].reshape(out.shape[0], nh, nw, out.shape[2]), out[:, :P0]
         out, _, (nh, nw, P0) = self._tokens(frames, channel, dtype)
         return out[:, P0:].reshape(out.shape[0], nh, nw, out.shape[2]), out[:, :P0]
 

@@ -16,6 +16,8 @@
  *                                          the patch tokens, averaged over heads (output_attentions=True), beside the CLS rows
  *   cbas_enc_forward_u8_tokens / _f32_tokens   compare_encoders.py:36 / the golden scripts' model(pixel_values=x): the whole
  *                                          last_hidden_state (n, T, D) instead of row 0, and cosine maps over the patch rows
+ *   cbas_enc_forward_u8_layers / _f32_layers   output_hidden_states=True / output_attentions=True of the same call: any layer's
+ *                                          hidden state and CLS attention, and the attention rollout over the layers
  *   cbas_patch_pca_*                       (no counterpart: the reference draws attention only) PCA of the patch rows of that
  *                                          last_hidden_state, fitted and projected on the device
  *   cbas_enc_submit_u8_host / cbas_enc_wait  backend/cbas.py:423-440 one iteration of the chunk loop
@@ -61,7 +63,8 @@ extern "C" {
 /* Still 11 with cbas_rows_gather_windows / cbas_head_train_step_rows, with cbas_head_score_rows / cbas_logits_nll, with
  * cbas_enc_set_pos_interp, with cbas_enc_set_fp8_plan, with cbas_probs_top1 / cbas_disagreement_runs, with
  * cbas_labels_median / cbas_label_runs / cbas_activity_bins, with cbas_enc_forward_u8_attn / cbas_enc_forward_f32_attn, with
- * cbas_enc_forward_u8_tokens / cbas_enc_forward_f32_tokens and with cbas_patch_pca_*: they are additions.  No structure and no existing signature
+ * cbas_enc_forward_u8_tokens / cbas_enc_forward_f32_tokens, with cbas_patch_pca_* and with cbas_enc_forward_u8_layers /
+ * cbas_enc_forward_f32_layers / cbas_enc_layers_scratch_bytes: they are additions.  No structure and no existing signature
  * changed, so a caller built against the earlier version 11 header runs unchanged. */
 #define CBAS_ABI_VERSION   11
 
@@ -231,6 +234,57 @@ int cbas_enc_forward_u8_tokens(cbas_enc* h, const uint8_t* frames_dev, int n, in
                                int64_t frame_stride, int64_t row_stride, int64_t pixel_stride,
                                float* tokens_f32_dev, uint16_t* tokens_f16_dev, int64_t ld_tokens,
                                const int32_t* query_idx_dev, float* sim_map_dev, void* stream);
+
+/* One unpruned forward on lane 0 that fills per-layer outputs - what transformers returns under output_hidden_states=True and
+ * output_attentions=True ([tf] DINOv3ViTModel.forward / DINOv3ViTEncoder: all_hidden_states, all_self_attentions; DINOv2:
+ * modeling_dinov2.py Dinov2Encoder.forward), DINO's get_intermediate_layers(n, norm=...), and the attention rollout of Abnar and
+ * Zuidema built from the head-averaged attentions (compare_encoders.py:36-49 draws the last layer's CLS row only).  No CLS rows
+ * are written: as in the ..._tokens forms the last layer runs on every row FOR THIS CALL ONLY, and no other call's results move.
+ * Whatever group of destinations is non-NULL is filled; all NULL is CBAS_EINVAL.  T = NP + P tokens per frame.
+ *   hidden states   hidden_layers (HOST array of n_hidden_layers indices): 0 = the embeddings output (prefix rows + patch
+ *                   embeddings, the residual stream before block 0), l = the stream after block l, up to L - transformers'
+ *                   hidden_states numbering.  Listed layer j goes to hidden_f32_dev / hidden_f16_dev + j * hidden_layer_stride
+ *                   (elements) as rows b T + t of ld_hidden elements (>= D, a multiple of 4; the stride a multiple of 4).
+ *                   hidden_norm = 0: the raw rows (fp16: rounded to nearest even); != 0: each through the encoder's final
+ *                   LayerNorm - index L then is bit for bit cbas_enc_forward_*_tokens' image.  fp32 16-byte, fp16 8-byte aligned.
+ *   CLS attention   attn_layers (HOST array of n_attn_layers layer numbers 1 .. L): listed layer j's attn_heads_dev
+ *                   + j n NH T as (n, NH, T) and attn_map_dev + j n P as (n, P), as cbas_enc_forward_*_attn defines them.
+ *   rollout         rollout_dev (n, P): with A_l the head mean (heads ascending) of layer l's softmax rows (T x T) and
+ *                   A^_l = 0.5 A_l + 0.5 I, columns NP .. T - 1 of row rollout_query_dev[b] (device; a token index in [0, T),
+ *                   clamped; NULL: row 0, the CLS token) of A^_L A^_(L-1) ... A^_(rollout_start_layer); no renormalisation.
+ *                   scratch_dev: cbas_enc_layers_scratch_bytes(h, n, height, width) = 3 n T T 4 bytes, 16-byte aligned - A^ of
+ *                   the current layer and the two products that alternate.  On return the query rows' product is in the second
+ *                   (L - start even) or third (odd) n T T block.
+ * All fp32 arithmetic in a fixed order, no atomics: a frame's outputs depend on neither n nor its place in the batch.
+ * CBAS_EINVAL with a message, nothing queued: a ConvNeXt or precision-2 handle, a layer outside its range, a scratch too small,
+ * a misaligned pointer, all destinations NULL, a frame whose token row does not fit the attention kernels' 64 KiB of LDS
+ * (about 8 000 tokens), struct_bytes != sizeof(cbas_enc_layers_args).  A handle that never makes these calls allocates nothing
+ * for them: every buffer is the caller's. */
+typedef struct cbas_enc_layers_args {
+    int64_t struct_bytes;              /* sizeof(cbas_enc_layers_args) */
+    const int32_t* hidden_layers;      /* host */
+    int32_t n_hidden_layers;
+    int32_t hidden_norm;
+    float* hidden_f32_dev;
+    uint16_t* hidden_f16_dev;
+    int64_t ld_hidden;
+    int64_t hidden_layer_stride;
+    const int32_t* attn_layers;        /* host */
+    int32_t n_attn_layers;
+    int32_t rollout_start_layer;
+    float* attn_heads_dev;
+    float* attn_map_dev;
+    float* rollout_dev;
+    const int32_t* rollout_query_dev;
+    void* scratch_dev;
+    int64_t scratch_bytes;
+} cbas_enc_layers_args;
+int64_t cbas_enc_layers_scratch_bytes(const cbas_enc* h, int n, int height, int width);      /* -1: refused (cbas_last_error) */
+int cbas_enc_forward_f32_layers(cbas_enc* h, const float* x_dev, int n, int height, int width,
+                                const cbas_enc_layers_args* args, void* stream);
+int cbas_enc_forward_u8_layers(cbas_enc* h, const uint8_t* frames_dev, int n, int height, int width,
+                               int64_t frame_stride, int64_t row_stride, int64_t pixel_stride,
+                               const cbas_enc_layers_args* args, void* stream);
 
 /* PCA of patch features: the picture that shows what an encoder separates (the top components of a frame's, or a batch's, patch
  * rows as colours), fitted and projected on the device.  The reference has no such tool; the arithmetic is the textbook one.

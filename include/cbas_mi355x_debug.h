@@ -157,6 +157,15 @@ int cbas_debug_attention_run(const cbas_debug_attention_args* a);
 int cbas_debug_cls_attention(int arith, const float* q_host, const float* K_host, int n, int T, int NH, int n_prefix,
                              int64_t ldq, int64_t ldk, float* heads_host, float* map_host);
 
+/* Tests: ONE launch of the head-mean attention kernel (attention_rollout.hip) on host arrays, operands as
+ * cbas_debug_cls_attention takes them except that q_host holds EVERY token's query: n T rows of stride ldq.  out_host (n, T, T)
+ * fp32: out[b][i][t] = the mean over the heads of softmax_t(q[b T + i] . K[b T + t]); blend != 0: 0.5 out + 0.5 I.  A T whose row
+ * does not fit the kernel's LDS is CBAS_EINVAL and nothing is launched. */
+int cbas_debug_attention_mean(int arith, const float* q_host, const float* K_host, int n, int T, int NH, int64_t ldq, int64_t ldk,
+                              int blend, float* out_host);
+/* ... and of the rollout chain step: out = A R per frame, (n, T, T) fp32 each. */
+int cbas_debug_rollout_step(const float* A_host, const float* R_host, int n, int T, float* out_host);
+
 /* Tests: ONE launch of a row-wise encoder kernel on host operands (tests/test_gpu_rows_reference.py compares it with the float64
  * references of oracle/kernel_ref.py).  The harness uploads x (x_bytes) and the caller's pre-filled output images (out_bytes /
  * out2_bytes / *counter), runs exactly one launcher on the default stream and copies the whole output images back: whatever
