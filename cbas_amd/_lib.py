@@ -73,6 +73,11 @@ SIGNATURES = {
     "cbas_patch_pca_fit": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_int64, c_void_p]),
     "cbas_patch_pca_project": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cbas_patch_kmeans_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "cbas_patch_kmeans_fit": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_int64, c_void_p]),
+    "cbas_patch_kmeans_assign": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                         c_void_p]),
     "cbas_enc_submit_u8_host": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int64, c_int64, c_int64]),
     "cbas_enc_wait": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "cbas_enc_submit_u8": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_void_p,
@@ -183,7 +188,8 @@ POS_INTERP_BICUBIC_AA, POS_INTERP_BICUBIC = 0, 1      # CBAS_POS_INTERP_* of inc
 MLP_GELU, MLP_SWIGLU = 0, 1                           # CBAS_MLP_* of include/cbas_mi355x.h
 PCA_FRAME, PCA_BATCH = 0, 1                           # CBAS_PCA_* of include/cbas_mi355x.h
 PCA_CHUNK, PCA_MEAN_CHUNK, PCA_MAX_K, PCA_MAX_D = 1024, 64, 8, 1536      # csrc/kernels.h: the fixed row chunks and limits of cbas_patch_pca_*
-EXPECTED_ABI = 11         # CBAS_ABI_VERSION of include/cbas_mi355x.h these ctypes structures mirror
+KMEANS_CHUNK, KMEANS_MAX_K = 64, 16                   # CBAS_KMEANS_* of include/cbas_mi355x.h: the fixed row chunk and the limit of cbas_patch_kmeans_*
+EXPECTED_ABI = 11        # CBAS_ABI_VERSION of include/cbas_mi355x.h these ctypes structures mirror
 PROF_CATS = ["patch_gemm", "layernorm", "qkv_gemm", "attention", "oproj_gemm", "up_gemm", "down_gemm", "other"]      # other: the CLS attention map and token similarity kernels
 
 

@@ -3,8 +3,8 @@ frames of a video - the picture the reference's encoder comparison tool draws (c
 the device by ``DinoEncoder.cls_attention`` beside the CLS rows.
 
     python -m cbas_amd.attention_maps --video V --frame N --encoder ID [--encoder ID ...] --out PNG [--precision P]
-                                      [--kind attention|similarity|pca|rollout] [--query Y,X] [--pca-scope frame|batch]
-                                      [--layer N|all]
+                                      [--kind attention|similarity|pca|rollout|clusters] [--query Y,X] [--pca-scope frame|batch]
+                                      [--layer N|all] [--clusters K] [--cluster-scope frame|batch]
 
 ``--kind similarity`` draws the other picture of the same question, from ``DinoEncoder.similarity_map``: the cosine of the CLS
 token's final hidden state (``--query Y,X``: of the patch under that pixel) to every patch token's.  It needs no attention, so it
@@ -14,6 +14,10 @@ is the kind DINOv3 ConvNeXt encoders have (their query row is the pooled one, th
 principal components, each stretched to [0, 1] over the picture, as red, green and blue - what the encoder separates, with no
 query and no attention, so every family has it and the pictures of two families can be compared.  ``--pca-scope batch`` fits one
 basis for all frames asked for (the same colours mean the same directions in each), ``frame`` (the default) one per frame.
+
+``--kind clusters`` draws the discrete picture, from ``DinoEncoder.patch_clusters``: k-means labels of the patch rows (``--clusters
+K``, default 4), one fixed colour per cluster with cluster 0 the largest, enlarged without blending.  ``--cluster-scope batch`` fits
+one set of centroids for all frames asked for, ``frame`` (the default) one per frame.  Every family has it.
 
 ``--kind attention --layer N`` draws layer N's CLS attention instead of the last one's (1 .. L, negative from the end), ``--layer
 all`` one map per layer side by side.  ``--kind rollout`` draws attention rollout (Abnar and Zuidema) from
@@ -35,8 +39,14 @@ from typing import Mapping, Sequence, Tuple, Union
 import numpy as np
 
 
-KINDS = ("attention", "similarity", "pca", "rollout")
+KINDS = ("attention", "similarity", "pca", "rollout", "clusters")
 PCA_SCOPES = ("frame", "batch")
+CLUSTER_SCOPES = ("frame", "batch")
+DEFAULT_CLUSTERS = 4
+# render_labels: one colour per cluster, 0 (the largest cluster) to 15 - fixed, so cluster j has one colour in every picture
+LABEL_PALETTE = np.array([(31, 119, 180), (255, 127, 14), (44, 160, 44), (214, 39, 40), (148, 103, 189), (140, 86, 75), (227, 119, 194),
+                          (127, 127, 127), (188, 189, 34), (23, 190, 207), (174, 199, 232), (255, 187, 120), (152, 223, 138), (255, 152, 150),
+                          (197, 176, 213), (196, 156, 148)], dtype=np.uint8)
 
 
 def refuse_kind(cfg, kind: str):
@@ -61,14 +71,16 @@ def parse_layer(text):
         raise ValueError(f"--layer {text!r}: an integer or 'all'") from None
 
 
-def frame_maps(encoder, path: str, frame_indices: Sequence[int], kind: str = "attention", query=None, pca_scope: str = "frame", layer=None):
+def frame_maps(encoder, path: str, frame_indices: Sequence[int], kind: str = "attention", query=None, pca_scope: str = "frame", layer=None,
+               n_clusters: int = DEFAULT_CLUSTERS, cluster_scope: str = "frame"):
     """Maps of the given frames of a video: ``kind`` "attention" (``cls_attention``), "similarity" (``similarity_map`` of
     ``query``: None, or a pixel (y, x)) or "pca" (``patch_pca``, three components).  Frames are read through
     ``pipeline.open_video`` (any source it knows) and encoded in batches of ``encoder.max_batch``.  Returns ``(maps, frames_green)``:
     float32 (n, nh, nw) and uint8 (n, H, W) numpy arrays, in the order of ``frame_indices``.  For "pca" ``maps`` is the finished
     picture instead, float32 (n, H, W, 3) in [0, 1] (``render_pca`` of each frame's scores); with ``pca_scope="batch"`` the basis
     fitted on the first batch of frames colours all of them.  "rollout": ``attention_rollout`` of ``query``.  ``layer`` ("attention"
-    only): a layer number, or "all" - ``maps`` then is (n, L, nh, nw)."""
+    only): a layer number, or "all" - ``maps`` then is (n, L, nh, nw).  "clusters": ``patch_clusters`` with ``n_clusters`` - ``maps``
+    is the int32 (n, nh, nw) label grid; with ``cluster_scope="batch"`` the set fitted on the first batch of frames labels all of them."""
     import torch
     from . import pipeline
     idx = [int(i) for i in frame_indices]
@@ -79,7 +91,9 @@ def frame_maps(encoder, path: str, frame_indices: Sequence[int], kind: str = "at
         raise ValueError("no frame index given")
     if kind == "pca" and pca_scope not in PCA_SCOPES:
         raise ValueError(f"unknown PCA scope {pca_scope!r}: one of {', '.join(PCA_SCOPES)}")
-    basis = None
+    if kind == "clusters" and cluster_scope not in CLUSTER_SCOPES:
+        raise ValueError(f"unknown cluster scope {cluster_scope!r}: one of {', '.join(CLUSTER_SCOPES)}")
+    basis = clusters = None
     src = pipeline.open_video(path)
     try:
         n_total = len(src)
@@ -98,6 +112,10 @@ def frame_maps(encoder, path: str, frame_indices: Sequence[int], kind: str = "at
                 basis = fitted if pca_scope == "batch" else None
                 size = (green.shape[2], green.shape[1])
                 maps.append(np.stack([render_pca(sc, size) for sc in scores.cpu().numpy()]))
+            elif kind == "clusters":
+                labels, fitted = encoder.patch_clusters(dev, n_clusters, cluster_scope, clusters)
+                clusters = fitted if cluster_scope == "batch" else None
+                maps.append(labels.cpu().numpy())
             elif kind == "rollout":
                 maps.append(encoder.attention_rollout(dev, query).cpu().numpy())
             else:
@@ -137,6 +155,18 @@ def render_pca(scores, size: Tuple[int, int]) -> np.ndarray:
     return out
 
 
+def render_labels(labels, size: Tuple[int, int]) -> np.ndarray:
+    """One frame's (nh, nw) cluster labels as a picture: label j painted ``LABEL_PALETTE[j]``, resized to ``size`` = (width, height)
+    with nearest-neighbour sampling (a label is a name, not a quantity: nothing is blended).  Returns uint8 (height, width, 3)."""
+    from PIL import Image
+    a = np.asarray(labels)
+    if a.ndim != 2 or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"render_labels takes one frame's (nh, nw) integer labels, got shape {a.shape} of {a.dtype}")
+    if a.size and (a.min() < 0 or a.max() >= len(LABEL_PALETTE)):
+        raise ValueError(f"labels outside 0 .. {len(LABEL_PALETTE) - 1}")
+    return np.asarray(Image.fromarray(LABEL_PALETTE[a]).resize((int(size[0]), int(size[1])), Image.NEAREST))
+
+
 def _to_u8(a: np.ndarray) -> np.ndarray:
     lo, hi = float(a.min()), float(a.max())
     if hi > lo:
@@ -145,7 +175,8 @@ def _to_u8(a: np.ndarray) -> np.ndarray:
 
 
 def compare_encoders(video: str, frame_idx: int, encoders: Mapping[str, Union[str, object]], out_png: str, precision=None,
-                     kind: str = "attention", query=None, pca_scope: str = "frame", layer=None) -> str:
+                     kind: str = "attention", query=None, pca_scope: str = "frame", layer=None, n_clusters: int = DEFAULT_CLUSTERS,
+                     cluster_scope: str = "frame") -> str:
     """One figure row per encoder: the frame as the encoder receives it (green plane) beside its rendered map (``kind``, ``query``:
     see ``frame_maps``).
     ``encoders`` maps a display name to a checkpoint directory, an HF-cache id or a ready ``DinoEncoder``; encoders built here
@@ -161,13 +192,13 @@ def compare_encoders(video: str, frame_idx: int, encoders: Mapping[str, Union[st
         if own:
             enc = DinoEncoder(enc, **({} if precision is None else {"precision": int(precision)}))
         try:
-            maps, green = frame_maps(enc, video, [frame_idx], kind, query, pca_scope, layer)
+            maps, green = frame_maps(enc, video, [frame_idx], kind, query, pca_scope, layer, n_clusters, cluster_scope)
             grid = token_grid(enc.config, green.shape[1], green.shape[2])[:2]
         finally:
             if own:
                 enc.close()
         size = (green.shape[2], green.shape[1])
-        pic = ((maps[0] * 255).astype(np.uint8) if kind == "pca" else
+        pic = ((maps[0] * 255).astype(np.uint8) if kind == "pca" else render_labels(maps[0], size) if kind == "clusters" else
                np.concatenate([render_map(m, size) for m in maps[0]], axis=1) if maps[0].ndim == 3 else render_map(maps[0], size))
         panels.append((name, green[0], grid, pic))
     who = "CLS token" if query is None else f"patch at pixel {tuple(query)}"
@@ -175,6 +206,7 @@ def compare_encoders(video: str, frame_idx: int, encoders: Mapping[str, Union[st
             ", mean of heads)" if kind == "attention" else
             f"attention rollout of the {who} over every layer" if kind == "rollout" else
             "patch features along their first three principal components (R, G, B)" if kind == "pca" else
+            f"k-means clusters of the patch features (k = {n_clusters}, one colour each, largest first)" if kind == "clusters" else
             "cosine of the final hidden states: " + ("CLS / pooled row" if query is None else f"patch at pixel {tuple(query)}") + " to each patch")
     _draw(Figure, FigureCanvasAgg, panels, f"{os.path.basename(video)}, frame {frame_idx}", out_png, what)
     return out_png
@@ -198,7 +230,7 @@ def _draw(Figure, Canvas, panels, caption: str, out_png: str, what: str) -> None
         rgb = pic.ndim == 3
         right.imshow(pic, interpolation="nearest", **({} if rgb else {"cmap": "inferno", "vmin": 0, "vmax": 255}))
         left.set_ylabel(name, fontsize=10)
-        right.set_xlabel(f"{nh} x {nw} patches, " + ("each component stretched to its own range over the frame" if rgb else
+        right.set_xlabel(f"{nh} x {nw} patches, " + (("one colour per cluster" if pic.dtype == np.uint8 and what.startswith("k-means") else "each component stretched to its own range over the frame") if rgb else
                                                     "stretched to the map's own range"), fontsize=8)
         for a in (left, right):
             a.set_xticks([])
@@ -219,8 +251,10 @@ def parse_cli(argv=None):
     ap.add_argument("--encoder", action="append", default=[], metavar="ID", help="checkpoint directory or HF-cache id; repeatable")
     ap.add_argument("--out", required=True, metavar="PNG")
     ap.add_argument("--precision", type=int, default=None)
-    ap.add_argument("--kind", choices=KINDS, default="attention", help="similarity and pca: the kinds a ConvNeXt encoder has")
+    ap.add_argument("--kind", choices=KINDS, default="attention", help="similarity, pca and clusters: the kinds a ConvNeXt encoder has")
     ap.add_argument("--pca-scope", choices=PCA_SCOPES, default=None, help="pca: one basis per frame (default) or one for all frames")
+    ap.add_argument("--clusters", type=int, default=None, metavar="K", help=f"clusters: how many (2 .. {len(LABEL_PALETTE)}, default {DEFAULT_CLUSTERS})")
+    ap.add_argument("--cluster-scope", choices=CLUSTER_SCOPES, default=None, help="clusters: one set per frame (default) or one for all frames")
     ap.add_argument("--query", default=None, metavar="Y,X", help="similarity, rollout: the pixel whose patch is the query (default: the CLS / pooled row)")
     ap.add_argument("--layer", default=None, metavar="N|all", help="attention: the layer whose CLS attention is drawn (default: the last), or every layer in a row")
     a = ap.parse_args(argv)
@@ -243,6 +277,12 @@ def parse_cli(argv=None):
     a.query = query
     if a.pca_scope is not None and a.kind != "pca":
         ap.error("--pca-scope goes with --kind pca")
+    if a.cluster_scope is not None and a.kind != "clusters":
+        ap.error("--cluster-scope goes with --kind clusters")
+    if a.clusters is not None and a.kind != "clusters":
+        ap.error("--clusters goes with --kind clusters")
+    if a.clusters is not None and not 2 <= a.clusters <= len(LABEL_PALETTE):
+        ap.error(f"--clusters {a.clusters}: 2 .. {len(LABEL_PALETTE)}")
     if not a.encoder:
         ap.error("at least one --encoder is needed")
     return ap, a
@@ -271,7 +311,8 @@ def main(argv=None) -> int:
             ap.error(f"--encoder {e}: {why}")
         names[e if e not in names else f"{e} ({len(names)})"] = e
     print(compare_encoders(a.video, a.frame, names, a.out, precision=a.precision, kind=a.kind, query=query,
-                           pca_scope=a.pca_scope or "frame", layer=a.layer))
+                           pca_scope=a.pca_scope or "frame", layer=a.layer, n_clusters=a.clusters or DEFAULT_CLUSTERS,
+                           cluster_scope=a.cluster_scope or "frame"))
     return 0
 
 

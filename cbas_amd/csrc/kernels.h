@@ -527,3 +527,25 @@ int launch_pca_eig(const float* C, int64_t c_stride, int nprob, int D, int k, in
 // scores [n][P][k] = (x - mean_b) . comp_b[j]; basis b of frame f is f * basis_step (0: one basis for every frame, 1: one per frame)
 int launch_pca_project(const float* x, int64_t ld, int n, int T, int n_prefix, int D, int k, int basis_step, const float* mean,
                        const float* comp, float* scores, hipStream_t st);
+
+// patch_kmeans.hip: k-means of patch features.  Rows and problems as above (PcaRows); every per-cluster sum
+// and the inertia are formed per chunk of KMEANS_CHUNK rows in ascending row order, the chunks then added in ascending order.
+constexpr int KMEANS_CHUNK = 64;         // rows per partial sum: fixed, whatever n and the device
+constexpr int KMEANS_MAX_K = 16;
+inline int64_t kmeans_chunks(int64_t M) { return (M + KMEANS_CHUNK - 1) / KMEANS_CHUNK; }
+// the seeds of every problem: cur [nprob][k][D] (seeding order), init_index [nprob][k]; scratch: rn, mind [nprob][M], tmp [nprob]
+// [chunks][D], mean [nprob][D], bestv / besti [nprob][chunks]
+int launch_kmeans_seed(const PcaRows& r, int nprob, int D, int k, int normalize, float* cur, int32_t* init_index, float* rn, float* mind,
+                       float* tmp, float* mean, float* bestv, int32_t* besti, hipStream_t st);
+// one pass over the rows: problem b's rows against the k centroids at cent + b * cent_stride (0: one set for every problem).
+// psum [nprob][chunks][k][D], pcount [nprob][chunks][16], pinertia [nprob][chunks]: all three, or all NULL (assignment only);
+// labels / dist2 [nprob][M]: each may be NULL
+int launch_kmeans_pass(const PcaRows& r, int nprob, int D, int k, int normalize, const float* cent, int64_t cent_stride, float* psum,
+                       int32_t* pcount, float* pinertia, int32_t* labels, float* dist2, hipStream_t st);
+// cur[j] = (sum of the chunks' psum[j]) / count_j where count_j > 0; inertia_out[b * inertia_ld] = the chunks' inertia
+int launch_kmeans_update(const float* psum, const int32_t* pcount, const float* pinertia, int64_t nch, int nprob, int D, int k, float* cur,
+                         float* inertia_out, int inertia_ld, hipStream_t st);
+// the final counts and inertia from a pass, the clusters ordered by descending count (ties: seeding order): centroids [nprob][k][D],
+// counts [nprob][k], order [nprob][16] (output position -> seeding position)
+int launch_kmeans_finish(const int32_t* pcount, const float* pinertia, int64_t nch, int nprob, int D, int k, const float* cur,
+                         float* inertia_out, int inertia_ld, float* centroids, int32_t* counts, int32_t* order, hipStream_t st);

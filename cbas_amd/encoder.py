@@ -170,6 +170,46 @@ class PatchPCABasis:
             raise ValueError(f"this basis was fitted on encoder {self.stamp!r}, not on {str(stamp)!r}: its directions mean nothing here")
 
 
+KMEANS_DEFAULT_ITERS = 16   # Lloyd rounds in ``patch_clusters``: chosen on the host by tests/test_patch_kmeans_host.py
+
+
+class PatchClusters:
+    """What ``DinoEncoder.patch_clusters`` fitted: ``centroids`` (b, k, D) float32 ordered by ``counts`` (b, k) int32 descending,
+    ``inertia`` (b, iters + 1) float32 - the sum of squared distances after 0 .. iters updates - and ``init_index`` (b, k) int32, the
+    seed rows in seeding order; b = 1 for scope "batch" and one per frame for scope "frame".  ``normalize``: whether rows are scaled
+    to unit length before they are compared; ``stamp``: the fitting encoder's (``DinoEncoder.stamp``).  A set labels only rows of
+    the encoder it was fitted on: ``check`` refuses another width or stamp, as ``PatchPCABasis.check`` does."""
+
+    def __init__(self, centroids, counts, inertia, init_index, scope: str, normalize: bool, stamp: str):
+        if scope not in ("frame", "batch"):
+            raise ValueError(f"scope {scope!r}: 'frame' or 'batch'")
+        if centroids.dim() != 3 or tuple(counts.shape) != tuple(centroids.shape[:2]) or tuple(init_index.shape) != tuple(centroids.shape[:2]) \
+                or inertia.dim() != 2 or inertia.shape[0] != centroids.shape[0]:
+            raise ValueError("a cluster set is centroids (b, k, D), counts (b, k), inertia (b, iters + 1), init_index (b, k)")
+        if scope == "batch" and centroids.shape[0] != 1:
+            raise ValueError("a batch-scope cluster set is one set")
+        self.centroids, self.counts, self.inertia, self.init_index = centroids, counts, inertia, init_index
+        self.scope, self.normalize, self.stamp = scope, bool(normalize), str(stamp)
+
+    @property
+    def n_sets(self) -> int:
+        return int(self.centroids.shape[0])
+
+    @property
+    def n_clusters(self) -> int:
+        return int(self.centroids.shape[1])
+
+    @property
+    def dim(self) -> int:
+        return int(self.centroids.shape[2])
+
+    def check(self, dim: int, stamp: str) -> None:
+        if self.dim != int(dim):
+            raise ValueError(f"these clusters were fitted on rows of width {self.dim}; the encoder's rows are {int(dim)} wide")
+        if self.stamp != str(stamp):
+            raise ValueError(f"these clusters were fitted on encoder {self.stamp!r}, not on {str(stamp)!r}: their centroids mean nothing here")
+
+
 # What an encoder built the reference's way - DinoEncoder(model_identifier, device), integration.install(),
 # `python -m cbas_amd.encode_files` - computes in: 4 = fp32 storage / attention / LayerNorm with the GEMM products as three-term
 # fp16 splits: the mode that meets BOTH halves of the path's contract (CLS within 1e-3 - by three orders of magnitude - and
@@ -679,6 +719,53 @@ class DinoEncoder:
         _lib.check(self._lib.cbas_patch_pca_project(tokens.data_ptr(), n, T, P0, D, D, k, basis.n_bases, mean.data_ptr(), comp.data_ptr(),
                                                     scores.data_ptr(), stream), "cbas_patch_pca_project")
         return scores, basis
+
+    def patch_clusters(self, frames: torch.Tensor, n_clusters: int = 4, scope: str = "frame", clusters: Optional[PatchClusters] = None,
+                       iters: Optional[int] = None, normalize: bool = True, channel: int = 1):
+        """k-means of the patch rows of ``hidden_state(frames)``, fitted and assigned on the device (cbas_patch_kmeans_fit /
+        cbas_patch_kmeans_assign): a cluster label per patch - which patches belong together.
+
+        Returns ``(labels, clusters)``: ``labels`` int32 (n, nh, nw) on the device, cluster 0 the largest; ``clusters`` a
+        ``PatchClusters``.  ``scope="frame"`` fits one set per frame (a frame's result does not depend on its batch),
+        ``scope="batch"`` one for all frames.  With ``clusters=`` given nothing is fitted and the rows are only assigned (one set for
+        every frame, or one per frame): a set fitted on one batch labels a whole clip consistently; its ``n_clusters``, ``scope`` and
+        ``normalize`` are the ones used.  A set of another width or encoder is refused.  ``iters``: Lloyd rounds, exactly that many
+        (default ``KMEANS_DEFAULT_ITERS``); ``normalize``: compare rows scaled to unit length (cosine geometry, the usual choice
+        for DINO features).  The start is deterministic farthest-point seeding, so two calls give the same bits.  Frames,
+        families and precisions: as ``hidden_state``; ``encode_u8`` before and after gives the same bits."""
+        if clusters is None and scope not in ("frame", "batch"):
+            raise ValueError(f"scope {scope!r}: 'frame' or 'batch'")
+        D = self.config.hidden_size
+        if clusters is not None:
+            clusters.check(D, self.stamp)
+        tokens, _, (nh, nw, P0) = self._tokens(frames, channel, torch.float32)
+        n, T, _ = tokens.shape
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if clusters is None:
+            k, rounds = int(n_clusters), int(KMEANS_DEFAULT_ITERS if iters is None else iters)
+            sc = _lib.PCA_BATCH if scope == "batch" else _lib.PCA_FRAME
+            nb = 1 if scope == "batch" else n
+            need = int(self._lib.cbas_patch_kmeans_workspace_bytes(n, T, P0, D, k, sc))
+            if need < 0:
+                _lib.check(int(need), "cbas_patch_kmeans_workspace_bytes")
+            if rounds < 0:
+                raise ValueError(f"iters = {rounds}: at least 0")
+            ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
+            i32 = dict(dtype=torch.int32, device=self.device)
+            clusters = PatchClusters(torch.empty((nb, k, D), dtype=torch.float32, device=self.device), torch.empty((nb, k), **i32),
+                                     torch.empty((nb, rounds + 1), dtype=torch.float32, device=self.device), torch.empty((nb, k), **i32),
+                                     scope, normalize, self.stamp)
+            _lib.check(self._lib.cbas_patch_kmeans_fit(tokens.data_ptr(), n, T, P0, D, D, k, sc, rounds, int(bool(normalize)),
+                                                       clusters.centroids.data_ptr(), clusters.counts.data_ptr(), clusters.inertia.data_ptr(),
+                                                       clusters.init_index.data_ptr(), ws.data_ptr(), need, stream), "cbas_patch_kmeans_fit")
+        elif clusters.n_sets not in (1, n):
+            raise ValueError(f"a cluster set of {clusters.n_sets} frames cannot label {n} frames (one set, or one per frame)")
+        cent = clusters.centroids.to(self.device, torch.float32).contiguous()
+        labels = torch.empty((n, nh, nw), dtype=torch.int32, device=self.device)
+        _lib.check(self._lib.cbas_patch_kmeans_assign(tokens.data_ptr(), n, T, P0, D, D, clusters.n_clusters, clusters.n_sets,
+                                                      int(clusters.normalize), cent.data_ptr(), labels.data_ptr(), None, stream),
+                   "cbas_patch_kmeans_assign")
+        return labels, clusters
 
     def submit_host(self, slot: int, frames: np.ndarray, channel: int = 1) -> None:
         """Queue one host chunk (uint8 (n,H,W,3) or (n,H,W), C-contiguous) on ``slot``."""

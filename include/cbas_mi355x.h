@@ -20,6 +20,7 @@
  *                                          hidden state and CLS attention, and the attention rollout over the layers
  *   cbas_patch_pca_*                       (no counterpart: the reference draws attention only) PCA of the patch rows of that
  *                                          last_hidden_state, fitted and projected on the device
+ *   cbas_patch_kmeans_*                    (no counterpart) k-means of the same patch rows: a cluster label per patch
  *   cbas_enc_submit_u8_host / cbas_enc_wait  backend/cbas.py:423-440 one iteration of the chunk loop
  *                                          (H2D copy, encode, D2H copy), made asynchronous
  *   cbas_head_create / cbas_head_destroy   backend/workthreads.py:427-447 ClassifierLSTMDeltas(...)
@@ -313,6 +314,48 @@ int cbas_patch_pca_fit(const float* rows_dev, int n, int T, int n_prefix, int D,
                        void* workspace_dev, int64_t workspace_bytes, void* stream);
 int cbas_patch_pca_project(const float* rows_dev, int n, int T, int n_prefix, int D, int64_t ld, int k, int n_bases,
                            const float* mean_dev, const float* components_dev, float* scores_dev, void* stream);
+
+/* k-means of patch features: the discrete picture - a cluster label per patch - fitted and assigned on the device.  Rows, n_prefix,
+ * P, ld and the two scopes are cbas_patch_pca_fit's (FRAME: nb = n problems of M = P rows; BATCH: nb = 1 problem of M = n P rows,
+ * row m = patch m % P of frame m / P); rows are finite.  u = fp32, every sum below has the order stated and none uses an atomic:
+ * two calls give the same bits, and a frame's FRAME-scope result has the bits it has when fitted alone.
+ *   the working row   u = x (normalize = 0), or u = fl(x * rn), rn = fp32(1 / sqrt(s)), s = sum x_d^2 in fp64, rn = 0 when s = 0
+ *                     (normalize = 1).  No normalised copy is written: rn is applied wherever a row is used.
+ *   start             farthest-point seeding.  mean = the column mean of u (rows in chunks of CBAS_KMEANS_CHUNK added in ascending
+ *                     order, the chunks in ascending order, / M).  d(m, t) = sum_d (u_md - t_d)^2: 64 fmaf chains over
+ *                     d = l, l + 64, ... added by the xor tree 32, 16, .., 1.  Seed 0 = the row of largest d(m, mean); seed j = the
+ *                     row of largest min_{i < j} d(m, seed i); ties to the lowest row.  init_index_dev (nb, k): the rows chosen, in
+ *                     this order, an index within the problem (the frame's P rows, or the n P rows).  Seed centroids are u rows.
+ *   a round           every row goes to the centroid of largest score_j = fmaf(rn, x . c_j, -h_j), h_j = |c_j|^2 / 2 (the form
+ *                     u . c - |c|^2 / 2 of the squared distance; ties to the lowest j).  x . c_j is the sum, in this order, of four
+ *                     fp32 fmaf chains: chain w runs over the columns d with (d / 16) % 4 = w, ascending in d / 16, within a block
+ *                     of 16 in the order d % 4, then (d % 16) / 4 (v_mfma_f32_16x16x4_f32: exact products).  Its squared distance is
+ *                     dist2 = max(0, fmaf(-2, score, |u|^2)), |u|^2 = fp32(s), or 1 (0 for a zero row) when normalize = 1.
+ *                     New centroid j = (sum of rn x over its rows) / count_j: per chunk of CBAS_KMEANS_CHUNK rows one fmaf chain
+ *                     per element in ascending row order, the chunks added in ascending order, one division.  A centroid without
+ *                     rows keeps its value.  Exactly `iters` rounds: no tolerance, no host synchronisation.
+ *   finish            one more assignment against the final centroids gives the counts; the clusters are then ordered by
+ *                     descending count, ties by seeding order: centroids_dev (nb, k, D), counts_dev (nb, k).
+ *   inertia_dev       (nb, iters + 1): inertia[t] = the sum of dist2 (per chunk in ascending row order, chunks in ascending order)
+ *                     of the assignment against the centroids after t updates.
+ * The workspace (cbas_patch_kmeans_workspace_bytes, -1 for a refused shape; 16-byte aligned) holds on return, first, the final
+ * centroids in SEEDING order, nb * k * D floats, then (rounded up to 4 floats) nb * 16 int32: order[b][r] = the seeding position of
+ * output cluster r (-1 past k).
+ * cbas_patch_kmeans_assign: the round's assignment against given centroids, frame b's own set (n_sets = n) or one set for every
+ * frame (n_sets = 1): labels_dev (n, P) int32 and, unless NULL, dist2_dev (n, P).
+ * CBAS_EINVAL with a message, nothing queued: k outside 2 .. 16 or k > M, D % 32 != 0 or D > 1536, ld < D or ld % 4 != 0, rows,
+ * centroids or workspace not 16-byte aligned, iters < 0 (0 returns the seeds), normalize not 0 or 1, n outside 1 .. 65535, n_sets
+ * not 1 or n, a NULL pointer (dist2_dev may be NULL), a workspace too small, a problem of more than 65535 chunks. */
+#define CBAS_KMEANS_FRAME CBAS_PCA_FRAME
+#define CBAS_KMEANS_BATCH CBAS_PCA_BATCH
+#define CBAS_KMEANS_CHUNK 64
+#define CBAS_KMEANS_MAX_K 16
+int64_t cbas_patch_kmeans_workspace_bytes(int n, int T, int n_prefix, int D, int k, int scope);
+int cbas_patch_kmeans_fit(const float* rows_dev, int n, int T, int n_prefix, int D, int64_t ld, int k, int scope, int iters,
+                          int normalize, float* centroids_dev, int32_t* counts_dev, float* inertia_dev, int32_t* init_index_dev,
+                          void* workspace_dev, int64_t workspace_bytes, void* stream);
+int cbas_patch_kmeans_assign(const float* rows_dev, int n, int T, int n_prefix, int D, int64_t ld, int k, int n_sets, int normalize,
+                             const float* centroids_dev, int32_t* labels_dev, float* dist2_dev, void* stream);
 
 /* Host-streamed form (one iteration of encode_file's chunk loop).  `slot` in [0, CBAS_ENC_SLOTS):
  * submit copies the pixels host->HBM on the handle's copy stream (from pinned staging), encodes
