@@ -177,6 +177,7 @@ DEBUG_SIGNATURES = {
     "cbas_debug_rollout_step": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "cbas_debug_rows_run": (c_int, [c_void_p]),
     "cbas_debug_head_run": (c_int, [c_void_p]),
+    "cbas_debug_head_seq_run": (c_int, [c_void_p]),
     "cbas_debug_build": (c_int, []),
     "cbas_debug_pos_interp_matrix": (c_int, [c_int, c_int, c_int, c_void_p]),
     "cbas_debug_pos_table": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),

@@ -1280,3 +1280,113 @@ extern "C" int cbas_debug_head_run(const cbas_debug_head_args* a) {
             if (E[j].out[i] && E[j].out_bytes[i] > 0 && dout[j][i]) HIP_TRY(hipMemcpy(E[j].out[i], dout[j][i], (size_t)E[j].out_bytes[i], hipMemcpyDeviceToHost));
     return CBAS_OK;
 }
+
+// ---- tests: one launch of a sequential classifier-head kernel (LSTM, BPTT, attention pooling, centre) on host operands ----
+extern "C" int cbas_debug_head_seq_run(const cbas_debug_head_seq_args* a) {
+    if (!a || a->struct_bytes != (int64_t)sizeof(cbas_debug_head_seq_args))
+        return cbas_fail(CBAS_EINVAL, "cbas_debug_head_seq_args: struct_bytes %lld, library expects %lld", a ? (long long)a->struct_bytes : -1ll,
+                         (long long)sizeof(cbas_debug_head_seq_args));
+    constexpr int NI = 10, NO = 5;
+    const int op = a->op, h = a->h, H2 = a->H2, T = a->T, lo = a->lo, hi = a->hi, Cn = a->C, L0 = a->L0;
+    const int64_t nw = a->n_windows;
+    if (op < CBAS_DEBUG_SEQ_LSTM_INFER || op > CBAS_DEBUG_SEQ_CENTRE) return cbas_fail(CBAS_EINVAL, "op %d", op);
+    const bool lstm = op <= CBAS_DEBUG_SEQ_LSTM_TRAIN_BWD, centre = op == CBAS_DEBUG_SEQ_CENTRE, pool = !lstm && !centre;
+    const bool pool_train = op == CBAS_DEBUG_SEQ_POOL_TRAIN_FWD || op == CBAS_DEBUG_SEQ_POOL_TRAIN_BWD;
+    // everything the launchers do not check, before anything is allocated: a refusal must not become a launch
+    if (nw < 1 || nw > (1 << 24) || T < 1 || T > (1 << 16)) return cbas_fail(CBAS_EINVAL, "n_windows = %lld, T = %d: both at least 1", (long long)nw, T);
+    if (lstm && (h < 16 || h > 128 || h % 16)) return cbas_fail(CBAS_EINVAL, "h = %d: the LSTM kernels exist for h = 16, 32, .. 128", h);
+    if ((op == CBAS_DEBUG_SEQ_LSTM_INFER || pool) && !(0 <= lo && lo < hi && hi <= T))
+        return cbas_fail(CBAS_EINVAL, "centre range [lo, hi) = [%d, %d) of T = %d: 0 <= lo < hi <= T", lo, hi, T);
+    if (pool) {
+        if (Cn < 1 || Cn > 64) return cbas_fail(CBAS_EINVAL, "C = %d: the pooling kernels hold 1 .. 64 classes", Cn);
+        if (H2 < 1 || H2 > 256) return cbas_fail(CBAS_EINVAL, "H2 = %d: the pooling kernels hold 2h <= 256 columns", H2);
+        if (!pool_train && H2 % 2) return cbas_fail(CBAS_EINVAL, "POOL_INFER: H2 = %d is not 2 h", H2);
+        if (pool_train && H2 % 32) return cbas_fail(CBAS_EINVAL, "H2 = %d: training pooling needs H2 %% 32 == 0", H2);
+        if (pool_train && hi - lo > 128) return cbas_fail(CBAS_EINVAL, "hi - lo = %d: training pooling holds at most 128 scores", hi - lo);
+    }
+    if (centre && (L0 < 1 || L0 > (1 << 20))) return cbas_fail(CBAS_EINVAL, "L0 = %d: at least 1", L0);
+    // bytes the launch reads (in) and writes (out); opt: the image may be NULL
+    int64_t in_need[NI] = {}, out_need[NO] = {};
+    bool in_opt[NI] = {}, out_opt[NO] = {};
+    const int64_t nc = hi - lo;
+    const int64_t g8 = nw * T * 8 * h * 4, s2 = nw * T * 2 * h * 4, whh = (int64_t)2 * 4 * h * h * 4;
+    switch (op) {
+        case CBAS_DEBUG_SEQ_LSTM_INFER: in_need[0] = g8; in_need[1] = whh; out_need[0] = nw * nc * 2 * h * 4; break;
+        case CBAS_DEBUG_SEQ_LSTM_TRAIN_FWD: in_need[0] = g8; in_need[1] = whh; out_need[0] = g8; out_need[1] = out_need[2] = s2; break;
+        case CBAS_DEBUG_SEQ_LSTM_TRAIN_BWD:
+            in_need[0] = s2; in_need[1] = g8; in_need[2] = in_need[3] = s2; in_need[4] = whh; out_need[0] = g8; out_need[1] = s2;
+            break;
+        case CBAS_DEBUG_SEQ_POOL_INFER:
+        case CBAS_DEBUG_SEQ_POOL_TRAIN_FWD:
+        case CBAS_DEBUG_SEQ_POOL_TRAIN_BWD:
+            in_need[0] = nw * (pool_train ? T : nc) * H2 * 4; in_need[1] = nw * Cn * 4; in_need[2] = (int64_t)H2 * 4;
+            in_need[3] = (int64_t)Cn * H2 * 4; in_need[4] = (int64_t)Cn * 4;
+            if (op == CBAS_DEBUG_SEQ_POOL_INFER) {
+                out_need[0] = out_need[1] = nw * Cn * 4; out_need[2] = nw * H2 * 4;
+                out_opt[0] = out_opt[1] = out_opt[2] = true;
+                if (!a->out[0] && !a->out[1] && !a->out[2]) return cbas_fail(CBAS_EINVAL, "POOL_INFER: probs, logits and latent are all NULL");
+            } else if (op == CBAS_DEBUG_SEQ_POOL_TRAIN_FWD) {
+                out_need[0] = out_need[1] = nw * nc * 4; out_need[2] = nw * H2 * 4; out_need[3] = out_need[4] = nw * Cn * 4;
+            } else {
+                in_need[5] = in_need[6] = nw * nc * 4; in_need[7] = in_need[8] = nw * Cn * 4; in_need[9] = nw * H2 * 4; in_opt[9] = true;
+                out_need[0] = nw * T * H2 * 4; out_need[1] = out_need[2] = nw * Cn * 4; out_need[3] = nw * (H2 + 12) * 4;
+            }
+            break;
+        case CBAS_DEBUG_SEQ_CENTRE: out_need[0] = nw * T * L0 * 4; break;
+    }
+    for (int i = 0; i < NI; ++i)
+        if (in_need[i] && !(in_opt[i] && !a->in[i]) && (!a->in[i] || a->in_bytes[i] < in_need[i]))
+            return cbas_fail(CBAS_EINVAL, "op %d: in[%d] is missing (NULL) or too small (%lld of %lld bytes)", op, i, (long long)a->in_bytes[i],
+                             (long long)in_need[i]);
+    for (int i = 0; i < NO; ++i)
+        if (out_need[i] && !(out_opt[i] && !a->out[i]) && (!a->out[i] || a->out_bytes[i] < out_need[i]))
+            return cbas_fail(CBAS_EINVAL, "op %d: out[%d] is missing (NULL) or too small (%lld of %lld bytes)", op, i, (long long)a->out_bytes[i],
+                             (long long)out_need[i]);
+    DevBufs B;
+    char* din[NI] = {};
+    char* dout[NO] = {};
+    for (int i = 0; i < NI; ++i)
+        if (in_need[i] && a->in[i]) {
+            HIP_TRY(B.alloc(&din[i], (size_t)a->in_bytes[i]));
+            HIP_TRY(hipMemcpy(din[i], a->in[i], (size_t)a->in_bytes[i], hipMemcpyHostToDevice));
+        }
+    for (int i = 0; i < NO; ++i)
+        if (out_need[i] && a->out[i]) {
+            HIP_TRY(B.alloc(&dout[i], (size_t)a->out_bytes[i]));
+            HIP_TRY(hipMemcpy(dout[i], a->out[i], (size_t)a->out_bytes[i], hipMemcpyHostToDevice));
+        }
+    float* scal = nullptr;                                            // training pooling reads its three scalars from memory
+    if (pool_train) {
+        const float hs[3] = {a->b_att, a->att_temp, a->gate};
+        HIP_TRY(B.alloc(&scal, sizeof(hs)));
+        HIP_TRY(hipMemcpy(scal, hs, sizeof(hs), hipMemcpyHostToDevice));
+    }
+    const auto fin = [&](int i) { return reinterpret_cast<const float*>(din[i]); };
+    const auto fout = [&](int i) { return reinterpret_cast<float*>(dout[i]); };
+    HeadDims d{};
+    d.C = Cn; d.T = T; d.L0 = L0; d.h = lstm ? h : H2 / 2; d.lo = lo; d.hi = hi;
+    TrainPoolParams pp{};
+    pp.hout = fin(0); pp.lin_logits = fin(1); pp.w_att = fin(2); pp.w_lin2 = fin(3); pp.b_lin2 = fin(4);
+    pp.b_att = scal; pp.att_temp = scal ? scal + 1 : nullptr; pp.gate = scal ? scal + 2 : nullptr;
+    pp.T = T; pp.H2 = H2; pp.C = Cn; pp.lo = lo; pp.hi = hi;
+    int rc = -1;
+    switch (op) {
+        case CBAS_DEBUG_SEQ_LSTM_INFER: rc = launch_head_lstm(fin(0), fin(1), d, lo, hi, nw, fout(0), 0); break;
+        case CBAS_DEBUG_SEQ_LSTM_TRAIN_FWD: rc = launch_lstm_train_fwd(fin(0), fin(1), h, T, nw, fout(0), fout(1), fout(2), 0); break;
+        case CBAS_DEBUG_SEQ_LSTM_TRAIN_BWD: rc = launch_lstm_train_bwd(fin(0), fin(1), fin(2), fin(3), fin(4), h, T, nw, fout(0), fout(1), 0); break;
+        case CBAS_DEBUG_SEQ_POOL_INFER:
+            rc = launch_head_pool(fin(0), fin(1), d, fin(2), a->b_att, a->att_temp, fin(3), fin(4), a->gate, a->temperature, nw, fout(0), fout(1),
+                                  fout(2), 0);
+            break;
+        case CBAS_DEBUG_SEQ_POOL_TRAIN_FWD: rc = launch_pool_train_fwd(pp, nw, fout(0), fout(1), fout(2), fout(3), fout(4), 0); break;
+        case CBAS_DEBUG_SEQ_POOL_TRAIN_BWD:
+            rc = launch_pool_train_bwd(pp, nw, fin(5), fin(6), fin(7), fin(8), fin(9), fout(0), fout(1), fout(2), fout(3), 0);
+            break;
+        case CBAS_DEBUG_SEQ_CENTRE: rc = launch_head_centre(fout(0), nw, T, L0, 0); break;
+    }
+    if (rc) return cbas_fail(CBAS_EINVAL, "head sequence kernel launch failed (op %d: rc=%d)", op, rc);
+    HIP_TRY(hipDeviceSynchronize());
+    for (int i = 0; i < NO; ++i)
+        if (dout[i]) HIP_TRY(hipMemcpy(a->out[i], dout[i], (size_t)a->out_bytes[i], hipMemcpyDeviceToHost));
+    return CBAS_OK;
+}

@@ -103,9 +103,11 @@ static __device__ __forceinline__ float gelu_erf(float x) {
     return 0.5f * x * (1.0f + erf_bf(x * 0.70710678118654752440f));
 }
 //   tanh = sign(x) (1 - e) / (1 + e), e = exp(-2 |x|) with the product's rounding residual carried into the result
-//        (absolute error ~6e-8, all the LSTM's gates need)
+//        (absolute error ~6e-8, all the LSTM's gates need).  The clamp is a compare and select, not fmaxf: fmaxf drops a NaN
+//        and tanh_bf(NaN) came out as +-1; the select hands NaN on and gives the same bits for every other x
 static __device__ __forceinline__ float tanh_bf(float x) {
-    const float v = fmaxf(-2.0f * fabsf(x), -100.f);
+    const float a = fabsf(x);
+    const float v = a > 50.f ? -100.f : -2.0f * a;
     const float t = v * 1.44269504f;
     float r = fmaf(v, 1.44269504f, -t);
     r = fmaf(v, 1.92596299e-8f, r);

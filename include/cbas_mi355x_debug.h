@@ -282,6 +282,47 @@ typedef struct cbas_debug_head_args {
 } cbas_debug_head_args;
 int cbas_debug_head_run(const cbas_debug_head_args* a);
 
+/* Tests: ONE launch of a sequential classifier-head kernel on host operands (tests/test_gpu_head_seq_reference.py compares it with
+ * the float64 references of oracle/kernel_ref.py): the recurrent LSTM of inference (head_kernels.hip) and of training with its
+ * BPTT (head_train_kernels.hip), the attention pooling of both, and head_centre.  The harness uploads every in[] image and the
+ * caller's pre-filled out[] images whole, runs exactly one launcher on the default stream, synchronises and copies every out[]
+ * image back whole: what the launch does not own is the caller's canary.  It refuses (CBAS_EINVAL, nothing allocated or
+ * launched): h not one of 16, 32, .. 128 (LSTM ops); n_windows < 1, T < 1; 0 <= lo < hi <= T violated; pooling with C outside
+ * 1 .. 64 or H2 outside 1 .. 256, training pooling also with H2 % 32 != 0 or hi - lo > 128; CENTRE with L0 < 1; a NULL
+ * non-optional image; an image smaller than what the launch reads or writes.
+ *   op               launcher               in[]                                                     out[]
+ *   LSTM_INFER       launch_head_lstm       gin [w][T][8h], w_hh [2][4h][h]                          hout [w][hi-lo][2h]
+ *   LSTM_TRAIN_FWD   launch_lstm_train_fwd  gin, w_hh                                                act [w][T][8h], cst, hout [w][T][2h]
+ *   LSTM_TRAIN_BWD   launch_lstm_train_bwd  dhout [w][T][2h], act, cst, hout, w_hh                   dgin [w][T][8h], hprev [w][T][2h]
+ *   POOL_INFER       launch_head_pool       hout [w][hi-lo][H2], lin_logits [w][C], w_att [H2],      probs [w][C], logits [w][C], latent [w][H2]
+ *                                           w_lin2 [C][H2], b_lin2 [C]                               (each may be NULL, not all)
+ *   POOL_TRAIN_FWD   launch_pool_train_fwd  hout [w][T][H2], lin_logits, w_att, w_lin2, b_lin2       attw, scores [w][hi-lo], latent [w][H2],
+ *                                                                                                    lstm_logits, final_logits [w][C]
+ *   POOL_TRAIN_BWD   launch_pool_train_bwd  the five above, attw, scores, lstm_logits, dfinal        dhout [w][T][H2], dlstm_logits, dlin_logits
+ *                                           [w][C], dlat_cov [w][H2] or NULL                         [w][C], part [w][H2 + 12]
+ *   CENTRE           launch_head_centre     -                                                        xl [w][T][L0], in place
+ * b_att, att_temp and gate are the scalars of the struct: POOL_INFER takes att_temp as the temperature already formed and gate
+ * as sigmoid(gate); the training ops take the raw parameters (uploaded as one-element images) and form softplus / sigmoid. */
+enum {
+    CBAS_DEBUG_SEQ_LSTM_INFER = 0, CBAS_DEBUG_SEQ_LSTM_TRAIN_FWD = 1, CBAS_DEBUG_SEQ_LSTM_TRAIN_BWD = 2, CBAS_DEBUG_SEQ_POOL_INFER = 3,
+    CBAS_DEBUG_SEQ_POOL_TRAIN_FWD = 4, CBAS_DEBUG_SEQ_POOL_TRAIN_BWD = 5, CBAS_DEBUG_SEQ_CENTRE = 6
+};
+typedef struct cbas_debug_head_seq_args {
+    int64_t struct_bytes;        /* sizeof(cbas_debug_head_seq_args): a mismatch is rejected */
+    int op;
+    int h;                       /* LSTM ops: hidden units per direction */
+    int H2;                      /* pooling ops: width of a hout row (2 h) */
+    int T, lo, hi;               /* window length; the centre range (CENTRE ignores lo / hi; LSTM_TRAIN_*: unused) */
+    int C, L0;
+    int64_t n_windows;
+    float b_att, att_temp, gate, temperature;
+    const void* in[10];
+    int64_t in_bytes[10];
+    void* out[5];                /* in / out */
+    int64_t out_bytes[5];
+} cbas_debug_head_seq_args;
+int cbas_debug_head_seq_run(const cbas_debug_head_seq_args* a);
+
 /* Root-cause probe (round 5): run a kernel from a separately built code object IN PLACE of the library's head_expand_kernel
  * on this handle (same grid, block, dynamic LDS and arguments: scripts/probes/expand_r4/expand_r4.hip has the signature).
  * hsaco_path = NULL restores the library's kernel.  scripts/expand_rootcause.py builds instruction-level variants of the

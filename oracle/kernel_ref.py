@@ -887,3 +887,418 @@ def ratio(y, ref, bound) -> float:
     y = np.asarray(y, np.float64)
     d = np.where(np.isfinite(y), np.abs(y - ref), np.inf)
     return float((d / bound).max()) if d.size else 0.0
+
+
+# ---- classifier head: the sequential kernels (LSTM, BPTT, attention pooling, centre) -----------------------------------------
+# Used by tests/test_gpu_head_seq_reference.py through cbas_debug_head_seq_run.  Plain float64 from the kernels' headers and
+# classifier_head.py's mathematics; every bound is fixed from where the kernels round, with u1 = 1.01 * 2^-24:
+#   a sum of n products (fmaf chain, MFMA chain, lane partials + a butterfly)       n_levels u1 sum |terms|
+#   a libm call (expf, tanhf): the project's budget for one, GELU_LIB_U u32 of the result (1 ulp); expf followed by log1pf
+#       (softplus) or by logf: CE_LSE_U u32 (1 + |result|); a division, a product, an addition: u1 of the result
+#   tanh_bf: the absolute 6e-8 that common.h CLAIMS for it (the header's figure, not a measurement)
+# Where the carried state cannot be observed (inference LSTM, BPTT) the error is propagated to first order in float64 beside
+# the values (e_c(t) = f_t e_c(t-1) + ..., likewise e_h, e_dh, e_dc) and the result doubled for the second-order terms.
+U1 = 1.01 * U32
+TANH_BF_ABS = 6e-8            # common.h: "absolute error ~6e-8"
+LIBM_U = GELU_LIB_U           # one libm call, u32 of its result
+F32_TINY = 2.0 ** -126        # results below the normal range may be flushed
+
+
+def _wide(x):
+    """fp32 images widened to float64; float64 input (the CPU checks against torch.autograd) passes unrounded."""
+    x = np.asarray(x)
+    return x if x.dtype == np.float64 else x.astype(np.float32).astype(np.float64)
+
+
+def _sig64(x):
+    return 1.0 / (1.0 + np.exp(-x))
+
+
+def _sig_err(s, E_x):
+    """sigmoidf_(x) = 1 / (1 + expf(-x)) given |error of x| <= E_x: expf's share scales with e / (1 + e) = 1 - s, then the
+    addition and the division."""
+    return s * (1.0 - s) * E_x + U1 * s * (LIBM_U * (1.0 - s) + 2.0)
+
+
+def _tanh_err(t, kind):
+    return TANH_BF_ABS if kind == "infer" else LIBM_U * U1 * np.abs(t)
+
+
+def lstm_step64(g, W, hp, cp, e_h, e_c, kind, levels=None):
+    """One LSTM step of one direction in float64 with its first-order error.  g [w][4h] (gate order i, f, g, o), W [4h][h],
+    hp / cp [w][h] the previous state, e_h / e_c [w][h] the bound on the DEVICE's previous state against hp / cp (zeros:
+    teacher-forced).  kind "infer" (MFMA chain, tanh_bf) or "train" (fmaf chain, tanhf).  pre = one fp32 addend + H products:
+    (H + 1) u1 (|g| + sum |w| |h|); levels = 1 for permutation weights (one exact product and one rounding whatever the order).
+    Returns act [w][4h], c, h, E_act, E_c, E_h."""
+    H = W.shape[1]
+    levels = H + 1 if levels is None else levels
+    aW = np.abs(W)
+    pre = g + hp @ W.T
+    E_pre = levels * U1 * (np.abs(g) + np.abs(hp) @ aW.T) + e_h @ aW.T
+    act = _sig64(pre)
+    E_act = _sig_err(act, E_pre)
+    gg = np.tanh(pre[:, 2 * H:3 * H])
+    act[:, 2 * H:3 * H] = gg
+    E_act[:, 2 * H:3 * H] = (1.0 - gg * gg) * E_pre[:, 2 * H:3 * H] + _tanh_err(gg, kind)
+    i, f, o = act[:, :H], act[:, H:2 * H], act[:, 3 * H:]
+    Ei, Ef, Eg, Eo = E_act[:, :H], E_act[:, H:2 * H], E_act[:, 2 * H:3 * H], E_act[:, 3 * H:]
+    c = f * cp + i * gg
+    E_c = f * e_c + np.abs(cp) * Ef + np.abs(gg) * Ei + i * Eg + 2.0 * U1 * (np.abs(f * cp) + np.abs(i * gg))
+    tc = np.tanh(c)
+    h = o * tc
+    E_h = np.abs(tc) * Eo + o * ((1.0 - tc * tc) * E_c + _tanh_err(tc, kind)) + U1 * np.abs(h)
+    return act, c, h, E_act, E_c, E_h
+
+
+def lstm_fwd_ref(gin, w_hh, kind, levels=None):
+    """Free-running bidirectional LSTM forward: gin [w][T][8h], w_hh [2][4h][h] (the fp32 values widened).  Direction 1 runs
+    t = T-1 .. 0.  Returns dict act [w][T][8h], c, h [w][T][2h], their propagated bounds E_* (already doubled) and one-step
+    bounds S_* (the same step with an exact previous state)."""
+    gin = _wide(gin)
+    W = _wide(w_hh)
+    nw, T, G8 = gin.shape
+    H = G8 // 8
+    out = {k: np.zeros((nw, T, 8 * H)) for k in ("act", "E_act", "S_act")}
+    out.update({k: np.zeros((nw, T, 2 * H)) for k in ("c", "h", "E_c", "E_h", "S_c", "S_h")})
+    z = np.zeros((nw, H))
+    for d in range(2):
+        hp, cp, e_h, e_c = z, z, z, z
+        for s in range(T):
+            t = T - 1 - s if d else s
+            g = gin[:, t, d * 4 * H:(d + 1) * 4 * H]
+            act, c, h, Ea, Ec, Eh = lstm_step64(g, W[d], hp, cp, e_h, e_c, kind, levels)
+            _, _, _, Sa, Sc, Sh = lstm_step64(g, W[d], hp, cp, z, z, kind, levels)
+            for k, v in (("act", act), ("E_act", 2 * Ea), ("S_act", Sa)):
+                out[k][:, t, d * 4 * H:(d + 1) * 4 * H] = v
+            for k, v in (("c", c), ("h", h), ("E_c", 2 * Ec), ("E_h", 2 * Eh), ("S_c", Sc), ("S_h", Sh)):
+                out[k][:, t, d * H:(d + 1) * H] = v
+            hp, cp, e_h, e_c = h, c, Eh, Ec
+    return out
+
+
+def lstm_infer_ref(gin, w_hh, lo, hi, levels=None):
+    """head_lstm's output [w][hi-lo][2h] and its bound: the forward direction runs steps 0 .. hi-1, the reverse T-1 .. lo, so
+    rows [lo, hi) of the full run are what it stores."""
+    r = lstm_fwd_ref(gin, w_hh, "infer", levels)
+    return r["h"][:, lo:hi], r["E_h"][:, lo:hi], r
+
+
+def lstm_train_fwd_teacher_ref(gin, w_hh, cst_dev, hout_dev, levels=None):
+    """lstm_train_fwd step by step from the DEVICE's own previous c and h (teacher-forced): only the one-step bound applies."""
+    gin = _wide(gin)
+    W = _wide(w_hh)
+    cd = _wide(cst_dev)
+    hd = _wide(hout_dev)
+    nw, T, G8 = gin.shape
+    H = G8 // 8
+    out = {k: np.zeros((nw, T, 8 * H)) for k in ("act", "S_act")}
+    out.update({k: np.zeros((nw, T, 2 * H)) for k in ("c", "h", "S_c", "S_h")})
+    z = np.zeros((nw, H))
+    for d in range(2):
+        for s in range(T):
+            t = T - 1 - s if d else s
+            tp = t + 1 if d else t - 1
+            hp = hd[:, tp, d * H:(d + 1) * H] if s else z
+            cp = cd[:, tp, d * H:(d + 1) * H] if s else z
+            act, c, h, Sa, Sc, Sh = lstm_step64(gin[:, t, d * 4 * H:(d + 1) * 4 * H], W[d], hp, cp, z, z, "train", levels)
+            out["act"][:, t, d * 4 * H:(d + 1) * 4 * H] = act
+            out["S_act"][:, t, d * 4 * H:(d + 1) * 4 * H] = Sa
+            for k, v in (("c", c), ("h", h), ("S_c", Sc), ("S_h", Sh)):
+                out[k][:, t, d * H:(d + 1) * H] = v
+    return out
+
+
+def lstm_bwd_ref(dhout, act, cst, hout, w_hh):
+    """BPTT from the saved images (the very fp32 values handed to the device, widened): returns dgin [w][T][8h], hprev [w][T][2h]
+    (hout of the step that fed t, +0 at a direction's first step: exact), the propagated bound E (doubled) and the one-step
+    bound S of dgin.  The recurrences: dh = dhout + dh_rec, dc = dc_rec + dh o (1 - tanh^2 c), dc_rec' = dc f,
+    dh_rec' = W^T da.  Rounding: 1 - x^2 is absolute u1 (x^2 + |1 - x^2|); a product of k factors k u1; dh_rec' is four fmaf
+    chains of H and two levels of additions: (H + 2) u1 sum |w| |da|."""
+    dh_in = _wide(dhout)
+    A = _wide(act)
+    Cc = _wide(cst)
+    Hh = _wide(hout)
+    W = _wide(w_hh)
+    nw, T, G8 = A.shape
+    H = G8 // 8
+    dgin, E, S = np.zeros_like(A), np.zeros_like(A), np.zeros_like(A)
+    hprev = np.zeros_like(Hh)
+    z = np.zeros((nw, H))
+
+    def step(a, c, cp, dho, dh_rec, dc_rec, e_dh, e_dc):
+        ig, fg, gg, og = a[:, :H], a[:, H:2 * H], a[:, 2 * H:3 * H], a[:, 3 * H:]
+        tc = np.tanh(c)
+        E_tc = LIBM_U * U1 * np.abs(tc)
+        dh = dho + dh_rec
+        E_dh = e_dh + U1 * np.abs(dh)
+        s = 1.0 - tc * tc
+        E_s = 2.0 * np.abs(tc) * E_tc + U1 * (tc * tc + np.abs(s))
+        term = dh * og * s
+        E_term = np.abs(og * s) * E_dh + np.abs(dh * og) * E_s + 2.0 * U1 * np.abs(term)
+        dc = dc_rec + term
+        E_dc = e_dc + E_term + U1 * np.abs(dc)
+        dai = dc * gg * ig * (1.0 - ig)
+        daf = dc * cp * fg * (1.0 - fg)
+        s2 = 1.0 - gg * gg
+        dag = dc * ig * s2
+        dao = dh * tc * og * (1.0 - og)
+        E_da = np.concatenate([
+            np.abs(gg * ig * (1.0 - ig)) * E_dc + 4.0 * U1 * np.abs(dai),
+            np.abs(cp * fg * (1.0 - fg)) * E_dc + 4.0 * U1 * np.abs(daf),
+            np.abs(ig * s2) * E_dc + np.abs(dc * ig) * U1 * (gg * gg + np.abs(s2)) + 2.0 * U1 * np.abs(dag),
+            np.abs(tc * og * (1.0 - og)) * E_dh + np.abs(dh * og * (1.0 - og)) * E_tc + 4.0 * U1 * np.abs(dao)], 1)
+        da = np.concatenate([dai, daf, dag, dao], 1)
+        return da, E_da, dc * fg, fg * E_dc + U1 * np.abs(dc * fg)
+
+    for d in range(2):
+        Wd, aW = W[d], np.abs(W[d])
+        dh_rec, dc_rec, e_dh, e_dc = z, z, z, z
+        sl4, sl = slice(d * 4 * H, (d + 1) * 4 * H), slice(d * H, (d + 1) * H)
+        for st in range(T - 1, -1, -1):
+            t = T - 1 - st if d else st
+            tp = t + 1 if d else t - 1
+            cp = Cc[:, tp, sl] if st else z
+            hprev[:, t, sl] = Hh[:, tp, sl] if st else 0.0
+            da, E_da, dc_next, e_dc_next = step(A[:, t, sl4], Cc[:, t, sl], cp, dh_in[:, t, sl], dh_rec, dc_rec, e_dh, e_dc)
+            _, S_da, _, _ = step(A[:, t, sl4], Cc[:, t, sl], cp, dh_in[:, t, sl], dh_rec, dc_rec, z, z)
+            dgin[:, t, sl4], E[:, t, sl4], S[:, t, sl4] = da, 2.0 * E_da, S_da
+            dh_rec = da @ Wd
+            e_dh = E_da @ aW + (H + 2) * U1 * (np.abs(da) @ aW)
+            dc_rec, e_dc = dc_next, e_dc_next
+    return dgin, hprev, E + F32_TINY, S + F32_TINY
+
+
+def softplus_temp_ref(raw):
+    """softplus(raw) + 1e-3 with the kernel's switch at raw > 20 (fp32 raw), its derivative, and the bound of the value:
+    expf + log1pf CE_LSE_U u32 (1 + |softplus|), the addition u1."""
+    raw = float(np.float32(raw))
+    k = float(np.float32(1e-3))
+    if raw > 20.0:
+        return raw + k, 1.0, U1 * (raw + k), 0.0
+    sp = math.log1p(math.exp(raw))
+    sg = 1.0 / (1.0 + math.exp(-raw))
+    return sp + k, sg, CE_LSE_U * U1 * (1.0 + abs(sp)) + U1 * (sp + k), float(_sig_err(sg, 0.0))
+
+
+def _attention64(hc, w_att, b_att, temp, E_temp, levels):
+    """scores, softmax weights and latent of attention pooling over hc [w][nc][H2] with their bounds.  A score is H2 products
+    summed in `levels` roundings, + b, / temp; the weight e_t / den: expf's argument carries both scores' errors and one
+    subtraction, expf LIBM_U, den nc additions, the division; the latent nc more."""
+    nc = hc.shape[1]
+    dot = hc @ w_att
+    adot = np.abs(hc) @ np.abs(w_att)
+    sc = (dot + b_att) / temp
+    E_sc = (levels * U1 * adot + U1 * np.abs(dot + b_att)) / abs(temp) + np.abs(sc) * (E_temp / abs(temp) + U1)
+    mx = sc.max(1, keepdims=True)
+    E_arg = E_sc + E_sc.max(1, keepdims=True) + U1 * np.abs(sc - mx)
+    e = np.exp(sc - mx)
+    den = e.sum(1, keepdims=True)
+    aw = e / den
+    R = E_arg + LIBM_U * U1                                    # relative error of e_t
+    R_aw = R + R.max(1, keepdims=True) + (nc + 1) * U1         # ... of e_t / den
+    lat = (aw[:, :, None] * hc).sum(1)
+    E_lat = ((aw * (R_aw + (nc + 2) * U1))[:, :, None] * np.abs(hc)).sum(1) + F32_TINY
+    return sc, E_sc, aw, aw * R_aw + F32_TINY, lat, E_lat
+
+
+def _lerp_bound(lin, lstm, E_lstm, g, E_g):
+    """final = lerp(lin, lstm, g) in either of torch.lerp's forms (mathematically one value): the larger of the two forms'
+    roundings."""
+    d = lstm - lin
+    E_d = E_lstm + U1 * np.abs(d)
+    fin = lin + g * d
+    lo_form = abs(g) * E_d + np.abs(d) * E_g + U1 * np.abs(g * d) + U1 * np.abs(fin)
+    hi_form = E_lstm + abs(1.0 - g) * E_d + np.abs(d) * (E_g + U1 * abs(1.0 - g)) + U1 * np.abs(d * (1.0 - g)) + U1 * np.abs(fin)
+    return fin, np.maximum(lo_form, hi_form)
+
+
+def pool_infer_ref(hout, lin_logits, w_att, b_att, att_temp, w_lin2, b_lin2, gate_sigmoid, temperature):
+    """head_pool: hout [w][nc][H2] -> latent [w][H2], logits = lerp(lin, latent W2^T + b2, g) [w][C], probs =
+    softmax(logits / max(1e-3, temperature)).  A lane holds per = ceil(H2 / 64) columns; wave sums add 6 levels.  Returns
+    (probs, logits, latent), (E_probs, E_logits, E_latent)."""
+    hc = _wide(hout)
+    lin = _wide(lin_logits)
+    wa = _wide(w_att)
+    W2 = _wide(w_lin2)
+    b2 = _wide(b_lin2)
+    H2 = hc.shape[2]
+    levels = (H2 + 63) // 64 + 7
+    _, _, _, _, lat, E_lat = _attention64(hc, wa, float(np.float32(b_att)), float(np.float32(att_temp)), 0.0, levels)
+    lstm = lat @ W2.T + b2
+    E_lstm = E_lat @ np.abs(W2).T + levels * U1 * (np.abs(lat) @ np.abs(W2).T) + U1 * np.abs(lstm)
+    g = float(np.float32(gate_sigmoid))
+    fin, E_fin = _lerp_bound(lin, lstm, E_lstm, g, 0.0)
+    tdiv = max(float(np.float32(1e-3)), float(np.float32(temperature)))
+    zz = fin / tdiv
+    E_z = E_fin / tdiv + U1 * np.abs(zz)
+    zmax = zz.max(1, keepdims=True)
+    e = np.exp(zz - zmax)
+    p = e / e.sum(1, keepdims=True)
+    Rp = E_z + E_z.max(1, keepdims=True) + U1 * np.abs(zz - zmax) + LIBM_U * U1
+    E_p = p * (Rp + Rp.max(1, keepdims=True) + (6 + 1) * U1) + F32_TINY      # the wave sum of the exponentials, the division
+    return (p, fin, lat), (E_p, E_fin, E_lat)
+
+
+def pool_train_fwd_ref(hout, lin_logits, w_att, b_att, raw_temp, w_lin2, b_lin2, raw_gate, lo, hi):
+    """pool_train_fwd on hout [w][T][H2], rows [lo, hi): attw, scores [w][nc], latent [w][H2], lstm_logits, final_logits [w][C]
+    and their bounds.  block_sum: a product, 6 butterfly levels, up to 4 waves: 11 roundings."""
+    hc = _wide(hout)[:, lo:hi]
+    lin = _wide(lin_logits)
+    wa = _wide(w_att)
+    W2 = _wide(w_lin2)
+    b2 = _wide(b_lin2)
+    H2 = hc.shape[2]
+    temp, _, E_temp, _ = softplus_temp_ref(raw_temp)
+    sc, E_sc, aw, E_aw, lat, E_lat = _attention64(hc, wa, float(np.float32(b_att)), temp, E_temp, 11)
+    lstm = lat @ W2.T + b2
+    E_lstm = E_lat @ np.abs(W2).T + (H2 + 1) * U1 * (np.abs(lat) @ np.abs(W2).T + np.abs(b2))
+    g = float(_sig64(float(np.float32(raw_gate))))
+    fin, E_fin = _lerp_bound(lin, lstm, E_lstm, g, float(_sig_err(g, 0.0)))
+    return (aw, sc, lat, lstm, fin), (E_aw, E_sc, E_lat, E_lstm, E_fin)
+
+
+def pool_train_bwd_ref(hout, lin_logits, w_att, raw_temp, w_lin2, raw_gate, lo, hi, attw, scores, lstm_logits, dfinal, dlat_cov):
+    """pool_train_bwd from the saved attw / scores / lstm_logits images (fp32, widened): dhout [w][T][H2] (exactly +0 outside
+    [lo, hi)), dlstm_logits, dlin_logits [w][C], part [w][H2 + 12] = [d w_att | d b_att,0,0,0 | d gate,0,0,0 | d att_temp,0,0,0]
+    and their bounds (see the derivation beside each line)."""
+    f64 = _wide
+    hf, lin, wa, W2, aw, sc, lstm, df = (f64(x) for x in (hout, lin_logits, w_att, w_lin2, attw, scores, lstm_logits, dfinal))
+    nw, T, H2 = hf.shape
+    C = lin.shape[1]
+    nc = hi - lo
+    hc = hf[:, lo:hi]
+    temp, dsp, E_temp, E_dsp = softplus_temp_ref(raw_temp)
+    g = float(_sig64(float(np.float32(raw_gate))))
+    E_g = float(_sig_err(g, 0.0))
+    dl = g * df
+    E_dl = np.abs(df) * E_g + U1 * np.abs(dl)
+    dlin = (1.0 - g) * df
+    E_dlin = np.abs(df) * (E_g + U1 * (1.0 - g)) + U1 * np.abs(dlin)
+    P = g * (1.0 - g)                                            # d gate: sum_c df (lstm - lin) g (1 - g), a block sum
+    E_P = (1.0 - g) * E_g + g * (E_g + U1 * (1.0 - g)) + U1 * P
+    term = df * (lstm - lin) * P
+    dgate = term.sum(1)
+    E_dgate = (np.abs(df * (lstm - lin)) * E_P + 4.0 * U1 * np.abs(term)).sum(1) + 11 * U1 * np.abs(term).sum(1)
+    dlat = dl @ W2 + (f64(dlat_cov) if dlat_cov is not None else 0.0)       # fmaf chain over the classes
+    E_dlat = E_dl @ np.abs(W2) + (C + 1) * U1 * (np.abs(dl) @ np.abs(W2) + (np.abs(f64(dlat_cov)) if dlat_cov is not None else 0.0))
+    dav = np.einsum("wu,wtu->wt", dlat, hc)                      # block sums
+    E_dav = np.einsum("wu,wtu->wt", E_dlat, np.abs(hc)) + 11 * U1 * np.einsum("wu,wtu->wt", np.abs(dlat), np.abs(hc))
+    dot = (aw * dav).sum(1, keepdims=True)                       # fmaf chain over the steps
+    E_dot = (aw * E_dav).sum(1, keepdims=True) + (nc + 1) * U1 * np.abs(aw * dav).sum(1, keepdims=True)
+    ds = aw * (dav - dot)
+    E_ds = aw * (E_dav + E_dot + U1 * np.abs(dav - dot)) + U1 * np.abs(ds)
+    q = ds / temp
+    E_q = E_ds / temp + np.abs(q) * (E_temp / temp + U1)
+    dh = np.zeros_like(hf)
+    E_dhout = np.zeros_like(hf)
+    dh[:, lo:hi] = aw[:, :, None] * dlat[:, None, :] + q[:, :, None] * wa[None, None, :]
+    E_dhout[:, lo:hi] = (aw[:, :, None] * E_dlat[:, None, :] + E_q[:, :, None] * np.abs(wa)[None, None, :]
+                         + 2.0 * U1 * (np.abs(aw[:, :, None] * dlat[:, None, :]) + np.abs(q[:, :, None] * wa[None, None, :])) + F32_TINY)
+    dwatt = np.einsum("wt,wtu->wu", q, hc)
+    E_dwatt = np.einsum("wt,wtu->wu", E_q, np.abs(hc)) + (nc + 1) * U1 * np.einsum("wt,wtu->wu", np.abs(q), np.abs(hc))
+    dbatt = q.sum(1)
+    E_dbatt = E_q.sum(1) + nc * U1 * np.abs(q).sum(1)
+    r = ds * sc / temp
+    dtemp = -r.sum(1)
+    E_dtemp = (np.abs(sc / temp) * E_ds + np.abs(r) * (E_temp / temp + 2.0 * U1)).sum(1) + nc * U1 * np.abs(r).sum(1)
+    part = np.zeros((nw, H2 + 12))
+    E_part = np.zeros((nw, H2 + 12))
+    part[:, :H2], E_part[:, :H2] = dwatt, E_dwatt + F32_TINY
+    part[:, H2], E_part[:, H2] = dbatt, E_dbatt + F32_TINY
+    part[:, H2 + 4], E_part[:, H2 + 4] = dgate, E_dgate + F32_TINY
+    part[:, H2 + 8] = dtemp * dsp
+    E_part[:, H2 + 8] = dsp * E_dtemp + np.abs(dtemp) * E_dsp + U1 * np.abs(dtemp * dsp) + F32_TINY
+    return (dh, dl, dlin, part), (E_dhout, E_dl + F32_TINY, E_dlin + F32_TINY, E_part)
+
+
+def centre_ref(xl):
+    """head_centre: xl [w][T][L0] minus its time mean; the mean is a sequential sum of T terms and a division, then one
+    subtraction: (T + 2) u1 of the magnitudes involved."""
+    x = _wide(xl)
+    T = x.shape[1]
+    m = x.mean(1, keepdims=True)
+    am = np.abs(x).mean(1, keepdims=True)
+    return x - m, (T + 2) * U1 * (am + np.abs(x - m)) + F32_TINY
+
+
+def lstm_case(nw, T, h, seed, row_l1=0.5, gin_amp=3.0):
+    """gin in +-gin_amp and W_hh whose rows have sum |w| = row_l1: a contraction, so that the propagated bound stays within a
+    small multiple of the one-step bound."""
+    rng = np.random.default_rng(seed)
+    gin = rng.uniform(-gin_amp, gin_amp, (nw, T, 8 * h)).astype(np.float32)
+    W = rng.standard_normal((2, 4 * h, h))
+    W *= row_l1 * 0.999 / np.abs(W).sum(2, keepdims=True)
+    return gin, W.astype(np.float32)
+
+
+def lstm_perm_weights(h, seed=0):
+    """W_hh[dir][g h + u][k] = 2^-s(g, dir) if k = pi_{g,dir}(u) else 0: a different permutation and shift per gate and direction, so
+    every pre-activation is one fp32 addend plus one exact product."""
+    rng = np.random.default_rng(1000 + h + seed)
+    W = np.zeros((2, 4 * h, h), np.float32)
+    for d in range(2):
+        for g in range(4):
+            pi = rng.permutation(h)
+            W[d, g * h + np.arange(h), pi] = 2.0 ** -(1 + g + 4 * d)
+    return W
+
+
+LSTM_H = (16, 32, 48, 64, 80, 96, 112, 128)
+LSTM_NW_INFER = (1, 15, 16, 17, 33)
+LSTM_NW_TRAIN = (1, 3)
+LSTM_T = (1, 2, 3, 7, 31)
+RANGE_KINDS = ("full", "centre3", "first", "last", "centre1")
+
+
+def centre_range(kind, T):
+    """[lo, hi) of a range kind; centre3 is (T/2 - 1, T/2 + 2) where T holds it, else the full range."""
+    if kind == "first":
+        return 0, 1
+    if kind == "last":
+        return T - 1, T
+    if kind == "centre1":
+        return T // 2, T // 2 + 1
+    if kind == "centre3" and T >= 5:
+        return T // 2 - 1, T // 2 + 2
+    return 0, T
+
+
+def lstm_suite_cases():
+    """The covering set of the LSTM tests: 40 cases (h, nw_infer, nw_train, T, kind, lo, hi) in which every h, window count, T
+    and range kind appears with at least two different h (tests/test_kernel_reference_bounds.py asserts the coverage)."""
+    cases = []
+    for i in range(40):
+        r = i // 8
+        h = LSTM_H[i % 8]
+        T = LSTM_T[(i + r) % 5]
+        kind = RANGE_KINDS[(3 * i + 2 * r) % 5]
+        lo, hi = centre_range(kind, T)
+        cases.append((h, LSTM_NW_INFER[(2 * i + r) % 5], LSTM_NW_TRAIN[(i + r) % 2], T, kind, lo, hi))
+    return cases
+
+
+# pooling shapes of the suite.  Training (H2, C, hi - lo, raw att_temp): H2 = 32, 96, 224 leave dead threads in the last wave,
+# hi - lo = 128 fills the score buffer, raw = 25 takes softplus' linear branch.  Inference (H2, C, hi - lo, windows, gate_sigmoid,
+# temperature): both lerp forms and g = 0.5 itself, 1e-4 is clamped to 1e-3, four windows per block.
+POOL_TRAIN_CASES = [(32, 1, 1, -2.0), (96, 7, 3, 0.5), (128, 64, 128, 25.0), (224, 1, 3, 25.0), (256, 7, 128, -2.0), (32, 64, 3, 0.5),
+                    (96, 64, 1, 25.0), (224, 7, 1, 0.5), (256, 1, 128, 0.5), (128, 7, 3, -2.0)]
+POOL_INFER_CASES = [(32, 1, 1, 1, 0.3, 1.0), (96, 2, 3, 3, 0.5, 0.5), (128, 7, 31, 4, 0.7, 1e-4), (160, 64, 1, 5, 0.5, 1.0), (224, 2, 31, 1, 0.7, 0.5),
+                    (256, 7, 3, 4, 0.3, 1e-4), (32, 64, 31, 5, 0.7, 1.0), (96, 1, 3, 4, 0.3, 0.5), (160, 7, 1, 3, 0.3, 1e-4), (256, 64, 3, 1, 0.5, 0.5),
+                    (224, 64, 31, 3, 0.3, 1.0), (128, 2, 1, 5, 0.7, 1.0)]
+
+
+def pool_case(nw, H2, C, nc, seed, train, temp=0.75, gap=False):
+    """Operands of one pooling launch: hout in +-1 like an LSTM's output ([nw][T][H2] with T = nc + 3 and [lo, hi) = [1, nc + 1)
+    for training, hout_c = its rows [lo, hi)), w_att scaled by the temperature so that the scores' spread is about one - the
+    attention softmax is neither flat nor one-hot.  gap: row 0 of window 0 scores 150 above the rest (expf underflows to 0)."""
+    rng = np.random.default_rng(seed)
+    T, lo = (nc + 3, 1) if train else (nc, 0)
+    hi = lo + nc
+    hout = rng.uniform(-1, 1, (nw, T, H2)).astype(np.float32)
+    w_att = (rng.standard_normal(H2) * 1.5 * temp / math.sqrt(H2)).astype(np.float32)
+    if gap:
+        hout[0, lo] = (np.sign(w_att) * 150.0 * temp / np.abs(w_att).sum()).astype(np.float32)
+    return dict(hout=hout, hout_c=np.ascontiguousarray(hout[:, lo:hi]), lin=rng.standard_normal((nw, C)).astype(np.float32), w_att=w_att,
+                b_att=float(np.float32(0.125)), att_temp=float(np.float32(temp)), gate=0.25,
+                w_lin2=(rng.standard_normal((C, H2)) / math.sqrt(H2)).astype(np.float32), b_lin2=rng.standard_normal(C).astype(np.float32),
+                lo=lo, hi=hi, T=T)
