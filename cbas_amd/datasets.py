@@ -284,6 +284,32 @@ def plan_store(manifests: Sequence[list], in_features: int) -> StorePlan:
     return plan
 
 
+def plan_files(paths: Sequence[str], in_features: Optional[int] = None) -> StorePlan:
+    """``plan_store`` for a plain list of files (no manifest): their rows back to back in the order given, a path named twice
+    counted once.  ``in_features=None`` takes the width of the first readable file; a file of another width is a
+    ``ValueError`` that names it."""
+    plan = StorePlan()
+    plan.dim = 0 if in_features is None else int(in_features)
+    for path in dict.fromkeys(paths):
+        try:
+            with h5io.ClsReader(path) as r:
+                shape, half = tuple(r.shape), bool(r.is_half)
+        except Exception as e:  # noqa: BLE001
+            _warn_once(path, "open H5 file", e)
+            plan.unreadable.append(path)
+            continue
+        if len(shape) == 2 and plan.dim == 0:
+            plan.dim = int(shape[1])
+        if len(shape) != 2 or shape[1] != plan.dim:
+            raise ValueError(f"{path}: 'cls' has shape {shape}, but the other files hold rows of width {plan.dim} "
+                             f"(all files of one store must have the same row width)")
+        if not half:
+            plan.not_half.append(path)
+        plan.files[path] = (plan.total_rows, int(shape[0]))
+        plan.total_rows += int(shape[0])
+    return plan
+
+
 def manifest_windows(manifest: list, seq_len: int, files: Dict[str, Tuple[int, int]]):
     """Per manifest entry: the first row of its window in the store laid out by ``files`` (int64; -1 when its file has no
     rows or the window is not inside the file) and its label (int64; -1 with it)."""

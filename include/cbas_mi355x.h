@@ -357,6 +357,41 @@ int cbas_patch_kmeans_fit(const float* rows_dev, int n, int T, int n_prefix, int
 int cbas_patch_kmeans_assign(const float* rows_dev, int n, int T, int n_prefix, int D, int64_t ld, int k, int n_sets, int normalize,
                              const float* centroids_dev, int32_t* labels_dev, float* dist2_dev, void* stream);
 
+/* Cosine search over resident CLS rows: "where else does a frame like this one occur?" - every row scored against a few query
+ * vectors in one streaming pass, then the k best PEAKS of each query, so that a bout of near-identical neighbouring frames gives one
+ * result.  Beyond the reference, which has no search over features.  rows_f16_dev (n_rows, dim) fp16 with row stride ld (in halves),
+ * finite; queries_dev (n_queries, dim) fp32, contiguous, finite; clip_table_dev (n_clips, 2) int64 = (first row, rows) of every
+ * clip, cbas_labels_median's table; clips do not overlap, and a row outside every clip is never a candidate.  mask_dev, unless NULL:
+ * n_rows uint8, 0 = never return this row.  No atomics; every sum has the order stated: two calls give the same bytes, and a row's
+ * score does not depend on n_rows, on the slot or group of 16 its query sits in, on where the row lies, or on the device.
+ *   the score     trace_dev (n_queries, n_rows) fp32, all of it written: score[q][m] = fl(fl(dot(x_m, q) * rn_m) * rq_q), x = the
+ *                 row widened to fp32 (exact).  dot = chain0 + chain1: chain p is the fp32 fmaf chain, from 0, over the columns d
+ *                 with (d / 32) % 2 = p in ascending order of (d / 32, d % 8, (d % 32) / 8) (v_mfma_f32_16x16x4_f32: exact products).
+ *                 rn_m = fp32(1 / sqrt((double)s_m)), 0 when s_m = 0; s_m = (l0 + l1) + (l2 + l3) in fp32, l_j the fmaf chain, from 0,
+ *                 of x_d^2 over the columns d with (d % 32) / 8 = j, ascending.  rq_q = fp32(1 / sqrt(s)), 0 when s = 0, s the fp64 sum
+ *                 of q_d^2: 64 fma chains over d = l, l + 64, ... added by the xor tree 32, 16, .., 1.  A zero row or a zero query
+ *                 scores exactly 0.  |score - cosine| <= (2 dim + 8) 2^-24.
+ *   the peaks     row m of a clip is a peak of query q iff every row m' of the SAME clip with 0 < |m - m'| <= min_gap has
+ *                 score[m'] < score[m], or score[m'] == score[m] and m' > m.  min_gap = 0: every row is a peak (plain top-k).
+ *                 Masked rows take part in the comparison (a labelled bout suppresses its neighbours) and are never returned.  With
+ *                 use_threshold != 0 a result also has score >= threshold (fp32).  Two results of one clip are therefore more than
+ *                 min_gap rows apart.  This is a rule on the scores alone, not greedy suppression: whether a row is returned does not
+ *                 depend on k or on what else was returned.
+ *   the result    per query the k best unmasked peaks by (score descending, row ascending): index_dev (n_queries, k) int64, the
+ *                 row's index in rows_f16_dev, and score_dev (n_queries, k) fp32; fewer than k peaks: (-1, -inf) past the last.
+ * The workspace (cbas_rows_search_workspace_bytes, -1 for a refused shape) is scratch: about 4 n_rows bytes and
+ * 13 k n_queries n_rows / 1024 bytes of lists.  The clip table is checked on the device before anything is indexed with it and the
+ * flags are read back: THE CALL SYNCHRONISES `stream` once, before the scores are queued.
+ * CBAS_EINVAL with a message, nothing queued and no output written: dim % 32 != 0 or dim > 1536, ld < dim or ld % 8 != 0, rows,
+ * queries, trace or workspace not 16-byte aligned, n_rows < 1, n_queries outside 1 .. 64, k outside 1 .. 64, min_gap outside
+ * 0 .. 65535, n_clips < 1, a NULL pointer (mask_dev may be NULL), a workspace too small.  CBAS_EINVAL with a message, only the
+ * workspace written: a clip table entry outside the rows, or two entries that overlap. */
+int64_t cbas_rows_search_workspace_bytes(int64_t n_rows, int32_t n_queries, int32_t k);
+int cbas_rows_search(const uint16_t* rows_f16_dev, int64_t n_rows, int32_t dim, int64_t ld, const float* queries_dev, int32_t n_queries,
+                     const int64_t* clip_table_dev, int32_t n_clips, const uint8_t* mask_dev, int32_t min_gap, int32_t use_threshold,
+                     float threshold, int32_t k, float* trace_dev, int64_t* index_dev, float* score_dev, void* workspace_dev,
+                     int64_t workspace_bytes, void* stream);
+
 /* Host-streamed form (one iteration of encode_file's chunk loop).  `slot` in [0, CBAS_ENC_SLOTS):
  * submit copies the pixels host->HBM on the handle's copy stream (from pinned staging), encodes
  * on the compute stream and copies the CLS rows back; wait blocks until that slot is done and
