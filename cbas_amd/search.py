@@ -191,6 +191,13 @@ class FrameIndex:
             results.append(hits)
         return (results, trace) if return_trace else results
 
+    # ---- k-NN labels (cbas_amd/knn.py) -----------------------------------------------------------------------------------------
+    def knn_labels(self, bank, k: int = 20, temperature: float = 0.07, exclude: bool = False, class_weights=None, return_neighbours: bool = False):
+        """``knn.knn_labels(self, bank, ...)``: the (N, C) weighted k-NN probabilities of every row from a ``knn.LabelBank``."""
+        from . import knn as _knn
+        return _knn.knn_labels(self, bank, k=k, temperature=temperature, exclude=exclude, class_weights=class_weights,
+                               return_neighbours=return_neighbours)
+
 
 # ---- command line ---------------------------------------------------------------------------------------------------------------
 def parse_span(text: str, need_end: bool = False) -> Tuple[str, int, Optional[int]]:

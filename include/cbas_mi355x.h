@@ -392,6 +392,40 @@ int cbas_rows_search(const uint16_t* rows_f16_dev, int64_t n_rows, int32_t dim, 
                      float threshold, int32_t k, float* trace_dev, int64_t* index_dev, float* score_dev, void* workspace_dev,
                      int64_t workspace_bytes, void* stream);
 
+/* Weighted k-nearest-neighbour labels for resident CLS rows: "I have labelled a few hundred bouts; what does that say about every
+ * frame?" - the evaluation protocol of the self-supervised encoders (DINO, DINOv2, DINOv3).  Every store row takes its k most similar
+ * labelled rows by cosine and each votes for its label with weight exp(cos / T).  Beyond the reference, whose pre-labels need a trained
+ * head.  rows_f16_dev (N, D) fp16 with row stride ld (in halves); bank_f16_dev (M, D) fp16 with row stride bank_ld, the labelled rows;
+ * bank_label_dev (M) int32 in [0, C); bank_group_dev (M) and row_group_dev (N) int32, either may be NULL; class_weight_dev (C) fp32 or
+ * NULL = ones.  The (N, M) matrix of cosines is never in memory unless sims_dev asks for it (tests and small shapes).  No atomics.
+ *   the cosine    cos[m][j] = fl(fl(dot * rn_row[m]) * rn_bank[j]); dot = the fp32-accumulated sum of the exact products of the two
+ *                 fp16 rows on the fp16 matrix pipe (v_mfma_f32_16x16x32_f16), 32 columns an instruction in ascending order into one
+ *                 accumulator; rn = fp32(1 / sqrt((double)s)), 0 when s = 0, s the fp32 sum of cbas_rows_search: (l0 + l1) + (l2 + l3),
+ *                 l_j the fmaf chain, from 0, of x_d^2 over the columns d with (d % 32) / 8 = j, ascending.  A zero row scores exactly
+ *                 0 with everything.  |cos - cosine| <= (2 D + 8) 2^-24.  sims_dev (N, M), unless NULL, receives every pair's cosine,
+ *                 excluded ones included.
+ *   excluded      bank entry j for row m when both group arrays are given and bank_group[j] == row_group[m] >= 0 (leave one instance
+ *                 or one file out).
+ *   neighbours    the k best entries that are not excluded: a beats b when cos[a] > cos[b], or cos[a] == cos[b] and a < b.
+ *                 nn_index_dev (N, k) int32 and nn_score_dev (N, k) fp32, unless NULL, in that order; (-1, -inf) past the last.  A
+ *                 function of the cosine bits and the bank indices alone: not of N, of where a row lies, or of the grid.
+ *   the vote      s_0 = the best neighbour's score; w_r = fl(expf(fl(fl(s_r - s_0) / T)) * cw[label_r]); Z = the fp32 sum of w_r in
+ *                 ascending rank, num_c that of the neighbours with label c; probs_dev[m][c] = num_c / Z, (N, C) fp32.  A row
+ *                 without a neighbour gets zeros.
+ * The workspace (cbas_rows_knn_workspace_bytes, -1 for a refused shape) holds the reciprocal norms: about 4 (N + M) bytes.  The labels
+ * are checked on the device before one is used as an index and the flag is read back: THE CALL SYNCHRONISES `stream` once, before the
+ * pass is queued.  N = 0: nothing is done.
+ * CBAS_EINVAL with a message, nothing queued and no output written: D % 32 != 0 or D outside 32 .. 1536, ld or bank_ld < D or not a
+ * multiple of 8, M outside 1 .. 65536, k outside 1 .. 64, C outside 1 .. 64, a temperature that is not finite or not greater than 0,
+ * N < 0, rows, bank or workspace not 16-byte aligned, a NULL rows, bank, bank_label, probs or workspace, a workspace too small.
+ * CBAS_EINVAL with a message, only the workspace written: a label outside [0, C). */
+int64_t cbas_rows_knn_workspace_bytes(int64_t n_rows, int32_t n_bank, int32_t k);
+int cbas_rows_knn(const void* rows_f16_dev, int64_t n_rows, int32_t dim, int64_t ld, const void* bank_f16_dev, int32_t n_bank,
+                  int64_t bank_ld, const int32_t* bank_label_dev, const int32_t* bank_group_dev, const int32_t* row_group_dev,
+                  int32_t n_classes, const float* class_weight_dev, int32_t k, float temperature, float* probs_dev,
+                  int32_t* nn_index_dev, float* nn_score_dev, float* sims_dev, void* workspace_dev, int64_t workspace_bytes,
+                  void* stream);
+
 /* Host-streamed form (one iteration of encode_file's chunk loop).  `slot` in [0, CBAS_ENC_SLOTS):
  * submit copies the pixels host->HBM on the handle's copy stream (from pinned staging), encodes
  * on the compute stream and copies the CLS rows back; wait blocks until that slot is done and
