@@ -18,7 +18,7 @@
 //                 w_r in ascending rank; num_c = the fp32 sum of w_r over the neighbours with label c in ascending rank;
 //                 probs[m][c] = num_c / Z.  A row without a neighbour gets zeros.
 //
-//   rk_norm_kernel    rn of every store row and of every bank row: 4 lanes a row, lane j the chain l_j
+//   rows_rn_kernel    (rows_rn.h) rn of every store row and of every bank row: 4 lanes a row, lane j the chain l_j
 //   rk_label_kernel   a label outside [0, C) sets a flag, read back before the pass is queued
 //   rk_knn_kernel     THE PASS.  A workgroup owns RK_TILE = 128 store rows and walks the bank in blocks of RK_BLOCK = 64 entries;
 //                     both operands come through LDS in chunks of RK_KC = 64 columns, two buffers, the next chunk's global loads in
@@ -30,6 +30,7 @@
 //                     lists are put in order by rank placement and the same thread votes.  No atomics.
 #include "api_common.h"
 #include "kernels.h"
+#include "rows_rn.h"
 
 namespace {
 
@@ -41,27 +42,6 @@ constexpr int RK_LDA = RK_KC + 8;                    // halves between staged ro
 constexpr int RK_LDS = RK_BLOCK + 1;                 // floats between the rows of the block of cosines
 constexpr int RK_STAGE = (RK_TILE + RK_BLOCK) * RK_LDA;      // halves per staging buffer
 constexpr int RK_MAX_M = 65536, RK_MAX_K = 64, RK_MAX_C = 64, RK_MAX_D = 1536;
-
-// grid (ceil(4 n / 256)), 256 threads
-__global__ __launch_bounds__(RK_THREADS) void rk_norm_kernel(const uint16_t* __restrict__ x, int64_t n, int D, int64_t ld, float* __restrict__ rn) {
-    const int64_t gid = (int64_t)blockIdx.x * RK_THREADS + threadIdx.x, row = gid >> 2;
-    const int kr = (int)(gid & 3);
-    float ss = 0.f;
-    if (row < n) {
-        const uint16_t* const p = x + row * ld + 8 * kr;
-        for (int c = 0; c < (D >> 5); ++c) {
-            const f16x8 h = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(p + 32 * c));
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float v = (float)h[e];
-                ss = fmaf(v, v, ss);
-            }
-        }
-    }
-    ss += __shfl_xor(ss, 1, 64);                     // (l0 + l1) and (l2 + l3), then their sum: the same bits in all four
-    ss += __shfl_xor(ss, 2, 64);
-    if (row < n && kr == 0) rn[row] = ss > 0.f ? (float)(1.0 / sqrt((double)ss)) : 0.f;
-}
 
 __global__ __launch_bounds__(RK_THREADS) void rk_label_kernel(const int32_t* __restrict__ label, int M, int C, unsigned* __restrict__ flags) {
     const int j = blockIdx.x * RK_THREADS + threadIdx.x;
@@ -368,9 +348,9 @@ extern "C" int cbas_rows_knn(const void* rows_f16_dev, int64_t N, int32_t D, int
     // the labels, before anything is indexed with one; the reciprocal norms meanwhile
     HIP_TRY(hipMemsetAsync(flags, 0, 16, st));
     hipLaunchKernelGGL(rk_label_kernel, dim3((M + RK_THREADS - 1) / RK_THREADS), wg, 0, st, bank_label_dev, M, C, flags);
-    hipLaunchKernelGGL(rk_norm_kernel, dim3((unsigned)(((int64_t)M * 4 + RK_THREADS - 1) / RK_THREADS)), wg, 0, st, (const uint16_t*)bank_f16_dev,
+    hipLaunchKernelGGL(rows_rn_kernel, dim3((unsigned)(((int64_t)M * 4 + RK_THREADS - 1) / RK_THREADS)), wg, 0, st, (const uint16_t*)bank_f16_dev,
                        (int64_t)M, D, bank_ld, rn_bank);
-    hipLaunchKernelGGL(rk_norm_kernel, dim3((unsigned)((N * 4 + RK_THREADS - 1) / RK_THREADS)), wg, 0, st, (const uint16_t*)rows_f16_dev, N, D, ld,
+    hipLaunchKernelGGL(rows_rn_kernel, dim3((unsigned)((N * 4 + RK_THREADS - 1) / RK_THREADS)), wg, 0, st, (const uint16_t*)rows_f16_dev, N, D, ld,
                        rn_rows);
     HIP_TRY(hipGetLastError());
     unsigned bad = 0u;

@@ -24,6 +24,7 @@
 // score, or an equal score and a lower row); rows are distinct, so the ranks are too.  No atomics anywhere.
 #include "api_common.h"
 #include "kernels.h"
+#include "rows_rn.h"
 
 namespace {
 
@@ -108,7 +109,7 @@ __global__ __launch_bounds__(RS_THREADS) void rs_score_kernel(const uint16_t* __
         }
         ss += __shfl_xor(ss, 16, 64);                            // (l0 + l1) and (l2 + l3), then their sum: the same bits in all four
         ss += __shfl_xor(ss, 32, 64);
-        const float rn = ss > 0.f ? (float)(1.0 / sqrt((double)ss)) : 0.f;
+        const float rn = rows_rn(ss);
         // acc[e]: row 4 kr + e of the tile against query fc; that row's rn sits in lane 4 kr + e
 #pragma unroll
         for (int e = 0; e < 4; ++e) {

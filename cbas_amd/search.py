@@ -198,6 +198,12 @@ class FrameIndex:
         return _knn.knn_labels(self, bank, k=k, temperature=temperature, exclude=exclude, class_weights=class_weights,
                                return_neighbours=return_neighbours)
 
+    # ---- motifs (cbas_amd/motifs.py) -------------------------------------------------------------------------------------------
+    def cluster(self, n_clusters: int = 16, iters: int = 20, normalize: bool = True, init=None, clusters=None):
+        """``motifs.cluster_frames(self, ...)``: ``(labels, dist2, clusters)``, every row's k-means motif."""
+        from . import motifs as _motifs
+        return _motifs.cluster_frames(self, n_clusters=n_clusters, iters=iters, normalize=normalize, init=init, clusters=clusters)
+
 
 # ---- command line ---------------------------------------------------------------------------------------------------------------
 def parse_span(text: str, need_end: bool = False) -> Tuple[str, int, Optional[int]]:

@@ -426,6 +426,56 @@ int cbas_rows_knn(const void* rows_f16_dev, int64_t n_rows, int32_t dim, int64_t
                   int32_t* nn_index_dev, float* nn_score_dev, float* sims_dev, void* workspace_dev, int64_t workspace_bytes,
                   void* stream);
 
+/* k-means over resident CLS rows: "what behaviours are in these recordings at all?" - every frame of the store grouped into k motifs
+ * before anything is labelled.  Beyond the reference, which has no unsupervised grouping.  rows_f16_dev (n_rows, dim) fp16 with row
+ * stride ld (in halves), finite; centroids (k, dim) fp32, contiguous.  The definition is cbas_patch_kmeans_fit's with the sums of
+ * this family; every sum below has the order stated, a function of (n_rows, dim, k) alone - not of the grid, the device or the
+ * stream - and none uses an atomic: two calls give the same bytes.
+ *   the working row   u = x widened to fp32 (normalize = 0), or u = fl(x * rn) (normalize = 1), rn cbas_rows_search's: rn = fp32(1 /
+ *                     sqrt((double)s)), 0 when s = 0, s = (l0 + l1) + (l2 + l3) in fp32, l_j the fmaf chain, from 0, of x_d^2 over the
+ *                     columns d with (d % 32) / 8 = j, ascending.  No normalised copy is written.
+ *   start             farthest-point seeding, unless init_centroids_dev (k, dim) is given (then init_index_dev is -1 everywhere).
+ *                     mean = the column mean of u: per SEGMENT of CBAS_ROWS_KMEANS_SEGMENT rows one fp32 sum per column in ascending
+ *                     row order, the segments added in ascending order, / (float)n_rows.  d(m, t) = sum_d (u_md - t_d)^2: 64 fmaf
+ *                     chains, chain l over the columns d with (d / 8) % 64 = l in ascending order, added by the xor tree 32, 16, .., 1.
+ *                     Seed 0 = the row of largest d(m, mean); seed j = the row of largest min_{i < j} d(m, seed i); ties to the
+ *                     lowest row.  init_index_dev (k) int64: the rows chosen, in this order.  Seed centroids are u rows.
+ *   a round           every row goes to the centroid of largest score_j = fmaf(rn, x . c_j, -h_j) (rn = 1 without normalize); ties
+ *                     to the lowest j.  x . c_j = chain0 + chain1, cbas_rows_search's dot: chain p is the fp32 fmaf chain, from 0, over
+ *                     the columns d with (d / 32) % 2 = p in ascending order of (d / 32, d % 8, (d % 32) / 8) (v_mfma_f32_16x16x4_f32:
+ *                     exact products).  h_j = 0.5 * |c_j|^2, |c_j|^2 one fp32 fmaf chain, from 0, over d ascending.
+ *                     dist2 = max(0, fmaf(-2, score, |u|^2)), |u|^2 = s, or 1 (0 for a zero row) when normalize = 1.
+ *                     New centroid j = (sum of u over its rows) / (float)count_j: per segment one fp32 sum per element in ascending
+ *                     row order, the segments added in ascending order, one division.  A centroid without rows keeps its value.
+ *                     Exactly `iters` rounds: no tolerance, no host synchronisation.
+ *   finish            one more assignment against the final centroids gives the counts; the clusters are then numbered by descending
+ *                     count, ties by seeding order: centroids_dev (k, dim), counts_dev (k) int64.  labels_dev (n_rows) int32 and
+ *                     dist2_dev (n_rows), unless NULL, are that assignment in the output numbering.  They have the bytes of
+ *                     cbas_rows_kmeans_assign against centroids_dev, except for a row whose two best scores are EQUAL in fp32: it keeps
+ *                     the cluster of the lower seeding position (the one that was counted), which _assign gives only when that cluster
+ *                     also has the lower output number.
+ *   inertia_dev       (iters + 1): inertia[t] = the sum of dist2 (per segment one fp32 sum in ascending row order, the segments in
+ *                     ascending order) of the assignment against the centroids after t updates.
+ * The workspace (cbas_rows_kmeans_workspace_bytes, -1 for a refused shape; 16-byte aligned) takes, each part rounded up to 16 bytes,
+ *   4 k dim + 512 + 4 dim + 16 n_rows + 12 ceil(n_rows / 64) + (4 k dim + 260) ceil(n_rows / CBAS_ROWS_KMEANS_SEGMENT)  bytes:
+ * O(n_rows) plus one (k, dim) block of partial sums per segment.  On return it holds, first, the final centroids in SEEDING order,
+ * k * dim floats, then 64 int32: order[r] = the seeding position of output cluster r (-1 past k) - what a caller passes as
+ * init_centroids_dev to continue the fit.
+ * cbas_rows_kmeans_assign: the round's assignment against given centroids: labels_dev (n_rows) int32 and, unless NULL, dist2_dev.  A
+ * row's label and dist2 do not depend on n_rows or on where the row lies in the call; n_rows may be less than k.
+ * CBAS_EINVAL with a message, nothing queued and no output written: k outside 2 .. 64 or (fit) k > n_rows, dim % 32 != 0 or dim
+ * outside 32 .. 1536, ld < dim or ld % 8 != 0, n_rows < 1, iters < 0 (0 returns the start), normalize not 0 or 1, rows, centroids or
+ * workspace not 16-byte aligned, a NULL pointer (init_centroids_dev, labels_dev of fit and dist2_dev may be NULL), a workspace too
+ * small. */
+#define CBAS_ROWS_KMEANS_SEGMENT 4096
+int64_t cbas_rows_kmeans_workspace_bytes(int64_t n_rows, int32_t dim, int32_t k);
+int cbas_rows_kmeans_fit(const void* rows_f16_dev, int64_t n_rows, int32_t dim, int64_t ld, int32_t k, int32_t iters, int32_t normalize,
+                         const float* init_centroids_dev, float* centroids_dev, int64_t* counts_dev, float* inertia_dev,
+                         int64_t* init_index_dev, int32_t* labels_dev, float* dist2_dev, void* workspace_dev, int64_t workspace_bytes,
+                         void* stream);
+int cbas_rows_kmeans_assign(const void* rows_f16_dev, int64_t n_rows, int32_t dim, int64_t ld, int32_t k, int32_t normalize,
+                            const float* centroids_dev, int32_t* labels_dev, float* dist2_dev, void* stream);
+
 /* Host-streamed form (one iteration of encode_file's chunk loop).  `slot` in [0, CBAS_ENC_SLOTS):
  * submit copies the pixels host->HBM on the handle's copy stream (from pinned staging), encodes
  * on the compute stream and copies the CLS rows back; wait blocks until that slot is done and
