@@ -188,6 +188,8 @@ DEBUG_SIGNATURES = {
     "cbas_debug_rows_run": (c_int, [c_void_p]),
     "cbas_debug_head_run": (c_int, [c_void_p]),
     "cbas_debug_head_seq_run": (c_int, [c_void_p]),
+    "cbas_debug_head_expand_run": (c_int, [c_void_p]),
+    "cbas_debug_build_temporal": (c_int, [c_int, c_float, c_int, c_int, c_void_p, c_void_p]),
     "cbas_debug_build": (c_int, []),
     "cbas_debug_pos_interp_matrix": (c_int, [c_int, c_int, c_int, c_void_p]),
     "cbas_debug_pos_table": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),

@@ -1390,3 +1390,110 @@ extern "C" int cbas_debug_head_seq_run(const cbas_debug_head_seq_args* a) {
         if (dout[i]) HIP_TRY(hipMemcpy(a->out[i], dout[i], (size_t)a->out_bytes[i], hipMemcpyDeviceToHost));
     return CBAS_OK;
 }
+
+// ---- tests: one launch of a classifier-head expand kernel (inference, training forward, training backward) on host operands ----
+extern "C" int cbas_debug_build_temporal(int T, float alpha, int lo, int hi, float* tmat, float* lin_vec) {
+    if (T < 3 || T > 101 || !(0 <= lo && lo < hi && hi <= T) || !tmat || !lin_vec)
+        return cbas_fail(CBAS_EINVAL, "cbas_debug_build_temporal: T = %d (3 .. 101), [lo, hi) = [%d, %d), or a NULL image", T, lo, hi);
+    head_build_temporal(T, (double)alpha, lo, hi, tmat, lin_vec);      // the widening api_head_train.hip's trainer_init applies
+    return CBAS_OK;
+}
+
+extern "C" int cbas_debug_head_expand_run(const cbas_debug_head_expand_args* a) {
+    if (!a || a->struct_bytes != (int64_t)sizeof(cbas_debug_head_expand_args))
+        return cbas_fail(CBAS_EINVAL, "cbas_debug_head_expand_args: struct_bytes %lld, library expects %lld", a ? (long long)a->struct_bytes : -1ll,
+                         (long long)sizeof(cbas_debug_head_expand_args));
+    constexpr int NI = 9, NO = 3;
+    constexpr int64_t BIG = (int64_t)1 << 40;
+    const int op = a->op, T = a->T, Bn = a->Bn, NS = a->NS, Cn = a->C, NP = a->NPROJ, lo = a->lo, hi = a->hi;
+    const int64_t nw = a->n_windows;
+    if (op < CBAS_DEBUG_EXPAND_INFER || op > CBAS_DEBUG_EXPAND_TRAIN_BWD) return cbas_fail(CBAS_EINVAL, "op %d", op);
+    const bool infer = op == CBAS_DEBUG_EXPAND_INFER, bwd = op == CBAS_DEBUG_EXPAND_TRAIN_BWD;
+    const bool sliding = infer && a->sliding != 0;
+    // everything the launchers do not check, before anything is allocated: a refusal must not become a launch
+    if (nw < 1 || nw > (1 << 16)) return cbas_fail(CBAS_EINVAL, "n_windows = %lld: 1 .. 65536", (long long)nw);
+    if (T < 3 || T > 101) return cbas_fail(CBAS_EINVAL, "T = %d: the expand kernels serve windows of 3 .. 101 positions", T);
+    if (Bn < 64 || Bn > 256 || Bn % 64) return cbas_fail(CBAS_EINVAL, "Bn = %d: a multiple of 64 in 64 .. 256", Bn);
+    if (NS != 2 && NS != 3) return cbas_fail(CBAS_EINVAL, "NS = %d: 2 or 3 bottleneck streams", NS);
+    const int F = NS * Bn;
+    if (Cn < 1 || Cn > 64 || Cn > F) return cbas_fail(CBAS_EINVAL, "C = %d: 1 .. 64 classes, at most NS Bn", Cn);
+    if (NP < F + Cn || NP % 4 || NP > (1 << 16))
+        return cbas_fail(CBAS_EINVAL, "NPROJ = %d: a multiple of 4, at least NS Bn + C = %d", NP, F + Cn);
+    if (bwd && NP - F > F) return cbas_fail(CBAS_EINVAL, "NPROJ = %d: the backward's block of %d threads writes at most that many columns past NS Bn", NP, F);
+    if (infer && !(0 <= lo && lo < hi && hi <= T))
+        return cbas_fail(CBAS_EINVAL, "centre range [lo, hi) = [%d, %d) of T = %d: 0 <= lo < hi <= T", lo, hi, T);
+    if (infer ? (size_t)T * F * sizeof(float) > 160 * 1024 : train_expand_lds_bytes(T, Bn, NP) > 160 * 1024)
+        return cbas_fail(CBAS_EINVAL, "LDS: T = %d, Bn = %d, NS = %d, NPROJ = %d needs more than 160 KiB", T, Bn, NS, NP);
+    if (!infer && a->thr >= (1u << 24)) return cbas_fail(CBAS_EINVAL, "thr = %u: a 24-bit threshold (below 2^24)", a->thr);
+    // bytes the launch reads (in) and writes (out)
+    int64_t in_need[NI] = {}, out_need[NO] = {};
+    const int64_t rows = nw * T;
+    if (infer) {
+        int64_t proj_rows = rows;
+        if (sliding) {
+            const int64_t nf = a->n_frames, w0 = a->w0, r0 = a->r0;
+            if (nf < 1 || nf > BIG) return cbas_fail(CBAS_EINVAL, "sliding: n_frames = %lld: at least 1", (long long)nf);
+            if (w0 < -BIG || w0 > BIG || r0 < -BIG || r0 > BIG) return cbas_fail(CBAS_EINVAL, "sliding: w0 = %lld or r0 = %lld out of range", (long long)w0, (long long)r0);
+            // row_of(w, t) = clamp(w0 + w + t - T / 2, 0, n_frames - 1) - r0 is monotone in w + t: its extremes sit at the corners
+            const auto clampf = [&](int64_t f) { return f < 0 ? 0 : (f > nf - 1 ? nf - 1 : f); };
+            const int64_t rmin = clampf(w0 - T / 2) - r0, rmax = clampf(w0 + (nw - 1) + (T - 1) - T / 2) - r0;
+            const int64_t have = a->in[0] ? a->in_bytes[0] / ((int64_t)NP * 4) : 0;
+            if (rmin < 0 || rmax >= have)
+                return cbas_fail(CBAS_EINVAL, "sliding: the windows read proj rows %lld .. %lld, the image holds rows 0 .. %lld (in[0] NULL or too small)",
+                                 (long long)rmin, (long long)rmax, (long long)have - 1);
+            proj_rows = rmax + 1;
+        }
+        in_need[0] = proj_rows * NP * 4; in_need[1] = in_need[2] = in_need[3] = (int64_t)F * 4; in_need[4] = (int64_t)Cn * 4;
+        out_need[0] = rows * F * 4; out_need[1] = nw * Cn * 4;
+    } else if (!bwd) {
+        in_need[0] = rows * NP * 4; in_need[1] = in_need[2] = in_need[3] = (int64_t)F * 4; in_need[4] = (int64_t)Cn * 4;
+        in_need[5] = (int64_t)3 * T * T * 4; in_need[6] = (int64_t)T * 4;
+        out_need[0] = out_need[1] = rows * F * 4; out_need[2] = nw * Cn * 4;
+    } else {
+        in_need[0] = rows * F * 4; in_need[2] = (int64_t)F * 4; in_need[5] = (int64_t)3 * T * T * 4; in_need[6] = (int64_t)T * 4;
+        in_need[7] = rows * F * 4; in_need[8] = nw * Cn * 4;
+        out_need[0] = rows * NP * 4; out_need[1] = nw * 3 * F * 4;
+    }
+    for (int i = 0; i < NI; ++i)
+        if (in_need[i] && (!a->in[i] || a->in_bytes[i] < in_need[i]))
+            return cbas_fail(CBAS_EINVAL, "op %d: in[%d] is missing (NULL) or too small (%lld of %lld bytes)", op, i, (long long)a->in_bytes[i],
+                             (long long)in_need[i]);
+    for (int i = 0; i < NO; ++i)
+        if (out_need[i] && (!a->out[i] || a->out_bytes[i] < out_need[i]))
+            return cbas_fail(CBAS_EINVAL, "op %d: out[%d] is missing (NULL) or too small (%lld of %lld bytes)", op, i, (long long)a->out_bytes[i],
+                             (long long)out_need[i]);
+    DevBufs B;
+    char* din[NI] = {};
+    char* dout[NO] = {};
+    for (int i = 0; i < NI; ++i)
+        if (in_need[i]) {
+            HIP_TRY(B.alloc(&din[i], (size_t)a->in_bytes[i]));
+            HIP_TRY(hipMemcpy(din[i], a->in[i], (size_t)a->in_bytes[i], hipMemcpyHostToDevice));
+        }
+    for (int i = 0; i < NO; ++i)
+        if (out_need[i]) {
+            HIP_TRY(B.alloc(&dout[i], (size_t)a->out_bytes[i]));
+            HIP_TRY(hipMemcpy(dout[i], a->out[i], (size_t)a->out_bytes[i], hipMemcpyHostToDevice));
+        }
+    const auto fin = [&](int i) { return reinterpret_cast<const float*>(din[i]); };
+    const auto fout = [&](int i) { return reinterpret_cast<float*>(dout[i]); };
+    int rc = -1;
+    if (infer) {
+        HeadDims d{};
+        d.C = Cn; d.T = T; d.Bn = Bn; d.NS = NS; d.lo = lo; d.hi = hi; d.NPROJ = NP; d.alpha = a->alpha;
+        rc = launch_head_expand(fin(0), d, fin(1), fin(2), fin(3), fin(4), nw, sliding ? 1 : 0, a->w0, a->r0, a->n_frames, fout(0), fout(1), 0);
+    } else {
+        TrainExpandParams p{};
+        p.proj = bwd ? nullptr : fin(0); p.tmat = fin(5); p.lin_vec = fin(6); p.b_bott = fin(1); p.ln_w = fin(2); p.ln_b = fin(3); p.b_lin1 = fin(4);
+        p.T = T; p.Bn = Bn; p.NPROJ = NP; p.C = Cn; p.NS = NS;
+        for (int k = 0; k < 3; ++k) p.key[k] = a->key[k];
+        p.thr = a->thr; p.scale = a->scale;
+        rc = bwd ? launch_train_expand_bwd(p, nw, fin(0), fin(7), fin(8), fout(0), fout(1), 0)
+                 : launch_train_expand_fwd(p, nw, fout(0), fout(1), fout(2), 0);
+    }
+    if (rc) return cbas_fail(CBAS_EINVAL, "head expand kernel launch failed (op %d: rc=%d)", op, rc);
+    HIP_TRY(hipDeviceSynchronize());
+    for (int i = 0; i < NO; ++i)
+        if (dout[i]) HIP_TRY(hipMemcpy(a->out[i], dout[i], (size_t)a->out_bytes[i], hipMemcpyDeviceToHost));
+    return CBAS_OK;
+}

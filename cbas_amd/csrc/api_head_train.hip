@@ -213,6 +213,14 @@ int trainer_init(cbas_head_trainer* t, const float* weights_host, const float* c
 
 }  // namespace
 
+// build_temporal for the debug harness (kernels.h): tmat [3][T][T] and lin_vec [T] as a trainer of this shape uploads them
+void head_build_temporal(int T, double alpha, int lo, int hi, float* tmat, float* lin_vec) {
+    std::vector<float> tm, lv;
+    build_temporal(T, alpha, lo, hi, tm, lv);
+    memcpy(tmat, tm.data(), tm.size() * sizeof(float));
+    memcpy(lin_vec, lv.data(), lv.size() * sizeof(float));
+}
+
 extern "C" void cbas_head_train_destroy(cbas_head_trainer* t) {
     if (!t) return;
     (void)hipSetDevice(t->device);

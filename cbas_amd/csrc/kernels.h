@@ -352,6 +352,8 @@ struct TrainPoolParams {
 // dst [cols][rows_pad] = src^T, columns rows..rows_pad zero-filled
 int launch_transpose_pad(const float* src, int64_t rows, int cols, int64_t ld, float* dst, int64_t rows_pad, hipStream_t st);
 size_t train_expand_lds_bytes(int T, int Bn, int NPROJ);     // dynamic LDS the expand kernels need (<= 160 KiB)
+// host (api_head_train.hip): the temporal operators a trainer uploads, tmat [3][T][T] and lin_vec [T]; T >= 3, 0 <= lo < hi <= T
+void head_build_temporal(int T, double alpha, int lo, int hi, float* tmat, float* lin_vec);
 int launch_train_expand_fwd(const TrainExpandParams& p, int64_t n_windows, float* Y, float* aug, float* lin_logits, hipStream_t st);
 int launch_train_expand_bwd(const TrainExpandParams& p, int64_t n_windows, const float* Y, const float* daug, const float* dlin,
                             float* dproj, float* part, hipStream_t st);

@@ -323,6 +323,45 @@ typedef struct cbas_debug_head_seq_args {
 } cbas_debug_head_seq_args;
 int cbas_debug_head_seq_run(const cbas_debug_head_seq_args* a);
 
+/* Tests: ONE launch of a classifier-head expand kernel on host operands (tests/test_gpu_head_expand_reference.py compares it with
+ * the float64 references of oracle/kernel_ref.py), handled like cbas_debug_head_seq_run: every in[] image and the caller's
+ * pre-filled out[] images are uploaded whole, one launcher runs on the default stream, every out[] image is copied back whole.
+ *   op          launcher                 in[]                                                          out[]
+ *   INFER       launch_head_expand       0 proj [rows][NPROJ], 1 b_bott, 2 ln_w, 3 ln_b [NS Bn],        aug [w][T][NS Bn], lin_logits [w][C]
+ *                                        4 b_lin1 [C]
+ *   TRAIN_FWD   launch_train_expand_fwd  0 .. 4 as above (proj [w][T][NPROJ]), 5 tmat [3][T][T],        Y, aug [w][T][NS Bn], lin_logits [w][C]
+ *                                        6 lin_vec [T]
+ *   TRAIN_BWD   launch_train_expand_bwd  0 Y [w][T][NS Bn], 2 ln_w, 5 tmat, 6 lin_vec,                  dproj [w][T][NPROJ], part [w][3 NS Bn]
+ *                                        7 daug [w][T][NS Bn], 8 dlin [w][C]
+ * INFER without `sliding` reads proj row w T + t; with it, row clamp(w0 + w + t - T / 2, 0, n_frames - 1) - r0.
+ * It refuses (CBAS_EINVAL, nothing allocated or launched): n_windows < 1; T outside 3 .. 101; Bn not 64, 128, 192 or 256; NS not
+ * 2 or 3; C outside 1 .. 64; NPROJ below NS Bn + C or not a multiple of 4, TRAIN_BWD also NPROJ - NS Bn above the block's NS Bn
+ * threads; INFER without 0 <= lo < hi <= T; a shape whose LDS need exceeds 160 KiB (INFER: T NS Bn floats; training:
+ * train_expand_lds_bytes); training with thr >= 2^24; sliding with n_frames < 1 or with a clamped row outside the proj image;
+ * a NULL image the op reads or writes, or one smaller than that.
+ * cbas_debug_build_temporal (host only): tmat [3][T][T] and lin_vec [T] as a trainer with this T, ema_alpha and centre window
+ * builds them (api_head_train.hip build_temporal); T in 3 .. 101, 0 <= lo < hi <= T. */
+enum { CBAS_DEBUG_EXPAND_INFER = 0, CBAS_DEBUG_EXPAND_TRAIN_FWD = 1, CBAS_DEBUG_EXPAND_TRAIN_BWD = 2 };
+typedef struct cbas_debug_head_expand_args {
+    int64_t struct_bytes;        /* sizeof(cbas_debug_head_expand_args): a mismatch is rejected */
+    int op;
+    int T, Bn, NS, C, NPROJ;
+    int lo, hi;                  /* INFER: the linear branch's centre window */
+    int sliding;                 /* INFER */
+    float alpha;                 /* INFER: the EMA weight */
+    float scale;                 /* training: 1 / (1 - p) */
+    uint32_t thr;                /* training: keep <=> top 24 hash bits >= thr */
+    int64_t n_windows;
+    int64_t w0, r0, n_frames;    /* INFER, sliding */
+    uint64_t key[3];             /* training: the three streams' dropout keys */
+    const void* in[9];
+    int64_t in_bytes[9];
+    void* out[3];                /* in / out */
+    int64_t out_bytes[3];
+} cbas_debug_head_expand_args;
+int cbas_debug_head_expand_run(const cbas_debug_head_expand_args* a);
+int cbas_debug_build_temporal(int T, float alpha, int lo, int hi, float* tmat, float* lin_vec);
+
 /* Root-cause probe (round 5): run a kernel from a separately built code object IN PLACE of the library's head_expand_kernel
  * on this handle (same grid, block, dynamic LDS and arguments: scripts/probes/expand_r4/expand_r4.hip has the signature).
  * hsaco_path = NULL restores the library's kernel.  scripts/expand_rootcause.py builds instruction-level variants of the

@@ -4,7 +4,9 @@ producers), and element-wise error bounds derived from where each kernel rounds.
 
 Used by tests/test_gpu_kernel_reference.py (the kernels through cbas_debug_gemm_run / cbas_debug_attention_run),
 tests/test_gpu_rows_reference.py (cbas_debug_rows_run), tests/test_gpu_head_kernels_reference.py (the classifier head's
-exact-fp32 GEMM and small training kernels through cbas_debug_head_run) and tests/test_kernel_reference_bounds.py (the
+exact-fp32 GEMM and small training kernels through cbas_debug_head_run), tests/test_gpu_head_seq_reference.py and
+tests/test_gpu_head_expand_reference.py (the head's sequential and expand kernels through cbas_debug_head_seq_run /
+cbas_debug_head_expand_run) and tests/test_kernel_reference_bounds.py (the
 references and bounds themselves, on the CPU).
 
 Units: u32 = 2^-24 (fp32 unit roundoff), u16 = 2^-11 (fp16).  A bound is a float64 array shaped like the output; a kernel
@@ -1302,3 +1304,344 @@ def pool_case(nw, H2, C, nc, seed, train, temp=0.75, gap=False):
                 b_att=float(np.float32(0.125)), att_temp=float(np.float32(temp)), gate=0.25,
                 w_lin2=(rng.standard_normal((C, H2)) / math.sqrt(H2)).astype(np.float32), b_lin2=rng.standard_normal(C).astype(np.float32),
                 lo=lo, hi=hi, T=T)
+
+
+# ---- classifier head: the expand kernels (head_expand, train_expand_fwd, train_expand_bwd) -----------------------------------
+# Used by tests/test_gpu_head_expand_reference.py through cbas_debug_head_expand_run.  Written from classifier_head.py's
+# definition on the PROJECTED rows (the bottleneck Linears and lin1 commute with the EMA and the zero-sum stencils): stream k
+# of window w is Op_k(P[w][:, k Bn : (k + 1) Bn]) + b_bott, GELU, dropout, LayerNorm(Bn); the linear branch is the mean over
+# [lo, hi) of EMA(P[w][:, F : F + C]) + b_lin1.  Bounds are sums of the terms named beside each line, in u1 = 1.01 u32 like the
+# section above; the LayerNorm terms are ln_ref's (ln_stats_ref returns its intermediate quantities for the backward).
+EXPAND_EPS = 1e-5
+EXPAND_T_MAX = 101
+EXPAND_SLACK = 1.0 + 2.0 ** -10      # second-order terms of the backward's products of bounds
+
+
+def expand_temporal_ref(T, alpha, lo, hi):
+    """_calculate_robust_deltas as matrices over the window's positions, float64: E (the EMA: x_smooth = E x), D (dx[:, 1:]) and
+    A (ddx) on the reflect-padded [s2, s1 | s0, s1, ..], and the centre mean of E's rows [lo, hi).  alpha is the fp32 value."""
+    a = float(np.float32(alpha))
+    t = np.arange(T)[:, None]
+    s = np.arange(T)[None, :]
+    E = np.where(s <= t, np.where(s == 0, 1.0, a) * (1.0 - a) ** np.maximum(t - s, 0), 0.0)
+    pad = np.concatenate([E[[2, 1]], E], 0)                  # F.pad(.., (2, 0), 'reflect')
+    dx = pad[1:] - pad[:-1]
+    ddx = dx[1:] - dx[:-1]
+    return E, dx[1:], ddx, E[lo:hi].mean(0)
+
+
+def expand_lds_bytes(T, Bn, NPROJ, fwd, big):
+    """head_train_kernels.hip expand_lds."""
+    if big:
+        return (T * 3 * Bn + 12 * T) * 4
+    return (T * NPROJ + 3 * T * T + T * 3 * Bn) * 4 if fwd else (3 * T * T + T * 3 * Bn + 12 * T) * 4
+
+
+def expand_is_big(T, Bn, NPROJ):
+    return max(expand_lds_bytes(T, Bn, NPROJ, True, False), expand_lds_bytes(T, Bn, NPROJ, False, False)) > 160 * 1024
+
+
+def expand_rows(nw, T, sliding, w0=0, r0=0, n_frames=0):
+    """proj row of (w, t): w T + t, or in sliding mode clamp(w0 + w + t - T // 2, 0, n_frames - 1) - r0."""
+    if not sliding:
+        return np.arange(nw * T, dtype=np.int64).reshape(nw, T)
+    f = w0 + np.arange(nw, dtype=np.int64)[:, None] + np.arange(T, dtype=np.int64)[None, :] - T // 2
+    return np.clip(f, 0, n_frames - 1) - r0
+
+
+def _ema64(x, a):
+    """s_0 = x_0, s_t = s_{t-1} + a (x_t - s_{t-1}) along axis 1 in float64, and the bound of the fp32 recurrence in EITHER form
+    (e0 + a * (x - e0) with the product rounded, or contracted into one fma): the difference and the product round once each
+    (2 u1 a |x - s|, the contracted form only the first), the sum once (u1 |s_t|), and the step's incoming error is carried
+    through (1 - a); (1 + 4 u1) covers the roundings of the error itself."""
+    s = np.empty_like(x)
+    E = np.zeros_like(x)
+    s[:, 0] = x[:, 0]
+    for t in range(1, x.shape[1]):
+        d = x[:, t] - s[:, t - 1]
+        s[:, t] = s[:, t - 1] + a * d
+        E[:, t] = ((1.0 - a) * E[:, t - 1] + U1 * (2.0 * a * np.abs(d) + np.abs(s[:, t]))) * (1.0 + 4.0 * U1)
+    return s, E
+
+
+def expand_infer_ref(X, alpha, b_bott, ln_w, ln_b, b_lin1, Bn, NS, C, lo, hi):
+    """head_expand on the gathered rows X [w][T][>= NS Bn + C]: (aug [w][T][NS Bn], lin_logits [w][C]) and their bounds.
+      EMA      _ema64 (both lerp forms)
+      d1, d2   differences of the rounded EMA values a, b, c = s_t, s_|t-1|, s_|t-2| (the reflect padding): each subtraction
+               carries its operands' bounds and rounds once (it is exact only where Sterbenz' lemma applies)
+      + bias   u1 |pre|;  gelu_erf: GELU_SLOPE E_pre + ERF_BF_U u32 (|pre| + |g|) + u32 |g| (head_gemm_gelu_ref's terms)
+      LN       ln_ref over Bn with that input error (per + 5 <= ln_levels(Bn) additions per value)
+      lin      the EMA of the lin1 columns, hi - lo sequential additions, a division, + b_lin1"""
+    X = _wide(X)
+    a = float(np.float32(alpha))
+    nw, T = X.shape[:2]
+    F = NS * Bn
+    s, Es = _ema64(X[:, :, :F], a)
+    i1, i2 = np.abs(np.arange(T) - 1), np.abs(np.arange(T) - 2)
+    b, Eb, c, Ec = s[:, i1], Es[:, i1], s[:, i2], Es[:, i2]
+    d1 = s - b
+    E1 = Es + Eb + U1 * np.abs(d1)
+    bc = b - c
+    Ebc = Eb + Ec + U1 * np.abs(bc)
+    d2 = d1 - bc
+    E2 = E1 + Ebc + U1 * np.abs(d2)
+    k = (np.arange(F) // Bn)[None, None, :]
+    v = np.where(k == 0, s, np.where(k == 1, d1, d2))
+    Ev = np.where(k == 0, Es, np.where(k == 1, E1, E2))
+    pre = v + _wide(b_bott)
+    Epre = Ev * (1.0 + U1) + U1 * np.abs(pre)
+    g = gelu64(pre)
+    Eg = GELU_SLOPE * Epre + ERF_BF_U * U32 * (np.abs(pre) + Epre + np.abs(g)) + U32 * np.abs(g) + 2.0 ** -149
+    aug, Eaug = ln_ref(g.reshape(nw, T, NS, Bn), _wide(ln_w).reshape(NS, Bn), _wide(ln_b).reshape(NS, Bn), EXPAND_EPS, Eg.reshape(nw, T, NS, Bn))
+    sl, El = _ema64(X[:, :, F:F + C], a)
+    n = hi - lo
+    acc = sl[:, lo:hi].sum(1)
+    Eacc = El[:, lo:hi].sum(1) + (n - 1) * U1 * (np.abs(sl[:, lo:hi]) + El[:, lo:hi]).sum(1)
+    mean = acc / n
+    Emean = Eacc / n + U1 * (np.abs(mean) + Eacc / n)
+    lin = mean + _wide(b_lin1)
+    Elin = Emean + U1 * (np.abs(lin) + Emean) + 2.0 ** -149
+    return (aug.reshape(nw, T, F), lin), (Eaug.reshape(nw, T, F), Elin)
+
+
+def expand_keep_mask(keys, nw, T, Bn, NS, thr):
+    """[w][T][NS][Bn]: stream k keeps element (w, t, c) <=> its hash at index (w T + t) Bn + c of the stream's OWN (B, T, Bn)
+    tensor under the stream's key reaches thr."""
+    return np.stack([dropout_keep_mask(int(keys[k]), nw * T * Bn, thr).reshape(nw, T, Bn) for k in range(NS)], 2)
+
+
+def _expand_dropped_gelu(y, keep, scale):
+    """U = gelu_erf_lib(y) drop_scale and its bound (gelu_dropout_fwd_ref's terms); a dropped element is exactly zero."""
+    g = gelu64(y)
+    U = np.where(keep, g * scale, 0.0)
+    return U, np.where(keep, GELU_LIB_U * U32 * (np.abs(y) + np.abs(g)) * scale + U32 * np.abs(U) + 2.0 ** -149, 0.0)
+
+
+def expand_train_fwd_ref(proj, tmat, lin_vec, b_bott, ln_w, ln_b, b_lin1, Bn, NS, C, keys, thr, scale):
+    """train_expand_fwd on proj [w][T][NPROJ] with the temporal operators as operands.  fp32 operands: Y and lin_logits are the
+    kernel's bits (the fmaf chain over s = 0 .. T - 1 from +0, then ONE fp32 addition of the bias), and aug is judged against
+    float64 from those Y.  float64 operands (the CPU check against autograd): everything in float64.  Returns a dict: Y, lin
+    (fp32 bit for bit, or float64), aug and E_aug (the dropped GELU's bound through ln_ref), U, keep."""
+    P = np.asarray(proj)
+    exact = P.dtype != np.float64
+    nw, T, _ = P.shape
+    F = NS * Bn
+    tm = np.asarray(tmat).reshape(3, T, T)
+    if exact:
+        Y = np.empty((nw, T, F), np.float32)
+        for k in range(NS):
+            cols = np.ascontiguousarray(P[:, :, k * Bn:(k + 1) * Bn].transpose(0, 2, 1)).reshape(nw * Bn, T)
+            Y[:, :, k * Bn:(k + 1) * Bn] = fmaf_chain(tm[k], cols).reshape(T, nw, Bn).transpose(1, 0, 2)
+        with np.errstate(over="ignore", invalid="ignore"):
+            Y = (Y + np.asarray(b_bott, np.float32)).astype(np.float32)
+            lc = np.ascontiguousarray(P[:, :, F:F + C].transpose(0, 2, 1)).reshape(nw * C, T)
+            lin = (fmaf_chain(np.asarray(lin_vec, np.float32)[None, :], lc).reshape(nw, C) + np.asarray(b_lin1, np.float32)).astype(np.float32)
+    else:
+        Y = np.einsum("kts,wskc->wtkc", tm[:NS], P[:, :, :F].reshape(nw, T, NS, Bn)).reshape(nw, T, F) + np.asarray(b_bott)
+        lin = np.einsum("s,wsc->wc", np.asarray(lin_vec), P[:, :, F:F + C]) + np.asarray(b_lin1)
+    keep = expand_keep_mask(keys, nw, T, Bn, NS, thr)
+    U, EU = _expand_dropped_gelu(_wide(Y).reshape(nw, T, NS, Bn), keep, float(np.float32(scale)))
+    aug, Eaug = ln_ref(U, _wide(ln_w).reshape(NS, Bn), _wide(ln_b).reshape(NS, Bn), EXPAND_EPS, EU)
+    return dict(Y=Y, lin=lin, aug=aug.reshape(nw, T, F), E_aug=Eaug.reshape(nw, T, F), U=U, keep=keep)
+
+
+def ln_stats_ref(x, eps, Ex=None):
+    """ln_ref's intermediate quantities (same derivation, same symbols): mean, c = x - mean, rstd, and the bounds K (common
+    offset of the centred values), r (each centred value's own error) and rel (relative error of rstd)."""
+    x = np.asarray(x, np.float64)
+    D = x.shape[-1]
+    L = ln_levels(D)
+    e = float(np.float32(eps))
+    ex = np.zeros_like(x) if Ex is None else np.asarray(Ex, np.float64)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        mean = x.mean(-1, keepdims=True)
+        K = (L * U32 * (np.abs(x) + ex).sum(-1, keepdims=True) / D + DIV_U * U32 * np.abs(mean)) * (1 + 2 * L * U32) + ex.mean(-1, keepdims=True)
+        c = x - mean
+        ac = np.abs(c)
+        r = U32 * (ac + K + ex) + ex
+        var = (c * c).mean(-1, keepdims=True)
+        Eq = D * K * K + (r * (2 * ac + 2 * K + r)).sum(-1, keepdims=True) + (L + 1) * U32 * ((ac + K + r) ** 2).sum(-1, keepdims=True)
+        t = var + e
+        Et = Eq / D + (DIV_U + 1) * U32 * (t + Eq / D)
+        lo = np.where(t > Et, t - Et, np.nan)
+        rel = np.maximum(np.sqrt(t / lo) - 1.0, 1.0 - np.sqrt(t / (t + Et))) + (SQRT_U + DIV_U) * U32 * (1 + 2.0 ** -20)
+        rel = np.where(np.isfinite(rel), rel, np.inf)
+    return dict(mean=mean, c=c, rstd=1.0 / np.sqrt(t), K=K, r=r, rel=rel, var=var)
+
+
+def expand_train_bwd_ref(Y, daug, dlin, tmat, lin_vec, ln_w, Bn, NS, C, NPROJ, keys, thr, scale):
+    """train_expand_bwd from a saved Y [w][T][NS Bn]: (dproj [w][T][NPROJ], part [w][3 NS Bn] = [d b_bott | d ln_w | d ln_b]) and
+    their bounds.  With L = ln_levels(Bn), per (w, t, k) row and its element c:
+      U, xhat   the dropped GELU (bound as in the forward) and (U - mean) rstd with ln_stats_ref's K, r, rel, one product
+      dxh       daug ln_w, one rounding; s1 = sum dxh / Bn and s2 = sum dxh xhat / Bn: the terms' errors, L roundings of the
+                sum (lane partials and the butterfly), the division
+      du        rstd (daug ln_w - s1 - xhat s2): four roundings inside the bracket, rstd's rel, one product
+      dyv       fl(fl(du scale) gelu'(y)) where kept (gelu_dropout_bwd_ref's terms), exactly zero where dropped
+      part      three sums over t in kernel order: the terms' errors + T u1 sum |terms| (dgam's product adds one more)
+      dproj     bottleneck columns: the fmaf chain over t of tmat[k][t][s] dyv_t: sum |tm| E_dyv + T u1 sum |tm dyv|;
+                lin1 columns: the ONE product lin_vec[s] dlin[w][c], bit for bit (bound 0); padding columns: +0 (bound 0)."""
+    y = np.asarray(Y)
+    exact = y.dtype != np.float64
+    nw, T, F = y.shape
+    y = _wide(y).reshape(nw, T, NS, Bn)
+    dy = _wide(daug).reshape(nw, T, NS, Bn)
+    gam = _wide(ln_w).reshape(NS, Bn)
+    tm = _wide(np.asarray(tmat).reshape(3, T, T))[:NS]
+    sc = float(np.float32(scale))
+    L = ln_levels(Bn)
+    keep = expand_keep_mask(keys, nw, T, Bn, NS, thr)
+    U, EU = _expand_dropped_gelu(y, keep, sc)
+    st = ln_stats_ref(U, EXPAND_EPS, EU)
+    rstd, rel = st["rstd"], st["rel"]
+    xhat = st["c"] * rstd
+    Ex = rstd * ((1 + rel) * (st["K"] + st["r"]) + np.abs(st["c"]) * rel)
+    Ex = Ex + U1 * (np.abs(xhat) + Ex)
+    dxh = dy * gam
+    Edxh = U1 * np.abs(dxh)
+    s1 = dxh.mean(-1, keepdims=True)
+    Es1 = (Edxh.sum(-1, keepdims=True) + L * U1 * np.abs(dxh).sum(-1, keepdims=True)) / Bn
+    Es1 = Es1 + U1 * (np.abs(s1) + Es1)
+    term = dxh * xhat
+    Eterm = np.abs(dxh) * Ex + Edxh * (np.abs(xhat) + Ex) + 2 * U1 * np.abs(term)
+    s2 = term.mean(-1, keepdims=True)
+    Es2 = (Eterm.sum(-1, keepdims=True) + L * U1 * (np.abs(term) + Eterm).sum(-1, keepdims=True)) / Bn
+    Es2 = Es2 + U1 * (np.abs(s2) + Es2)
+    inner = dxh - s1 - xhat * s2
+    Einner = (Es1 + np.abs(xhat) * Es2 + np.abs(s2) * Ex + Ex * Es2
+              + U1 * (np.abs(dxh) + np.abs(dxh - s1) + np.abs(xhat * s2) + np.abs(inner))) * EXPAND_SLACK
+    du = rstd * inner
+    Edu = rstd * (Einner * (1 + rel) + np.abs(inner) * rel)
+    Edu = Edu + U1 * (np.abs(du) + Edu)
+    gp = gelu_grad64(y)
+    dyv = np.where(keep, du * sc * gp, 0.0)
+    Edyv = np.where(keep, Edu * sc * np.abs(gp) + GELU_GRAD_U * U32 * (np.abs(du) + Edu) * sc * (1.0 + np.abs(gp)) + 2 * U32 * np.abs(dyv) + 2.0 ** -149, 0.0) * EXPAND_SLACK
+    part = np.concatenate([dyv.sum(1).reshape(nw, F), (dy * xhat).sum(1).reshape(nw, F), dy.sum(1).reshape(nw, F)], 1)
+    Epart = np.concatenate([(Edyv.sum(1) + T * U1 * (np.abs(dyv) + Edyv).sum(1)).reshape(nw, F),
+                            ((np.abs(dy) * Ex).sum(1) + (T + 1) * U1 * (np.abs(dy) * (np.abs(xhat) + Ex)).sum(1)).reshape(nw, F),
+                            (T * U1 * np.abs(dy).sum(1)).reshape(nw, F)], 1) * EXPAND_SLACK + F32_TINY
+    dproj = np.zeros((nw, T, NPROJ))
+    Edproj = np.zeros((nw, T, NPROJ))
+    dproj[:, :, :F] = np.einsum("kts,wtkc->wskc", tm, dyv).reshape(nw, T, F)
+    Edproj[:, :, :F] = (np.einsum("kts,wtkc->wskc", np.abs(tm), Edyv)
+                        + T * U1 * np.einsum("kts,wtkc->wskc", np.abs(tm), np.abs(dyv) + Edyv)).reshape(nw, T, F) * EXPAND_SLACK + F32_TINY
+    lp = _wide(lin_vec)[None, :, None] * _wide(dlin)[:, None, :]          # exact in float64: 24 + 24 bits
+    with np.errstate(over="ignore", invalid="ignore"):
+        dproj[:, :, F:F + C] = lp.astype(np.float32).astype(np.float64) if exact else lp
+    return (dproj, part), (Edproj, Epart), dict(keep=keep, rel=rel, var=st["var"], xhat=xhat)
+
+
+# The suite's shapes, shared by tests/test_gpu_head_expand_reference.py and tests/test_kernel_reference_bounds.py (which checks the
+# coverage, the conditioning and every planted defect on exactly these).
+EXPAND_BN_NS = ((64, 2), (64, 3), (128, 3), (256, 3))
+EXPAND_INFER_T = (3, 4, 15, 31)
+EXPAND_TRAIN_T = (3, 15, 31)
+EXPAND_INFER_C = (1, 3, 64)
+EXPAND_TRAIN_C = (1, 3, 4, 64)
+EXPAND_NW = (1, 2, 5)
+EXPAND_THR_HALF = 1 << 23            # floor(0.5 * 2^24)
+
+
+def round_up(n, m):
+    return (n + m - 1) // m * m
+
+
+def expand_big_threshold(Bn, NS, C):
+    """(T, T + 1): the longest window whose training forms are resident in LDS and the shortest that takes the big form."""
+    NP = round_up(NS * Bn + C, 4)
+    T = 3
+    while not expand_is_big(T + 1, Bn, NP):
+        T += 1
+    return T, T + 1
+
+
+def expand_infer_cases():
+    """(Bn, NS, T, C, kind, lo, hi, nw): every value of each list with every (Bn, NS) where the count allows, C = 64 at (64, 2)
+    (thread 63 is a linear-branch thread), and the shortest T of the training suite's big form at Bn = 256."""
+    cases = []
+    for i in range(24):
+        r = i // 4
+        Bn, NS = EXPAND_BN_NS[i % 4]
+        T = EXPAND_INFER_T[(i + r) % 4]
+        C = EXPAND_INFER_C[(i + r) % 3]
+        kind = RANGE_KINDS[(i + 2 * r) % 5]
+        cases.append((Bn, NS, T, C, kind) + centre_range(kind, T) + (EXPAND_NW[(i + r) % 3],))
+    cases.append((64, 2, 15, 64, "centre3") + centre_range("centre3", 15) + (2,))
+    Tb = expand_big_threshold(256, 3, 4)[1]
+    cases.append((256, 3, Tb, 4, "centre3") + centre_range("centre3", Tb) + (1,))
+    return cases
+
+
+def expand_train_cases():
+    """(Bn, NS, T, C, thr, nw): the (Bn, NS) set with every T, C and both thresholds, both sides of the big threshold at
+    Bn = 256 (NS = 3, C = 4), and the big form at Bn = 64 with the longest window served."""
+    cases = []
+    for i in range(16):
+        r = i // 4
+        Bn, NS = EXPAND_BN_NS[i % 4]
+        cases.append((Bn, NS, EXPAND_TRAIN_T[(i + r) % 3], EXPAND_TRAIN_C[(i + r) % 4], (0, EXPAND_THR_HALF)[(i + r // 2) % 2], EXPAND_NW[(i + r) % 3]))
+    lo_T, hi_T = expand_big_threshold(256, 3, 4)
+    cases += [(256, 3, lo_T, 4, EXPAND_THR_HALF, 2), (256, 3, hi_T, 4, EXPAND_THR_HALF, 2), (64, 3, EXPAND_T_MAX, 4, EXPAND_THR_HALF, 1),
+              (64, 2, 15, 64, 0, 1), (128, 3, 3, 2, 0, 1)]                   # C = 2: the only class count here that leaves 2 padding columns
+    return cases
+
+
+def expand_case(nw, T, Bn, NS, C, seed, thr=0, amp=2.0):
+    """Operands of one expand launch: proj [nw][T][NPROJ] in about +-amp with finite padding columns (the GPU tests poison
+    them), biases and LayerNorm parameters away from the trivial 0 / 1, cotangents for the backward, three distinct stream keys
+    of which key k makes element 7 + k of its stream hash to exactly thr."""
+    rng = np.random.default_rng(seed)
+    F = NS * Bn
+    NP = round_up(F + C, 4)
+    f = lambda *s: rng.standard_normal(s).astype(np.float32)
+    return dict(proj=(f(nw, T, NP) * np.float32(amp)), b_bott=f(F) * np.float32(0.5), ln_w=(1 + 0.3 * f(F)).astype(np.float32), ln_b=f(F) * np.float32(0.3),
+                b_lin1=f(C), daug=f(nw, T, F), dlin=f(nw, C), NPROJ=NP, keys=[dropout_key_hitting(thr, 7 + k, salt=seed + k) for k in range(3)],
+                thr=thr, scale=float(np.float32(1.0 / (1.0 - thr / 2.0 ** 24))))
+
+
+EXPAND_ALPHA = 0.3
+# sliding inference at T = 7 (Bn = 64, NS = 3, C = 3): (n_frames, w0, windows).  With 1, 2 and 5 frames every row is clamped; in the
+# clip of 40, w0 = 0 clamps at the first frame, 17 is interior, 35 and 38 end past the last frame
+EXPAND_SLIDING = [(1, 0, 3), (2, 0, 2), (2, 1, 1), (5, 0, 5), (5, 3, 4), (40, 0, 2), (40, 17, 5), (40, 35, 5), (40, 38, 2)]
+
+
+def expand_sliding_layout(n_frames, w0, nw, T):
+    """(r0, rows [nw][T], image rows) of a sliding case: the image starts one frame before the first frame the windows read
+    (r0 > 0 wherever that frame exists) and ends two rows after the last - rows no window may touch."""
+    f = np.clip(w0 + np.arange(nw, dtype=np.int64)[:, None] + np.arange(T, dtype=np.int64)[None, :] - T // 2, 0, n_frames - 1)
+    r0 = max(int(f.min()) - 1, 0)
+    return r0, f - r0, int(f.max()) - r0 + 3
+
+
+def expand_seed(Bn, T, C, nw):
+    return Bn + 3 * T + C + nw
+
+
+_expand_cache = {}
+
+
+def expand_infer_suite_case(case):
+    """(operands, (aug, lin), (E_aug, E_lin)) of one expand_infer_cases() entry, computed once per process."""
+    if ("i", case) not in _expand_cache:
+        Bn, NS, T, C, kind, lo, hi, nw = case
+        p = expand_case(nw, T, Bn, NS, C, expand_seed(Bn, T, C, nw))
+        ref, E = expand_infer_ref(p["proj"], EXPAND_ALPHA, p["b_bott"], p["ln_w"], p["ln_b"], p["b_lin1"], Bn, NS, C, lo, hi)
+        _expand_cache[("i", case)] = (p, ref, E)
+    return _expand_cache[("i", case)]
+
+
+def expand_train_suite_case(case):
+    """(operands, tmat, lin_vec, forward reference, Y for the backward, backward reference) of one expand_train_cases() entry,
+    computed once per process.  tmat / lin_vec: expand_temporal_ref at the centre3 window, rounded to fp32.  The backward is
+    judged on its own: its Y is the float64 forward's (operands widened), rounded to fp32 - not the device's."""
+    if ("t", case) not in _expand_cache:
+        Bn, NS, T, C, thr, nw = case
+        p = expand_case(nw, T, Bn, NS, C, expand_seed(Bn, T, C, nw), thr)
+        E, D, A, lv = expand_temporal_ref(T, EXPAND_ALPHA, *centre_range("centre3", T))
+        tm, lv = np.stack([E, D, A]).astype(np.float32), lv.astype(np.float32)
+        fw = expand_train_fwd_ref(p["proj"], tm, lv, p["b_bott"], p["ln_w"], p["ln_b"], p["b_lin1"], Bn, NS, C, p["keys"], thr, p["scale"])
+        w = lambda x: np.asarray(x, np.float64)
+        f64 = expand_train_fwd_ref(w(p["proj"]), w(tm), w(lv), w(p["b_bott"]), p["ln_w"], p["ln_b"], w(p["b_lin1"]), Bn, NS, C, p["keys"], thr, p["scale"])
+        Yb = f64["Y"].astype(np.float32)
+        bw = expand_train_bwd_ref(Yb, p["daug"], p["dlin"], tm, lv, p["ln_w"], Bn, NS, C, p["NPROJ"], p["keys"], thr, p["scale"])
+        _expand_cache[("t", case)] = (p, tm, lv, fw, Yb, bw)
+    return _expand_cache[("t", case)]

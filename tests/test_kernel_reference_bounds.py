@@ -1037,3 +1037,337 @@ def test_centre_reference():
     got = (x - (x.sum(1, keepdims=True, dtype=F32) / F32(31))).astype(F32)
     assert R.ratio(got, y, E) <= 1.0
     assert R.ratio(x, y, E) > 1.0                     # the mean not subtracted
+
+
+# ---- classifier head: the expand kernels (tests/test_gpu_head_expand_reference.py) ---------------------------------------------
+EXP_ALPHA, EXP_SLIDING = R.EXPAND_ALPHA, R.EXPAND_SLIDING
+
+
+def _f64sum32(x, axis):
+    return np.sum(x, axis=axis, keepdims=True, dtype=F32)
+
+
+def _fma32(a, b, c):
+    return (np.asarray(a, np.float64) * np.asarray(b, np.float64) + np.asarray(c, np.float64)).astype(F32)
+
+
+def _ln32(u, g, b, Bn, defect):
+    """Two-pass fp32 LayerNorm of rows [..][Bn] (numpy's pairwise sums stand in for the lane partials and the butterfly)."""
+    div = F32(3 * Bn) if defect == "mean_over_F" else F32(Bn)
+    mean = (_f64sum32(u, -1) / div).astype(F32)
+    dv = (u - mean).astype(F32)
+    q = _f64sum32((dv * dv).astype(F32), -1)
+    eps = F32(0) if defect == "no_eps" else F32(R.EXPAND_EPS)
+    with np.errstate(divide="ignore"):
+        rstd = (F32(1) / np.sqrt(((q / F32(Bn)).astype(F32) + eps).astype(F32))).astype(F32)
+    return mean, rstd, ((((dv * rstd).astype(F32) * g).astype(F32)) + b).astype(F32)
+
+
+def _ema32(x, alpha, contract):
+    al = F32(alpha)
+    s = np.empty_like(x)
+    s[:, 0] = x[:, 0]
+    for t in range(1, x.shape[1]):
+        d = (x[:, t] - s[:, t - 1]).astype(F32)
+        s[:, t] = _fma32(al, d, s[:, t - 1]) if contract else (s[:, t - 1] + (al * d).astype(F32)).astype(F32)
+    return s
+
+
+def _emu_expand_infer(img, p, Bn, NS, C, lo, hi, nw, T, contract, sliding=None, defect=None):
+    """fp32 emulation of head_expand_kernel on the proj image [rows][NPROJ]; sliding = (w0, r0, n_frames).  A row the defective
+    row map takes from outside the image reads as 0."""
+    F_ = NS * Bn
+    if sliding is None:
+        rows = R.expand_rows(nw, T, False)
+    else:
+        w0, r0, nf = sliding
+        f = w0 + np.arange(nw)[:, None] + np.arange(T)[None, :] - T // 2
+        f = np.clip(f, -10 ** 9 if defect == "no_clamp_first" else 0, 10 ** 9 if defect == "no_clamp_last" else nf - 1)
+        rows = f - r0
+    ok = (rows >= 0) & (rows < img.shape[0])
+    X = np.where(ok[:, :, None], img[np.clip(rows, 0, img.shape[0] - 1)], F32(0)).astype(F32)
+    s = _ema32(X[:, :, :F_], EXP_ALPHA, contract)
+    i1, i2 = np.abs(np.arange(T) - 1), np.abs(np.arange(T) - 2)
+    if defect == "reflect_t0":
+        i1 = i1.copy(); i1[0] = 0                            # replicate: s_{-1} = s_0
+    if defect == "reflect_t1":
+        i2 = i2.copy(); i2[1] = 0                            # s_{-1} = s_0 again
+    if defect == "reflect_t2":
+        i2 = i2.copy(); i2[2] = 1                            # the padding's mirror applied where the interior stencil belongs
+    b, c = s[:, i1], s[:, i2]
+    d1 = (s - b).astype(F32)
+    d2 = (d1 - (b - c).astype(F32)).astype(F32)
+    k = (np.arange(F_) // Bn)[None, None, :]
+    v = np.where(k == 0, s, np.where(k == 1, d1, d2))
+    g = R.gelu64((v + p["b_bott"]).astype(F32)).astype(F32).reshape(nw, T, NS, Bn)
+    aug = _ln32(g, p["ln_w"].reshape(NS, Bn), p["ln_b"].reshape(NS, Bn), Bn, defect)[2].reshape(nw, T, F_)
+    sl = _ema32(X[:, :, F_:F_ + C], EXP_ALPHA, contract)
+    a, z = (lo, hi + 1) if defect == "mean_lo_hi_inclusive" else ((0, T) if defect == "mean_0_T" else (lo, hi))
+    acc = np.zeros((nw, C), F32)
+    for t in range(a, z):
+        acc = (acc + sl[:, t]).astype(F32)
+    return aug, ((acc / F32(z - a)).astype(F32) + p["b_lin1"]).astype(F32)
+
+
+def _emu_keep(keys, nw, T, Bn, NS, thr, defect):
+    if defect == "keys_permuted":
+        keys = [keys[1], keys[0], keys[2]]
+    if defect == "drop_idx_F":                               # the index taken in the fused F-wide row
+        F_ = NS * Bn
+        idx = (np.arange(nw * T, dtype=np.uint64)[:, None] * np.uint64(F_) + np.arange(F_, dtype=np.uint64)[None, :]).reshape(nw, T, NS, Bn)
+        with np.errstate(over="ignore"):
+            return np.stack([(R.mix64(np.uint64(keys[k]) + idx[:, :, k]) >> np.uint64(40)).astype(np.int64) >= thr for k in range(NS)], 2)
+    return R.expand_keep_mask(keys, nw, T, Bn, NS, thr)
+
+
+def _emu_expand_train_fwd(Y, p, Bn, NS, defect=None):
+    """fp32 emulation of train_expand_fwd_kernel after its (bit-exact) fmaf chain: GELU, dropout, LayerNorm."""
+    nw, T, F_ = Y.shape
+    keep = _emu_keep(p["keys"], nw, T, Bn, NS, p["thr"], defect)
+    u = (R.gelu64(Y).astype(F32).reshape(nw, T, NS, Bn) * np.where(keep, F32(p["scale"]), F32(0))).astype(F32)
+    return _ln32(u, p["ln_w"].reshape(NS, Bn), p["ln_b"].reshape(NS, Bn), Bn, defect)[2].reshape(nw, T, F_)
+
+
+def _emu_expand_train_bwd(Y, p, tm, lv, Bn, NS, C, defect=None):
+    """fp32 emulation of train_expand_bwd_kernel (numpy's sums stand in for the kernel's orders)."""
+    nw, T, F_ = Y.shape
+    NP = p["NPROJ"]
+    keep = _emu_keep(p["keys"], nw, T, Bn, NS, p["thr"], defect)
+    ds = np.where(keep, F32(p["scale"]), F32(0))
+    y = Y.reshape(nw, T, NS, Bn)
+    u = (R.gelu64(y).astype(F32) * ds).astype(F32)
+    gam = p["ln_w"].reshape(NS, Bn)
+    dy = p["daug"].reshape(nw, T, NS, Bn)
+    mean, rstd, xh = _ln32(u, F32(1), F32(0), Bn, defect)
+    dxh = (dy * gam).astype(F32)
+    s1 = (_f64sum32(dxh, -1) / F32(Bn)).astype(F32)
+    s2 = (_f64sum32((dxh * xh).astype(F32), -1) / F32(Bn)).astype(F32)
+    if defect == "st_slots":                                 # streams 0 and 1 read each other's row statistics
+        sw = [1, 0, 2][:NS]
+        mean, rstd, s1, s2 = (a[:, :, sw] for a in (mean, rstd, s1, s2))
+        xh = ((u - mean).astype(F32) * rstd).astype(F32)
+    du = (rstd * ((dxh - s1).astype(F32) - (xh * s2).astype(F32)).astype(F32)).astype(F32)
+    dyv = ((du * ds).astype(F32) * R.gelu_grad64(y).astype(F32)).astype(F32)
+    dgam, dbet = (dy * xh).astype(F32).sum(1, dtype=F32), dy.sum(1, dtype=F32)
+    if defect == "dgam_dbet":
+        dgam, dbet = dbet, dgam
+    part = np.concatenate([dyv.sum(1, dtype=F32).reshape(nw, F_), dgam.reshape(nw, F_), dbet.reshape(nw, F_)], 1)
+    dproj = np.zeros((nw, T, NP), F32)
+    dproj[:, :, :F_] = np.einsum("kts,wtkc->wskc", tm.reshape(3, T, T)[:NS], dyv).astype(F32).reshape(nw, T, F_)
+    dproj[:, :, F_:F_ + C] = (lv[None, :, None] * p["dlin"][:, None, :]).astype(F32)
+    return dproj, part
+
+
+_expand_infer_case, _expand_train_case = R.expand_infer_suite_case, R.expand_train_suite_case
+
+
+def test_expand_suites_cover_every_value_and_both_storage_forms():
+    ic, tc = R.expand_infer_cases(), R.expand_train_cases()
+    for bn_ns in R.EXPAND_BN_NS:
+        mine = [c for c in ic if c[:2] == bn_ns]
+        assert {c[2] for c in mine} >= set(R.EXPAND_INFER_T) and {c[3] for c in mine} >= set(R.EXPAND_INFER_C)
+        assert {c[4] for c in mine} >= set(R.RANGE_KINDS) and {c[7] for c in mine} >= set(R.EXPAND_NW)
+        mine = [c for c in tc if c[:2] == bn_ns]
+        assert {c[2] for c in mine} >= set(R.EXPAND_TRAIN_T) and {c[3] for c in mine} >= set(R.EXPAND_TRAIN_C) and {c[4] for c in mine} == {0, R.EXPAND_THR_HALF}
+        assert {R.round_up(c[0] * c[1] + c[3], 4) - c[0] * c[1] - c[3] for c in tc} == {0, 1, 2, 3}          # padding columns
+    assert (64, 2, 15, 64) in {c[:4] for c in ic} and (64, 2, 15, 64) in {c[:4] for c in tc}
+    lo_T, hi_T = R.expand_big_threshold(256, 3, 4)
+    NP = R.round_up(3 * 256 + 4, 4)
+    assert NP == 772 and not R.expand_is_big(lo_T, 256, NP) and R.expand_is_big(hi_T, 256, NP) and hi_T == lo_T + 1
+    assert R.expand_lds_bytes(lo_T, 256, NP, True, False) <= 160 * 1024 < R.expand_lds_bytes(hi_T, 256, NP, True, False)
+    assert {(256, 3, lo_T, 4), (256, 3, hi_T, 4)} <= {c[:4] for c in tc} and (256, 3, hi_T, 4) in {c[:4] for c in ic}
+    big64 = [c for c in tc if c[0] == 64 and R.expand_is_big(c[2], 64, R.round_up(c[0] * c[1] + c[3], 4))]
+    assert big64 and big64[0][2] == R.EXPAND_T_MAX and R.expand_lds_bytes(R.EXPAND_T_MAX, 64, 196, True, True) <= 160 * 1024
+    for c in tc:                                             # every training case is served: its LDS need fits
+        NPc = R.round_up(c[0] * c[1] + c[3], 4)
+        big = R.expand_is_big(c[2], c[0], NPc)
+        assert max(R.expand_lds_bytes(c[2], c[0], NPc, True, big), R.expand_lds_bytes(c[2], c[0], NPc, False, big)) <= 160 * 1024
+
+
+def test_ln_stats_ref_restates_ln_ref():
+    rng = np.random.default_rng(5)
+    x, ex = rng.standard_normal((7, 128)), np.abs(rng.standard_normal((7, 128))) * 1e-6
+    y, E = R.ln_ref(x, 1.0, 0.0, 1e-5, ex)
+    st = R.ln_stats_ref(x, 1e-5, ex)
+    ac = np.abs(st["c"])
+    E2 = st["rstd"] * ((1 + st["rel"]) * (st["K"] + st["r"]) + ac * st["rel"])
+    E2 = E2 + 2 * R.U32 * (np.abs(st["c"] * st["rstd"]) + E2) + R.U32 * (np.abs(y) + E2)
+    assert np.array_equal(y, st["c"] * st["rstd"]) and np.allclose(E, E2, rtol=1e-12, atol=0)
+
+
+def test_expand_temporal_ref_is_the_models_padding_and_differences():
+    """x_smooth, dx[:, 1:], ddx of _calculate_robust_deltas (torch, float64, the model's own pad / slice / lerp calls) on the
+    identity: its columns are the operators' columns."""
+    import torch
+    for T in (3, 4, 15):
+        a = float(F32(EXP_ALPHA))
+        x = torch.eye(T, dtype=torch.float64)[None]
+        xs = torch.zeros_like(x)
+        xs[:, 0] = x[:, 0]
+        for t in range(1, T):
+            xs[:, t] = torch.lerp(xs[:, t - 1], x[:, t], a)
+        padded = torch.nn.functional.pad(xs.permute(0, 2, 1), (2, 0), "reflect").permute(0, 2, 1)
+        dx = padded[:, 1:] - padded[:, :-1]
+        ddx = dx[:, 1:] - dx[:, :-1]
+        lo, hi = R.centre_range("centre3", T)
+        E, D, A, lv = R.expand_temporal_ref(T, EXP_ALPHA, lo, hi)
+        for got, want in ((E, xs[0]), (D, dx[0, 1:]), (A, ddx[0]), (lv, xs[0, lo:hi].mean(0))):
+            assert np.abs(got - want.numpy()).max() <= 1e-15
+
+
+def _torch_model(P, p, Bn, NS, C, lo, hi, mask):
+    """A direct transcription of ClassifierLSTMDeltas.forward up to x_augmented and linear_logits on projected rows, float64."""
+    import torch
+    Fn = torch.nn.functional
+    F_ = NS * Bn
+    a = float(F32(EXP_ALPHA))
+    x = P[:, :, :F_ + C]
+    xs = [x[:, 0]]
+    for t in range(1, x.shape[1]):
+        xs.append(torch.lerp(xs[-1], x[:, t], a))
+    xs = torch.stack(xs, 1)
+    padded = Fn.pad(xs.permute(0, 2, 1), (2, 0), "reflect").permute(0, 2, 1)
+    dx = padded[:, 1:] - padded[:, :-1]
+    ddx = dx[:, 1:] - dx[:, :-1]
+    outs, pre = [], []
+    for k, st in enumerate((xs, dx[:, 1:], ddx)[:NS]):
+        sl = slice(k * Bn, (k + 1) * Bn)
+        v = st[:, :, sl] + p["b_bott"][sl]
+        pre.append(v)
+        outs.append(Fn.layer_norm(Fn.gelu(v) * mask[:, :, k], (Bn,), p["ln_w"][sl], p["ln_b"][sl], float(F32(R.EXPAND_EPS))))
+    return torch.cat(outs, -1), xs[:, lo:hi, F_:F_ + C].mean(1) + p["b_lin1"], torch.cat(pre, -1)
+
+
+@pytest.mark.parametrize("Bn,NS,T,C,thr,nw", [(64, 2, 3, 3, 0, 1), (64, 3, 15, 64, R.EXPAND_THR_HALF, 2), (128, 3, 7, 1, R.EXPAND_THR_HALF, 1)])
+def test_expand_references_agree_with_autograd_on_the_model(Bn, NS, T, C, thr, nw):
+    import torch
+    c = R.expand_case(nw, T, Bn, NS, C, 11 + T, thr)
+    lo, hi = R.centre_range("centre3", T)
+    F_ = NS * Bn
+    tp = {k: torch.tensor(np.asarray(c[k], np.float64), requires_grad=True) for k in ("b_bott", "ln_w", "ln_b", "b_lin1")}
+    P = torch.tensor(c["proj"].astype(np.float64), requires_grad=True)
+    keep = R.expand_keep_mask(c["keys"], nw, T, Bn, NS, thr)
+    ones = torch.ones((nw, T, NS, Bn), dtype=torch.float64)
+    aug_i, lin_i, _ = _torch_model(P, tp, Bn, NS, C, lo, hi, ones)
+    (ra, rl), _ = R.expand_infer_ref(c["proj"].astype(np.float64), EXP_ALPHA, c["b_bott"], c["ln_w"], c["ln_b"], c["b_lin1"], Bn, NS, C, lo, hi)
+    assert np.abs(ra - aug_i.detach().numpy()).max() <= 1e-11 and np.abs(rl - lin_i.detach().numpy()).max() <= 1e-12
+    aug, lin, pre = _torch_model(P, tp, Bn, NS, C, lo, hi, torch.tensor(keep * float(F32(c["scale"]))))
+    E, D, A, lv = R.expand_temporal_ref(T, EXP_ALPHA, lo, hi)
+    tm = np.stack([E, D, A])
+    f64 = lambda k: np.asarray(c[k], np.float64)
+    fw = R.expand_train_fwd_ref(f64("proj"), tm, lv, f64("b_bott"), f64("ln_w"), f64("ln_b"), f64("b_lin1"), Bn, NS, C, c["keys"], thr, c["scale"])
+    assert np.abs(fw["Y"] - pre.detach().numpy()).max() <= 1e-12 and np.abs(fw["lin"] - lin.detach().numpy()).max() <= 1e-12
+    assert np.abs(fw["aug"] - aug.detach().numpy()).max() <= 1e-11
+    ((aug * torch.tensor(f64("daug"))).sum() + (lin * torch.tensor(f64("dlin"))).sum()).backward()
+    (dp, part), _, _ = R.expand_train_bwd_ref(fw["Y"], f64("daug"), f64("dlin"), tm, lv, f64("ln_w"), Bn, NS, C, c["NPROJ"], c["keys"], thr, c["scale"])
+    assert np.abs(dp - P.grad.numpy()).max() <= 1e-10 and not dp[:, :, F_ + C:].any()
+    for i, k in enumerate(("b_bott", "ln_w", "ln_b")):       # the per-window sums against the parameter gradients
+        assert np.abs(part[:, i * F_:(i + 1) * F_].sum(0) - tp[k].grad.numpy()).max() <= 1e-10, k
+    if nw == 1:
+        assert np.abs(part[0, :F_] - tp["b_bott"].grad.numpy()).max() <= 1e-10
+
+
+EXP_INFER_DEFECTS = ("reflect_t0", "reflect_t1", "reflect_t2", "mean_lo_hi_inclusive", "mean_0_T", "no_eps", "mean_over_F")
+EXP_TRAIN_FWD_DEFECTS = ("drop_idx_F", "keys_permuted", "no_eps", "mean_over_F")
+EXP_TRAIN_BWD_DEFECTS = EXP_TRAIN_FWD_DEFECTS + ("st_slots", "dgam_dbet")
+_expand_worst = {}
+
+
+@pytest.mark.parametrize("case", R.expand_infer_cases(), ids=lambda c: "-".join(str(v) for v in c))
+def test_expand_inference_bound_accepts_both_lerp_forms_and_rejects_the_defects(case):
+    Bn, NS, T, C, kind, lo, hi, nw = case
+    p, ref, E = _expand_infer_case(case)
+    assert np.isfinite(E[0]).all() and E[0].max() < 1e-3, "a LayerNorm row's variance is lost: the bound is vacuous"
+    img = p["proj"].reshape(nw * T, -1)
+    for contract in (False, True):
+        aug, lin = _emu_expand_infer(img, p, Bn, NS, C, lo, hi, nw, T, contract)
+        r = max(R.ratio(aug, ref[0], E[0]), R.ratio(lin, ref[1], E[1]))
+        _expand_worst["infer"] = max(_expand_worst.get("infer", 0.0), r)
+        assert r <= 1.0, (case, contract, r)
+    for defect in EXP_INFER_DEFECTS:
+        if (defect == "mean_lo_hi_inclusive" and hi == T) or (defect == "mean_0_T" and (lo, hi) == (0, T)) or (defect in ("reflect_t1", "reflect_t2") and NS == 2):
+            continue                                         # the defect does not exist at this shape (the second difference: stream 2 only)
+        aug, lin = _emu_expand_infer(img, p, Bn, NS, C, lo, hi, nw, T, False, defect=defect)
+        assert max(R.ratio(aug, ref[0], E[0]), R.ratio(lin, ref[1], E[1])) > 1.0, (case, defect)
+
+
+@pytest.mark.parametrize("sl", EXP_SLIDING, ids=lambda s: "-".join(str(v) for v in s))
+def test_expand_sliding_row_map_and_its_clamps(sl):
+    """The sliding cases of the GPU suite: the reference on the gathered rows accepts the emulation reading through the row
+    map, and rejects a map without its clamp wherever a window of the case crosses that end of the clip."""
+    nf, w0, nw = sl
+    T, Bn, NS, C = 7, 64, 3, 3
+    r0, rows, n_img = R.expand_sliding_layout(nf, w0, nw, T)
+    assert np.array_equal(rows, R.expand_rows(nw, T, True, w0, r0, nf)) and rows.min() == (1 if r0 else 0) and rows.max() == n_img - 3
+    p = R.expand_case(1, n_img, Bn, NS, C, 40 + nf + w0)
+    img = p["proj"][0]
+    lo, hi = R.centre_range("centre3", T)
+    ref, E = R.expand_infer_ref(img[rows], EXP_ALPHA, p["b_bott"], p["ln_w"], p["ln_b"], p["b_lin1"], Bn, NS, C, lo, hi)
+    aug, lin = _emu_expand_infer(img, p, Bn, NS, C, lo, hi, nw, T, True, sliding=(w0, r0, nf))
+    assert max(R.ratio(aug, ref[0], E[0]), R.ratio(lin, ref[1], E[1])) <= 1.0
+    f = w0 + np.arange(nw)[:, None] + np.arange(T)[None, :] - T // 2
+    for defect, crosses in (("no_clamp_first", (f < 0).any()), ("no_clamp_last", (f > nf - 1).any())):
+        if crosses:
+            aug, lin = _emu_expand_infer(img, p, Bn, NS, C, lo, hi, nw, T, True, sliding=(w0, r0, nf), defect=defect)
+            assert R.ratio(aug, ref[0], E[0]) > 1.0, (sl, defect)
+    if nf <= 5:                                              # the short clips: every window crosses an end
+        assert ((f < 0) | (f > nf - 1)).any(1).all()
+
+
+def test_expand_sliding_cases_cover_both_ends_the_interior_and_r0():
+    lay = {sl: R.expand_sliding_layout(*sl, 7) for sl in EXP_SLIDING}
+    assert {sl[0] for sl in EXP_SLIDING} == {1, 2, 5, 40}
+    assert any(r0 > 0 for r0, _, _ in lay.values()) and any(r0 == 0 for r0, _, _ in lay.values())
+    f = lambda sl: sl[1] + np.arange(sl[2])[:, None] + np.arange(7)[None, :] - 3
+    assert any((f(sl) >= 0).all() and (f(sl) <= sl[0] - 1).all() for sl in EXP_SLIDING)           # interior
+    assert any(sl[1] > 0 and (f(sl) > sl[0] - 1).any() and sl[0] == 40 for sl in EXP_SLIDING)
+
+
+@pytest.mark.parametrize("case", R.expand_train_cases(), ids=lambda c: "-".join(str(v) for v in c))
+def test_expand_training_bounds_accept_the_emulations_and_reject_the_defects(case):
+    Bn, NS, T, C, thr, nw = case
+    p, tm, lv, fw, Yb, ((dp, part), (Edp, Epart), info) = _expand_train_case(case)
+    F_ = NS * Bn
+    # conditioning: no row's variance is lost, and the threshold element of each stream exists (kept: hash == thr)
+    assert np.isfinite(fw["E_aug"]).all() and fw["E_aug"].max() < 1e-3 and info["rel"].max() < 1e-5 and info["var"].min() > 1e-3
+    for k in range(NS):
+        h = int(R.mix64(np.uint64((p["keys"][k] + 7 + k) & ((1 << 64) - 1))) >> np.uint64(40))
+        assert h == thr and fw["keep"].reshape(-1, NS, Bn)[0, k, 7 + k]
+    assert len(set(p["keys"])) == 3
+    aug = _emu_expand_train_fwd(fw["Y"], p, Bn, NS)
+    r = R.ratio(aug, fw["aug"], fw["E_aug"])
+    _expand_worst["fwd"] = max(_expand_worst.get("fwd", 0.0), r)
+    assert r <= 1.0, (case, r)
+    m = Edp > 0
+    g, pt = _emu_expand_train_bwd(Yb, p, tm, lv, Bn, NS, C)
+    r = max(R.ratio(g[m], dp[m], Edp[m]), R.ratio(pt, part, Epart))
+    _expand_worst["bwd"] = max(_expand_worst.get("bwd", 0.0), r)
+    assert r <= 1.0, (case, r)
+    assert np.array_equal(g[~m].view(np.uint32), dp[~m].astype(F32).view(np.uint32))
+    for defect in EXP_TRAIN_BWD_DEFECTS:
+        if defect in ("drop_idx_F", "keys_permuted") and thr == 0:
+            continue                                         # nothing is dropped: the index and the key are not used
+        if defect in EXP_TRAIN_FWD_DEFECTS:
+            assert R.ratio(_emu_expand_train_fwd(fw["Y"], p, Bn, NS, defect), fw["aug"], fw["E_aug"]) > 1.0, (case, defect, "forward")
+        g, pt = _emu_expand_train_bwd(Yb, p, tm, lv, Bn, NS, C, defect)
+        assert max(R.ratio(g[m], dp[m], Edp[m]), R.ratio(pt, part, Epart)) > 1.0, (case, defect, "backward")
+
+
+def test_expand_temporal_defects_leave_the_rounded_reference():
+    """What the GPU suite's bit-for-bit check of build_temporal would see of a wrong stencil row or a wrong centre mean."""
+    for T in (3, 15, 31, 101):
+        for kind in R.RANGE_KINDS:
+            lo, hi = R.centre_range(kind, T)
+            E, D, A, lv = R.expand_temporal_ref(T, EXP_ALPHA, lo, hi)
+            interior_D = np.concatenate([np.zeros((1, T)), E[1:] - E[:-1]])                      # replicate instead of reflect at t = 0
+            interior_A = A.copy()
+            interior_A[1] = E[1] - E[0]                                                          # likewise at t = 1
+            assert not np.array_equal(D.astype(F32), interior_D.astype(F32)) and not np.array_equal(A.astype(F32), interior_A.astype(F32))
+            if hi < T:
+                assert not np.array_equal(lv.astype(F32), E[lo:hi + 1].mean(0).astype(F32))
+            if (lo, hi) != (0, T):
+                assert not np.array_equal(lv.astype(F32), E.mean(0).astype(F32))
+
+
+def test_zz_expand_print_the_largest_emulation_ratios():
+    print(f"[expand bounds] largest emulation error / bound: {_expand_worst}")
