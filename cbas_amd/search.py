@@ -198,6 +198,17 @@ class FrameIndex:
         return _knn.knn_labels(self, bank, k=k, temperature=temperature, exclude=exclude, class_weights=class_weights,
                                return_neighbours=return_neighbours)
 
+    # ---- linear probe (cbas_amd/probe.py) ------------------------------------------------------------------------------------
+    def linear_probe(self, bank, **kw):
+        """``probe.fit_probe(self, bank, ...)``: softmax regression on the rows of a ``knn.LabelBank``, a ``probe.LinearProbe``."""
+        from . import probe as _probe
+        return _probe.fit_probe(self, bank, **kw)
+
+    def probe_labels(self, probe, **kw):
+        """``probe.probe_labels(self, probe, ...)``: the (N, C) probabilities of every row from a ``probe.LinearProbe``."""
+        from . import probe as _probe
+        return _probe.probe_labels(self, probe, **kw)
+
     # ---- motifs (cbas_amd/motifs.py) -------------------------------------------------------------------------------------------
     def cluster(self, n_clusters: int = 16, iters: int = 20, normalize: bool = True, init=None, clusters=None):
         """``motifs.cluster_frames(self, ...)``: ``(labels, dist2, clusters)``, every row's k-means motif."""

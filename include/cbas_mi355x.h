@@ -476,6 +476,62 @@ int cbas_rows_kmeans_fit(const void* rows_f16_dev, int64_t n_rows, int32_t dim, 
 int cbas_rows_kmeans_assign(const void* rows_f16_dev, int64_t n_rows, int32_t dim, int64_t ld, int32_t k, int32_t normalize,
                             const float* centroids_dev, int32_t* labels_dev, float* dist2_dev, void* stream);
 
+/* A linear probe on resident CLS rows: softmax regression on the frozen, normalised rows - the second half of the evaluation protocol of
+ * the self-supervised encoders (cbas_rows_knn is the first), and pre-labels for every frame from one (C, D) matrix.  Beyond the
+ * reference, which has no probe.  train_f16_dev (n_train, dim) fp16 with row stride ld (in halves), finite; label_dev (n_train) int32
+ * in [0, n_classes); sample_weight_dev (n_train) fp32, omega_m >= 0 and finite, NULL = ones.  Every sum below has the order stated, a
+ * function of (n_train, dim, n_classes) alone - not of the grid, the device or the stream - and none uses an atomic: two calls give
+ * the same bytes.
+ *   the working row   u = fl(x * rn), rn cbas_rows_search's: rn = fp32(1 / sqrt((double)s)), 0 when s = 0 (a zero row has u = 0), s =
+ *                     (l0 + l1) + (l2 + l3) in fp32, l_j the fmaf chain, from 0, of x_d^2 over the columns d with (d % 32) / 8 = j,
+ *                     ascending.  There is no un-normalised mode: with |u| <= 1 the step size is known on the host, which keeps
+ *                     the fit free of synchronisation.  No normalised copy is written.
+ *   the model         W (C, dim) fp32, b (C) fp32; z_c = fmaf(rn, x . w_c, b_c), x . w_c = chain0 + chain1, cbas_rows_search's dot:
+ *                     chain p is the fp32 fmaf chain, from 0, over the columns d with (d / 32) % 2 = p in ascending order of (d / 32,
+ *                     d % 8, (d % 32) / 8) (v_mfma_f32_16x16x4_f32: exact products).  The logits of a zero row are the bias.
+ *   the softmax       mx = the largest logit; e_c = expf(z_c - mx); S = (per j = c % 16 the e_c with c % 16 = j added in ascending c),
+ *                     then these sixteen by the xor tree 1, 2, 4, 8 over j; p_c = e_c / S; lse = mx + logf(S).
+ *   the objective     F(W, b) = (1 / Omega) sum_m omega_m (lse_m - z_{m, y_m}) + (l2 / 2) (|W|^2 + |b|^2): the bias is the weight of
+ *                     a constant feature 1 and is regularised like every other weight.  Omega = sum_m omega_m: per SEGMENT of
+ *                     CBAS_ROWS_PROBE_SEGMENT rows one fp32 sum in ascending row order, the segments added in ascending order; the
+ *                     loss terms fl(omega_m * fl(lse_m - z_y)) are added the same way and divided by Omega.  |W|^2 + |b|^2 = the
+ *                     |w_c|^2 (each one fmaf chain, from 0, over d ascending) added in ascending c, then |b|^2 (one fmaf chain over
+ *                     c ascending); F = fmaf(0.5 l2, that, data term).
+ *   the gradient      r_mc = fl(omega_m * (p_mc - [c = y_m])) (the subtraction rounds, then the product).  Per segment and element
+ *                     one fmaf chain, from 0, of r_mc * u_md over the segment's rows in ascending order (the fp32 matrix pipe, its
+ *                     k dimension over the rows); the bias' element is the plain fp32 sum of r_mc in that order.  The segments are
+ *                     added in ascending order; g = fmaf(l2, v, sum * (1 / Omega)).
+ *   the iteration     Nesterov's constant-step scheme for strongly convex functions, exactly `iters` steps, no tolerance, no host
+ *                     synchronisation: L = 1 + l2 (the data term's Hessian is at most 1/2 max |(u, 1)|^2 = 1), q = l2 / L, beta =
+ *                     (1 - sqrt q) / (1 + sqrt q); v_t = w_t + beta (w_t - w_{t-1}), w_{-1} = w_0; w_{t+1} = v_t - (1 / L) grad
+ *                     F(v_t), as w_{t+1} = fmaf(-1/L, g, v_t), v_{t+1} = fmaf(beta, w_{t+1} - w_t, w_{t+1}).  beta and 1 / L are
+ *                     computed on the host in double and rounded once to fp32.  w_0 = init_weights_dev (C, dim) / init_bias_dev
+ *                     (C), zeros where NULL.  A fit continued from given weights restarts the momentum (v_0 = w_0): `a` steps and
+ *                     then `b` more are not a + b steps.
+ *   loss_dev          (iters + 1): loss[t] = F(v_t) for t < iters, a by-product of the gradient pass; loss[iters] = F(w_iters),
+ *                     from one closing forward pass.  iters = 0 returns the start and loss[0] = F(w_0).
+ * weights_dev (C, dim) and bias_dev (C) receive w_iters.  The call synchronises `stream` ONCE, before the iteration is queued, to
+ * read back the checks of the labels, the sample weights and Omega; never after.
+ * The workspace (cbas_rows_probe_workspace_bytes, -1 for a refused shape; 16-byte aligned) takes, each part rounded up to 16 bytes,
+ *   32 + 2 (4 C dim + 256) + 320 + 8 n_train + 4 n_train C + (4 C dim + 264) ceil(n_train / CBAS_ROWS_PROBE_SEGMENT)  bytes:
+ * O(n_train C) plus one (C, dim) block of partial sums per segment.
+ * cbas_rows_probe_predict: probs_dev (n_rows, C) = p and, unless NULL, logits_dev (n_rows, C) = z of every row against given
+ * weights.  A row's outputs do not depend on n_rows, on where the row lies in the call or on whether logits_dev is given; n_rows =
+ * 0 does nothing.  Nothing is synchronised.
+ * CBAS_EINVAL with a message, nothing queued and no output written: dim % 32 != 0 or dim outside 32 .. 1536, ld < dim or ld % 8 != 0,
+ * n_classes outside 2 .. 64, n_train outside 1 .. 4 194 304, n_rows < 0, iters < 0, l2 not finite or not > 0, rows, weights or
+ * workspace not 16-byte aligned, a NULL pointer (sample_weight_dev, init_weights_dev, init_bias_dev and logits_dev may be NULL), a
+ * workspace too small.  CBAS_EINVAL with only the workspace written: a label outside [0, n_classes), a sample weight that is negative
+ * or not finite, Omega = 0. */
+#define CBAS_ROWS_PROBE_SEGMENT 1024
+int64_t cbas_rows_probe_workspace_bytes(int64_t n_train, int32_t dim, int32_t n_classes);
+int cbas_rows_probe_fit(const void* train_f16_dev, int64_t n_train, int32_t dim, int64_t ld, const int32_t* label_dev,
+                        const float* sample_weight_dev, int32_t n_classes, float l2, int32_t iters,
+                        const float* init_weights_dev, const float* init_bias_dev, float* weights_dev, float* bias_dev,
+                        float* loss_dev, void* workspace_dev, int64_t workspace_bytes, void* stream);
+int cbas_rows_probe_predict(const void* rows_f16_dev, int64_t n_rows, int32_t dim, int64_t ld, const float* weights_dev,
+                            const float* bias_dev, int32_t n_classes, float* probs_dev, float* logits_dev, void* stream);
+
 /* Host-streamed form (one iteration of encode_file's chunk loop).  `slot` in [0, CBAS_ENC_SLOTS):
  * submit copies the pixels host->HBM on the handle's copy stream (from pinned staging), encodes
  * on the compute stream and copies the CLS rows back; wait blocks until that slot is done and
