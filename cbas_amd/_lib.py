@@ -92,6 +92,11 @@ SIGNATURES = {
     "cbas_rows_probe_fit": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_void_p, c_int32, c_float, c_int32, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "cbas_rows_probe_predict": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "cbas_rows_pca_workspace_bytes": (c_int64, [c_int64, c_int32, c_int32]),
+    "cbas_rows_pca_fit": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_int64, c_void_p]),
+    "cbas_rows_pca_project": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p]),
     "cbas_enc_submit_u8_host": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int64, c_int64, c_int64]),
     "cbas_enc_wait": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "cbas_enc_submit_u8": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_void_p,

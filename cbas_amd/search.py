@@ -215,6 +215,12 @@ class FrameIndex:
         from . import motifs as _motifs
         return _motifs.cluster_frames(self, n_clusters=n_clusters, iters=iters, normalize=normalize, init=init, clusters=clusters)
 
+    # ---- the map (cbas_amd/framemap.py) ----------------------------------------------------------------------------------------
+    def pca(self, n_components: int = 3, normalize: bool = True, iters=None, basis=None):
+        """``framemap.pca_frames(self, ...)``: ``(scores, basis)``, every row's principal-component scores and the ``FramePCA``."""
+        from . import framemap as _framemap
+        return _framemap.pca_frames(self, n_components=n_components, normalize=normalize, iters=iters, basis=basis)
+
 
 # ---- command line ---------------------------------------------------------------------------------------------------------------
 def parse_span(text: str, need_end: bool = False) -> Tuple[str, int, Optional[int]]:

@@ -532,6 +532,54 @@ int cbas_rows_probe_fit(const void* train_f16_dev, int64_t n_train, int32_t dim,
 int cbas_rows_probe_predict(const void* rows_f16_dev, int64_t n_rows, int32_t dim, int64_t ld, const float* weights_dev,
                             const float* bias_dev, int32_t n_classes, float* probs_dev, float* logits_dev, void* stream);
 
+/* PCA over resident CLS rows: "what does the whole store look like?" - every frame a point in k <= 8 dimensions, and its squared
+ * distance from that k-dimensional subspace.  Beyond the reference, which has no map of its features.  rows_f16_dev (n_rows, dim) fp16
+ * with row stride ld (in halves), finite.  The definition is cbas_patch_pca_fit's with one problem; every sum below has the order
+ * stated, a function of (n_rows, dim) alone - not of the grid, the device or the stream - and none uses an atomic: two calls give the
+ * same bytes.
+ *   the working row   u = x widened to fp32 (normalize = 0), or u = fl(x * rn) (normalize = 1), rn cbas_rows_search's: rn = fp32(1 /
+ *                     sqrt((double)s)), 0 when s = 0 (a zero row has u = 0), s = (l0 + l1) + (l2 + l3) in fp32, l_j the fmaf chain,
+ *                     from 0, of x_d^2 over the columns d with (d % 32) / 8 = j, ascending.  No normalised copy is written.
+ *   the mean          mean_dev (dim): per CHUNK of CBAS_ROWS_PCA_CHUNK rows one fp32 sum per column in ascending row order, the
+ *                     chunks added in ascending order, / (float)n_rows.
+ *   the covariance    C = sum_m c_m c_m^T / (n_rows - 1), c_md = fl(u_md - mean_d).  The chunks are dealt to PARTS: a part is P =
+ *                     ceil(ceil(n_rows / CBAS_ROWS_PCA_CHUNK) / CBAS_ROWS_PCA_MAX_PARTS) consecutive chunks, so there are
+ *                     ceil(chunks / P) <= CBAS_ROWS_PCA_MAX_PARTS parts whatever n_rows.  Per element (i <= j) and chunk one fp32 fmaf
+ *                     chain, from 0, over the chunk's rows in ascending order (v_mfma_f32_16x16x4_f32: exact products); within a part
+ *                     the chunks' results are added in ascending order, from 0; the parts are added in ascending order, from part 0's
+ *                     value; one division by (float)(n_rows - 1).  (i, j) and (j, i) are written from the same value: C is symmetric
+ *                     bit for bit, and is left at the front of the workspace, dim * dim floats.
+ *   the eigenvectors  cbas_patch_pca_fit's solver on that C, unchanged: `iters` rounds of subspace iteration from its fixed start,
+ *                     Rayleigh-Ritz, eigenvalues descending, each component's entry of largest magnitude positive (ties to the lowest
+ *                     index).  components_dev (k, dim), eigenvalues_dev (k), total_variance_dev (1) = the trace of C.
+ * cbas_rows_pca_fit synchronises nothing.
+ * The workspace (cbas_rows_pca_workspace_bytes, -1 for a refused shape; 16-byte aligned) takes, each part rounded up to 16 bytes,
+ *   4 dim^2 parts + 4 k dim + 4 dim ceil(n_rows / CBAS_ROWS_PCA_CHUNK) + 4 n_rows  bytes:
+ * at most CBAS_ROWS_PCA_MAX_PARTS dim x dim blocks whatever n_rows, one row of column sums per chunk, and the reciprocal norms.
+ * cbas_rows_pca_project: scores_dev (n_rows, k) and, unless NULL, residual_dev (n_rows) of every row against a given mean (dim) and
+ * components (k, dim), one streaming pass.
+ *   score_mj          = chain0 + chain1, chain p the fp32 fmaf chain, from 0, of c_md * q_jd over the columns d with (d / 32) % 2 = p
+ *                     in ascending order of (d / 32, d % 8, (d % 32) / 8) (cbas_rows_search's dot, with the centred value c_md = fl(u_md -
+ *                     mean_d) in the row's place); then * scale_j, one rounding, when scale_dev (k) is given (whitening: the caller
+ *                     passes 1 / sqrt(eigenvalue_j)).
+ *   residual_m        = max(0, |c_m|^2 - sum_j score_mj^2) from the unscaled scores: |c_m|^2 = (n0 + n1) + (n2 + n3), n_j the fmaf
+ *                     chain, from 0, of c_md^2 over the columns d with (d % 32) / 8 = j, ascending; the scores' squares one fmaf chain,
+ *                     from 0, over j ascending.  The squared distance of the frame from the subspace.
+ * A row's outputs do not depend on n_rows, on where the row lies in the call or on whether residual_dev is given; n_rows = 0 does
+ * nothing.  Nothing is synchronised.
+ * CBAS_EINVAL with a message, nothing queued and no output written: dim % 32 != 0 or dim outside 32 .. 1536, k outside 1 .. 8 or k >
+ * dim, ld < dim or ld % 8 != 0, n_rows outside 2 .. 16 777 216 (fit) or < 0 (project), normalize not 0 or 1, iters < 1, rows, mean,
+ * components or workspace not 16-byte aligned, a NULL pointer (scale_dev and residual_dev may be NULL), a workspace too small. */
+#define CBAS_ROWS_PCA_CHUNK 1024
+#define CBAS_ROWS_PCA_MAX_PARTS 64
+int64_t cbas_rows_pca_workspace_bytes(int64_t n_rows, int32_t dim, int32_t k);
+int cbas_rows_pca_fit(const void* rows_f16_dev, int64_t n_rows, int32_t dim, int64_t ld, int32_t k, int32_t iters, int32_t normalize,
+                      float* mean_dev, float* components_dev, float* eigenvalues_dev, float* total_variance_dev, void* workspace_dev,
+                      int64_t workspace_bytes, void* stream);
+int cbas_rows_pca_project(const void* rows_f16_dev, int64_t n_rows, int32_t dim, int64_t ld, int32_t k, int32_t normalize,
+                          const float* mean_dev, const float* components_dev, const float* scale_dev, float* scores_dev,
+                          float* residual_dev, void* stream);
+
 /* Host-streamed form (one iteration of encode_file's chunk loop).  `slot` in [0, CBAS_ENC_SLOTS):
  * submit copies the pixels host->HBM on the handle's copy stream (from pinned staging), encodes
  * on the compute stream and copies the CLS rows back; wait blocks until that slot is done and
