@@ -195,6 +195,7 @@ DEBUG_SIGNATURES = {
     "cbas_debug_attention_mean": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_int64, c_int, c_void_p]),
     "cbas_debug_rollout_step": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "cbas_debug_rows_run": (c_int, [c_void_p]),
+    "cbas_debug_pack_run": (c_int, [c_void_p]),
     "cbas_debug_head_run": (c_int, [c_void_p]),
     "cbas_debug_head_seq_run": (c_int, [c_void_p]),
     "cbas_debug_head_expand_run": (c_int, [c_void_p]),

@@ -1066,6 +1066,124 @@ extern "C" int cbas_debug_rows_run(const cbas_debug_rows_args* a) {
     return CBAS_OK;
 }
 
+// ---- tests: one launch of a ViT ingest kernel or a create-time weight packer on host operands ----
+extern "C" int cbas_debug_pack_run(const cbas_debug_pack_args* a) {
+    if (!a || a->struct_bytes != (int64_t)sizeof(cbas_debug_pack_args))
+        return cbas_fail(CBAS_EINVAL, "cbas_debug_pack_args: struct_bytes %lld, library expects %lld", a ? (long long)a->struct_bytes : -1ll,
+                         (long long)sizeof(cbas_debug_pack_args));
+    const int op = a->op, n = a->n, h = a->h, w = a->w, ps = a->ps, D = a->D, K = a->K, NP = a->n_prefix;
+    const int64_t N = a->N, F = a->F;
+    if (op < CBAS_DEBUG_PACK_IM2COL_U8 || op > CBAS_DEBUG_PACK_FP8_W) return cbas_fail(CBAS_EINVAL, "op %d", op);
+    const bool im2col = op <= CBAS_DEBUG_PACK_IM2COL_F32_F32;
+    const bool u8 = op == CBAS_DEBUG_PACK_IM2COL_U8 || op == CBAS_DEBUG_PACK_IM2COL_U8_F32;
+    const bool patch_w = op == CBAS_DEBUG_PACK_PATCH_W || op == CBAS_DEBUG_PACK_PATCH_W_F32;
+    // what the launch reads (in_need) and writes (out_need), in bytes: the images must hold it.  A product that leaves int64
+    // is a size no image holds.
+    bool ovf = false;
+    const auto mul = [&ovf](int64_t x, int64_t y) { int64_t r = 0; if (__builtin_mul_overflow(x, y, &r)) ovf = true; return r; };
+    const auto add = [&ovf](int64_t x, int64_t y) { int64_t r = 0; if (__builtin_add_overflow(x, y, &r)) ovf = true; return r; };
+    int64_t in_need[2] = {0, 0}, out_need[4] = {0, 0, 0, 0};
+    bool out_opt[4] = {false, false, false, false};
+    if (im2col || patch_w) {
+        if (ps != 14 && ps != 16) return cbas_fail(CBAS_EINVAL, "ps = %d: 14 or 16", ps);
+        if (D <= 0) return cbas_fail(CBAS_EINVAL, "D = %d", D);
+    }
+    if (im2col) {
+        if (n <= 0 || h < ps || w < ps) return cbas_fail(CBAS_EINVAL, "%d frames of %d x %d: n > 0 and at least one %d x %d patch", n, h, w, ps, ps);
+        if (NP < 1 || D % 4) return cbas_fail(CBAS_EINVAL, "n_prefix = %d, D = %d: n_prefix >= 1, D a multiple of 4", NP, D);
+        const int nh = h / ps, nw = w / ps;
+        const int64_t P = (int64_t)nh * nw, T = P + NP;
+        if (mul(n, T) > 0x7fffffff) return cbas_fail(CBAS_EINVAL, "%d frames of %lld rows: beyond 2^31 - 1 rows", n, (long long)T);
+        if (u8) {
+            if (a->frame_stride <= 0 || a->row_stride <= 0 || a->pixel_stride <= 0) return cbas_fail(CBAS_EINVAL, "strides must be positive");
+            in_need[0] = add(add(mul(n - 1, a->frame_stride), mul(nh * ps - 1, a->row_stride)), add(mul(nw * ps - 1, a->pixel_stride), 1));
+        } else {
+            in_need[0] = mul(mul(n, h), mul(w, 4));
+        }
+        in_need[1] = mul(mul(NP, D), 4);
+        out_need[0] = mul(mul(n, P), op == CBAS_DEBUG_PACK_IM2COL_U8 ? 256 * 2 : 256 * 4);      // 256 fp16; 512 fp16 = 256 f32 slots
+        out_need[1] = mul(mul(n, T), mul(D, 4));
+    } else if (patch_w) {
+        if (D > (1 << 22)) return cbas_fail(CBAS_EINVAL, "D = %d: the packer indexes D * 512 elements in 32 bits", D);
+        in_need[0] = (int64_t)D * 3 * ps * ps * 4;
+        if (op == CBAS_DEBUG_PACK_PATCH_W) {
+            if ((a->out[1] == nullptr) != (a->out[3] == nullptr)) return cbas_fail(CBAS_EINVAL, "PATCH_W: lo and lo2 are NULL together or not at all");
+            out_need[0] = out_need[1] = (int64_t)D * 256 * 2;
+            out_need[2] = out_need[3] = (int64_t)D * 512 * 2;
+            out_opt[1] = out_opt[3] = true;
+        } else {
+            out_need[0] = (int64_t)D * 256 * 4;
+        }
+    } else if (op == CBAS_DEBUG_PACK_SPLIT_W) {
+        if (N <= 0 || K <= 0 || K % 32) return cbas_fail(CBAS_EINVAL, "SPLIT_W: N = %lld, K = %d: N > 0, K a positive multiple of 32", (long long)N, K);
+        in_need[0] = out_need[0] = mul(mul(N, K), 4);
+    } else if (op == CBAS_DEBUG_PACK_CONVERT_F16) {
+        if (N <= 0) return cbas_fail(CBAS_EINVAL, "CONVERT_F16: N = %lld", (long long)N);
+        in_need[0] = mul(N, 4);
+        out_need[0] = out_need[1] = mul(N, 2);
+        out_opt[1] = true;
+    } else if (op == CBAS_DEBUG_PACK_INTERLEAVE) {
+        if (F <= 0 || F % 32 || K <= 0) return cbas_fail(CBAS_EINVAL, "INTERLEAVE: F = %lld, K = %d: F a positive multiple of 32, K > 0", (long long)F, K);
+        in_need[0] = in_need[1] = mul(mul(F, K), 4);
+        out_need[0] = mul(in_need[0], 2);
+    } else {
+        if (N <= 0 || N > 0x7fffffff || K <= 0 || K % 128) return cbas_fail(CBAS_EINVAL, "FP8_W: N = %lld, K = %d: N > 0, K a positive multiple of 128", (long long)N, K);
+        if (a->n0 < 0 || a->n0 + N > a->n_total) return cbas_fail(CBAS_EINVAL, "FP8_W: columns %d .. %lld of %d", a->n0, (long long)(a->n0 + N), a->n_total);
+        in_need[0] = mul(mul(N, K), 4);
+        out_need[0] = mul(N, K);
+        out_need[1] = mul(mul(K / 128, a->n_total), 4);
+    }
+    if (ovf) return cbas_fail(CBAS_EINVAL, "op %d: a size or stride leaves 64 bits", op);
+    for (int i = 0; i < 2; ++i)
+        if (in_need[i] && (!a->in[i] || a->in_bytes[i] < in_need[i]))
+            return cbas_fail(CBAS_EINVAL, "op %d: in[%d] is missing or too small (%lld of %lld bytes)", op, i, (long long)a->in_bytes[i], (long long)in_need[i]);
+    for (int i = 0; i < 4; ++i) {
+        if (!out_need[i]) continue;
+        if (!a->out[i] ? !out_opt[i] : a->out_bytes[i] < out_need[i])
+            return cbas_fail(CBAS_EINVAL, "op %d: out[%d] is missing or too small (%lld of %lld bytes)", op, i, (long long)a->out_bytes[i], (long long)out_need[i]);
+    }
+    DevBufs B;
+    char *in[2] = {nullptr, nullptr}, *out[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int i = 0; i < 2; ++i)
+        if (in_need[i]) {
+            HIP_TRY(B.alloc(&in[i], (size_t)a->in_bytes[i]));
+            HIP_TRY(hipMemcpy(in[i], a->in[i], (size_t)a->in_bytes[i], hipMemcpyHostToDevice));
+        }
+    for (int i = 0; i < 4; ++i)
+        if (out_need[i] && a->out[i]) {
+            HIP_TRY(B.alloc(&out[i], (size_t)a->out_bytes[i]));
+            HIP_TRY(hipMemcpy(out[i], a->out[i], (size_t)a->out_bytes[i], hipMemcpyHostToDevice));
+        }
+    const float* in0 = reinterpret_cast<const float*>(in[0]);
+    const float* in1 = reinterpret_cast<const float*>(in[1]);
+    float* x = reinterpret_cast<float*>(out[1]);
+    const int T = im2col ? (h / ps) * (w / ps) + NP : 0;
+    const int split = a->split ? 1 : 0;
+    int rc = -1;
+    switch (op) {
+        case CBAS_DEBUG_PACK_IM2COL_U8:
+            rc = launch_im2col_u8((const uint8_t*)in[0], n, h, w, a->frame_stride, a->row_stride, a->pixel_stride, (f16*)out[0], x, in1, NP, D, T, ps, 0);
+            break;
+        case CBAS_DEBUG_PACK_IM2COL_F32: rc = launch_im2col_f32(in0, n, h, w, (f16*)out[0], x, in1, NP, D, T, ps, 0); break;
+        case CBAS_DEBUG_PACK_IM2COL_U8_F32:
+            rc = launch_im2col_u8_f32((const uint8_t*)in[0], n, h, w, a->frame_stride, a->row_stride, a->pixel_stride, (float*)out[0], x, in1, NP, D, T,
+                                      ps, split, 0);
+            break;
+        case CBAS_DEBUG_PACK_IM2COL_F32_F32: rc = launch_im2col_f32_f32(in0, n, h, w, (float*)out[0], x, in1, NP, D, T, ps, split, 0); break;
+        case CBAS_DEBUG_PACK_PATCH_W: rc = launch_pack_patch_weight(in0, (f16*)out[0], (f16*)out[1], (f16*)out[2], (f16*)out[3], D, ps, 0); break;
+        case CBAS_DEBUG_PACK_PATCH_W_F32: rc = launch_pack_patch_weight_f32(in0, (float*)out[0], D, ps, 0); break;
+        case CBAS_DEBUG_PACK_SPLIT_W: rc = launch_pack_split_weight(in0, (float*)out[0], N, K, a->scale, 0); break;
+        case CBAS_DEBUG_PACK_CONVERT_F16: rc = launch_convert_f16(in0, (f16*)out[0], (f16*)out[1], N, 0); break;
+        case CBAS_DEBUG_PACK_INTERLEAVE: rc = launch_interleave_gate_up(in0, in1, (float*)out[0], F, K, 0); break;
+        case CBAS_DEBUG_PACK_FP8_W: rc = launch_pack_fp8_weight(in0, (uint8_t*)out[0], (uint32_t*)out[1], (int)N, K, a->n_total, a->n0, 0); break;
+    }
+    if (rc) return cbas_fail(rc == -1 ? CBAS_EINVAL : CBAS_EHIP, "pack launch failed (op %d: rc=%d)", op, rc);
+    HIP_TRY(hipDeviceSynchronize());
+    for (int i = 0; i < 4; ++i)
+        if (out[i]) HIP_TRY(hipMemcpy(a->out[i], out[i], (size_t)a->out_bytes[i], hipMemcpyDeviceToHost));
+    return CBAS_OK;
+}
+
 // ---- tests: one launch of a classifier-head kernel (the exact-fp32 GEMM, the small training kernels) on host operands ----
 namespace {
 struct HeadNeed { int64_t in[4] = {0, 0, 0, 0}, out[3] = {0, 0, 0}; bool in_opt[4] = {false, false, false, false}; };

@@ -109,6 +109,14 @@ int launch_gemm_skinny(GemmEpilogue epi, const GemmParams& p, hipStream_t stream
 // ---------------------------------------------------------------------------------------------
 // ViT element-wise / attention kernels
 // ---------------------------------------------------------------------------------------------
+// The four ingest launchers (two here, two under precision 3): P = (height / ps) (width / ps) patches per frame in the 16 x 16
+// slot layout A[b P + py (width / ps) + px][16 i + j] = pixel (py ps + i, px ps + j), i, j < ps (ps = 14 or 16); slots with
+// j >= ps in rows i < ps are written as zeros, slot rows i >= ps are never written (the buffer is zeroed at allocation).  Pixel
+// rows and columns past the last whole patch are never read.  Rows b T + r, r < n_prefix, of x [n T][D] receive
+// prefix_tokens[r] bit for bit; nothing else of x is written.  -1: a null pointer, n <= 0, ps not 14 or 16, a frame smaller than
+// one patch, n_prefix < 1, D <= 0 or D % 4, T < P + n_prefix, a negative frame or row stride, a pixel stride below 1.
+bool im2col_args_ok(const void* frames, const void* A, const float* x, const float* prefix_tokens, int n, int height, int width,
+                    int n_prefix, int D, int T, int ps);
 // uint8 pixels -> im2col matrix A[n*P][256] fp16 holding the INTEGER pixel values (exact in fp16);
 // also writes the CLS/register prefix rows of the residual stream x.
 int launch_im2col_u8(const uint8_t* frames, int n, int height, int width, int64_t frame_stride,
@@ -194,10 +202,13 @@ int launch_token_similarity(const E* tokens, int64_t ld, int n, int T, int D, in
 // gated MLP, create time: out [2F][K] = rows of gate [F][K] and up [F][K] interleaved in blocks of 32 - out rows [64 b, 64 b + 32)
 // are gate rows [32 b, 32 b + 32), out rows [64 b + 32, 64 b + 64) the up rows of the same outputs (K = 1: the biases); F % 32 == 0
 int launch_interleave_gate_up(const float* gate, const float* up, float* out, int64_t F, int K, hipStream_t stream);
-// fp32 -> fp16 weight conversion (optionally also the fp16 residual), n elements
+// fp32 -> fp16 weight conversion, n elements: hi[i] = fp16(src[i]) (round to nearest even; beyond 65504 infinity), and, unless lo is
+// NULL, lo[i] = fp16(src[i] - hi[i]).  -1: src or hi NULL, n <= 0
 int launch_convert_f16(const float* src, f16* hi, f16* lo, int64_t n, hipStream_t stream);
-// patch weight (D,3,16,16) fp32 -> sum over the 3 identical input channels -> (D,256) fp16 hi (+lo),
-// and the same duplicated along K as (D,512) for the float-input path
+// patch weight (D,3,ps,ps) fp32 -> W' = (c0 + c1) + c2 over the 3 identical input channels, in fp32, in the 16 x 16 slot layout
+// (zero where i >= ps or j >= ps) -> hi = fp16(W'), lo = fp16(W' - hi), each (D,256), and hi2 / lo2 (D,512) = [W' | W'] along K for
+// the float-input path.  lo and lo2 may be NULL together.  -1: another null pointer, D <= 0, ps not 14 or 16
+// (launch_pack_patch_weight, declared below)
 // fp32 weight [N][K] -> MX-fp8: e4m3 bytes [N][K] + block scales [K/128][N] (GemmParams::W_sc layout); K % 128 == 0
 // sc row n of this call is column n0 + n of a scale array with n_total columns (q, k, v packed into one [3D][D] weight)
 int launch_pack_fp8_weight(const float* src, uint8_t* w8, uint32_t* sc, int N, int K, int n_total, int n0, hipStream_t stream);
@@ -245,7 +256,10 @@ int launch_im2col_u8_f32(const uint8_t* frames, int n, int height, int width, in
 // float32 (n,H,W) -> A[n*P][256] fp32, values as they are
 int launch_im2col_f32_f32(const float* frames, int n, int height, int width, float* A, float* x,
                           const float* prefix_tokens, int n_prefix, int D, int T, int ps, int split, hipStream_t stream);
-// precision 4: fp32 weight [N][K] -> split format at the same byte size, values multiplied by `scale` first
+// precision 4: fp32 weight [N][K] -> split format at the same byte size, values multiplied by `scale` first: hi = fp16(w scale),
+// lo = fp16(w scale - hi), bit for bit - except that the low half of a ZERO weight is a zero of either sign (measured: -0.0 for
+// w = -0.0, where the subtraction alone gives +0.0; the compiler fuses scale, rounding and subtraction into mixed-precision FMAs).
+// hi + lo is the same -0.0 either way.  -1: N <= 0, K % 32
 int launch_pack_split_weight(const float* w, float* out, int64_t N, int K, float scale, hipStream_t stream);
 // patch weight (D,3,ps,ps) fp32 -> (D,256) fp32 in the 16x16 slot layout, summed over the 3 identical input channels in
 // double and rounded once

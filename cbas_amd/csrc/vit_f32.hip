@@ -971,6 +971,9 @@ int launch_gemm_f32_vit(GemmEpilogue epi, const Gemm32VitParams& p, hipStream_t 
 int launch_im2col_u8_f32(const uint8_t* frames, int n, int height, int width, int64_t frame_stride, int64_t row_stride,
                          int64_t pixel_stride, float* A, float* x, const float* prefix_tokens, int n_prefix, int D, int T,
                          int ps, int split, hipStream_t stream) {
+    if (!im2col_args_ok(frames, A, x, prefix_tokens, n, height, width, n_prefix, D, T, ps) || frame_stride < 0 || row_stride < 0 ||
+        pixel_stride < 1)
+        return -1;
     const int nh = height / ps, nw = width / ps;
     const int64_t total = (int64_t)n * nh * ps * nw;
     hipLaunchKernelGGL(im2col_f32out_kernel<uint8_t>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, frames, n,
@@ -983,6 +986,7 @@ int launch_im2col_u8_f32(const uint8_t* frames, int n, int height, int width, in
 
 int launch_im2col_f32_f32(const float* frames, int n, int height, int width, float* A, float* x,
                           const float* prefix_tokens, int n_prefix, int D, int T, int ps, int split, hipStream_t stream) {
+    if (!im2col_args_ok(frames, A, x, prefix_tokens, n, height, width, n_prefix, D, T, ps)) return -1;
     const int nh = height / ps, nw = width / ps;
     const int64_t total = (int64_t)n * nh * ps * nw;
     hipLaunchKernelGGL(im2col_f32out_kernel<float>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, frames, n,
@@ -1001,6 +1005,7 @@ int launch_pack_split_weight(const float* w, float* out, int64_t N, int K, float
 }
 
 int launch_pack_patch_weight_f32(const float* w, float* out, int D, int ps, hipStream_t stream) {
+    if (!w || !out || D <= 0 || D > (1 << 22) || (ps != 14 && ps != 16)) return -1;
     hipLaunchKernelGGL(pack_patch_weight_f32_kernel, dim3((D * 256 + 255) / 256), dim3(256), 0, stream, w, out, D, ps);
     return CHECK_LAUNCH();
 }

@@ -846,9 +846,21 @@ __global__ void pack_patch_weight_kernel(const float* __restrict__ w, f16* __res
 
 #define CHECK_LAUNCH() (hipGetLastError() == hipSuccess ? 0 : -2)
 
+// what every ingest launcher refuses (-1): a null pointer, no frame, a patch size without a 16 x 16 slot layout, a frame smaller
+// than one patch, no prefix row, rows of x that are no whole 16-byte vectors, a T that does not hold the frame's rows
+bool im2col_args_ok(const void* frames, const void* A, const float* x, const float* prefix_tokens, int n, int height, int width,
+                    int n_prefix, int D, int T, int ps) {
+    if (!frames || !A || !x || !prefix_tokens || n <= 0 || (ps != 14 && ps != 16) || height < ps || width < ps) return false;
+    return n_prefix >= 1 && D > 0 && D % 4 == 0 && (int64_t)T >= (int64_t)(height / ps) * (width / ps) + n_prefix;
+}
+
 int launch_im2col_u8(const uint8_t* frames, int n, int height, int width, int64_t frame_stride,
                      int64_t row_stride, int64_t pixel_stride, f16* A, float* x, const float* prefix_tokens,
                      int n_prefix, int D, int T, int ps, hipStream_t stream) {
+    // strides as cbas_enc_submit_u8_host accepts them (a frame stride of 0 reads one frame n times)
+    if (!im2col_args_ok(frames, A, x, prefix_tokens, n, height, width, n_prefix, D, T, ps) || frame_stride < 0 || row_stride < 0 ||
+        pixel_stride < 1)
+        return -1;
     const int nh = height / ps, nw = width / ps;
     const int64_t total = (int64_t)n * nh * ps * nw;
     hipLaunchKernelGGL(im2col_u8_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, frames, n,
@@ -861,6 +873,7 @@ int launch_im2col_u8(const uint8_t* frames, int n, int height, int width, int64_
 
 int launch_im2col_f32(const float* frames, int n, int height, int width, f16* A, float* x,
                       const float* prefix_tokens, int n_prefix, int D, int T, int ps, hipStream_t stream) {
+    if (!im2col_args_ok(frames, A, x, prefix_tokens, n, height, width, n_prefix, D, T, ps)) return -1;
     const int nh = height / ps, nw = width / ps;
     const int64_t total = (int64_t)n * nh * ps * nw;
     hipLaunchKernelGGL(im2col_f32_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, frames, n,
@@ -985,12 +998,13 @@ int launch_interleave_gate_up(const float* gate, const float* up, float* out, in
 }
 
 int launch_convert_f16(const float* src, f16* hi, f16* lo, int64_t n, hipStream_t stream) {
+    if (!src || !hi || n <= 0) return -1;
     hipLaunchKernelGGL(convert_f16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, src, hi, lo, n);
     return CHECK_LAUNCH();
 }
 
 int launch_pack_fp8_weight(const float* src, uint8_t* w8, uint32_t* sc, int N, int K, int n_total, int n0, hipStream_t stream) {
-    if (K % 128) return -1;
+    if (N <= 0 || K % 128) return -1;
     const int64_t blocks = (int64_t)N * (K / 32);
     hipLaunchKernelGGL(pack_fp8_weight_kernel, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, stream, src, w8, sc, N, K,
                        n_total, n0);
@@ -998,6 +1012,8 @@ int launch_pack_fp8_weight(const float* src, uint8_t* w8, uint32_t* sc, int N, i
 }
 
 int launch_pack_patch_weight(const float* w, f16* hi, f16* lo, f16* hi2, f16* lo2, int D, int ps, hipStream_t stream) {
+    // lo and lo2 are NULL together (the kernel tests lo alone); D * 512 elements are indexed in 32 bits
+    if (!w || !hi || !hi2 || (lo == nullptr) != (lo2 == nullptr) || D <= 0 || D > (1 << 22) || (ps != 14 && ps != 16)) return -1;
     hipLaunchKernelGGL(pack_patch_weight_kernel, dim3((D * 256 + 255) / 256), dim3(256), 0, stream, w, hi, lo, hi2, lo2, D, ps);
     return CHECK_LAUNCH();
 }

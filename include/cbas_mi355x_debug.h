@@ -223,6 +223,52 @@ typedef struct cbas_debug_rows_args {
 } cbas_debug_rows_args;
 int cbas_debug_rows_run(const cbas_debug_rows_args* a);
 
+/* Tests: ONE launch of a ViT ingest kernel or a create-time weight packer on host operands (tests/test_gpu_ingest_reference.py
+ * compares it bit for bit with the references of oracle/kernel_ref.py), handled like cbas_debug_rows_run: the harness uploads
+ * every in[] image and the caller's pre-filled out[] images whole, runs exactly one launcher on the default stream, synchronises
+ * and copies every out[] image back whole - whatever the launch does not own is the caller's canary.
+ *   op              launcher                               in[]                                    out[]
+ *   IM2COL_U8       launch_im2col_u8                       0 bytes + the three strides,            0 A [n P][256] fp16, 1 x [n T][D] f32
+ *                                                          1 prefix [n_prefix][D] f32
+ *   IM2COL_F32      launch_im2col_f32                      0 [n][h][w] f32, 1 prefix               0 A [n P][512] fp16 (hi | lo), 1 x
+ *   IM2COL_U8_F32   launch_im2col_u8_f32 (split 0 / 1)     as IM2COL_U8                            0 A [n P][256] f32 / split image, 1 x
+ *   IM2COL_F32_F32  launch_im2col_f32_f32 (split 0 / 1)    as IM2COL_F32                           0 A [n P][256] f32 / split image, 1 x
+ *   PATCH_W         launch_pack_patch_weight               0 w (D, 3, ps, ps) f32                  0 hi, 1 lo (D, 256) fp16; 2 hi2, 3 lo2 (D, 512)
+ *   PATCH_W_F32     launch_pack_patch_weight_f32           0 w (D, 3, ps, ps) f32                  0 (D, 256) f32
+ *   SPLIT_W         launch_pack_split_weight               0 [N][K] f32; scale                     0 split image [N][K] float slots
+ *   CONVERT_F16     launch_convert_f16                     0 N floats                              0 hi, 1 lo [N] fp16
+ *   INTERLEAVE      launch_interleave_gate_up              0 gate, 1 up [F][K] f32                 0 [2 F][K] f32
+ *   FP8_W           launch_pack_fp8_weight                 0 [N][K] f32; n_total, n0               0 e4m3 bytes [N][K], 1 [K/128][n_total] dwords
+ * The im2col ops: P = (h / ps) (w / ps) patches per frame, T = P + n_prefix rows of x per frame; x rows b T + r, r < n_prefix,
+ * receive prefix row r and nothing else of x is written.  PATCH_W: out[1] and out[3] may be NULL together; CONVERT_F16: out[1] may
+ * be NULL.  It refuses (CBAS_EINVAL, nothing allocated or launched): a NULL image other than those; n, D, N or F <= 0; ps
+ * outside {14, 16}; h < ps or w < ps; n_prefix < 1; D % 4; K <= 0, K % 32 (SPLIT_W), K % 128 (FP8_W); F % 32; n0 < 0 or n0 + N >
+ * n_total; a non-positive stride; and any stride or size whose last read or write would leave the stated byte counts. */
+enum {
+    CBAS_DEBUG_PACK_IM2COL_U8 = 0, CBAS_DEBUG_PACK_IM2COL_F32 = 1, CBAS_DEBUG_PACK_IM2COL_U8_F32 = 2,
+    CBAS_DEBUG_PACK_IM2COL_F32_F32 = 3, CBAS_DEBUG_PACK_PATCH_W = 4, CBAS_DEBUG_PACK_PATCH_W_F32 = 5, CBAS_DEBUG_PACK_SPLIT_W = 6,
+    CBAS_DEBUG_PACK_CONVERT_F16 = 7, CBAS_DEBUG_PACK_INTERLEAVE = 8, CBAS_DEBUG_PACK_FP8_W = 9
+};
+typedef struct cbas_debug_pack_args {
+    int64_t struct_bytes;        /* sizeof(cbas_debug_pack_args): a mismatch is rejected */
+    int op, split;               /* split: the split = 1 form of IM2COL_U8_F32 / IM2COL_F32_F32 */
+    int n, h, w;                 /* im2col: frames, frame height / width in pixels */
+    int ps;                      /* im2col, PATCH_W*: patch size, 14 or 16 */
+    int n_prefix;                /* im2col: prefix rows per frame */
+    int D;                       /* im2col: width of x and prefix; PATCH_W*: output rows */
+    int K;                       /* SPLIT_W, INTERLEAVE, FP8_W: columns */
+    int n_total, n0;             /* FP8_W: columns of the scale image, this call's first column */
+    float scale;                 /* SPLIT_W */
+    int64_t N;                   /* SPLIT_W, FP8_W: rows; CONVERT_F16: elements */
+    int64_t F;                   /* INTERLEAVE: rows of gate and of up */
+    int64_t frame_stride, row_stride, pixel_stride;     /* IM2COL_U8, IM2COL_U8_F32: bytes */
+    const void* in[2];
+    int64_t in_bytes[2];
+    void* out[4];                /* in / out */
+    int64_t out_bytes[4];
+} cbas_debug_pack_args;
+int cbas_debug_pack_run(const cbas_debug_pack_args* a);
+
 /* Tests: ONE launch of a classifier-head kernel with an exact or tightly derivable reference on host operands
  * (tests/test_gpu_head_kernels_reference.py compares it with the references of oracle/kernel_ref.py): the exact-fp32 GEMM of
  * gemm_f32.hip (plain, fused GELU, split-K + its reduction) and the element-wise, reduction and optimiser kernels of

@@ -6,7 +6,8 @@ Used by tests/test_gpu_kernel_reference.py (the kernels through cbas_debug_gemm_
 tests/test_gpu_rows_reference.py (cbas_debug_rows_run), tests/test_gpu_head_kernels_reference.py (the classifier head's
 exact-fp32 GEMM and small training kernels through cbas_debug_head_run), tests/test_gpu_head_seq_reference.py and
 tests/test_gpu_head_expand_reference.py (the head's sequential and expand kernels through cbas_debug_head_seq_run /
-cbas_debug_head_expand_run) and tests/test_kernel_reference_bounds.py (the
+cbas_debug_head_expand_run), tests/test_gpu_ingest_reference.py (the ViT ingest kernels and the create-time weight packers
+through cbas_debug_pack_run: exact references, no bounds) and tests/test_kernel_reference_bounds.py (the
 references and bounds themselves, on the CPU).
 
 Units: u32 = 2^-24 (fp32 unit roundoff), u16 = 2^-11 (fp16).  A bound is a float64 array shaped like the output; a kernel
@@ -1645,3 +1646,108 @@ def expand_train_suite_case(case):
         bw = expand_train_bwd_ref(Yb, p["daug"], p["dlin"], tm, lv, p["ln_w"], Bn, NS, C, p["NPROJ"], p["keys"], thr, p["scale"])
         _expand_cache[("t", case)] = (p, tm, lv, fw, Yb, bw)
     return _expand_cache[("t", case)]
+
+
+# ---- ViT ingest and the create-time weight packers: exact references -----------------------------------------------------------
+# Used by tests/test_gpu_ingest_reference.py through cbas_debug_pack_run.  Written from the contracts in csrc/kernels.h (the slot
+# layout of the ingest launchers, the packers' sums and index formulas), not from the kernels; every one has an exact answer, so
+# there are no bounds here.  tests/test_kernel_reference_bounds.py ties the slot layout to oracle/vit_oracle.embeddings.
+def vit_im2col_ref(green, ps: int):
+    """The patch matrix of [n][h][w] planes in the 16 x 16 slot layout: A[b P + py nw + px][16 i + j] = pixel (py ps + i,
+    px ps + j) for i, j < ps, in the planes' own dtype; P = nh nw whole patches, the rows and columns past them are not read.
+    Returns (A [n P][256], owned [256]): owned marks the slots a launch writes, i < ps (zeros where j >= ps); the slot rows
+    i >= ps are never written and hold 0 here."""
+    g = np.asarray(green)
+    n, h, w = g.shape
+    nh, nw = h // ps, w // ps
+    A = np.zeros((n, nh, nw, 16, 16), g.dtype)
+    for py in range(nh):
+        for px in range(nw):
+            A[:, py, px, :ps, :ps] = g[:, py * ps:(py + 1) * ps, px * ps:(px + 1) * ps]
+    return A.reshape(n * nh * nw, 256), (np.arange(256) // 16) < ps
+
+
+def u8_to_unit_f32(p) -> np.ndarray:
+    """backend/cbas.py:431 on one byte: the float64 quotient p / 255.0, rounded once to float32."""
+    return np.float32(np.float64(p) / 255.0)
+
+
+def f16_pair(v):
+    """(hi, lo) fp16 of fp32 values: hi = RNE fp16(v), lo = RNE fp16(v - hi) with the difference taken in fp32 (the K = 512 ingest
+    form, launch_convert_f16, launch_pack_patch_weight).  Beyond 65504 hi is an infinity and lo the opposite one."""
+    v = np.asarray(v, np.float32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        hi = v.astype(np.float16)
+        lo = (v - hi.astype(np.float32)).astype(np.float16)
+    return hi, lo
+
+
+def split_operand_bits(x, scale: float) -> np.ndarray:
+    """The split image of rows [R][K] fp32 (K % 32 == 0) as uint16 [R][2 K], the inverse of decode_split_operand: K-tile t of a
+    row is 64 halves = [hi 32 | lo 32] of x * scale, the value of column 32 t + 16 h + 4 g + e at position 8 g + 4 h + e."""
+    x = np.asarray(x, np.float32)
+    R, K = x.shape
+    hi, lo = f16_pair(x * np.float32(scale))
+    k = np.arange(32)
+    pos = 8 * ((k % 16) // 4) + 4 * (k // 16) + k % 4
+    img = np.zeros((R, K // 32, 2, 32), np.uint16)
+    img[:, :, 0, pos] = hi.view(np.uint16).reshape(R, K // 32, 32)
+    img[:, :, 1, pos] = lo.view(np.uint16).reshape(R, K // 32, 32)
+    return img.reshape(R, 2 * K)
+
+
+def patch_weight_ref(w, ps: int, wide: bool = False) -> np.ndarray:
+    """The patch weight (D, 3, ps, ps) summed over its 3 input channels (the model sees 3 identical ones) as (c0 + c1) + c2, in the
+    slot layout [D][16 i + j], zero where i >= ps or j >= ps.  wide = False: the sum in float32 (launch_pack_patch_weight, which
+    then splits it with f16_pair); wide = True: in float64, rounded once to float32 (launch_pack_patch_weight_f32)."""
+    w = np.asarray(w, np.float32)
+    D = w.shape[0]
+    c = w.astype(np.float64) if wide else w
+    s = ((c[:, 0] + c[:, 1]) + c[:, 2]).astype(np.float32)
+    out = np.zeros((D, 16, 16), np.float32)
+    out[:, :ps, :ps] = s
+    return out.reshape(D, 256)
+
+
+def interleave_ref(gate, up) -> np.ndarray:
+    """launch_interleave_gate_up: out [2 F][K], rows [64 b, 64 b + 32) = gate rows [32 b, 32 b + 32), rows [64 b + 32, 64 b + 64) =
+    the up rows of the same outputs; F % 32 == 0."""
+    gate, up = np.asarray(gate), np.asarray(up)
+    F, K = gate.shape
+    out = np.empty((2 * F, K), gate.dtype)
+    for b in range(F // 32):
+        out[64 * b:64 * b + 32] = gate[32 * b:32 * b + 32]
+        out[64 * b + 32:64 * b + 64] = up[32 * b:32 * b + 32]
+    return out
+
+
+def fp8_weight_ref(w, sc_image, n_total: int, n0: int):
+    """launch_pack_fp8_weight on w [N][K] (K % 128 == 0): oracle.mx_oracle.mx_quant's e4m3 elements [N][K] (in units of their
+    block's scale) and the scale image after the call - a copy of sc_image [K / 128][n_total] dwords with the E8M0 byte of block
+    (n, k / 32) placed in dword (k / 128) * n_total + n0 + n, byte (k % 128) / 32 (little endian); every other byte as it was."""
+    from oracle.mx_oracle import mx_quant
+    w = np.asarray(w, np.float32)
+    N, K = w.shape
+    _, q, sb = mx_quant(w)
+    img = np.array(sc_image, np.uint32).reshape(K // 128, n_total).view(np.uint8).reshape(K // 128, n_total, 4)
+    for kb in range(K // 32):
+        img[kb // 4, n0:n0 + N, kb % 4] = sb[:, kb]
+    return q, img.reshape(K // 128, n_total * 4).view(np.uint32)
+
+
+def ingest_float_planes(n: int, h: int, w: int, ps: int, seed: int) -> np.ndarray:
+    """The float frames of the ingest tests, fp32 [n][h][w]: the pixels past the last whole patch hold NaN (never read); the
+    pixels read hold, at random places, 0, -0.0, 1.0, the 256 values k / 255, values below 2^-14 (hi subnormal) and below 2^-24
+    (hi zero or the smallest subnormal), and uniforms in [0, 1) everywhere else."""
+    rng = np.random.default_rng(seed)
+    nh, nw = h // ps, w // ps
+    m = n * nh * ps * nw * ps
+    tiny = [2.0 ** -14, 1.5 * 2.0 ** -15, 2.0 ** -14 - 2.0 ** -25, 1.3 * 2.0 ** -20, -1.3 * 2.0 ** -20, 2.0 ** -24, 3 * 2.0 ** -25,
+            2.0 ** -25, 1.0001 * 2.0 ** -25, 2.0 ** -26, 1.7 * 2.0 ** -30, 2.0 ** -126, 2.0 ** -149]
+    special = np.concatenate([[0.0, -0.0, 1.0], np.arange(256) / 255.0, tiny]).astype(np.float32)
+    vals = rng.random(m, np.float32)
+    assert m >= 2 * len(special)
+    vals[rng.permutation(m)[:len(special)]] = special
+    g = np.full((n, h, w), np.nan, np.float32)
+    g[:, :nh * ps, :nw * ps] = vals.reshape(n, nh * ps, nw * ps)
+    return g

@@ -1371,3 +1371,106 @@ def test_expand_temporal_defects_leave_the_rounded_reference():
 
 def test_zz_expand_print_the_largest_emulation_ratios():
     print(f"[expand bounds] largest emulation error / bound: {_expand_worst}")
+
+
+# ---- ViT ingest and the create-time weight packers (tests/test_gpu_ingest_reference.py): the exact references ----------------------
+@pytest.mark.parametrize("ps", [14, 16])
+def test_ingest_slot_layout_is_the_models_patch_convolution(ps):
+    """vit_im2col_ref(g) @ patch_weight_ref(w).T against oracle/vit_oracle.embeddings on the 3-times repeated green plane: ties the
+    slot layout of the two references to the model definition, not to each other.  Pixels are bytes and the weights multiples of
+    2^-4 below 2, so every product, every channel sum and every dot product (below 2^19, in steps of 2^-4: 23 bits) is exact in
+    float32 and float64 alike, whatever the order - embeddings rounds its result to float32 - and the comparison is equality."""
+    from oracle import vit_oracle as V
+    rng = np.random.default_rng(50 + ps)
+    n, h, w, D = 2, 2 * ps + 3, 3 * ps + 5, 5
+    g = rng.integers(0, 256, (n, h, w)).astype(np.float64)
+    wt = (rng.integers(-31, 32, (D, 3, ps, ps)) / 16.0).astype(F32)
+    A, owned = R.vit_im2col_ref(g, ps)
+    assert owned.sum() == 16 * ps and not A[:, ~owned].any()
+    for wide in (False, True):
+        got = A @ R.patch_weight_ref(wt, ps, wide).astype(np.float64).T
+        weights = {"embeddings.patch_embeddings.weight": wt.astype(np.float64), "embeddings.patch_embeddings.bias": np.zeros(D),
+                   "embeddings.cls_token": np.zeros((1, 1, D)), "embeddings.register_tokens": np.zeros((1, 0, D))}
+        want = V.embeddings(np.repeat(g[:, None], 3, axis=1), weights, ps)[:, 1:]
+        assert want.shape == (n, 6, D) and np.array_equal(got.reshape(n, 6, D), want.astype(np.float64))
+    # a py / px swap or a transposed slot is another matrix
+    swapped = A.reshape(n, 2, 3, 256).transpose(0, 2, 1, 3).reshape(n * 6, 256)
+    assert not np.array_equal(swapped, A) and not np.array_equal(A.reshape(-1, 16, 16).transpose(0, 2, 1).reshape(-1, 256), A)
+
+
+def test_patch_weight_sums_differ_between_float32_and_float64_on_cancelling_triples():
+    w = np.zeros((1, 3, 14, 14), F32)
+    w[0, :, 0, 0] = [1.0, 2.0 ** -30, -1.0]                       # float32: (1 + 2^-30) - 1 = 0; float64: 2^-30
+    w[0, :, 0, 1] = [16777216.0, 1.0, 1.0]                        # float32: 2^24 + 1 -> 2^24 (tie to even), + 1 -> 2^24; float64: 2^24 + 2
+    n32, n64 = R.patch_weight_ref(w, 14, False), R.patch_weight_ref(w, 14, True)
+    assert n32[0, 0] == 0.0 and n64[0, 0] == F32(2.0 ** -30)
+    assert n32[0, 1] == F32(16777216.0) and n64[0, 1] == F32(16777218.0)
+    assert not n32[0, 14:16].any() and not n32[0, 14 * 16:].any()
+
+
+@pytest.mark.parametrize("ps", [14, 16])
+def test_ingest_hi_lo_reproduce_the_float_inputs(ps):
+    """hi + lo against v on the float frames of the GPU suite.  hi is off by at most 2^-11 |v|; lo rounds that residual to 2^-11 of
+    itself - 2^-22 |v| in all - wherever the residual is a normal fp16 (>= 2^-14) or zero.  A smaller residual lands on fp16's
+    subnormal grid (step 2^-24) and is off by up to F16_SUB = 2^-25 instead: no pair of fp16 values does better there (a value below
+    2^-25 is lost whole), which is why kernels.h promises x = hi + lo to about 2^-22 for pixels in [0, 1], not relative to x."""
+    g = R.ingest_float_planes(3, 2 * ps + 3, 3 * ps + 5, ps, 700 + ps)
+    v, _ = R.vit_im2col_ref(g, ps)
+    assert np.isfinite(v).all(), "the NaN remainder was gathered"
+    hi, lo = R.f16_pair(v)
+    v64 = v.astype(np.float64)
+    err = np.abs(hi.astype(np.float64) + lo.astype(np.float64) - v64)
+    resid = np.abs((v - hi.astype(F32)).astype(np.float64))
+    normal = (resid >= 2.0 ** -14) | (resid == 0)
+    assert normal.sum() > 100 and (~normal).sum() > 100
+    assert (err[normal] <= 2.0 ** -22 * np.abs(v64[normal])).all()
+    assert (err[~normal] <= R.F16_SUB).all()
+    assert np.array_equal(R.split_value(v, 1.0), hi.astype(np.float64) + lo.astype(np.float64))
+    # the inputs do reach the edges they are there for: hi subnormal, hi zero with v != 0, -0.0 kept
+    assert ((np.abs(hi) < 2.0 ** -14) & (hi != 0)).any() and ((hi == 0) & (v != 0)).any()
+    assert (np.signbit(v) & (v == 0)).any() and np.array_equal(hi[v == 0].view(np.uint16), v[v == 0].view(np.uint32) >> 16)
+    # the split image is the same pair, placed: decode_split_operand undoes split_operand_bits
+    img = R.split_operand_bits(v, 1.0).view(F32)
+    assert np.array_equal(R.decode_split_operand(img, 256, 1.0), R.split_value(v, 1.0))
+
+
+def test_u8_to_unit_f32_is_the_reference_preprocessing():
+    from oracle import vit_oracle as V
+    p = np.arange(256, dtype=np.uint8)
+    want = V.preprocess_green(np.repeat(p.reshape(1, 16, 16, 1), 3, axis=3)).reshape(-1)
+    assert np.array_equal(R.u8_to_unit_f32(p).view(np.uint32), want.view(np.uint32))
+    # a kernel that multiplied by the rounded reciprocal instead of dividing would show on these 256 values
+    assert (R.u8_to_unit_f32(p) != p.astype(F32) * F32(1.0 / 255.0)).any()
+
+
+@pytest.mark.parametrize("F,K", [(32, 1), (32, 5), (96, 40)])
+def test_interleave_ref_is_a_permutation_with_an_inverse(F, K):
+    gate = (np.arange(F * K, dtype=np.int64).reshape(F, K)).astype(F32)
+    up = gate + F32(F * K)
+    out = R.interleave_ref(gate, up)
+    assert out.shape == (2 * F, K) and np.array_equal(np.sort(out.reshape(-1)), np.arange(2 * F * K, dtype=F32))
+    blocks = out.reshape(F // 32, 2, 32, K)
+    assert np.array_equal(blocks[:, 0].reshape(F, K), gate) and np.array_equal(blocks[:, 1].reshape(F, K), up)
+    # the index formula of kernels.h, element by element
+    for r in range(2 * F):
+        src = (gate if r % 64 < 32 else up)[32 * (r // 64) + r % 32]
+        assert np.array_equal(out[r], src)
+
+
+def test_fp8_weight_ref_routes_three_calls_into_one_scale_image():
+    from oracle.mx_oracle import mx_quant
+    rng = np.random.default_rng(81)
+    N, K = 3, 256
+    nt = 3 * N + 4
+    img = np.full((K // 128, nt), 0xA5A5A5A5, np.uint32)
+    ws = [rng.standard_normal((N, K)).astype(F32) * F32(10.0 ** i) for i in range(3)]
+    for i, n0 in enumerate((0, N, 2 * N + 4)):
+        q, img = R.fp8_weight_ref(ws[i], img, nt, n0)
+        assert np.array_equal(q, mx_quant(ws[i])[1])
+    by = img.view(np.uint8).reshape(K // 128, nt, 4)
+    for i, n0 in enumerate((0, N, 2 * N + 4)):
+        sb = mx_quant(ws[i])[2]
+        for n in range(N):
+            for k in range(0, K, 32):
+                assert by[k // 128, n0 + n, (k % 128) // 32] == sb[n, k // 32]
+    assert (img[:, 2 * N:2 * N + 4] == 0xA5A5A5A5).all()
