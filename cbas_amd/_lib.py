@@ -190,6 +190,7 @@ DEBUG_SIGNATURES = {
     "cbas_head_debug_expand_repeat": (c_int, [c_void_p, c_int, c_int]),
     "cbas_head_debug_expand_stats": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int]),
     "cbas_debug_gemm_run": (c_int, [c_void_p]),
+    "cbas_debug_gemm_f8_run": (c_int, [c_void_p]),
     "cbas_debug_attention_run": (c_int, [c_void_p]),
     "cbas_debug_cls_attention": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p]),
     "cbas_debug_attention_mean": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_int64, c_int, c_void_p]),

@@ -727,6 +727,105 @@ extern "C" int cbas_debug_gemm_run(const cbas_debug_gemm_args* a) {
     return CBAS_OK;
 }
 
+// ONE MX-fp8 launch as vit_qkv / vit_tail issue it (see the header): M_pad, sc_lda and the W window (n0, n_total) are the
+// caller's, the operand and scale arrays are allocated at exactly the sizes the launch is told about.
+extern "C" int cbas_debug_gemm_f8_run(const cbas_debug_gemm_f8_args* a) {
+    if (!a || a->struct_bytes != (int64_t)sizeof(cbas_debug_gemm_f8_args))
+        return cbas_fail(CBAS_EINVAL, "cbas_debug_gemm_f8_args: struct_bytes %lld, library expects %lld", a ? (long long)a->struct_bytes : -1ll,
+                         (long long)sizeof(cbas_debug_gemm_f8_args));
+    const int epi = a->epi;
+    if (epi != EPI_QKV && epi != EPI_RESID && epi != EPI_GELU) return cbas_fail(CBAS_EINVAL, "epi %d: EPI_QKV, EPI_RESID or EPI_GELU", epi);
+    if (a->tile != 0 && (a->tile < GEMM_TILE_PP_256x256 || a->tile > GEMM_TILE_PP_AUTO)) return cbas_fail(CBAS_EINVAL, "tile %d: 0 or 13..17", a->tile);
+    if (a->M <= 0 || a->M_alloc < a->M || a->N <= 0 || a->N % 256 || a->K <= 0 || a->K % 256 || a->sc_lda < a->M_alloc || a->n0 < 0 ||
+        (int64_t)a->n0 + a->N > a->n_total || a->ldo < a->N || a->out_rows < a->M || a->group_m < 0)
+        return cbas_fail(CBAS_EINVAL, "bad fp8 GEMM test shape (N %% 256, K %% 256, M <= M_alloc <= sc_lda, n0 + N <= n_total, N <= ldo, M <= out_rows)");
+    if ((int64_t)a->M_alloc * a->K >= (1ll << 31) || (int64_t)a->n_total * a->K >= (1ll << 31))
+        return cbas_fail(CBAS_EINVAL, "operands beyond the kernel's 32-bit byte offsets");
+    if (!a->A8 || !a->A_sc || !a->W8 || !a->W_sc || !a->bias || !a->out || (a->quantise && (!a->A || !a->W)) || (epi == EPI_RESID && !a->lambda))
+        return cbas_fail(CBAS_EINVAL, "fp8 GEMM test: missing pointer (quantise needs A and W, EPI_RESID lambda)");
+    const bool rope = epi == EPI_QKV && a->rope_cos && a->rope_sin;
+    if (epi == EPI_QKV && (a->T <= 0 || a->n_prefix < 0 || a->D <= 0 || a->D % 64 || a->N % a->D || a->sec0 < 0 || a->N / a->D + a->sec0 > 3))
+        return cbas_fail(CBAS_EINVAL, "EPI_QKV needs T, n_prefix, D %% 64 == 0, N a multiple of D and sec0 + N / D <= 3");
+    if (rope && (a->rope_nh <= 0 || a->rope_nw <= 0 || a->P != a->rope_nh * a->rope_nw || a->T > a->n_prefix + a->P))
+        return cbas_fail(CBAS_EINVAL, "RoPE: P = nh x nw and T <= n_prefix + P");
+    const int M_alloc = a->M_alloc, N = a->N, K = a->K, n_total = a->n_total;
+    const bool out16 = epi != EPI_RESID;
+    const size_t osz = (size_t)a->out_rows * a->ldo * (out16 ? 2 : 4);
+    const size_t na = (size_t)M_alloc * K, nw = (size_t)n_total * K;
+    const size_t nsa = (size_t)(K / 128) * a->sc_lda, nsw = (size_t)(K / 128) * n_total;       // dwords
+    DevBufs B;
+    uint8_t *A8, *W8;
+    uint32_t *Asc, *Wsc;
+    float *bias, *lam = nullptr, *rc = nullptr, *rs = nullptr, *fac = nullptr;
+    void* out;
+    HIP_TRY(B.alloc(&A8, na));
+    HIP_TRY(B.alloc(&W8, nw));
+    HIP_TRY(B.alloc(&Asc, nsa * 4));
+    HIP_TRY(B.alloc(&Wsc, nsw * 4));
+    HIP_TRY(B.alloc(&bias, (size_t)N * 4));
+    HIP_TRY(B.alloc(&out, osz));
+    HIP_TRY(hipMemcpy(A8, a->A8, na, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(W8, a->W8, nw, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(Asc, a->A_sc, nsa * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(Wsc, a->W_sc, nsw * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(bias, a->bias, (size_t)N * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(out, a->out, osz, hipMemcpyHostToDevice));
+    if (a->lambda) { HIP_TRY(B.alloc(&lam, (size_t)N * 4)); HIP_TRY(hipMemcpy(lam, a->lambda, (size_t)N * 4, hipMemcpyHostToDevice)); }
+    if (a->quantise) {
+        float *A32, *W32;
+        HIP_TRY(B.alloc(&A32, na * 4));
+        HIP_TRY(B.alloc(&W32, nw * 4));
+        HIP_TRY(hipMemcpy(A32, a->A, na * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(W32, a->W, nw * 4, hipMemcpyHostToDevice));
+        LAUNCH_TRY(launch_pack_fp8_weight(A32, A8, Asc, M_alloc, K, a->sc_lda, 0, 0));
+        LAUNCH_TRY(launch_pack_fp8_weight(W32, W8, Wsc, n_total, K, n_total, 0, 0));
+    }
+    const int nh = a->rope_nh, nwd = a->rope_nw;
+    if (rope) {
+        const size_t nt = (size_t)a->P * 64;
+        HIP_TRY(B.alloc(&rc, nt * 4));
+        HIP_TRY(B.alloc(&rs, nt * 4));
+        HIP_TRY(hipMemcpy(rc, a->rope_cos, nt * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(rs, a->rope_sin, nt * 4, hipMemcpyHostToDevice));
+        if (a->rope_lds) {             // the by-axis copy, built from the tables as cbas_debug_gemm_run builds it
+            std::vector<float> f((size_t)(nh + nwd) * 32);
+            for (int iy = 0; iy < nh; ++iy)
+                for (int d = 0; d < 16; ++d) {
+                    f[(size_t)iy * 32 + d] = a->rope_cos[(size_t)(iy * nwd) * 64 + d];
+                    f[(size_t)iy * 32 + 16 + d] = a->rope_sin[(size_t)(iy * nwd) * 64 + d];
+                }
+            for (int ix = 0; ix < nwd; ++ix)
+                for (int d = 0; d < 16; ++d) {
+                    f[(size_t)(nh + ix) * 32 + d] = a->rope_cos[(size_t)ix * 64 + 16 + d];
+                    f[(size_t)(nh + ix) * 32 + 16 + d] = a->rope_sin[(size_t)ix * 64 + 16 + d];
+                }
+            HIP_TRY(B.alloc(&fac, f.size() * 4));
+            HIP_TRY(hipMemcpy(fac, f.data(), f.size() * 4, hipMemcpyHostToDevice));
+        }
+    }
+    GemmParams p{};
+    p.tile = a->tile; p.group_m = a->group_m;
+    p.A8 = A8; p.A_sc = Asc; p.sc_lda = a->sc_lda; p.lda = K;
+    p.W8 = W8 + (size_t)a->n0 * K; p.W_sc = Wsc + a->n0;
+    if (n_total != N) p.sc_ldw = n_total;
+    p.M = a->M; p.M_pad = M_alloc; p.N = N; p.K = K; p.bias = bias; p.lambda = lam; p.ldo = a->ldo;
+    if (out16) p.out_f16 = (f16*)out; else p.out_f32 = (float*)out;
+    p.tokens_per_frame = a->T; p.n_prefix = a->n_prefix; p.D = a->D; p.sec0 = a->sec0;
+    p.rope_cos = rc; p.rope_sin = rs; p.rope_fac = fac; p.rope_nh = nh; p.rope_nw = nwd;
+    p.rope_magic = rope ? (unsigned)((1ull << 32) / (unsigned)nwd) + 1u : 0u;
+    const int rcode = launch_gemm((GemmEpilogue)epi, p, 0);
+    if (rcode) return cbas_fail(CBAS_EINVAL, "fp8 GEMM launch failed (epi %d, tile %d: rc=%d)", epi, a->tile, rcode);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(a->out, out, osz, hipMemcpyDeviceToHost));
+    if (a->quantise) {
+        HIP_TRY(hipMemcpy(a->A8, A8, na, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(a->W8, W8, nw, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(a->A_sc, Asc, nsa * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(a->W_sc, Wsc, nsw * 4, hipMemcpyDeviceToHost));
+    }
+    return CBAS_OK;
+}
+
 extern "C" int cbas_debug_attention_run(const cbas_debug_attention_args* a) {
     if (!a || a->struct_bytes != (int64_t)sizeof(cbas_debug_attention_args))
         return cbas_fail(CBAS_EINVAL, "cbas_debug_attention_args: struct_bytes %lld, library expects %lld", a ? (long long)a->struct_bytes : -1ll,

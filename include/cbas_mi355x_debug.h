@@ -135,6 +135,41 @@ typedef struct cbas_debug_gemm_args {
 } cbas_debug_gemm_args;
 int cbas_debug_gemm_run(const cbas_debug_gemm_args* a);
 
+/* Tests: ONE MX-fp8 GEMM launch (gemm_f16_8ph.hip, F8 = true) as api_enc.hip's vit_qkv / vit_tail issue it
+ * (tests/test_gpu_fp8_gemm_reference.py compares it with the float64 product of exactly the bytes and scales it was given).
+ *   epi      EPI_QKV 1 (fp16 out), EPI_RESID 2 (fp32 out: rows < M of `out` hold the residual), EPI_GELU 3 (fp16 out)
+ *   tile     0 = launch_gemm's own choice (the 128-row tile, or the planner from 120 256-row tiles on), 13..17 = a ping-pong tile
+ *   M_alloc  rows of A, passed as M_pad (>= M, any value: the kernel clamps its A rows and scale rows at M_alloc - 1)
+ *   sc_lda   row stride of the A scale image in dwords (>= M_alloc)
+ *   n_total, n0   W and its scale image have n_total rows; the launch multiplies by rows n0 .. n0 + N: W8 + n0 K, W_sc + n0 and,
+ *            when n_total != N, sc_ldw = n_total (how vit_qkv hands the k | v weights of the fused q|k|v image to the launch)
+ *   quantise 1: A [M_alloc][K] and W [n_total][K] are fp32 and are packed on the device with launch_pack_fp8_weight; the bytes and
+ *               scale images come back in A8 / A_sc / W8 / W_sc
+ *            0: A8 / A_sc / W8 / W_sc are the operands, used as given (A and W are not read)
+ *   In both forms the four arrays are uploaded first, so what the packer does not write (scale dwords of rows M_alloc .. sc_lda)
+ *   keeps the caller's fill.  A8 [M_alloc][K], A_sc [K/128][sc_lda], W8 [n_total][K], W_sc [K/128][n_total]: exactly these sizes
+ *   are allocated on the device.  Byte b of a scale dword = block b of that 128-wide K-tile.
+ *   The q|k|v fields, bias, lambda and out ([out_rows][ldo], uploaded first, copied back whole) are those of cbas_debug_gemm_args.
+ * N % 256 == 0, K % 256 == 0. */
+typedef struct cbas_debug_gemm_f8_args {
+    int64_t struct_bytes;        /* sizeof(cbas_debug_gemm_f8_args): a mismatch is rejected */
+    int epi, tile, group_m, quantise;
+    int M, M_alloc, N, K, sc_lda, n_total, n0, ldo, out_rows;
+    int D, sec0, T, n_prefix, P, rope_nh, rope_nw, rope_lds;
+    const float* A;              /* quantise 1: [M_alloc][K] */
+    const float* W;              /* quantise 1: [n_total][K] */
+    uint8_t* A8;                 /* [M_alloc][K] e4m3 bytes: out (quantise 1) / in (0) */
+    uint32_t* A_sc;              /* [K/128][sc_lda] */
+    uint8_t* W8;                 /* [n_total][K] */
+    uint32_t* W_sc;              /* [K/128][n_total] */
+    const float* bias;           /* [N] */
+    const float* lambda;         /* [N] (EPI_RESID), or NULL */
+    const float* rope_cos;       /* [P][64] (EPI_QKV), or NULL: no RoPE */
+    const float* rope_sin;
+    void* out;                   /* in / out: [out_rows][ldo], fp16 (EPI_QKV / EPI_GELU) or fp32 (EPI_RESID) */
+} cbas_debug_gemm_f8_args;
+int cbas_debug_gemm_f8_run(const cbas_debug_gemm_f8_args* a);
+
 /* Tests: ONE attention launch on a host q|k|v image [rows_alloc][3D] (q already x 1/8 and RoPE'd; rows_alloc >= n T, the
  * rows past n T are uploaded as given).  arith 0: fp16 operands (launch_attention); 3: fp32 (launch_attention_f32); 4: the
  * head-split operands of precision 4 (packed with store_head_split4 and the ATT_* scales), context in the split operand

@@ -3,7 +3,7 @@ exact precision-3 accumulator, the row-wise kernels between the GEMMs (LayerNorm
 producers), and element-wise error bounds derived from where each kernel rounds.
 
 Used by tests/test_gpu_kernel_reference.py (the kernels through cbas_debug_gemm_run / cbas_debug_attention_run),
-tests/test_gpu_rows_reference.py (cbas_debug_rows_run), tests/test_gpu_head_kernels_reference.py (the classifier head's
+tests/test_gpu_fp8_gemm_reference.py (the MX-fp8 GEMM through cbas_debug_gemm_f8_run), tests/test_gpu_rows_reference.py (cbas_debug_rows_run), tests/test_gpu_head_kernels_reference.py (the classifier head's
 exact-fp32 GEMM and small training kernels through cbas_debug_head_run), tests/test_gpu_head_seq_reference.py and
 tests/test_gpu_head_expand_reference.py (the head's sequential and expand kernels through cbas_debug_head_seq_run /
 cbas_debug_head_expand_run), tests/test_gpu_ingest_reference.py (the ViT ingest kernels and the create-time weight packers
@@ -13,7 +13,7 @@ references and bounds themselves, on the CPU).
 Units: u32 = 2^-24 (fp32 unit roundoff), u16 = 2^-11 (fp16).  A bound is a float64 array shaped like the output; a kernel
 output y passes when |y - ref| <= bound everywhere (non-finite y never passes).  Every bound is a sum of the terms its
 docstring names; no term is fitted to measured errors, except the device math library's budgets in the classifier-head
-section, which are measured as their comment describes.
+section and the scaled MFMA's accumulation (MX_ACC_U), which are measured as their comments describe.
 """
 from __future__ import annotations
 
@@ -151,6 +151,82 @@ def gemm_acc(arith: int, A, W, a_scale: float = 1.0, w_scale: float = 1.0):
         sub = (np.ones_like(a) / a_scale) @ np.abs(w).T + np.abs(a) @ (np.ones_like(w) / w_scale).T
         E = E + 3 * 2.0 ** -22 * S + 2 * F16_SUB * sub
     return acc, E, S
+
+
+# ---- MX-fp8 operands (gemm_f16_8ph.hip, F8 = true) ---------------------------------------------------------------------
+# Used by tests/test_gpu_fp8_gemm_reference.py through cbas_debug_gemm_f8_run.  The reference is the float64 product of exactly
+# the e4m3 bytes and E8M0 scale bytes the launch was given; the epilogues and their bounds are those of the fp16 form above.
+#
+# MX_ACC_U: the accumulator's error per unit of S = sum_k |a_k w_k|.  v_mfma_scale_f32_16x16x128_f8f6f4 does not accumulate its
+# 128 products as an fp32 fma chain, and no public document gives its internal alignment, so this ONE figure is measured, not
+# derived: the largest |kernel - acc| / S of the accumulator-only launch (residual epilogue on x = 0, bias 0, lambda 1) against
+# the float64 product of the dequantised operands, over every random-operand case and tile form of
+# tests/test_gpu_fp8_gemm_reference.py (mx_random_cases), doubled for operand draws not in the suite and rounded up to a power
+# of two.  Measured on an MI355X on 2026-10-21: see MX_ACC_MEASURED below.  It must stay <= 2^-11: above that a single
+# mis-decoded element at K = 256 (~S / 256) is no longer reliably outside the bound (tests/test_kernel_reference_bounds.py).
+MX_ACC_MEASURED = 1.18e-4     # = 2^-13.05: the largest |kernel - acc| / S seen (tile forms q|k|v operands, M 1015 N 768 K 256)
+MX_ACC_U = 2.0 ** -12         # 2 x 1.18e-4 = 2.36e-4, rounded up to a power of two (2.44e-4)
+MX_INT_BYTE = {0: 0x00, 1: 0x38, 2: 0x40, 3: 0x44, 4: 0x48}      # e4m3 codes of the lossless cases' magnitudes
+
+
+def mx_dequant(bytes8, sc_image, rows: int, ld: int) -> np.ndarray:
+    """float64 [rows][K] of e4m3 bytes [rows][K] and the scale image [K / 128][ld] dwords (byte b of dword (t, r) = the E8M0
+    scale of block b of K-tile t of row r, GemmParams A_sc / W_sc): oracle.mx_oracle.e4m3_decode x 2^(scale byte - 127).
+    The e4m3 NaN codes (0x7f, 0xff) and the E8M0 NaN (0xff) give NaN."""
+    from oracle.mx_oracle import e4m3_decode
+    b = np.asarray(bytes8, np.uint8)
+    assert b.shape[0] == rows and b.shape[1] % 128 == 0
+    K = b.shape[1]
+    sb = np.ascontiguousarray(np.asarray(sc_image, np.uint32).reshape(K // 128, ld)).view(np.uint8).reshape(K // 128, ld, 4)
+    sb = sb[:, :rows].transpose(1, 0, 2).reshape(rows, K // 32).astype(np.float64)
+    scale = np.where(sb == 255.0, np.nan, np.exp2(sb - 127.0))
+    el = np.where((b & 0x7f) == 0x7f, np.nan, e4m3_decode(b).astype(np.float64))
+    return el * np.repeat(scale, 32, axis=1)
+
+
+def mx_scale_image(sb, ld: int, fill: int = 0xFFFFFFFF) -> np.ndarray:
+    """The inverse of mx_dequant's scale routing: scale bytes [rows][K / 32] -> dwords [K / 128][ld], rows past `rows` = fill."""
+    sb = np.asarray(sb, np.uint8)
+    rows, nb = sb.shape
+    img = np.full((nb // 4, ld), fill, np.uint32)
+    img.view(np.uint8).reshape(nb // 4, ld, 4)[:, :rows] = sb.reshape(rows, nb // 4, 4).transpose(1, 0, 2)
+    return img
+
+
+def gemm_acc_mx(a, w):
+    """Accumulator reference of the MX-fp8 GEMM on dequantised operands a [M][K], w [N][K] (float64, mx_dequant): (acc, E, S)
+    with acc = a w^T, S = |a| |w|^T and E = MX_ACC_U S; feeds gemm_epilogue_ref / out_rounding like gemm_acc's triple."""
+    a = np.asarray(a, np.float64)
+    w = np.asarray(w, np.float64)
+    acc = a @ w.T
+    S = np.abs(a) @ np.abs(w).T
+    return acc, MX_ACC_U * S, S
+
+
+def mx_int_bytes(v) -> np.ndarray:
+    """e4m3 bytes of integers in [-4, 4] (exactly representable)."""
+    v = np.asarray(v, np.int64)
+    lut = np.array([MX_INT_BYTE[i] for i in range(5)], np.uint8)
+    return (lut[np.abs(v)] | np.where(v < 0, 0x80, 0).astype(np.uint8)).astype(np.uint8)
+
+
+def mx_lossless_case(M_alloc: int, n_total: int, K: int, seed: int, sc_lda: int, sb_lo: int = 125, sb_hi: int = 129):
+    """The lossless operands of the bit-for-bit cases: elements drawn from {0, +-1, .., +-4}, every (row, block) scale byte
+    drawn independently from sb_lo .. sb_hi, for A [M_alloc][K] and W [n_total][K].  Every product is an integer multiple of
+    2^(2 sb_lo - 254) no larger than 16 x 2^(2 sb_hi - 254), so any partial sum over K <= 768 stays below 2^24 units: exact in
+    fp32 in any order.  Returns dict(ai, wi (the integers), sa, sw (scale bytes), A8, W8, A_sc [K/128][sc_lda], W_sc [K/128][n_total])."""
+    rng = np.random.default_rng(seed)
+    ai = rng.integers(-4, 5, (M_alloc, K))
+    wi = rng.integers(-4, 5, (n_total, K))
+    sa = rng.integers(sb_lo, sb_hi + 1, (M_alloc, K // 32)).astype(np.uint8)
+    sw = rng.integers(sb_lo, sb_hi + 1, (n_total, K // 32)).astype(np.uint8)
+    return dict(ai=ai, wi=wi, sa=sa, sw=sw, A8=mx_int_bytes(ai), W8=mx_int_bytes(wi), A_sc=mx_scale_image(sa, sc_lda),
+                W_sc=mx_scale_image(sw, n_total))
+
+
+def mx_lossless_values(ints, sb) -> np.ndarray:
+    """What mx_lossless_case's operands mean: integer x 2^(scale byte - 127), float64 (exact)."""
+    return np.asarray(ints, np.float64) * np.repeat(np.exp2(np.asarray(sb, np.float64) - 127.0), 32, axis=1)
 
 
 def out_rounding(ref: np.ndarray, kind: str) -> np.ndarray:

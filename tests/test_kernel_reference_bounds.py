@@ -1474,3 +1474,159 @@ def test_fp8_weight_ref_routes_three_calls_into_one_scale_image():
             for k in range(0, K, 32):
                 assert by[k // 128, n0 + n, (k % 128) // 32] == sb[n, k // 32]
     assert (img[:, 2 * N:2 * N + 4] == 0xA5A5A5A5).all()
+
+
+# ---- the MX-fp8 GEMM: the bound of tests/test_gpu_fp8_gemm_reference.py at its cap, MX_ACC_U = 2^-11 ----------------------------
+MX_CAP = 2.0 ** -11
+
+
+def _mx_bytes(q) -> np.ndarray:
+    """e4m3 codes of values that ARE e4m3 numbers (mx_quant's elements)."""
+    from oracle.mx_oracle import e4m3_decode
+    table = e4m3_decode(np.arange(256, dtype=np.uint8)).astype(np.float64)
+    codes = np.concatenate([np.arange(0, 0x7F), np.arange(0x81, 0xFF)])           # no NaN codes, one zero
+    order = np.argsort(table[codes])
+    idx = np.searchsorted(table[codes][order], np.asarray(q, np.float64))
+    out = codes[order][idx].astype(np.uint8)
+    assert np.array_equal(table[out], np.asarray(q, np.float64))
+    return out
+
+
+def _mx_case(epi, seed, n_total=256, n0=0, D=128, sec0=0):
+    """Random operands as the GPU cases draw them (rows of different scale, every 7th column x 30, one all-zero row), quantised
+    on the CPU: K = 256, N = 256, M = 64 of M_alloc = 128 rows (rows 64 .. 127 are other rows' worth of scales)."""
+    from oracle.mx_oracle import mx_quant
+    rng = np.random.default_rng(seed)
+    M, M_alloc, N, K = 64, 128, 256, 256
+    A = (rng.standard_normal((M_alloc, K)) * np.exp(rng.standard_normal((M_alloc, 1)))).astype(np.float32)
+    A[:, ::7] *= 30.0
+    A[3] = 0.0
+    W = (rng.standard_normal((n_total, K)) * 0.05).astype(np.float32)
+    _, qa, sa = mx_quant(A)
+    _, qw, sw = mx_quant(W)
+    d = dict(M=M, N=N, K=K, n0=n0, A8=_mx_bytes(qa), W8=_mx_bytes(qw), sa=sa.astype(np.uint8), sw=sw.astype(np.uint8),
+             A_sc=R.mx_scale_image(sa, M_alloc + 128), W_sc=R.mx_scale_image(sw, n_total), sc_lda=M_alloc + 128, n_total=n_total,
+             bias=(0.5 * rng.standard_normal(N)).astype(np.float32))
+    if epi == R.EPI_RESID:
+        d.update(lam=(0.3 * rng.standard_normal(N)).astype(np.float32), x0=rng.standard_normal((M, N)).astype(np.float32))
+    if epi == R.EPI_QKV:
+        cos, sin = R.rope_cos_sin(5, 7, 64, 100.0)
+        d.update(D=D, sec0=sec0, T=40, n_prefix=5, cos=cos, sin=sin)
+    return d
+
+
+def _mx_operands(d, *, a_sc=None, a8=None, w_n0=None):
+    M, N = d["M"], d["N"]
+    n0 = d["n0"] if w_n0 is None else w_n0
+    a = R.mx_dequant((d["A8"] if a8 is None else a8)[:M], d["A_sc"] if a_sc is None else a_sc, M, d["sc_lda"])
+    w = R.mx_dequant(d["W8"][d["n0"]:d["n0"] + N], d["W_sc"][:, n0:n0 + N], N, N)
+    return a, w
+
+
+def _mx_acc32(a, w):
+    """fp32 accumulation block by block: each block's 32 products summed in fp32, the blocks chained in fp32."""
+    acc = np.zeros((a.shape[0], w.shape[0]), np.float32)
+    for k in range(0, a.shape[1], 32):
+        acc = acc + a[:, k:k + 32].astype(np.float32) @ w[:, k:k + 32].astype(np.float32).T
+    return acc
+
+
+def _mx_reference(epi, d):
+    a, w = _mx_operands(d)
+    acc = a @ w.T
+    S = np.abs(a) @ np.abs(w).T
+    y, Ey, _ = R.gemm_epilogue_ref(epi, acc, MX_CAP * S, S, bias=d["bias"], lam=d.get("lam"), x0=d.get("x0"), T=d.get("T"),
+                                   n_prefix=d.get("n_prefix", 0), cos=d.get("cos"), sin=d.get("sin"), D=d.get("D"), sec0=d.get("sec0", 0))
+    if epi == R.EPI_GELU:
+        v = acc + d["bias"][None, :]
+        Ey = Ey + 2e-7 * np.abs(v) + 8 * R.U32 * (np.abs(v) + np.abs(y))
+    return y, Ey + R.out_rounding(y, "f32" if epi == R.EPI_RESID else "f16")
+
+
+def _rows_rejected(out, y, bound):
+    return (np.where(np.isfinite(out), np.abs(out - y), np.inf) / bound).max(axis=1) > 1.0
+
+
+def test_mx_acc_u_is_within_the_cap_the_defect_tests_are_written_for():
+    assert R.MX_ACC_U <= MX_CAP and np.log2(R.MX_ACC_U) == round(np.log2(R.MX_ACC_U))
+    assert R.MX_ACC_MEASURED is None or 2.0 * R.MX_ACC_MEASURED <= R.MX_ACC_U < 4.0 * R.MX_ACC_MEASURED
+
+
+@pytest.mark.parametrize("epi", [R.EPI_QKV, R.EPI_RESID, R.EPI_GELU])
+def test_mx_gemm_bound_accepts_the_simulated_launch_and_rejects_operand_defects_row_by_row(epi):
+    d = _mx_case(epi, 300 + epi)
+    y, bound = _mx_reference(epi, d)
+    a, w = _mx_operands(d)
+    assert R.ratio(_simulate(0, epi, d, _mx_acc32(a, w)), y, bound) <= 1.0
+    M, K = d["M"], d["K"]
+    nz = np.any(a != 0.0, axis=1)
+    assert not nz[3] and nz.sum() == M - 1
+    sa = d["sa"].astype(np.int64)
+    # block b of an A row takes the scale byte of block b ^ 1
+    swapped = sa.reshape(sa.shape[0], -1, 2)[:, :, ::-1].reshape(sa.shape)
+    a_def, _ = _mx_operands(d, a_sc=R.mx_scale_image(swapped, d["sc_lda"]))
+    hit = np.any(a_def != a, axis=1)
+    assert hit.sum() >= M // 4                                                 # enough rows have neighbouring blocks of different scale
+    rej = _rows_rejected(_simulate(0, epi, d, _mx_acc32(a_def, w)), y, bound)
+    assert np.all(rej[hit]) and not np.any(rej[~hit]), "scale byte of block b ^ 1"
+    # a row's scale dword taken from row + 64
+    a_def, _ = _mx_operands(d, a_sc=R.mx_scale_image(np.roll(sa, -64, axis=0), d["sc_lda"]))
+    hit = np.any(a_def != a, axis=1)
+    assert hit.sum() >= M - 2
+    rej = _rows_rejected(_simulate(0, epi, d, _mx_acc32(a_def, w)), y, bound)
+    assert np.all(rej[hit]) and not np.any(rej[~hit]), "scale dword of row + 64"
+    # one e4m3 byte of a row replaced by its neighbour code: the row's largest element (a SMALL element's neighbour code moves the
+    # row by far less than S / 256 - no per-element bound at K = 256 can see that, and none is claimed)
+    a8 = d["A8"].copy()
+    k = np.argmax(np.abs(a), axis=1)
+    r = np.arange(M)
+    mag = a8[r, k] & 0x7F
+    a8[r, k] = (a8[r, k] & 0x80) | np.where(mag < 0x7E, mag + 1, mag - 1)
+    a_def, _ = _mx_operands(d, a8=a8)
+    rej = _rows_rejected(_simulate(0, epi, d, _mx_acc32(a_def, w)), y, bound)
+    assert np.all(rej[nz]), "neighbour code"
+
+
+def test_mx_gemm_bound_rejects_w_scales_read_at_column_0_of_the_fused_image():
+    """The k | v launch: n0 = D of a 3 D-wide image; the defect reads the q columns' scales."""
+    d = _mx_case(R.EPI_QKV, 41, n_total=384, n0=128, D=128, sec0=1)
+    y, bound = _mx_reference(R.EPI_QKV, d)
+    a, w = _mx_operands(d)
+    # _simulate rotates columns [0, 2 D) and scales [0, D): told D = 64 without the q scale it rotates k (columns [0, 128)) alone
+    def run(aa, ww):
+        return _simulate(0, R.EPI_QKV, dict(d, D=64), _mx_acc32(aa, ww), no_q_scale=True)
+
+    assert R.ratio(run(a, w), y, bound) <= 1.0
+    _, w_def = _mx_operands(d, w_n0=0)
+    assert np.any(w_def != w)
+    rej = _rows_rejected(run(a, w_def), y, bound)
+    nz = np.any(a != 0.0, axis=1)
+    assert np.all(rej[nz]) and not np.any(rej[~nz])
+
+
+def test_mx_gemm_bound_rejects_rope_on_a_prefix_row_and_a_missing_q_scale():
+    d = _mx_case(R.EPI_QKV, 42)
+    y, bound = _mx_reference(R.EPI_QKV, d)
+    a, w = _mx_operands(d)
+    acc32 = _mx_acc32(a, w)
+    rej = _rows_rejected(_simulate(0, R.EPI_QKV, d, acc32, rope_prefix=True), y, bound)
+    t = np.arange(d["M"]) % d["T"]
+    assert np.array_equal(rej, t == d["n_prefix"] - 1)                        # the last prefix row of each frame, nothing else
+    rej = _rows_rejected(_simulate(0, R.EPI_QKV, d, acc32, no_q_scale=True), y, bound)
+    assert np.all(rej)                                                        # the all-zero row too: its q is the bias
+
+
+@pytest.mark.parametrize("K", [256, 768])
+def test_mx_lossless_operands_are_the_integers_that_generated_them(K):
+    M_alloc, n_total, ld = 384, 768, 512
+    L = R.mx_lossless_case(M_alloc, n_total, K, 40 + K, ld)
+    a = R.mx_dequant(L["A8"], L["A_sc"], M_alloc, ld)
+    w = R.mx_dequant(L["W8"], L["W_sc"], n_total, n_total)
+    assert np.array_equal(a, R.mx_lossless_values(L["ai"], L["sa"])) and np.array_equal(w, R.mx_lossless_values(L["wi"], L["sw"]))
+    assert set(np.unique(L["ai"])) == set(range(-4, 5)) and set(np.unique(L["sa"])) == set(range(125, 130))
+    assert np.all(L["A_sc"][:, M_alloc:] == 0xFFFFFFFF)
+    # every partial sum, in any order, is an integer number of the smallest product 2^(2 * 125 - 254) = 2^-4 and below 2^24 of them
+    unit = 2.0 ** -4
+    S = (np.abs(a) @ np.abs(w).T) / unit
+    assert np.array_equal(S, np.round(S)) and S.max() < 2.0 ** 24
+    assert 768 * 16 * 2.0 ** (2 * 129 - 254) / unit < 2.0 ** 24               # and so would the worst draw at K = 768
