@@ -206,6 +206,14 @@ DEBUG_SIGNATURES = {
     "cbas_debug_pos_table": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
 }
 
+# include/cbas_mi355x_ext.h: the extension surface (cbasx_*), exported by both builds; the core tables above stay closed
+EXT_SIGNATURES = {
+    "cbasx_viterbi_scores": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
+    "cbasx_viterbi_workspace_bytes": (c_int64, [c_int64, c_int32, c_int32]),
+    "cbasx_viterbi_decode": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                     c_void_p]),
+}
+
 ENC_SLOTS = 3
 TRAIN_MULTI_MAX = 8                                   # CBAS_TRAIN_MULTI_MAX of include/cbas_mi355x.h
 POS_INTERP_BICUBIC_AA, POS_INTERP_BICUBIC = 0, 1      # CBAS_POS_INTERP_* of include/cbas_mi355x.h
@@ -257,7 +265,7 @@ def load(build_if_missing: bool = True):
                 print(f"cbas_amd: {path} is older than its sources; run `python -m cbas_amd.build` "
                       "(or set CBAS_AUTOBUILD=1)", file=sys.stderr)
         lib = C.CDLL(path)
-        for name, (res, args) in list(SIGNATURES.items()) + (list(DEBUG_SIGNATURES.items()) if debug else []):
+        for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + (list(DEBUG_SIGNATURES.items()) if debug else []):
             fn = getattr(lib, name)      # AttributeError if the .so lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

@@ -209,6 +209,12 @@ class FrameIndex:
         from . import probe as _probe
         return _probe.probe_labels(self, probe, **kw)
 
+    # ---- bouts (cbas_amd/bouts.py) ---------------------------------------------------------------------------------------------
+    def bouts(self, probs, transitions, prior=None, min_frames: int = 1):
+        """``bouts.index_bouts(self, probs, transitions, ...)``: the Viterbi bouts of every file from (N, C) probabilities."""
+        from . import bouts as _bouts
+        return _bouts.index_bouts(self, probs, transitions, prior=prior, min_frames=min_frames)
+
     # ---- motifs (cbas_amd/motifs.py) -------------------------------------------------------------------------------------------
     def cluster(self, n_clusters: int = 16, iters: int = 20, normalize: bool = True, init=None, clusters=None):
         """``motifs.cluster_frames(self, ...)``: ``(labels, dist2, clusters)``, every row's k-means motif."""
