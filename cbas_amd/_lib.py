@@ -212,6 +212,9 @@ EXT_SIGNATURES = {
     "cbasx_viterbi_workspace_bytes": (c_int64, [c_int64, c_int32, c_int32]),
     "cbasx_viterbi_decode": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                      c_void_p]),
+    "cbasx_hmm_workspace_bytes": (c_int64, [c_int64, c_int32, c_int32]),
+    "cbasx_hmm_posteriors": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
 ENC_SLOTS = 3

@@ -215,6 +215,12 @@ class FrameIndex:
         from . import bouts as _bouts
         return _bouts.index_bouts(self, probs, transitions, prior=prior, min_frames=min_frames)
 
+    def smooth(self, probs, transitions, prior=None, return_counts: bool = False, emission_prior=None):
+        """``bouts.index_posteriors(self, probs, transitions, ...)``: the forward-backward posteriors of every file, (N, C)
+        probabilities smoothed by the transition model and still graded."""
+        from . import bouts as _bouts
+        return _bouts.index_posteriors(self, probs, transitions, prior=prior, return_counts=return_counts, emission_prior=emission_prior)
+
     # ---- motifs (cbas_amd/motifs.py) -------------------------------------------------------------------------------------------
     def cluster(self, n_clusters: int = 16, iters: int = 20, normalize: bool = True, init=None, clusters=None):
         """``motifs.cluster_frames(self, ...)``: ``(labels, dist2, clusters)``, every row's k-means motif."""

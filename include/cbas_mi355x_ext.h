@@ -7,6 +7,8 @@
  *
  * Sequence decoding (csrc/seq_viterbi.hip): the most likely label sequence of every clip under a
  * first-order transition model, from per-frame probabilities that are already on the device.
+ * Forward-backward (csrc/seq_hmm.hip): the posterior probabilities of every frame under the same model,
+ * the expected transition counts and the log-likelihood.
  */
 #ifndef CBAS_MI355X_EXT_H
 #define CBAS_MI355X_EXT_H
@@ -62,6 +64,54 @@ int64_t cbasx_viterbi_workspace_bytes(int64_t n_total, int32_t n_clips, int32_t 
 int cbasx_viterbi_decode(const int32_t* scores_dev, int64_t n_total, const int64_t* clip_table_dev, int32_t n_clips, int32_t C,
                          const int32_t* log_trans_dev, const int32_t* log_prior_dev, int32_t* labels_dev,
                          int64_t* clip_score_dev, void* workspace_dev, int64_t workspace_bytes, void* stream);
+
+/* Forward-backward (csrc/seq_hmm.hip): the sum half of the same model.  Transitions and prior are
+ * float32 PROBABILITIES here, not integer scores: every entry finite and at least 0, every row (and the prior) summing to 1
+ * within CBASX_HMM_ROW_TOL. */
+#define CBASX_HMM_MAX_CLASSES 64
+/* Frames one wave walks; a clip of more frames is cut into pieces of this many, relative to its own first frame, as
+ * cbasx_viterbi_decode cuts it (the walk along the pieces of a 2 000 000-frame clip has about as many
+ * steps as the frame walk inside one piece). */
+#define CBASX_HMM_CHUNK 1024
+#define CBASX_HMM_FLOOR_LOG2 (-32)               /* an emission is max(p, 2^-32) */
+#define CBASX_HMM_ROW_TOL 1e-4f
+#define CBASX_HMM_FLAG_EMISSION 1u               /* *flags_dev: a probability of a clip's frame was a NaN or negative */
+#define CBASX_HMM_FLAG_POSTERIOR 2u              /* *flags_dev: alpha o beta of a frame summed to 0 or not finitely; its row is NaN */
+
+/* Bytes of workspace cbasx_hmm_posteriors needs for this shape, or -1 for a shape it refuses (n_total < 0, n_clips < 1,
+ * C outside 1 .. 64, more than 2^31 - 1 pieces).  With K = n_total / 1024 + n_clips and KT = 2 * (n_total / 1024) + 1, every
+ * part rounded up to 256 bytes: 256 + 2 * 4 n_clips + 2 * 8 (n_clips + 1) + KT * (4 C^2 + 12 C) + K * (8 C^2 + 8). */
+int64_t cbasx_hmm_workspace_bytes(int64_t n_total, int32_t n_clips, int32_t C);
+
+/* gamma_dev (n_total, C) float32: per clip of clip_table_dev (n_clips, 2) int64 = (first frame, frames), with frames
+ * 0 .. T-1, emissions b_t[j] = max(p_t[j], 2^-32) from probs_dev (n_total, C) float32, A[i][j] = trans_dev[i * C + j] (from
+ * state i to state j) and prior = prior_dev (NULL: 1 / C),
+ *     a_0 = prior o b_0,  a_t = (alpha_{t-1} A) o b_t,  alpha_t = a_t / sum(a_t),  loglik = sum_t log2 sum(a_t)
+ *     beta_{T-1} = 1,     beta_t ~ A (b_{t+1} o beta_{t+1})
+ *     gamma_t = alpha_t o beta_t / its sum
+ *     xi_t[i][j] = alpha_t[i] A[i][j] b_{t+1}[j] beta_{t+1}[j] / its sum over i, j
+ * gamma_t is P(state_t | the whole clip).  When not NULL, xi_dev (C, C) float64 gets the sum of xi_t over all clips and
+ * t < T-1, pi_dev (C) float64 the sum of gamma_0 over all clips, loglik_dev (n_clips) float64 every clip's log-likelihood in
+ * bits.  Frames outside every clip get a gamma row of zeros; a clip of 0 frames contributes nothing and has loglik 0.  alpha
+ * and beta run in float64 and are kept in range by powers of two only, never by each other's sums.  A NaN or negative
+ * probability inside a clip counts as 2^-32 and ORs CBASX_HMM_FLAG_EMISSION into *flags_dev; a frame whose alpha o beta sums to 0 or not finitely gets
+ * a row of NaN, counts nothing in xi and ORs CBASX_HMM_FLAG_POSTERIOR.  The caller zeroes *flags_dev.  gamma_dev must not
+ * overlap probs_dev: it holds alpha between the two passes, so no (n_total, C) workspace is needed.  Clips must not overlap.
+ *
+ * A clip of more than CBASX_HMM_CHUNK frames is cut into pieces and walked by several waves; the sums are added per clip in
+ * ascending piece order and then in ascending clip order in float64, without atomics, so two calls agree bit for bit and a
+ * clip's gamma and loglik depend neither on the other clips of the call nor on where the clip lies.  gamma does not depend
+ * on which of xi_dev / pi_dev / loglik_dev are NULL.
+ *
+ * Refusals (CBAS_EINVAL): a NULL pointer other than prior_dev / xi_dev / pi_dev / loglik_dev; C outside 1 .. 64; n_total < 0;
+ * n_clips < 1; a workspace smaller than cbasx_hmm_workspace_bytes or not 256-byte aligned; a table entry that reaches outside
+ * n_total; a transition row or a prior that is not finite, negative or off 1 by more than 1e-4.  The last three are found
+ * by one checking pass on the device that writes only into the workspace; the call SYNCHRONISES `stream` ONCE to read its
+ * verdict, exactly as cbasx_viterbi_decode does, and queues the kernels that write the outputs only after it.  So a refused
+ * call leaves gamma_dev, xi_dev, pi_dev and loglik_dev untouched, and an accepted call returns with the work queued. */
+int cbasx_hmm_posteriors(const float* probs_dev, int64_t n_total, const int64_t* clip_table_dev, int32_t n_clips, int32_t C,
+                         const float* trans_dev, const float* prior_dev, float* gamma_dev, double* xi_dev, double* pi_dev,
+                         double* loglik_dev, uint32_t* flags_dev, void* workspace_dev, int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
