@@ -417,7 +417,8 @@ def posteriors_host(probs, clip_table, transitions, prior=None, dtype=np.float64
             flags |= FLAG_POSTERIOR
         if n > 1:
             # sum_t xi_t = A * sum_t (alpha_t / Z_t) (x) W[t + 1], and Z_t = sum_ij alpha_t[i] A[i][j] W[t + 1][j] is the sum of xi_t
-            Xi += A.astype(np.float64) * (coef.astype(np.float64).T @ W[1:].astype(np.float64))
+            # (a coefficient of 0 does not silence a W that is not finite: 0 * inf is a NaN, so such a step's W goes too)
+            Xi += A.astype(np.float64) * (coef.astype(np.float64).T @ np.where(bad[:-1, None], 0, W[1:]).astype(np.float64))
         Pi += gamma[first].astype(np.float64)
     return gamma, Xi, Pi, loglik, flags
 

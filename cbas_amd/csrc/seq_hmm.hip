@@ -403,12 +403,13 @@ __device__ __forceinline__ float hm_backward_step(const float (&arow)[CP], int C
     bad |= !ok;
     const double inv = 1.0 / Z;
     if (XI) {
-        const double coef = ok ? (double)a_prev * inv : 0.0;   // a step without a posterior counts nothing
+        const double coef = ok ? (double)a_prev * inv : 0.0;   // a step without a posterior counts nothing: its w may be
+        const double wc = ok ? w : 0.0;                        // infinite, and 0 * inf would be a NaN
 #pragma unroll
         for (int j = 0; j < CP; ++j) {
             if (j < C) {
                 unsigned hi;
-                S[j] = fma(coef, hm_lane(w, j, hi), S[j]);
+                S[j] = fma(coef, hm_lane(wc, j, hi), S[j]);
             }
         }
     }
