@@ -286,6 +286,21 @@ def check(rc: int, what: str) -> None:
         raise RuntimeError(f"{what} failed (code {rc}): {msg.decode(errors='replace') if msg else '?'}")
 
 
+def workspace_bytes(name: str, *args) -> int:
+    """What the library's ``name`` (a ``*_workspace_bytes`` function) returns for ``args``; a refusal raises with the library's message."""
+    need = int(getattr(load(), name)(*args))
+    if need < 0:
+        check(need, name)
+    return need
+
+
+def workspace(name: str, device, *args):
+    """The workspace an entry point asks for: (a uint8 tensor on ``device``, its size in bytes)."""
+    import torch
+    need = workspace_bytes(name, *args)
+    return torch.empty(need, dtype=torch.uint8, device=device), need
+
+
 def device_info(device_id: int = 0):
     lib = load()
     buf = C.create_string_buffer(64)

@@ -244,10 +244,7 @@ def device_decode(scores: torch.Tensor, table: np.ndarray, A: np.ndarray, prior:
         prior_dev = None if prior is None else torch.from_numpy(prior).to(dev)
         labels = torch.empty(N, dtype=torch.int32, device=dev)
         clip_score = torch.empty(table.shape[0], dtype=torch.int64, device=dev)
-        need = int(lib.cbasx_viterbi_workspace_bytes(N, int(table.shape[0]), C))
-        if need < 0:
-            _lib.check(need, "cbasx_viterbi_workspace_bytes")
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws, need = _lib.workspace("cbasx_viterbi_workspace_bytes", dev, N, int(table.shape[0]), C)
         _lib.check(lib.cbasx_viterbi_decode(scores.data_ptr(), N, table_dev.data_ptr(), int(table.shape[0]), C, A_dev.data_ptr(),
                                             None if prior_dev is None else prior_dev.data_ptr(), labels.data_ptr(), clip_score.data_ptr(),
                                             ws.data_ptr(), need, torch.cuda.current_stream(dev).cuda_stream), "cbasx_viterbi_decode")
@@ -458,10 +455,7 @@ def device_posteriors(probs: torch.Tensor, table_dev: torch.Tensor, A_dev: torch
         xi = torch.empty((C, C), dtype=torch.float64, device=dev) if counts else None
         pi = torch.empty(C, dtype=torch.float64, device=dev) if counts else None
         loglik = torch.empty(n_clips, dtype=torch.float64, device=dev) if counts else None
-        need = int(lib.cbasx_hmm_workspace_bytes(N, n_clips, C))
-        if need < 0:
-            _lib.check(need, "cbasx_hmm_workspace_bytes")
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws, need = _lib.workspace("cbasx_hmm_workspace_bytes", dev, N, n_clips, C)
         src = probs if N else torch.empty((1, C), dtype=torch.float32, device=dev)
         _lib.check(lib.cbasx_hmm_posteriors(src.data_ptr(), N, table_dev.data_ptr(), n_clips, C, A_dev.data_ptr(),
                                             None if prior_dev is None else prior_dev.data_ptr(), store.data_ptr(),

@@ -42,6 +42,16 @@ static inline int cbas_fail(int code, const char* fmt, ...) {
                              hipGetErrorString(_e), __FILE__, __LINE__);                                           \
     } while (0)
 
+// makes the device that owns dev_ptr the calling thread's, as every entry point that takes device pointers and no handle does before
+// its first launch; 0, or CBAS_EHIP with the message set.  device: where to leave its number, or NULL
+static inline int cbas_use_device_of(const void* dev_ptr, int* device = nullptr) {
+    hipPointerAttribute_t attr;
+    HIP_TRY(hipPointerGetAttributes(&attr, dev_ptr));
+    HIP_TRY(hipSetDevice(attr.device));
+    if (device) *device = attr.device;
+    return CBAS_OK;
+}
+
 #define LAUNCH_TRY(expr)                                                                      \
     do {                                                                                       \
         int _r = (expr);                                                                       \

@@ -496,9 +496,7 @@ extern "C" int64_t cbas_disagreement_runs(const int32_t* pred_dev, const float* 
                          HEAD_SCORE_MAX_CLASSES);
     if (capacity < 0 || (capacity > 0 && !records_dev)) return cbas_fail(CBAS_EINVAL, "capacity=%lld with records_dev %s",
                                                                          (long long)capacity, records_dev ? "set" : "NULL");
-    hipPointerAttribute_t attr;
-    HIP_TRY(hipPointerGetAttributes(&attr, pred_dev));
-    HIP_TRY(hipSetDevice(attr.device));
+    if (cbas_use_device_of(pred_dev) != CBAS_OK) return CBAS_EHIP;
     hipStream_t st = (hipStream_t)stream;
     // scratch: [flags: 16 bytes][offsets: n_instances + 1 int64][counts: n_instances int32]
     RunsScratch scratch;
@@ -546,9 +544,7 @@ extern "C" int cbas_labels_median(const int32_t* pred_dev, int64_t n_frames_tota
                          "and 1 <= n_classes <= %d", (long long)n_frames_total, n_clips, n_classes, HEAD_SCORE_MAX_CLASSES);
     if (kernel_size < 1 || !(kernel_size & 1))
         return cbas_fail(CBAS_EINVAL, "cbas_labels_median: kernel_size=%d must be odd and >= 1", kernel_size);
-    hipPointerAttribute_t attr;
-    HIP_TRY(hipPointerGetAttributes(&attr, pred_dev));
-    HIP_TRY(hipSetDevice(attr.device));
+    if (cbas_use_device_of(pred_dev) != CBAS_OK) return CBAS_EHIP;
     hipStream_t st = (hipStream_t)stream;
     RunsScratch scratch;                                       // the flags: a 16-byte block
     HIP_TRY(hipMalloc(&scratch.p, 16));
@@ -575,9 +571,7 @@ extern "C" int64_t cbas_label_runs(const int32_t* key_dev, const float* conf_dev
     if (use_threshold && threshold != threshold) return cbas_fail(CBAS_EINVAL, "cbas_label_runs: the threshold is NaN");
     if (capacity < 0 || (capacity > 0 && !records_dev)) return cbas_fail(CBAS_EINVAL, "cbas_label_runs: capacity=%lld with records_dev %s",
                                                                          (long long)capacity, records_dev ? "set" : "NULL");
-    hipPointerAttribute_t attr;
-    HIP_TRY(hipPointerGetAttributes(&attr, key_dev));
-    HIP_TRY(hipSetDevice(attr.device));
+    if (cbas_use_device_of(key_dev) != CBAS_OK) return CBAS_EHIP;
     hipStream_t st = (hipStream_t)stream;
     // scratch: [flags: 16 bytes][offsets: n_clips + 1 int64][counts: n_clips int32]
     RunsScratch scratch;
@@ -614,9 +608,7 @@ extern "C" int cbas_activity_bins(const float* probs_dev, int64_t n_total, int32
     if (bin_frames < 1 || n_bins != (n_total - 1) / bin_frames + 1)
         return cbas_fail(CBAS_EINVAL, "cbas_activity_bins: bin_frames=%lld, n_bins=%lld: bin_frames >= 1 and n_bins = ceil(n_total / bin_frames)",
                          (long long)bin_frames, (long long)n_bins);
-    hipPointerAttribute_t attr;
-    HIP_TRY(hipPointerGetAttributes(&attr, probs_dev));
-    HIP_TRY(hipSetDevice(attr.device));
+    if (cbas_use_device_of(probs_dev) != CBAS_OK) return CBAS_EHIP;
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipMemsetAsync(bins_dev, 0, (size_t)n_bins * sizeof(int64_t), st));
     LAUNCH_TRY(launch_activity_bins(probs_dev, n_total, n_classes, behavior, threshold, bin_frames,

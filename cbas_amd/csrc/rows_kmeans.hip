@@ -28,8 +28,8 @@
 //   rkm_finish_kernel     final counts and inertia, clusters by descending count (ties: seeding order)
 //   rkm_remap_kernel      the last assignment in the output numbering
 // No atomics anywhere.
-#include "api_common.h"
 #include "kernels.h"
+#include "rows_api.h"
 #include "rows_rn.h"
 
 namespace {
@@ -409,8 +409,6 @@ __global__ __launch_bounds__(RKM_THREADS) void rkm_remap_kernel(const int32_t* _
     if (dist2_out) dist2_out[m] = dist2[m];
 }
 
-int64_t rkm_round16(int64_t bytes) { return (bytes + 15) / 16 * 16; }
-
 // byte offsets into the workspace, each a multiple of 16
 struct RkmLayout {
     int64_t nseg, nblk;
@@ -421,14 +419,12 @@ struct RkmLayout {
 int rkm_layout(const char* what, int64_t n_rows, int32_t dim, int32_t k, bool fit, RkmLayout* L) {
     if (n_rows < 1 || (n_rows + RKM_SEED_ROWS - 1) / RKM_SEED_ROWS > 0x7fffffff)
         return cbas_fail(CBAS_EINVAL, "%s: n_rows = %lld (1 .. %lld)", what, (long long)n_rows, (long long)0x7fffffff * RKM_SEED_ROWS);
-    if (dim < 32 || dim % 32 != 0 || dim > RKM_MAX_D)
-        return cbas_fail(CBAS_EINVAL, "%s: dim = %d (the width is a multiple of 32 up to %d)", what, dim, RKM_MAX_D);
+    if (rows_width_ok(what, "dim", dim, RKM_MAX_D) != CBAS_OK) return CBAS_EINVAL;
     if (k < 2 || k > RKM_MAX_K) return cbas_fail(CBAS_EINVAL, "%s: k = %d clusters (2 .. %d)", what, k, RKM_MAX_K);
     if (fit && k > n_rows) return cbas_fail(CBAS_EINVAL, "%s: k = %d clusters of %lld rows", what, k, (long long)n_rows);
     L->nseg = (n_rows + RKM_SEG - 1) / RKM_SEG;
     L->nblk = (n_rows + RKM_SEED_ROWS - 1) / RKM_SEED_ROWS;
-    int64_t at = 0;
-    auto take = [&](int64_t bytes) { const int64_t o = at; at += rkm_round16(bytes); return o; };
+    RowsTake take;
     L->cur = take((int64_t)k * dim * 4);
     L->order = take(64 * 4);
     L->pos = take(64 * 4);
@@ -442,12 +438,12 @@ int rkm_layout(const char* what, int64_t n_rows, int32_t dim, int32_t k, bool fi
     L->psum = take(L->nseg * k * dim * 4);
     L->pcount = take(L->nseg * 64 * 4);
     L->pinertia = take(L->nseg * 4);
-    L->total = at;
+    L->total = take.at;
     return CBAS_OK;
 }
 
 int rkm_rows_ok(const char* what, const void* rows, int32_t dim, int64_t ld, int32_t normalize) {
-    if (ld < dim || ld % 8 != 0) return cbas_fail(CBAS_EINVAL, "%s: ld = %lld (at least dim = %d, a multiple of 8)", what, (long long)ld, dim);
+    if (rows_ld_ok(what, "ld", ld, "dim", dim) != CBAS_OK) return CBAS_EINVAL;
     if (normalize != 0 && normalize != 1) return cbas_fail(CBAS_EINVAL, "%s: normalize = %d (0 or 1)", what, normalize);
     if (!rows) return cbas_fail(CBAS_EINVAL, "%s: a NULL pointer", what);
     return CBAS_OK;
@@ -490,9 +486,7 @@ extern "C" int cbas_rows_kmeans_fit(const void* rows_f16_dev, int64_t n_rows, in
     if (workspace_bytes < L.total)
         return cbas_fail(CBAS_EINVAL, "%s: workspace of %lld bytes, %lld needed (cbas_rows_kmeans_workspace_bytes)", what,
                          (long long)workspace_bytes, (long long)L.total);
-    hipPointerAttribute_t attr;
-    HIP_TRY(hipPointerGetAttributes(&attr, rows_f16_dev));
-    HIP_TRY(hipSetDevice(attr.device));
+    if (cbas_use_device_of(rows_f16_dev) != CBAS_OK) return CBAS_EHIP;
     hipStream_t st = (hipStream_t)stream;
     const uint16_t* const rows = (const uint16_t*)rows_f16_dev;
     char* const ws = (char*)workspace_dev;
@@ -512,8 +506,7 @@ extern "C" int cbas_rows_kmeans_fit(const void* rows_f16_dev, int64_t n_rows, in
     const dim3 wg(RKM_THREADS);
     const unsigned nseg = (unsigned)L.nseg, slabs = (unsigned)((dim + RKM_SLAB - 1) / RKM_SLAB);
     const size_t sum_lds = (size_t)(64 + (size_t)k * RKM_SLAB) * 4;
-    if (sum_lds > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&rkm_sum_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    if (rows_lds_opt_in(&rkm_sum_kernel, sum_lds) != CBAS_OK) return CBAS_EHIP;
 
     if (normalize)
         hipLaunchKernelGGL(rows_rn_kernel, dim3((unsigned)((n_rows * 4 + RKM_THREADS - 1) / RKM_THREADS)), wg, 0, st, rows, n_rows, dim, ld, rn);
@@ -562,9 +555,7 @@ extern "C" int cbas_rows_kmeans_assign(const void* rows_f16_dev, int64_t n_rows,
     if (!centroids_dev || !labels_dev) return cbas_fail(CBAS_EINVAL, "%s: a NULL pointer (only dist2 may be NULL)", what);
     if (((uintptr_t)rows_f16_dev | (uintptr_t)centroids_dev) % 16) return cbas_fail(CBAS_EINVAL, "%s: rows and centroids must be 16-byte aligned", what);
     if (((uintptr_t)labels_dev | (uintptr_t)dist2_dev) % 4) return cbas_fail(CBAS_EINVAL, "%s: labels and dist2 must be 4-byte aligned", what);
-    hipPointerAttribute_t attr;
-    HIP_TRY(hipPointerGetAttributes(&attr, rows_f16_dev));
-    HIP_TRY(hipSetDevice(attr.device));
+    if (cbas_use_device_of(rows_f16_dev) != CBAS_OK) return CBAS_EHIP;
     const RkmPass pass{(const uint16_t*)rows_f16_dev, n_rows, dim, ld, centroids_dev, k, normalize, labels_dev, dist2_dev};
     LAUNCH_TRY(rkm_pass(pass, (hipStream_t)stream));
     return CBAS_OK;

@@ -28,8 +28,8 @@
 //                     worst entry (the lowest score, among equal scores the highest index) in its place and finds the worst again.
 //                     The k best of a stream under a total order do not depend on the order of arrival.  After the last block the
 //                     lists are put in order by rank placement and the same thread votes.  No atomics.
-#include "api_common.h"
 #include "kernels.h"
+#include "rows_api.h"
 #include "rows_rn.h"
 
 namespace {
@@ -282,8 +282,6 @@ __global__ __launch_bounds__(RK_THREADS) void rk_knn_kernel(RkArgs a) {
     }
 }
 
-int64_t rk_round16(int64_t bytes) { return (bytes + 15) / 16 * 16; }
-
 // byte offsets into the workspace, each a multiple of 16
 struct RkLayout {
     int64_t flags, rn_bank, rn_rows, total;
@@ -295,10 +293,11 @@ int rk_layout(const char* what, int64_t N, int32_t M, int32_t k, RkLayout* L) {
         return cbas_fail(CBAS_EINVAL, "%s: N = %lld (0 .. %lld)", what, (long long)N, (long long)0x7fffffff * RK_TILE);
     if (M < 1 || M > RK_MAX_M) return cbas_fail(CBAS_EINVAL, "%s: M = %d (1 .. %d)", what, M, RK_MAX_M);
     if (k < 1 || k > RK_MAX_K) return cbas_fail(CBAS_EINVAL, "%s: k = %d (1 .. %d)", what, k, RK_MAX_K);
-    L->flags = 0;
-    L->rn_bank = 16;
-    L->rn_rows = L->rn_bank + rk_round16((int64_t)M * 4);
-    L->total = L->rn_rows + rk_round16(N * 4);
+    RowsTake take;
+    L->flags = take(16);
+    L->rn_bank = take((int64_t)M * 4);
+    L->rn_rows = take(N * 4);
+    L->total = take.at;
     return CBAS_OK;
 }
 
@@ -317,10 +316,9 @@ extern "C" int cbas_rows_knn(const void* rows_f16_dev, int64_t N, int32_t D, int
     const char* const what = "cbas_rows_knn";
     RkLayout L;
     if (rk_layout(what, N, M, k, &L) != CBAS_OK) return CBAS_EINVAL;
-    if (D < 32 || D % 32 != 0 || D > RK_MAX_D) return cbas_fail(CBAS_EINVAL, "%s: D = %d (the width is a multiple of 32 up to %d)", what, D, RK_MAX_D);
-    if (ld < D || ld % 8 != 0) return cbas_fail(CBAS_EINVAL, "%s: ld = %lld (at least D = %d, a multiple of 8)", what, (long long)ld, D);
-    if (bank_ld < D || bank_ld % 8 != 0)
-        return cbas_fail(CBAS_EINVAL, "%s: bank_ld = %lld (at least D = %d, a multiple of 8)", what, (long long)bank_ld, D);
+    if (rows_width_ok(what, "D", D, RK_MAX_D) != CBAS_OK || rows_ld_ok(what, "ld", ld, "D", D) != CBAS_OK ||
+        rows_ld_ok(what, "bank_ld", bank_ld, "D", D) != CBAS_OK)
+        return CBAS_EINVAL;
     if (C < 1 || C > RK_MAX_C) return cbas_fail(CBAS_EINVAL, "%s: C = %d (1 .. %d)", what, C, RK_MAX_C);
     if (!(temperature > 0.f) || !(temperature <= 3.402823466e38f))
         return cbas_fail(CBAS_EINVAL, "%s: temperature = %g (finite and greater than 0)", what, (double)temperature);
@@ -335,9 +333,7 @@ extern "C" int cbas_rows_knn(const void* rows_f16_dev, int64_t N, int32_t D, int
     if (workspace_bytes < L.total)
         return cbas_fail(CBAS_EINVAL, "%s: workspace of %lld bytes, %lld needed (cbas_rows_knn_workspace_bytes)", what, (long long)workspace_bytes,
                          (long long)L.total);
-    hipPointerAttribute_t attr;
-    HIP_TRY(hipPointerGetAttributes(&attr, rows_f16_dev));
-    HIP_TRY(hipSetDevice(attr.device));
+    if (cbas_use_device_of(rows_f16_dev) != CBAS_OK) return CBAS_EHIP;
     hipStream_t st = (hipStream_t)stream;
     char* const ws = (char*)workspace_dev;
     unsigned* const flags = (unsigned*)(ws + L.flags);
@@ -359,8 +355,7 @@ extern "C" int cbas_rows_knn(const void* rows_f16_dev, int64_t N, int32_t D, int
     if (bad) return cbas_fail(CBAS_EINVAL, "%s: a bank label lies outside [0, C = %d)", what, C);
 
     const size_t lds = (size_t)2 * RK_STAGE * 2 + (size_t)RK_TILE * RK_LDS * 4 + (size_t)2 * k * RK_TILE * 4;
-    if (lds > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&rk_knn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    if (rows_lds_opt_in(&rk_knn_kernel, lds) != CBAS_OK) return CBAS_EHIP;
     const RkArgs args{(const uint16_t*)rows_f16_dev, N, D, ld, (const uint16_t*)bank_f16_dev, M, bank_ld, bank_label_dev, bank_group_dev,
                       row_group_dev, C, class_weight_dev, k, temperature, rn_rows, rn_bank, probs_dev, nn_index_dev, nn_score_dev, sims_dev};
     hipLaunchKernelGGL(rk_knn_kernel, dim3((unsigned)((N + RK_TILE - 1) / RK_TILE)), wg, lds, st, args);

@@ -15,8 +15,8 @@
 //                      8 kr .. 8 kr + 7 of row fc (A operand) and of component fc (B operand, zero past k); the centred value
 //                      fl(u - mu) is formed in registers.  normalize = 1 reads the wave's rows twice: once for rn, once for the scores
 // Every sum has a fixed order, a function of (n_rows, dim) alone, and there are no atomics: two calls give the same bits.
-#include "api_common.h"
 #include "kernels.h"
+#include "rows_api.h"
 #include "rows_rn.h"
 
 namespace {
@@ -292,8 +292,6 @@ __global__ __launch_bounds__(FP_THREADS) void fp_project_kernel(const uint16_t* 
     }
 }
 
-int64_t fp_round16(int64_t bytes) { return (bytes + 15) / 16 * 16; }
-
 // byte offsets into the workspace, each a multiple of 16; the covariance comes first
 struct FpLayout {
     int64_t nchunks, cpp, nparts;
@@ -301,10 +299,9 @@ struct FpLayout {
 };
 
 int fp_shape(const char* what, int32_t dim, int64_t ld, int32_t k, int32_t normalize) {
-    if (dim < 32 || dim % 32 != 0 || dim > PCA_MAX_D)
-        return cbas_fail(CBAS_EINVAL, "%s: dim = %d (the width is a multiple of 32 up to %d)", what, dim, PCA_MAX_D);
+    if (rows_width_ok(what, "dim", dim, PCA_MAX_D) != CBAS_OK) return CBAS_EINVAL;
     if (k < 1 || k > PCA_MAX_K || k > dim) return cbas_fail(CBAS_EINVAL, "%s: k = %d (1 .. %d components, at most dim)", what, k, PCA_MAX_K);
-    if (ld < dim || ld % 8 != 0) return cbas_fail(CBAS_EINVAL, "%s: ld = %lld (at least dim = %d, a multiple of 8)", what, (long long)ld, dim);
+    if (rows_ld_ok(what, "ld", ld, "dim", dim) != CBAS_OK) return CBAS_EINVAL;
     if (normalize != 0 && normalize != 1) return cbas_fail(CBAS_EINVAL, "%s: normalize = %d (0 or 1)", what, normalize);
     return CBAS_OK;
 }
@@ -314,13 +311,12 @@ int fp_layout(const char* what, int64_t N, int32_t dim, int32_t k, FpLayout* L) 
     L->nchunks = (N + FP_CHUNK - 1) / FP_CHUNK;
     L->cpp = (L->nchunks + FP_MAX_PARTS - 1) / FP_MAX_PARTS;
     L->nparts = (L->nchunks + L->cpp - 1) / L->cpp;
-    int64_t at = 0;
-    auto take = [&](int64_t bytes) { const int64_t o = at; at += fp_round16(bytes); return o; };
+    RowsTake take;
     L->cov = take(L->nparts * dim * dim * 4);
     L->z = take((int64_t)k * dim * 4);
     L->tmp = take(L->nchunks * dim * 4);
     L->rn = take(N * 4);
-    L->total = at;
+    L->total = take.at;
     return CBAS_OK;
 }
 
@@ -349,9 +345,7 @@ extern "C" int cbas_rows_pca_fit(const void* rows_f16_dev, int64_t n_rows, int32
     if (workspace_bytes < L.total)
         return cbas_fail(CBAS_EINVAL, "%s: workspace of %lld bytes, %lld needed (cbas_rows_pca_workspace_bytes)", what,
                          (long long)workspace_bytes, (long long)L.total);
-    hipPointerAttribute_t attr;
-    HIP_TRY(hipPointerGetAttributes(&attr, rows_f16_dev));
-    HIP_TRY(hipSetDevice(attr.device));
+    if (cbas_use_device_of(rows_f16_dev) != CBAS_OK) return CBAS_EHIP;
     hipStream_t st = (hipStream_t)stream;
     const uint16_t* const rows = (const uint16_t*)rows_f16_dev;
     const int D = dim;
@@ -388,9 +382,7 @@ extern "C" int cbas_rows_pca_project(const void* rows_f16_dev, int64_t n_rows, i
         return cbas_fail(CBAS_EINVAL, "%s: rows, mean and components must be 16-byte aligned", what);
     if (((uintptr_t)scale_dev | (uintptr_t)scores_dev | (uintptr_t)residual_dev) % 4)
         return cbas_fail(CBAS_EINVAL, "%s: scale, scores and residual must be 4-byte aligned", what);
-    hipPointerAttribute_t attr;
-    HIP_TRY(hipPointerGetAttributes(&attr, rows_f16_dev));
-    HIP_TRY(hipSetDevice(attr.device));
+    if (cbas_use_device_of(rows_f16_dev) != CBAS_OK) return CBAS_EHIP;
     const dim3 grid((unsigned)((n_rows + FP_TILE - 1) / FP_TILE)), wg(FP_THREADS);
     const uint16_t* const rows = (const uint16_t*)rows_f16_dev;
     if (normalize)

@@ -27,8 +27,8 @@
 //   rp_step_kernel     per element: the segments' partials added in ascending order, * (1 / Omega), + l2 v (one fmaf); then
 //                      w' = fmaf(-1/L, g, v), v' = fmaf(beta, w' - w, w').  Thread 0: the loss of the weights the pass ran on.
 // No atomics anywhere.
-#include "api_common.h"
 #include "kernels.h"
+#include "rows_api.h"
 #include "rows_rn.h"
 
 #include <cmath>
@@ -384,8 +384,6 @@ __global__ __launch_bounds__(RP_THREADS) void rp_step_kernel(RpStep a) {
     a.v[idx] = fmaf(a.beta, __fsub_rn(wn, w), wn);
 }
 
-int64_t rp_round16(int64_t bytes) { return (bytes + 15) / 16 * 16; }
-
 // byte offsets into the workspace, each a multiple of 16
 struct RpLayout {
     int64_t nseg;
@@ -394,8 +392,7 @@ struct RpLayout {
 
 // the checks the entry points share; 0, or CBAS_EINVAL with the message set
 int rp_shape(const char* what, int32_t dim, int32_t C) {
-    if (dim < 32 || dim % 32 != 0 || dim > RP_MAX_D)
-        return cbas_fail(CBAS_EINVAL, "%s: dim = %d (the width is a multiple of 32 up to %d)", what, dim, RP_MAX_D);
+    if (rows_width_ok(what, "dim", dim, RP_MAX_D) != CBAS_OK) return CBAS_EINVAL;
     if (C < 2 || C > RP_MAX_C) return cbas_fail(CBAS_EINVAL, "%s: n_classes = %d (2 .. %d)", what, C, RP_MAX_C);
     return CBAS_OK;
 }
@@ -404,8 +401,7 @@ int rp_layout(const char* what, int64_t M, int32_t dim, int32_t C, RpLayout* L) 
     if (M < 1 || M > RP_MAX_M) return cbas_fail(CBAS_EINVAL, "%s: n_train = %lld (1 .. %lld)", what, (long long)M, (long long)RP_MAX_M);
     if (rp_shape(what, dim, C) != CBAS_OK) return CBAS_EINVAL;
     L->nseg = (M + RP_SEG - 1) / RP_SEG;
-    int64_t at = 0;
-    auto take = [&](int64_t bytes) { const int64_t o = at; at += rp_round16(bytes); return o; };
+    RowsTake take;
     L->flags = take(16);
     L->omega = take(16);
     L->w = take(((int64_t)C * dim + 64) * 4);
@@ -418,12 +414,7 @@ int rp_layout(const char* what, int64_t M, int32_t dim, int32_t C, RpLayout* L) 
     L->pb = take(L->nseg * 64 * 4);
     L->ploss = take(L->nseg * 4);
     L->pomega = take(L->nseg * 4);
-    L->total = at;
-    return CBAS_OK;
-}
-
-int rp_ld_ok(const char* what, int32_t dim, int64_t ld) {
-    if (ld < dim || ld % 8 != 0) return cbas_fail(CBAS_EINVAL, "%s: ld = %lld (at least dim = %d, a multiple of 8)", what, (long long)ld, dim);
+    L->total = take.at;
     return CBAS_OK;
 }
 
@@ -466,7 +457,7 @@ extern "C" int cbas_rows_probe_fit(const void* train_f16_dev, int64_t n_train, i
     const char* const what = "cbas_rows_probe_fit";
     RpLayout L;
     if (rp_layout(what, n_train, dim, n_classes, &L) != CBAS_OK) return CBAS_EINVAL;
-    if (rp_ld_ok(what, dim, ld) != CBAS_OK) return CBAS_EINVAL;
+    if (rows_ld_ok(what, "ld", ld, "dim", dim) != CBAS_OK) return CBAS_EINVAL;
     if (iters < 0) return cbas_fail(CBAS_EINVAL, "%s: iters = %d (at least 0)", what, iters);
     if (!(l2 > 0.f) || !(l2 <= 3.402823466e38f)) return cbas_fail(CBAS_EINVAL, "%s: l2 = %g (finite and greater than 0)", what, (double)l2);
     if (!train_f16_dev || !label_dev || !weights_dev || !bias_dev || !loss_dev || !workspace_dev)
@@ -478,9 +469,7 @@ extern "C" int cbas_rows_probe_fit(const void* train_f16_dev, int64_t n_train, i
     if (workspace_bytes < L.total)
         return cbas_fail(CBAS_EINVAL, "%s: workspace of %lld bytes, %lld needed (cbas_rows_probe_workspace_bytes)", what,
                          (long long)workspace_bytes, (long long)L.total);
-    hipPointerAttribute_t attr;
-    HIP_TRY(hipPointerGetAttributes(&attr, train_f16_dev));
-    HIP_TRY(hipSetDevice(attr.device));
+    if (cbas_use_device_of(train_f16_dev) != CBAS_OK) return CBAS_EHIP;
     hipStream_t st = (hipStream_t)stream;
     const uint16_t* const rows = (const uint16_t*)train_f16_dev;
     const int64_t M = n_train;
@@ -556,15 +545,13 @@ extern "C" int cbas_rows_probe_predict(const void* rows_f16_dev, int64_t n_rows,
     if (n_rows < 0 || (n_rows + RP_TILE - 1) / RP_TILE > 0x7fffffff)
         return cbas_fail(CBAS_EINVAL, "%s: n_rows = %lld (0 .. %lld)", what, (long long)n_rows, (long long)0x7fffffff * RP_TILE);
     if (rp_shape(what, dim, n_classes) != CBAS_OK) return CBAS_EINVAL;
-    if (rp_ld_ok(what, dim, ld) != CBAS_OK) return CBAS_EINVAL;
+    if (rows_ld_ok(what, "ld", ld, "dim", dim) != CBAS_OK) return CBAS_EINVAL;
     if (n_rows == 0) return CBAS_OK;
     if (!rows_f16_dev || !weights_dev || !bias_dev || !probs_dev) return cbas_fail(CBAS_EINVAL, "%s: a NULL pointer (only logits may be NULL)", what);
     if (((uintptr_t)rows_f16_dev | (uintptr_t)weights_dev) % 16) return cbas_fail(CBAS_EINVAL, "%s: rows and weights must be 16-byte aligned", what);
     if (((uintptr_t)bias_dev | (uintptr_t)probs_dev | (uintptr_t)logits_dev) % 4)
         return cbas_fail(CBAS_EINVAL, "%s: bias, probs and logits must be 4-byte aligned", what);
-    hipPointerAttribute_t attr;
-    HIP_TRY(hipPointerGetAttributes(&attr, rows_f16_dev));
-    HIP_TRY(hipSetDevice(attr.device));
+    if (cbas_use_device_of(rows_f16_dev) != CBAS_OK) return CBAS_EHIP;
     const RpPass pass{(const uint16_t*)rows_f16_dev, n_rows, dim, ld, weights_dev, bias_dev, n_classes, probs_dev, logits_dev, nullptr, nullptr,
                       nullptr, nullptr, nullptr};
     LAUNCH_TRY(rp_pass<false>(pass, (hipStream_t)stream));

@@ -1,6 +1,6 @@
-// The reciprocal norm of a resident fp16 row, written once: cbas_rows_search, cbas_rows_knn and cbas_rows_kmeans_* all include this
-// file, so the same row has the same rn in each.  s = (l0 + l1) + (l2 + l3) in fp32, l_j the fmaf chain, from 0, of x_d^2 over the
-// columns d with (d % 32) / 8 = j, ascending; rn = fp32(1 / sqrt((double)s)), 0 when s = 0.
+// The reciprocal norm of a resident fp16 row, written once: rows_search.hip, rows_knn.hip, rows_kmeans.hip, rows_probe.hip and
+// rows_pca.hip all include this file, so the same row has the same rn in each.  s = (l0 + l1) + (l2 + l3) in fp32, l_j the fmaf
+// chain, from 0, of x_d^2 over the columns d with (d % 32) / 8 = j, ascending; rn = fp32(1 / sqrt((double)s)), 0 when s = 0.
 #pragma once
 #include "common.h"
 

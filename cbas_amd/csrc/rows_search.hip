@@ -22,8 +22,8 @@
 //   rs_merge_kernel      RS_FAN lists into one, until one is left: the result
 // The k best of a workgroup's entries are placed by RANK: an entry's position is the number of entries that beat it (a larger
 // score, or an equal score and a lower row); rows are distinct, so the ranks are too.  No atomics anywhere.
-#include "api_common.h"
 #include "kernels.h"
+#include "rows_api.h"
 #include "rows_rn.h"
 
 namespace {
@@ -272,8 +272,6 @@ __global__ __launch_bounds__(RS_THREADS) void rs_merge_kernel(const float* __res
     rs_place(cs, ci, C, k, out_s + at, out_i + at);
 }
 
-int64_t rs_round16(int64_t bytes) { return (bytes + 15) / 16 * 16; }
-
 // byte offsets into the workspace, each a multiple of 16
 struct RsLayout {
     int64_t nch, nch2;
@@ -288,8 +286,7 @@ int rs_layout(const char* what, int64_t n_rows, int32_t n_queries, int32_t k, Rs
     L->nch = (n_rows + RS_CHUNK - 1) / RS_CHUNK;
     if (L->nch > 0x7fffffff) return cbas_fail(CBAS_EINVAL, "%s: n_rows = %lld is more than one call takes", what, (long long)n_rows);
     L->nch2 = (L->nch + RS_FAN - 1) / RS_FAN;
-    int64_t at = 0;
-    auto take = [&](int64_t bytes) { const int64_t o = at; at += rs_round16(bytes); return o; };
+    RowsTake take;
     L->rq = take(RS_MAX_Q * 4);
     L->flags = take(16);
     L->clip_id = take(n_rows * 4);
@@ -297,7 +294,7 @@ int rs_layout(const char* what, int64_t n_rows, int32_t n_queries, int32_t k, Rs
     L->a_i = take(L->nch * n_queries * k * 8);
     L->b_s = take(L->nch2 * n_queries * k * 4);
     L->b_i = take(L->nch2 * n_queries * k * 8);
-    L->total = at;
+    L->total = take.at;
     return CBAS_OK;
 }
 
@@ -316,9 +313,7 @@ extern "C" int cbas_rows_search(const uint16_t* rows_f16_dev, int64_t n_rows, in
     const char* const what = "cbas_rows_search";
     RsLayout L;
     if (rs_layout(what, n_rows, n_queries, k, &L) != CBAS_OK) return CBAS_EINVAL;
-    if (dim < 32 || dim % 32 != 0 || dim > RS_MAX_D)
-        return cbas_fail(CBAS_EINVAL, "%s: dim = %d (the width is a multiple of 32 up to %d)", what, dim, RS_MAX_D);
-    if (ld < dim || ld % 8 != 0) return cbas_fail(CBAS_EINVAL, "%s: ld = %lld (at least dim = %d, a multiple of 8)", what, (long long)ld, dim);
+    if (rows_width_ok(what, "dim", dim, RS_MAX_D) != CBAS_OK || rows_ld_ok(what, "ld", ld, "dim", dim) != CBAS_OK) return CBAS_EINVAL;
     if (min_gap < 0 || min_gap > RS_MAX_GAP) return cbas_fail(CBAS_EINVAL, "%s: min_gap = %d (0 .. %d)", what, min_gap, RS_MAX_GAP);
     if (n_clips < 1) return cbas_fail(CBAS_EINVAL, "%s: n_clips = %d (at least 1)", what, n_clips);
     if (!rows_f16_dev || !queries_dev || !clip_table_dev || !trace_dev || !index_dev || !score_dev || !workspace_dev)
@@ -330,11 +325,9 @@ extern "C" int cbas_rows_search(const uint16_t* rows_f16_dev, int64_t n_rows, in
     if (workspace_bytes < L.total)
         return cbas_fail(CBAS_EINVAL, "%s: workspace of %lld bytes, %lld needed (cbas_rows_search_workspace_bytes)", what,
                          (long long)workspace_bytes, (long long)L.total);
-    hipPointerAttribute_t attr;
-    HIP_TRY(hipPointerGetAttributes(&attr, rows_f16_dev));
-    HIP_TRY(hipSetDevice(attr.device));
-    int n_cu = 0;
-    HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, attr.device));
+    int device = 0, n_cu = 0;
+    if (cbas_use_device_of(rows_f16_dev, &device) != CBAS_OK) return CBAS_EHIP;
+    HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device));
     hipStream_t st = (hipStream_t)stream;
     char* const ws = (char*)workspace_dev;
     float* const rq = (float*)(ws + L.rq);
@@ -358,8 +351,7 @@ extern "C" int cbas_rows_search(const uint16_t* rows_f16_dev, int64_t n_rows, in
 
     // the scores
     const size_t lds = (size_t)16 * (dim + RS_QPAD) * sizeof(float);
-    if (lds > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&rs_score_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    if (rows_lds_opt_in(&rs_score_kernel, lds) != CBAS_OK) return CBAS_EHIP;
     hipLaunchKernelGGL(rs_qnorm_kernel, dim3((n_queries + 3) / 4), wg, 0, st, queries_dev, dim, n_queries, rq);
     int per_cu = (int)((160 * 1024) / lds);
     if (per_cu > 4) per_cu = 4;

@@ -565,9 +565,7 @@ extern "C" int cbasx_hmm_posteriors(const float* probs_dev, int64_t n_total, con
         ((uintptr_t)clip_table_dev | (uintptr_t)xi_dev | (uintptr_t)pi_dev | (uintptr_t)loglik_dev) % 8)
         return cbas_fail(CBAS_EINVAL, "cbasx_hmm_posteriors: probs, trans, prior, gamma and flags must be 4-byte aligned, clip_table, xi, pi "
                          "and loglik 8-byte aligned");
-    hipPointerAttribute_t attr;
-    HIP_TRY(hipPointerGetAttributes(&attr, gamma_dev));
-    HIP_TRY(hipSetDevice(attr.device));
+    if (cbas_use_device_of(gamma_dev) != CBAS_OK) return CBAS_EHIP;
     hipStream_t st = (hipStream_t)stream;
     char* ws = reinterpret_cast<char*>(workspace_dev);
     unsigned* bad_dev = reinterpret_cast<unsigned*>(ws + L.flags);

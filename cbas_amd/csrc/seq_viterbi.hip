@@ -497,9 +497,7 @@ extern "C" int cbasx_viterbi_decode(const int32_t* scores_dev, int64_t n_total, 
         ((uintptr_t)clip_table_dev | (uintptr_t)clip_score_dev) % 8)
         return cbas_fail(CBAS_EINVAL, "cbasx_viterbi_decode: scores, log_trans, log_prior and labels must be 4-byte aligned, clip_table and "
                          "clip_score 8-byte aligned");
-    hipPointerAttribute_t attr;
-    HIP_TRY(hipPointerGetAttributes(&attr, scores_dev));
-    HIP_TRY(hipSetDevice(attr.device));
+    if (cbas_use_device_of(scores_dev) != CBAS_OK) return CBAS_EHIP;
     hipStream_t st = (hipStream_t)stream;
     char* ws = reinterpret_cast<char*>(workspace_dev);
     unsigned* flags = reinterpret_cast<unsigned*>(ws + L.flags);

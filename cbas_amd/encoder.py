@@ -701,10 +701,7 @@ class DinoEncoder:
             k = int(n_components)
             sc = _lib.PCA_BATCH if scope == "batch" else _lib.PCA_FRAME
             nb = 1 if scope == "batch" else n
-            need = int(self._lib.cbas_patch_pca_workspace_bytes(n, T, P0, D, k, sc))
-            if need < 0:
-                _lib.check(int(need), "cbas_patch_pca_workspace_bytes")
-            ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
+            ws, need = _lib.workspace("cbas_patch_pca_workspace_bytes", self.device, n, T, P0, D, k, sc)
             f32 = dict(dtype=torch.float32, device=self.device)
             basis = PatchPCABasis(torch.empty((nb, D), **f32), torch.empty((nb, k, D), **f32), torch.empty((nb, k), **f32),
                                   torch.empty((nb,), **f32), scope, self.stamp)
@@ -745,12 +742,10 @@ class DinoEncoder:
             k, rounds = int(n_clusters), int(KMEANS_DEFAULT_ITERS if iters is None else iters)
             sc = _lib.PCA_BATCH if scope == "batch" else _lib.PCA_FRAME
             nb = 1 if scope == "batch" else n
-            need = int(self._lib.cbas_patch_kmeans_workspace_bytes(n, T, P0, D, k, sc))
-            if need < 0:
-                _lib.check(int(need), "cbas_patch_kmeans_workspace_bytes")
+            need = _lib.workspace_bytes("cbas_patch_kmeans_workspace_bytes", n, T, P0, D, k, sc)      # a refused shape first
             if rounds < 0:
                 raise ValueError(f"iters = {rounds}: at least 0")
-            ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
+            ws = torch.empty(need, dtype=torch.uint8, device=self.device)
             i32 = dict(dtype=torch.int32, device=self.device)
             clusters = PatchClusters(torch.empty((nb, k, D), dtype=torch.float32, device=self.device), torch.empty((nb, k), **i32),
                                      torch.empty((nb, rounds + 1), dtype=torch.float32, device=self.device), torch.empty((nb, k), **i32),

@@ -98,10 +98,7 @@ def fit_pca(index, n_components: int = 3, normalize: bool = True, iters: Optiona
         comp = torch.empty((k, D), dtype=torch.float32, device=dev)
         eig = torch.empty(k, dtype=torch.float32, device=dev)
         tv = torch.empty(1, dtype=torch.float32, device=dev)
-        need = int(lib.cbas_rows_pca_workspace_bytes(N, D, k))
-        if need < 0:
-            _lib.check(need, "cbas_rows_pca_workspace_bytes")
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws, need = _lib.workspace("cbas_rows_pca_workspace_bytes", dev, N, D, k)
         _lib.check(lib.cbas_rows_pca_fit(index.rows.data_ptr(), N, D, D, k, iters, int(bool(normalize)), mean.data_ptr(), comp.data_ptr(),
                                          eig.data_ptr(), tv.data_ptr(), ws.data_ptr(), need, stream), "cbas_rows_pca_fit")
         return FramePCA(mean.cpu().numpy(), comp.cpu().numpy(), eig.cpu().numpy(), float(tv.cpu().numpy()[0]), D, normalize, N, iters)

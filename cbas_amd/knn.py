@@ -132,10 +132,7 @@ def knn_labels(index, bank: LabelBank, k: int = 20, temperature: float = 0.07, e
         probs = torch.empty((N, C), dtype=torch.float32, device=index.device)
         nn_index = torch.empty((N, k), dtype=torch.int32, device=index.device) if return_neighbours else None
         nn_score = torch.empty((N, k), dtype=torch.float32, device=index.device) if return_neighbours else None
-        need = int(lib.cbas_rows_knn_workspace_bytes(N, M, k))
-        if need < 0:
-            _lib.check(need, "cbas_rows_knn_workspace_bytes")
-        ws = torch.empty(need, dtype=torch.uint8, device=index.device)
+        ws, need = _lib.workspace("cbas_rows_knn_workspace_bytes", index.device, N, M, k)
         _lib.check(lib.cbas_rows_knn(index.rows.data_ptr(), N, index.dim, index.dim, bank.rows.data_ptr(), M, bank.dim, bank.label.data_ptr(),
                                      bank.group.data_ptr() if exclude else None, bank.row_group.data_ptr() if exclude else None, C,
                                      None if cw is None else cw.data_ptr(), k, float(temperature), probs.data_ptr(),

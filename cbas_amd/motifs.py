@@ -112,10 +112,7 @@ def cluster_frames(index, n_clusters: int = 16, iters: int = 20, normalize: bool
         counts = torch.empty(k, dtype=torch.int64, device=dev)
         inertia = torch.empty(iters + 1, dtype=torch.float32, device=dev)
         seeds = torch.empty(k, dtype=torch.int64, device=dev)
-        need = int(lib.cbas_rows_kmeans_workspace_bytes(N, D, k))
-        if need < 0:
-            _lib.check(need, "cbas_rows_kmeans_workspace_bytes")
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws, need = _lib.workspace("cbas_rows_kmeans_workspace_bytes", dev, N, D, k)
         _lib.check(lib.cbas_rows_kmeans_fit(index.rows.data_ptr(), N, D, D, k, iters, int(bool(normalize)), None if start is None else start.data_ptr(),
                                             cent.data_ptr(), counts.data_ptr(), inertia.data_ptr(), seeds.data_ptr(), labels.data_ptr(),
                                             dist2.data_ptr(), ws.data_ptr(), need, stream), "cbas_rows_kmeans_fit")

@@ -155,10 +155,7 @@ def fit_probe(index, bank, l2: float = 1e-4, iters: int = 1000, class_weights="b
         weights = torch.empty((C, D), dtype=torch.float32, device=dev)
         bias = torch.empty(C, dtype=torch.float32, device=dev)
         loss = torch.empty(iters + 1, dtype=torch.float32, device=dev)
-        need = int(lib.cbas_rows_probe_workspace_bytes(M, D, C))
-        if need < 0:
-            _lib.check(need, "cbas_rows_probe_workspace_bytes")
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws, need = _lib.workspace("cbas_rows_probe_workspace_bytes", dev, M, D, C)
         ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
         _lib.check(lib.cbas_rows_probe_fit(bank.rows.data_ptr(), M, D, bank.dim, bank.label.data_ptr(), ptr(om), C, float(l2), iters, ptr(w0d),
                                            ptr(b0d), weights.data_ptr(), bias.data_ptr(), loss.data_ptr(), ws.data_ptr(), need, stream),

@@ -167,10 +167,7 @@ class FrameIndex:
             trace = torch.empty((Q, N), dtype=torch.float32, device=self.device)
             index = torch.empty((Q, k), dtype=torch.int64, device=self.device)
             score = torch.empty((Q, k), dtype=torch.float32, device=self.device)
-            need = int(lib.cbas_rows_search_workspace_bytes(N, min(Q, MAX_QUERIES), k))
-            if need < 0:
-                _lib.check(need, "cbas_rows_search_workspace_bytes")
-            ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            ws, need = _lib.workspace("cbas_rows_search_workspace_bytes", self.device, N, min(Q, MAX_QUERIES), k)
             for a in range(0, Q, MAX_QUERIES):
                 b = min(Q, a + MAX_QUERIES)
                 _lib.check(lib.cbas_rows_search(self.rows.data_ptr(), N, self.dim, self.dim, q_dev[a:b].data_ptr(), b - a,
