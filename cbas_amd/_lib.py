@@ -215,6 +215,11 @@ EXT_SIGNATURES = {
     "cbasx_hmm_workspace_bytes": (c_int64, [c_int64, c_int32, c_int32]),
     "cbasx_hmm_posteriors": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_int64, c_void_p]),
+    "cbasx_rows_emissions": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_int32, c_int32, c_void_p, c_float, c_void_p, c_void_p, c_void_p,
+                                     c_void_p]),
+    "cbasx_rows_weighted_sums_workspace_bytes": (c_int64, [c_int64, c_int32, c_int32]),
+    "cbasx_rows_weighted_sums": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_int64, c_void_p]),
 }
 
 ENC_SLOTS = 3

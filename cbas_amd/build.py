@@ -27,7 +27,7 @@ LIB_NAME = "libcbas_mi355x.so"
 LIB_PATH = os.path.join(HERE, LIB_NAME)
 DEBUG_LIB_NAME = "libcbas_mi355x_debug.so"
 DEBUG_LIB_PATH = os.path.join(HERE, DEBUG_LIB_NAME)
-SOURCES = ["gemm_f16.hip", "gemm_f16_8ph.hip", "gemm_f16_skinny.hip", "gemm_f32.hip", "vit_f32.hip", "convnext_f32.hip", "vit_kernels.hip", "cls_attention.hip", "attention_rollout.hip", "tokens_out.hip", "patch_pca.hip", "patch_kmeans.hip", "rows_search.hip", "rows_knn.hip", "rows_kmeans.hip", "rows_probe.hip", "rows_pca.hip", "head_kernels.hip", "head_train_kernels.hip", "rows_gather.hip", "head_score_kernels.hip", "head_report_kernels.hip", "head_post_kernels.hip", "seq_viterbi.hip", "seq_hmm.hip",
+SOURCES = ["gemm_f16.hip", "gemm_f16_8ph.hip", "gemm_f16_skinny.hip", "gemm_f32.hip", "vit_f32.hip", "convnext_f32.hip", "vit_kernels.hip", "cls_attention.hip", "attention_rollout.hip", "tokens_out.hip", "patch_pca.hip", "patch_kmeans.hip", "rows_search.hip", "rows_knn.hip", "rows_kmeans.hip", "rows_probe.hip", "rows_pca.hip", "head_kernels.hip", "head_train_kernels.hip", "rows_gather.hip", "head_score_kernels.hip", "head_report_kernels.hip", "head_post_kernels.hip", "seq_viterbi.hip", "seq_hmm.hip", "rows_hmm.hip",
            "api_enc.hip", "api_pca.hip", "api_head.hip", "api_head_train.hip", "api_fused.hip", "host_text.cpp", "host_mjpeg.cpp", "host_pixels.cpp"]
 DEBUG_ONLY_SOURCES = ["api_debug.hip"]            # harnesses: never in the product
 # -packed-fp32-ops: no v_pk_*_f32 at all in the head's kernels (VALU-light; nothing to gain from packed math) - the blunt way to
@@ -48,6 +48,7 @@ EXTRA_FLAGS = {"host_mjpeg.cpp": ["-mavx2"],      # host-only file: 8-lane integ
                "rows_pca.hip": NO_PACKED,        # fp32 centring and sums around fp32 MFMAs, run beside the encoder: as patch_pca.hip
                "seq_viterbi.hip": NO_PACKED,     # integer rows after one fp32 pass, run beside the encoder: as head_post_kernels.hip
                "seq_hmm.hip": NO_PACKED,         # serial scalar fp64 / fp32 fma chains, one wave per piece, run beside the encoder: as cls_attention.hip
+               "rows_hmm.hip": NO_PACKED,        # fp32 softmax rows and row scaling around fp32 MFMAs, run beside the encoder: as rows_kmeans.hip
                "attention_rollout.hip": NO_PACKED}      # scalar fp32 fmaf chains on the encoder's stream: as cls_attention.hip
 ARCH = "gfx950"
 HEADERS = [os.path.join(HERE, "..", "include", "cbas_mi355x.h"), os.path.join(HERE, "..", "include", "cbas_mi355x_debug.h"),

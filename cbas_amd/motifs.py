@@ -4,13 +4,15 @@ at first?" - the question before any frame is labelled.
     python -m cbas_amd.motifs --dir RECORDINGS | --files A_cls.h5 B_cls.h5 ... --clusters K [--iters N] [--no-normalize]
                               [--smooth W] [--load clusters.npz] [--save clusters.npz] --out frames.csv [--runs runs.csv]
                               [--exemplars exemplars.csv] [--write-outputs MODEL_NAME]
+                              [--hmm ITERS [--temperature T] [--mean-duration F] [--save-hmm hmm.npz] | --load-hmm hmm.npz]
 
 k-means over the fp16 rows of a ``search.FrameIndex`` (``cbas_rows_kmeans_fit`` / ``cbas_rows_kmeans_assign``,
 csrc/rows_kmeans.hip): deterministic farthest-point seeding, a fixed number of Lloyd rounds, clusters numbered by descending size.
 The per-frame motif then goes where a behaviour goes: ``motif_runs`` (bouts per file through ``postprocess.labels_median`` /
 ``label_runs``), ``transition_counts``, ``exemplars`` (the index's own cosine search around every centroid) and ``write_outputs``
 (one-hot ``_outputs.csv`` files that ``activity_bins`` and the actogram read).  The reference has no unsupervised grouping.
-DESIGN.md section 21.
+DESIGN.md section 21.  With ``--hmm`` the clustering only starts a motif HMM (``motif_hmm.fit``) and the
+outputs come from its Viterbi labels and posteriors; without it every output is what it was.
 """
 from __future__ import annotations
 
@@ -216,6 +218,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--per-motif", type=int, default=5)
     ap.add_argument("--min-gap", type=int, default=15)
     ap.add_argument("--write-outputs", default=None, metavar="MODEL_NAME", help="write <stem>_<MODEL_NAME>_outputs.csv beside every file")
+    ap.add_argument("--hmm", type=int, default=None, metavar="ITERS",
+                    help="fit a motif HMM (motif_hmm.fit) in ITERS rounds from the clustering; the outputs come from its Viterbi labels")
+    ap.add_argument("--temperature", type=float, default=None, metavar="T", help="1 / kappa of the HMM's emissions (default: calibrated)")
+    ap.add_argument("--mean-duration", type=float, default=40.0, metavar="F", help="mean bout length in frames of the HMM's starting transitions")
+    ap.add_argument("--save-hmm", default=None, metavar="hmm.npz", help="write the fitted HMM to this .npz")
+    ap.add_argument("--load-hmm", default=None, metavar="hmm.npz", help="segment with the HMM of this .npz instead of fitting")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--max-gb", type=float, default=None)
     return ap
@@ -224,8 +232,21 @@ def build_parser() -> argparse.ArgumentParser:
 def parse_cli(argv=None):
     ap = build_parser()
     a = ap.parse_args(argv)
-    if (a.clusters is None) == (a.load is None):
+    if a.load_hmm is not None:
+        if a.clusters is not None or a.load is not None or a.hmm is not None or a.save_hmm is not None:
+            ap.error("--load-hmm segments with a fitted model: not with --clusters, --load, --hmm or --save-hmm")
+    elif (a.clusters is None) == (a.load is None):
         ap.error("give --clusters K to fit, or --load clusters.npz to assign")
+    if a.hmm is not None and a.hmm < 0:
+        ap.error(f"--hmm {a.hmm}: at least 0 rounds")
+    if a.hmm is None and a.load_hmm is None and (a.temperature is not None or a.save_hmm is not None):
+        ap.error("--temperature and --save-hmm belong to --hmm")
+    if a.temperature is not None and not a.temperature > 0.0:
+        ap.error(f"--temperature {a.temperature}: positive")
+    if not a.mean_duration > 1.0:
+        ap.error(f"--mean-duration {a.mean_duration}: more than 1 frame")
+    if (a.hmm is not None or a.load_hmm is not None) and a.smooth != 1:
+        ap.error("--smooth is the median filter; with an HMM the transitions do the smoothing")
     if a.clusters is not None and not 2 <= a.clusters <= MAX_CLUSTERS:
         ap.error(f"--clusters {a.clusters}: 2 .. {MAX_CLUSTERS}")
     if a.iters < 0:
@@ -248,9 +269,70 @@ def write_frames_csv(path: str, index, labels: np.ndarray, dist2: np.ndarray) ->
                 w.writerow([file, t, int(labels[first + t]), f"{float(dist2[first + t]):.6g}"])
 
 
+HMM_FRAME_COLUMNS = ["file", "frame", "motif", "posterior"]
+
+
+def main_hmm(ap, a) -> int:
+    """``--hmm`` / ``--load-hmm``: the frames CSV (its last column the posterior of the frame's motif in place of dist2), ``--runs``
+    and ``--write-outputs`` from the HMM's Viterbi labels; ``--write-outputs`` writes the graded posteriors.  On ``--device cpu`` the
+    fit is the float64 numpy statement of the rounds (small files only) and ``--exemplars``, a search on the device, is refused."""
+    from . import bouts as _bouts, knn as _knn, motif_hmm as _hmm, search as _search
+    try:
+        index = _search.FrameIndex(a.dir if a.dir else a.files, a.device, a.max_gb)
+        on_gpu = index.device.type == "cuda"
+        if a.exemplars and not on_gpu:
+            raise ValueError("--exemplars searches on a GPU")
+        if a.load_hmm:
+            model = _hmm.MotifHMM.load(a.load_hmm)
+            gamma = model.posteriors(index)
+        else:
+            init = FrameClusters.load(a.load) if a.load else None
+            C = init.n_clusters if init is not None else a.clusters
+            gamma, model = _hmm.fit(index, n_states=C, iters=a.hmm, temperature=a.temperature, init=init, normalize=not a.no_normalize,
+                                    transitions=_bouts.sticky_transitions(C, mean_duration=a.mean_duration, as_probs=True))
+        labels = model.labels(index)
+    except (ValueError, MemoryError, OSError) as e:
+        ap.error(str(e))
+    if a.save_hmm:
+        model.save(a.save_hmm)
+    k = model.n_states
+    host = labels.cpu().numpy()
+    conf = gamma.cpu().numpy()[np.arange(index.n_rows), np.maximum(host, 0)]
+    with open(a.out, "w", newline="") as f:
+        w = csv.writer(f, lineterminator="\n")
+        w.writerow(HMM_FRAME_COLUMNS)
+        for file, (first, n) in zip(index.files, index._table):
+            for t in range(int(n)):
+                w.writerow([file, t, int(host[first + t]), f"{float(conf[first + t]):.6g}"])
+    rounds = model.loglik
+    print(f"{k} motifs over {index.n_rows} frames of {len(index.files)} files, temperature {model.temperature:.6g}"
+          + (f", log-likelihood {rounds[0]:.1f} -> {rounds[-1]:.1f} bits" if rounds.size and not a.load_hmm else "") + f" -> {a.out}")
+    if a.runs:
+        runs = motif_runs(index, labels, model, 1, a.min_frames) if on_gpu else runs_host(host, index._table, 1, a.min_frames)
+        with open(a.runs, "w", newline="") as f:
+            w = csv.writer(f, lineterminator="\n")
+            w.writerow(RUN_COLUMNS)
+            for file, file_runs in zip(index.files, runs):
+                for motif, start, end in file_runs:
+                    w.writerow([file, motif, start, end])
+    if a.exemplars:
+        with open(a.exemplars, "w", newline="") as f:
+            w = csv.writer(f, lineterminator="\n")
+            w.writerow(EXEMPLAR_COLUMNS)
+            for motif, hits in enumerate(exemplars(index, model, a.per_motif, a.min_gap)):
+                for rank, h in enumerate(hits):
+                    w.writerow([motif, rank, h["file"], h["frame"], f"{h['score']:.6f}"])
+    if a.write_outputs:
+        paths = _knn.write_outputs(index, gamma, motif_names(k), a.write_outputs)
+        print(f"{len(paths)} files like {paths[0]}")
+    return 0
+
+
 def main(argv=None) -> int:
     from . import search as _search
     ap, a = parse_cli(argv)
+    if a.hmm is not None or a.load_hmm is not None:
+        return main_hmm(ap, a)
     try:
         index = _search.FrameIndex(a.dir if a.dir else a.files, a.device, a.max_gb)
         loaded = FrameClusters.load(a.load) if a.load else None

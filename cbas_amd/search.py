@@ -224,6 +224,11 @@ class FrameIndex:
         from . import motifs as _motifs
         return _motifs.cluster_frames(self, n_clusters=n_clusters, iters=iters, normalize=normalize, init=init, clusters=clusters)
 
+    def motif_hmm(self, **kw):
+        """``motif_hmm.fit(self, ...)``: ``(gamma, model)``, a motif HMM whose emissions are learned with its transitions."""
+        from . import motif_hmm as _motif_hmm
+        return _motif_hmm.fit(self, **kw)
+
     # ---- the map (cbas_amd/framemap.py) ----------------------------------------------------------------------------------------
     def pca(self, n_components: int = 3, normalize: bool = True, iters=None, basis=None):
         """``framemap.pca_frames(self, ...)``: ``(scores, basis)``, every row's principal-component scores and the ``FramePCA``."""

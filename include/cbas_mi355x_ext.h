@@ -113,6 +113,57 @@ int cbasx_hmm_posteriors(const float* probs_dev, int64_t n_total, const int64_t*
                          const float* trans_dev, const float* prior_dev, float* gamma_dev, double* xi_dev, double* pi_dev,
                          double* loglik_dev, uint32_t* flags_dev, void* workspace_dev, int64_t workspace_bytes, void* stream);
 
+/* The motif HMM's two passes over resident rows (csrc/rows_hmm.hip).  rows_f16_dev is (n_rows, dim) fp16 with
+ * row stride ld, as cbas_rows_kmeans_* takes it: dim a multiple of 32 up to 1536, ld >= dim and a multiple of 8, 16-byte aligned.
+ * The working row u of a row x is x widened to fp32 (normalize = 0) or fl(x * rn) with rn = fp32(1 / sqrt(s)), s the fp32 sum of
+ * squares in the order s = (l0 + l1) + (l2 + l3), l_j the fmaf chain over the columns d with (d % 32) / 8 = j, ascending - the rn
+ * of cbas_rows_search and cbas_rows_kmeans_*; a zero row has rn = 0.  The rows are finite. */
+#define CBASX_ROWS_HMM_MAX_STATES 64
+#define CBASX_ROWS_HMM_MAX_DIM 1536
+#define CBASX_ROWS_HMM_MAX_PARTS 256             /* cbasx_rows_weighted_sums deals the rows to at most this many parts ... */
+#define CBASX_ROWS_HMM_PART_ROWS 64              /* ... of a multiple of this many rows each */
+
+/* probs_dev (n_rows, C) float32, the emission probabilities of every row under C mean directions means_dev (C, dim) float32
+ * with one shared concentration kappa (von Mises-Fisher emissions of equal kappa, whose normaliser cancels):
+ *     z_j = fmaf(kappa, fl(rn * (x . mu_j)), logw_j)       (rn = 1 with normalize = 0; logw = log_weights_dev, NULL: zeros)
+ *     probs_j = exp(z_j - max z) / sum_j exp(z_j - max z)
+ *     lognorm = (max z + log sum_j exp(z_j - max z)) * log2(e)
+ * lognorm_dev (n_rows) float32, when not NULL, is that log-normaliser in bits, the unit of cbasx_hmm_posteriors' loglik.
+ * Sum orders: x . mu_j = chain0 + chain1, chain p the fp32 fmaf chain, from 0, over the columns d with (d / 32) % 2 = p ordered by
+ * (d / 32, d % 8, (d % 32) / 8) ascending (cbas_rows_search's dot); the sum over j adds, for f = 0 .. 15, the states f, 16 + f,
+ * 32 + f, 48 + f in ascending order and then the 16 results by the pairwise tree of strides 1, 2, 4, 8; the division is
+ * correctly rounded.  A zero row (rn = 0) and kappa = 0 give exactly the softmax of logw.  A row's outputs depend neither on
+ * n_rows, nor on the grid, nor on where the row lies; two calls agree bit for bit.  One streaming pass, asynchronous on `stream`;
+ * nothing is copied, no atomics.
+ * A mean or a log-weight that is not finite is the caller's error: the probs and lognorm of the rows it meets are unspecified
+ * (NaN included; a log-weight of -infinity alone simply gives its state probability 0); nothing else is written.
+ * Refusals (CBAS_EINVAL, the outputs untouched): a NULL pointer other than log_weights_dev / lognorm_dev; C outside 1 .. 64; dim or
+ * ld out of range; n_rows < 0; normalize not 0 or 1; kappa negative or not finite; rows or means not 16-byte aligned. */
+int cbasx_rows_emissions(const void* rows_f16_dev, int64_t n_rows, int32_t dim, int64_t ld, int32_t C, int32_t normalize,
+                         const float* means_dev, float kappa, const float* log_weights_dev, float* probs_dev, float* lognorm_dev,
+                         void* stream);
+
+/* Bytes of workspace cbasx_rows_weighted_sums needs, or -1 for a shape it refuses.  With rpp = max(64, ceil(ceil(n_rows / 256) /
+ * 64) * 64) rows per part and parts = ceil(n_rows / rpp) <= 256 - functions of n_rows alone -: max(parts, 1) * (4 C dim + 256)
+ * bytes, every piece rounded up to 16: never more than 256 * (4 C dim + 256), however many rows. */
+int64_t cbasx_rows_weighted_sums_workspace_bytes(int64_t n_rows, int32_t dim, int32_t C);
+
+/* The M step: sums_dev (C, dim) float64 = sum_t w[t][c] u_t and mass_dev (C) float64 = sum_t w[t][c], from weights_dev
+ * (n_rows, C) float32 (the gamma of cbasx_hmm_posteriors).  The product runs on the fp32 matrix pipe straight from the fp16 rows;
+ * u = fl(x * rn) is formed between the load and the MFMA operand.
+ * Sum order: part p owns the rows p rpp .. (p + 1) rpp - 1.  Inside a part the 16-row blocks go to four lanes in turn (block b to
+ * lane b % 4); a lane is ONE fp32 fused-multiply-add chain per (state, column), from 0, over its rows in ascending order; the
+ * part's value is ((lane 0 + lane 1) + lane 2) + lane 3 in fp32; the parts are added in ascending order in float64.  mass is the
+ * same chain with u = 1.  No atomics: two calls agree bit for bit.  A row whose weights are all 0 contributes nothing (frames
+ * outside every clip are such rows in gamma); a NaN weight propagates into its state's sums and mass.  n_rows = 0 gives zeros.
+ * Asynchronous on `stream`; nothing is copied.
+ * Refusals (CBAS_EINVAL, the outputs untouched): a NULL pointer; C outside 1 .. 64; dim or ld out of range; n_rows < 0; normalize
+ * not 0 or 1; a workspace smaller than cbasx_rows_weighted_sums_workspace_bytes or not 16-byte aligned; rows not 16-byte aligned;
+ * sums or mass not 8-byte aligned. */
+int cbasx_rows_weighted_sums(const void* rows_f16_dev, int64_t n_rows, int32_t dim, int64_t ld, int32_t C, int32_t normalize,
+                             const float* weights_dev, double* sums_dev, double* mass_dev, void* workspace_dev,
+                             int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
